@@ -120,6 +120,10 @@ def parse():
     ap.add_argument("--bringup-timeout", type=int, default=150, help="seconds the process-group bring-up (init, first all-reduce, first "
                                                                       "neighbour exchange) may take before it counts as hung")
     ap.add_argument("--dump-film-f", default=None, help="write film-f of a fresh run (empty statistics, three steps) to this .npy (tests: legs against each other)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed back (the whole film's film-f) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a larger film: a fixed, seeded sample of its pixels); the inputs are seeded, so "
+                         "two builds run with the same arguments can be compared output for output")
     ap.add_argument("--share-device", action="store_true", help="debug: every rank uses cuda:0")
     ap.add_argument("--cpu-acc-rows", type=int, default=32, help="rows of the film the CPU baseline accumulates")
     ap.add_argument("--no-host-legs", action="store_true", help="skip the secondary host-side measurements (N = 1)")
@@ -147,9 +151,37 @@ def parse():
                          "placed buffers and on copies from torch's allocator, and the timed region uses the faster set -- a card whose GiB slots "
                          "mostly straddle interference classes gives the allocator nothing to choose from; the line says which set ran and both times)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region over --steps)")
     if args.film:
         args.width, args.height = (int(v) for v in args.film.lower().split("x"))
     return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all arrays together, .npy headers included
+
+
+def write_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: every array ([H, W, C] image) as dirname/<name>.npy in float32 (float64 stays float64), at most
+    DUMP_LIMIT_BYTES in all.  Arrays that would not fit are cut to the same share of their pixels each: a seeded sample, in
+    ascending pixel order, so one shape gives the same pixels on every run.  Returns what was written (for the result line)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        info = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if total > budget:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = px.shape[0] * budget // total
+            idx = np.sort(np.random.default_rng(seed).choice(px.shape[0], keep, replace=False))
+            a = px[idx]
+            info.update(sampled_pixels=int(keep), sample_seed=seed, stored_shape=list(a.shape))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = info
+    return {"dir": dirname, "arrays": written}
 
 
 def cpu_share():
@@ -1318,9 +1350,11 @@ def main():
         barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        last = step(True)
     barrier()
     elapsed = time.perf_counter() - t0
+    # --dump-outputs: the block the last timed step handed back, copied before anything after the timed region reuses its buffer
+    last_block = last.clone() if args.dump_outputs else None
     cdev = dev if args.backend == "nccl" else "cpu"
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -1465,6 +1499,12 @@ def main():
             if rank == 0:
                 import numpy as np
                 np.save(args.dump_film_f, whole.cpu().numpy())
+    outputs = None
+    if args.dump_outputs:
+        whole = pipe.gather_film(last_block, film_f) if world > 1 else last_block      # (collective: every rank takes part)
+        torch.cuda.synchronize()
+        if rank == 0:
+            outputs = write_outputs(args.dump_outputs, {"film_f": whole.cpu().numpy()})
 
     result = None
     if rank == 0:
@@ -1476,6 +1516,8 @@ def main():
                    parallelism="film blocks x%d, one process per GPU, halo exchange over torch.distributed (%s%s)"
                                % (world, args.backend, " = RCCL" if args.backend == "nccl" else ", halos via the host") if world > 1 else "single GPU")
         result = build_result(ctx)
+        if outputs is not None:
+            result["dumped_outputs"] = outputs
         if eight is not None:
             result["filter_8_feature_channels"] = eight
         # (before the host-side legs: their page-locked staging buffers and band pipelines keep threads and memory busy)
@@ -1872,6 +1914,10 @@ def main_peer(args):
         step(True)
     pf.synchronize()
     elapsed = time.perf_counter() - t0
+    last_film = None
+    if args.dump_outputs:          # the blocks still hold the last timed step's film-f: assembled into a fresh tensor
+        last_film = pf.gather()
+        pf.synchronize()
     host_ms = host_s[0] * 1e3 / args.steps
     variant = api.last_filter_variant()
 
@@ -1952,6 +1998,8 @@ def main_peer(args):
                host_enqueue_ms_per_step=round(host_ms, 4), devices=devices)
     result = build_result(ctx)
     result["n_gpus"] = n
+    if last_film is not None:
+        result["dumped_outputs"] = write_outputs(args.dump_outputs, {"film_f": last_film.cpu().numpy()})
     if eight is not None:
         result["filter_8_feature_channels"] = eight
     print(json.dumps(result), flush=True)

@@ -100,7 +100,47 @@ def buffer_catalogue():
     print("buffer_catalogue", {k: len(v) for k, v in cat.items()})
 
 
+def reference_stattile(ref):
+    """What the REFERENCE's own StatTile<Float> / StatTile<Vec3> (estimator.h:147-239, patched by patches/0001-0003, on
+    include/statmc_cv.hpp's cv::Vec) computes over SURVEY 8c's edge cases, through all twelve Add[Transform]SampleM{1,2,3}:
+    tools/check_reference_compiles.sh builds tests/cpp/ref_stattile_main.cpp with g++ (no contraction) and with clang -O3
+    -march=x86-64-v3 -ffp-contract=on (the reference's own recipe) and runs both.  Data only -- no reference source is stored.
+    Needs a reference checkout at `ref`:  python tests/golden/make_golden.py --reference <checkout>"""
+    import subprocess
+    import tempfile
+    from statmc_amd import build
+    build.build()
+    count, smp = edge_case_stream()
+    S, H, W, _ = smp.shape
+    out = dict(count=count, samples=smp)
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "stattile_in.bin"), os.path.join(d, "stattile_out")
+        with open(fin, "wb") as f:
+            f.write(np.array([W, H, S], np.int32).tobytes() + count.tobytes() + smp.tobytes())
+        root = os.path.dirname(os.path.dirname(HERE))
+        subprocess.check_call([os.path.join(root, "tools", "check_reference_compiles.sh"), ref],
+                              env=dict(os.environ, STATTILE_IN=fin, STATTILE_OUT=fout))
+        for tag in ("gcc", "clang"):
+            raw = open(fout + "." + tag, "rb").read()
+            off = 0
+            for c in (1, 3):
+                dt = oracle.TILE_PIXEL_DTYPE[c]
+                for transform in (0, 1):
+                    for moment in (1, 2, 3):
+                        got = np.frombuffer(raw, dtype=dt, count=W * H, offset=off).reshape(H, W)
+                        off += W * H * dt.itemsize
+                        key = "%s_c%d_t%d_m%d_" % (tag, c, transform, moment)
+                        for field in dt.names:
+                            out[key + field] = np.ascontiguousarray(got[field])
+            assert off == len(raw)
+    np.savez_compressed(os.path.join(HERE, "reference_stattile_edge_cases.npz"), **out)
+    print("reference_stattile_edge_cases", len(out), "arrays")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--reference":
+        reference_stattile(sys.argv[2])
+        sys.exit(0)
     main()
     accumulate_edge_cases()
     mean_vars_row_quirk()

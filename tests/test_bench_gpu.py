@@ -100,6 +100,23 @@ def test_step_fed_by_tile_blocks(gpu, tmp_path):
     assert films["film"].shape == (256, 512, 3) and (films["film"] == films["tiles"]).all()
 
 
+def test_dump_outputs_holds_the_last_timed_step(gpu, tmp_path):
+    """`--dump-outputs DIR`: film-f of the LAST timed step.  One warm-up and two timed steps from empty statistics are three steps, so it
+    is the same bits as `--dump-film-f` (a fresh run of three steps) in the same process; --steps is the number of timed steps."""
+    out_dir, fresh = tmp_path / "outputs", str(tmp_path / "fresh.npy")
+    args = ["--film", "512x256", "--spp", "8", "--steps", "2", "--warmup", "1"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-host-legs", "--no-cpu-baseline", "--dump-outputs", str(out_dir),
+                          "--dump-film-f", fresh] + args, capture_output=True, text=True, timeout=360)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = _line(out)
+    assert r["steps"] == 2 and r["ms_per_step"] > 0
+    assert r["dumped_outputs"]["arrays"]["film_f"] == {"shape": [256, 512, 3], "dtype": "float32"}
+    import numpy as np
+    got = np.load(out_dir / "film_f.npy")
+    assert sorted(os.listdir(out_dir)) == ["film_f.npy"] and got.dtype == np.float32 and np.isfinite(got).all()
+    assert np.array_equal(got, np.load(fresh))
+
+
 @pytest.mark.parametrize("grid,blocks", [("rows", "1x2"), ("blocks", "2x1")])
 def test_strong_scaling_two_ranks_share_the_device(gpu, grid, blocks):
     """`python bench.py --gpus 2` with NO launcher around it: bench.py starts its own ranks (fresh processes, before
@@ -183,13 +200,14 @@ def _clean_env(**extra):
 def test_peer_leg_one_process_all_blocks_and_same_bits_as_the_rank_leg(gpu, tmp_path):
     """`--backend peer`: ONE process drives both blocks through the C ABI (statmc_halo_exchange's device-to-device copies;
     here both blocks share the box's one GPU).  Its film-f equals the one-process-per-block leg's (gloo, halos via the
-    host) bit for bit, and -- the blocks being filtered under the default dispatch -- the whole film's within 1e-6."""
+    host) bit for bit, and -- the blocks being filtered under the default dispatch -- the whole film's within 1e-6.  So does the film
+    both legs write for --dump-outputs."""
     import numpy as np
     dumps = {}
     for backend in ("peer", "gloo"):
         dumps[backend] = str(tmp_path / ("film_f_%s.npy" % backend))
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend, "--share-device",
-               "--dump-film-f", dumps[backend]] + COMMON
+               "--dump-film-f", dumps[backend], "--dump-outputs", str(tmp_path / backend)] + COMMON
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=360, env=_clean_env())
         assert out.returncode == 0, out.stderr[-3000:]
         r = _line(out)
@@ -207,6 +225,9 @@ def test_peer_leg_one_process_all_blocks_and_same_bits_as_the_rank_leg(gpu, tmp_
             assert r["gather"]["bytes"] == 12 * 512 * 256
     a, b = np.load(dumps["peer"]), np.load(dumps["gloo"])
     assert a.shape == (256, 512, 3) and np.array_equal(a, b)
+    # --dump-outputs: the whole film of the last timed step, the same bits from both legs
+    a, b = (np.load(tmp_path / backend / "film_f.npy") for backend in ("peer", "gloo"))
+    assert a.shape == (256, 512, 3) and np.isfinite(a).all() and np.array_equal(a, b)
 
 
 @pytest.mark.parametrize("launcher,mode", [("self", "1"), ("torchrun", "1"), ("self", "hang"), ("torchrun", "hang")],

@@ -87,6 +87,31 @@ def test_oracle_reproduces_the_accumulate_edge_cases(oracle):
         assert np.array_equal(g["c3_t1_m3_" + k], g["fma_c3_t1_m3_" + k]), k
 
 
+def test_oracle_reproduces_the_reference_stattile_on_the_edge_cases(oracle):
+    """What the reference's OWN StatTile<Float> / StatTile<Vec3> (estimator.h:147-239, on include/statmc_cv.hpp's cv::Vec) computed
+    over the same edge cases, stored by make_golden.py --reference: g++ (no contraction) and clang -O3 -march=x86-64-v3
+    -ffp-contract=on (the reference's own recipe).  Every field of every pixel equals the oracle's BIT FOR BIT in the matching
+    contraction mode, here without a reference checkout (tests/test_host_cpu.py rebuilds and reruns it where one exists)."""
+    from conftest import edge_case_stream
+    g = np.load(os.path.join(GDIR, "reference_stattile_edge_cases.npz"))
+    count, smp = edge_case_stream()
+    assert np.array_equal(g["count"], count) and np.array_equal(g["samples"], smp)
+    H, W = count.shape
+    try:
+        for tag, contract in (("gcc", False), ("clang", True)):
+            oracle.set_fp_contract(contract)
+            for c, t, m in VARIANTS:
+                key = "%s_c%d_t%d_m%d_" % (tag, c, t, m)
+                assert np.array_equal(g[key + "n"], count)
+                for y in range(H):
+                    for x in range(W):
+                        want = oracle.add_samples_to_pixel(smp[:count[y, x], y, x, :c], c, t, m)
+                        for f in ("n",) + FIELDS:
+                            assert np.asarray(want[f]).tobytes() == g[key + f][y, x].tobytes(), (key, f, y, x)
+    finally:
+        oracle.set_fp_contract(False)
+
+
 def test_oracle_reproduces_the_mean_vars_quirk(oracle):
     g = np.load(os.path.join(GDIR, "mean_vars_row_quirk.npz"))
     q, p = oracle.mean_vars(g["n"], g["film_m2"], row_n_quirk=True), oracle.mean_vars(g["n"], g["film_m2"], row_n_quirk=False)

@@ -413,6 +413,56 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
                             const int32_t *tile_bounds, const int64_t *tile_offsets,
                             const int32_t *tile_samples, int n_tiles, void *stream);
 
+/* ---- combining independently accumulated statistics (no counterpart in the reference, whose renders can only be split by
+ * --baseseed and then not put back together: src/main/pbrt.cpp:71,165-168).  Per pixel and channel, part A in `dst`, part B
+ * in `src`, n = nA + nB, delta = meanB - meanA (Chan et al. 1979, Pebay 2008):
+ *     mean = meanA + delta nB / n
+ *     m2   = m2A + m2B + delta^2 nA nB / n
+ *     m3   = m3A + m3B + delta^3 nA nB (nA - nB) / n^2 + 3 delta (nA m2B - nB m2A) / n
+ * film_mean / film_m2 follow the mean / m2 lines with their own delta and the same counts.  These are the reference's Meng
+ * update (src/statistics/estimator.h:162-205, "m3 uses the updated m2") when B is one sample: with nB = 1, m2B = m3B = 0,
+ * d = delta and dN = d / n,
+ *     m2:  d^2 nA / n                          = d (d - dN)                                       (d - dN = d nA / n)
+ *     m3:  d^3 nA (nA - 1) / n^2 - 3 dN m2A    = -3 dN (m2A + d^2 nA / n) + d (d^2 - dN^2)
+ *          since n^2 - 1 - 3 nA = nA (nA - 1) for n = nA + 1, and m2A + d^2 nA / n is the updated m2.
+ * fp32 operation order (ints nA, nB; fA = (float)nA, fB = (float)nB, nf = (float)(nA + nB); r = refined 1 / nf and
+ * div(x) = x / nf rounded as the accumulation divides by its count; every operation rounds once, nothing is contracted):
+ *     d = meanB - meanA;  t = div(d * fB);  q = d * fA;  u = div(d)
+ *     mean = meanA + t
+ *     m2   = (m2A + m2B) + q * t
+ *     m3   = ((m3A + m3B) + (q * t) * ((fA - fB) * u)) + (3 * u) * (fA * m2B - fB * m2A)      (m2A, m2B: before the call)
+ * Exact cases, per pixel: nB == 0 leaves dst's bits unchanged; otherwise nA == 0 makes dst a bit copy of src; n is the
+ * integer sum; constant samples (delta = 0, m2 = m3 = 0 on both sides) give m2 = m3 = 0 exactly.
+ * Counts must sum below 2^24, the range in which (float)n and the refined reciprocal are exact; this is not checked per pixel.
+ *
+ * Each entry reuses statmc_stat_type for both sides:
+ *   - max_moment picks the fields: 1 = mean, 2 = mean and m2, 3 = mean, m2 and m3; dst and src agree on channels and max_moment;
+ *   - film_mean / film_m2 are combined when non-NULL and not the same pointers as mean / m2 (a non-transform type whose film
+ *     images alias its moments, estimator.cpp:127-137, is combined once); film_m2 without a film_mean of its own is an error;
+ *   - dst.samples, dst.n_samples and both `transform` fields are ignored, as are src.mean_corr / src.discriminator;
+ *   - dst.mean_corr / dst.discriminator (both or neither; max_moment 3 and own counts): the call's epilogue writes the
+ *     pre-pass of the combined moments there under the device's current spec and significance level -- the bits
+ *     statmc_prepass computes from them, like the accumulation's epilogue;
+ *   - count_of = -1: dst.n / src.n are the entry's counts, and dst.n becomes nA + nB.  count_of = k >= 0: the entry is
+ *     weighed with entry k's counts AS THEY WERE BEFORE THE CALL, whatever the entry order; dst.n and src.n are NULL and
+ *     entry k has count_of = -1.  This is how the "film" RGB image is combined (an M1 mean weighted by t0-b0-n: with StatMC's
+ *     box filter Film's weight sum per pixel is that count, film.h:152-190, statpath.cpp:355-358, apart from samples that
+ *     land exactly on a pixel edge), and G-buffer means of a dump that carries no n of their own (every camera sample feeds
+ *     radiance b0 and every G-buffer, statpath.cpp:357-371).
+ * No dst image may be its src counterpart; no two entries may own the same count image.  Images are packed width x height
+ * planes like statmc_accumulate's.  n_entries = 0 is a no-op, at most 16 (statmc::kMaxStatTypes); one launch serves all.
+ * Asynchronous on `stream`; both states on the current device (copy first with statmc_copy_rect). */
+typedef struct statmc_combine_entry {
+    statmc_stat_type dst; /* updated in place; samples / n_samples / transform ignored */
+    statmc_stat_type src; /* read only; mean_corr / discriminator ignored */
+    int32_t count_of;     /* -1: dst.n / src.n are this entry's counts, and dst.n is updated.
+                             k >= 0: weigh with entry k's counts as they were before the call;
+                             dst.n and src.n must be NULL; entry k must have count_of == -1 */
+} statmc_combine_entry;
+
+int statmc_combine_statistics(uint16_t width, uint16_t height, const statmc_combine_entry *entries, int n_entries,
+                              void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

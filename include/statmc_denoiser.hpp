@@ -1083,6 +1083,100 @@ class Estimator {
                     (*bufs)[i][j].download(stream);
     }
 
+    // Combines the statistics of `other` -- the same film rendered with other samples (pbrt --baseseed) -- into this
+    // Estimator's device images, so that they hold the statistics of the union of both sample sets
+    // (statmc_combine_statistics; include/statmc.h has the formulas).  Every enabled (type, bounce) is weighed with its own
+    // counts, the "film" image with the counts of the first (type, bounce) -- radiance b0, whose count is Film's weight sum
+    // under StatMC's box filter.  The types listed in `borrowCounts` (config indices) take those counts as well: the G-buffer
+    // means of a dump that carries no n of their own.  Both Estimators are on one device, of one size and configuration;
+    // pending device-accumulation samples of both are flushed first, and the call is ordered behind everything enqueued on
+    // `other`'s stream.  Asynchronous on this Estimator's stream; mean-corr / discriminator are left to Denoise().
+    // (Not "Merge": Merge*Tile(s) is the reference's tile scatter, estimator.cpp:341-407.)
+    void CombineStatistics(Estimator &other, const std::vector<unsigned char> &borrowCounts = {}) {
+        if (&other == this) throw Error(STATMC_ERR_INVALID, "CombineStatistics: an Estimator cannot be combined with itself");
+        if (!allocateDevice || !other.allocateDevice) throw Error(STATMC_ERR_INVALID, "CombineStatistics needs device images");
+        if (other.device != device) throw Error(STATMC_ERR_INVALID, "CombineStatistics: both Estimators must be on one device");
+        if (other.width != width || other.height != height) throw Error(STATMC_ERR_INVALID, "CombineStatistics: film sizes differ");
+        const auto &a = statTypeConfigs, &b = other.statTypeConfigs;
+        bool same = a.nEnabled == b.nEnabled;
+        for (unsigned char i = 0; same && i < a.nEnabled; i++)
+            same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
+                   a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
+        if (!same) throw Error(STATMC_ERR_INVALID, "CombineStatistics: the Estimators have different stat type configurations");
+        if (a.nEnabled == 0 || nBuffers.empty() || nBuffers[0].empty())
+            throw Error(STATMC_ERR_INVALID, "CombineStatistics: no statistics (call AllocateBuffers first)");
+        for (unsigned char t : borrowCounts)
+            if (t == 0 || t >= a.nEnabled) throw Error(STATMC_ERR_INVALID, "CombineStatistics: borrowCounts names type " + std::to_string(t));
+        check(statmc_set_device(device));
+        if (acc.enabled) FlushSamples();
+        if (other.acc.enabled) other.FlushSamples();
+        other.joinUploads();
+        joinUploads();
+        if (!combineEvent) {
+            void *ev = nullptr;
+            check(statmc_event_create(&ev));
+            combineEvent.reset(ev, [](void *e) { statmc_event_destroy(e); });
+        }
+        check(statmc_event_record(combineEvent.get(), other.stream.handle()));
+        check(statmc_stream_wait_event(stream.handle(), combineEvent.get()));
+
+        auto side = [](const StatTypeConfig &c, Buffer &n, Buffer &mean, Buffer &m2, Buffer &m3, Buffer &fm, Buffer &fm2, bool own) {
+            statmc_stat_type s;
+            std::memset(&s, 0, sizeof(s));
+            s.channels = c.nChannels;
+            s.transform = c.transform;
+            s.max_moment = c.maxMoment;
+            s.n = own ? static_cast<int32_t *>(n.gpuMat.data()) : nullptr;
+            s.mean = static_cast<float *>(mean.gpuMat.data());
+            s.m2 = static_cast<float *>(m2.gpuMat.data());
+            s.m3 = static_cast<float *>(m3.gpuMat.data());
+            s.film_mean = static_cast<float *>(fm.gpuMat.data());   // non-transform types: the mean's own storage (combined once)
+            s.film_m2 = static_cast<float *>(fm2.gpuMat.data());
+            return s;
+        };
+        // the owner of the borrowed counts and everything that borrows them go into the first call: a later call would see
+        // the counts already summed
+        std::vector<statmc_combine_entry> first, rest;
+        auto entry = [&](unsigned char i, unsigned char j, bool own) {
+            const StatTypeConfig &c = a[i];
+            statmc_combine_entry e;
+            std::memset(&e, 0, sizeof(e));
+            e.dst = side(c, nBuffers[i][j], meanBuffers[i][j], m2Buffers[i][j], m3Buffers[i][j], filmBuffers[i][j], filmM2Buffers[i][j], own);
+            e.src = side(c, other.nBuffers[i][j], other.meanBuffers[i][j], other.m2Buffers[i][j], other.m3Buffers[i][j],
+                         other.filmBuffers[i][j], other.filmM2Buffers[i][j], own);
+            e.count_of = own ? -1 : 0;
+            return e;
+        };
+        first.push_back(entry(0, 0, true));
+        for (unsigned char i = 0; i < a.nEnabled; i++) {
+            const bool borrow = std::find(borrowCounts.begin(), borrowCounts.end(), i) != borrowCounts.end();
+            for (unsigned char j = 0; j < a[i].nBounces; j++) {
+                if (i == 0 && j == 0) continue;
+                if (borrow) first.push_back(entry(i, j, false));
+                else rest.push_back(entry(i, j, true));
+            }
+        }
+        if (filmBuffer.gpuMat.data() && other.filmBuffer.gpuMat.data()) {   // the colour image: an M1 mean weighted by t0-b0-n
+            statmc_combine_entry e;
+            std::memset(&e, 0, sizeof(e));
+            e.dst.channels = e.src.channels = 3;
+            e.dst.max_moment = e.src.max_moment = 1;
+            e.dst.mean = static_cast<float *>(filmBuffer.gpuMat.data());
+            e.src.mean = static_cast<float *>(other.filmBuffer.gpuMat.data());
+            e.count_of = 0;
+            first.push_back(e);
+        }
+        const size_t cap = 16;   // statmc::kMaxStatTypes entries per call
+        if (first.size() > cap) throw Error(STATMC_ERR_INVALID, "CombineStatistics: more than 16 images borrow the first type's counts");
+        while (first.size() < cap && !rest.empty()) {
+            first.push_back(rest.back());
+            rest.pop_back();
+        }
+        check(statmc_combine_statistics(width, height, first.data(), (int)first.size(), stream.handle()));
+        for (size_t k = 0; k < rest.size(); k += cap)
+            check(statmc_combine_statistics(width, height, rest.data() + k, (int)std::min(cap, rest.size() - k), stream.handle()));
+    }
+
     const unsigned short width, height;
     const float filterDSFactor;
     const unsigned char filterRadius;
@@ -1140,6 +1234,7 @@ class Estimator {
     mutable std::tuple<int, int, int, int, int> planCacheKey{-1, -1, -1, -1, -1};
     mutable std::mutex planMutex;
     int deviceCUs = 0;
+    std::shared_ptr<void> combineEvent;   // CombineStatistics: orders this stream behind the other Estimator's
     int bandEdge(int k, int) const { return bandPlan().edge(k); }
     int arrivalEdge(int k, int) const { return bandPlan().arrival(k); }
     void ensurePipeline(int nb) {

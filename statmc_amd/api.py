@@ -75,6 +75,11 @@ class StatType(C.Structure):
     ]
 
 
+class CombineEntry(C.Structure):
+    """statmc_combine_entry: part A (dst, updated in place) and part B (src) of one set of statistics."""
+    _fields_ = [("dst", StatType), ("src", StatType), ("count_of", C.c_int32)]
+
+
 EXPORTS = [
     "statmc_last_error", "statmc_setup", "statmc_device_cus", "statmc_set_device", "statmc_set_significance", "statmc_get_significance", "statmc_set_t_quantiles",
     "statmc_set_filter_spec", "statmc_get_filter_spec", "statmc_reset_filter_spec", "statmc_pinned_from", "statmc_copy_device_settings",
@@ -83,7 +88,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -159,6 +164,7 @@ def load():
     lib.statmc_accumulate_row_ranges.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
     lib.statmc_accumulate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]
+    lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -496,6 +502,38 @@ def make_stat_type(samples, state, transform, max_moment, prepass_into=None):
     if prepass_into is not None:
         t.mean_corr, t.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
     return t
+
+
+def _state_side(state, channels, max_moment, own_counts):
+    t = StatType()
+    t.channels, t.max_moment = int(channels), int(max_moment)
+    ptr = lambda k: state[k].data_ptr() if state.get(k) is not None else None
+    t.n = ptr("n") if own_counts else None
+    t.mean, t.m2, t.m3 = ptr("mean"), ptr("m2"), ptr("m3")
+    t.film_mean, t.film_m2 = ptr("film_mean"), ptr("film_m2")
+    return t
+
+
+def make_combine_entry(dst, src, channels, max_moment, count_of=-1, prepass_into=None):
+    """One statmc_combine_entry: dst / src are state dicts of device tensors (n, mean, m2, m3, film_mean, film_m2; a missing
+    or None entry is not passed).  count_of = k >= 0: weigh with entry k's counts as they were before the call (dst / src
+    "n" are not passed then).  prepass_into = (mean_corr, discriminator): the call's epilogue writes the pre-pass of the
+    combined moments there (max_moment 3, own counts)."""
+    e = CombineEntry()
+    own = count_of < 0
+    e.dst = _state_side(dst, channels, max_moment, own)
+    e.src = _state_side(src, channels, max_moment, own)
+    e.count_of = -1 if own else int(count_of)
+    if prepass_into is not None:
+        e.dst.mean_corr, e.dst.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
+    return e
+
+
+def combine_statistics(width, height, entries, stream=None):
+    """statmc_combine_statistics: every entry's src statistics into its dst, in one launch (include/statmc.h)."""
+    arr = (CombineEntry * max(len(entries), 1))(*entries)
+    check(load().statmc_combine_statistics(int(width), int(height), arr, len(entries),
+                                           stream if stream is not None else current_stream_handle()))
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):

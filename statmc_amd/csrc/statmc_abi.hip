@@ -324,7 +324,7 @@ extern "C" {
 
 const char *statmc_last_error(void) { return g_err; }
 const char *statmc_last_filter_variant(void) { return g_variant; }
-int statmc_version(void) { return 100; }
+int statmc_version(void) { return 101; }
 
 int statmc_setup(int device) {
     int count = 0;
@@ -1343,6 +1343,103 @@ int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_s
     for (int i = 0; i < k.n_types && k.apart; i++)
         k.apart = statmc::placement_role_of(k.t[i].samples) == STATMC_MEM_STREAM && statmc::placement_role_of(k.t[i].mean) == STATMC_MEM_STATE;
     HIP_TRY(statmc::launch_accumulate(k, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_combine_statistics: validation (include/statmc.h) and the entry order of the launch -- entries that borrow counts
+// first, so that they read their owner's counts before the owner's lane writes n = nA + nB
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // NULL: an absent plane
+
+static int fill_combine_entry(const DeviceState &ds, const statmc_combine_entry *entries, int n_entries, int i,
+                              statmc::CombineEntry &k) {
+    const statmc_combine_entry &e = entries[i];
+    const statmc_stat_type &d = e.dst, &s = e.src;
+    if (d.channels != 1 && d.channels != 3) return fail(STATMC_ERR_INVALID, "entries[%d]: channels must be 1 or 3", i);
+    if (d.max_moment < 1 || d.max_moment > 3) return fail(STATMC_ERR_INVALID, "entries[%d]: max_moment must be 1..3", i);
+    if (s.channels != d.channels || s.max_moment != d.max_moment)
+        return fail(STATMC_ERR_INVALID, "entries[%d]: dst and src disagree on channels or max_moment", i);
+    if (e.count_of == -1) {
+        if (!d.n || !s.n) return fail(STATMC_ERR_INVALID, "entries[%d]: null n (count_of = -1: the entry's own counts)", i);
+        if (d.n == s.n) return fail(STATMC_ERR_INVALID, "entries[%d]: dst.n is src.n", i);
+        for (int j = 0; j < i; j++)
+            if (entries[j].count_of == -1 && entries[j].dst.n == d.n)
+                return fail(STATMC_ERR_INVALID, "entries[%d] and [%d] own the same count image", j, i);
+    } else if (e.count_of < 0 || e.count_of >= n_entries || e.count_of == i || entries[e.count_of].count_of != -1) {
+        return fail(STATMC_ERR_INVALID, "entries[%d]: bad count_of %d (-1, or an entry with counts of its own)", i, e.count_of);
+    } else if (d.n || s.n) {
+        return fail(STATMC_ERR_INVALID, "entries[%d]: borrows entry %d's counts, dst.n and src.n must be NULL", i, e.count_of);
+    }
+    const float *dp[statmc::kCombFields] = {d.mean, d.max_moment >= 2 ? d.m2 : nullptr, d.max_moment >= 3 ? d.m3 : nullptr,
+                                            nullptr, nullptr};
+    const float *sp[statmc::kCombFields] = {s.mean, s.max_moment >= 2 ? s.m2 : nullptr, s.max_moment >= 3 ? s.m3 : nullptr,
+                                            nullptr, nullptr};
+    static const char *names[statmc::kCombFields] = {"mean", "m2", "m3", "film_mean", "film_m2"};
+    // the raw-sample chain: film images of their own only (aliased ones are the moments, combined once)
+    const bool film_mean = d.film_mean && d.film_mean != d.mean;
+    const bool film_m2 = d.film_m2 && d.film_m2 != d.m2;
+    if (film_m2 && !film_mean) return fail(STATMC_ERR_INVALID, "entries[%d]: film_m2 without a film_mean of its own", i);
+    if (film_mean) {
+        dp[statmc::kCombFilmMean] = d.film_mean;
+        sp[statmc::kCombFilmMean] = s.film_mean;
+    }
+    if (film_m2) {
+        dp[statmc::kCombFilmM2] = d.film_m2;
+        sp[statmc::kCombFilmM2] = s.film_m2;
+    }
+    const int want = d.max_moment;
+    for (int f = 0; f < statmc::kCombFields; f++) {
+        const bool needed = f < want || (f == statmc::kCombFilmMean && film_mean) || (f == statmc::kCombFilmM2 && film_m2);
+        if (!needed) continue;
+        if (!dp[f] || !sp[f]) return fail(STATMC_ERR_INVALID, "entries[%d]: null %s", i, names[f]);
+        if (dp[f] == sp[f]) return fail(STATMC_ERR_INVALID, "entries[%d]: dst.%s is src.%s", i, names[f], names[f]);
+    }
+    k.cnt_dst = e.count_of == -1 ? d.n : entries[e.count_of].dst.n;
+    k.cnt_src = e.count_of == -1 ? s.n : entries[e.count_of].src.n;
+    k.write_n = e.count_of == -1;
+    for (int f = 0; f < statmc::kCombFields; f++) {
+        k.d[f] = const_cast<float *>(dp[f]);
+        k.s[f] = sp[f];
+    }
+    k.channels = d.channels;
+    k.mean_corr = nullptr;
+    k.disc = nullptr;
+    k.pre_table = 0;
+    k.pre_flags = 0;
+    if (d.mean_corr || d.discriminator) {
+        if (!d.mean_corr || !d.discriminator) return fail(STATMC_ERR_INVALID, "entries[%d]: mean_corr and discriminator come together", i);
+        if (d.max_moment < 3) return fail(STATMC_ERR_INVALID, "entries[%d]: the pre-pass epilogue needs max_moment 3", i);
+        if (e.count_of != -1) return fail(STATMC_ERR_INVALID, "entries[%d]: the pre-pass epilogue needs counts of the entry's own", i);
+        k.mean_corr = d.mean_corr;
+        k.disc = d.discriminator;
+        k.pre_table = prepass_table(ds);   // as statmc_prepass (prepass_impl) and the accumulation's epilogue (fill_stat_type)
+        k.pre_flags = (ds.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (ds.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0);
+    }
+    return STATMC_OK;
+}
+
+int statmc_combine_statistics(uint16_t width, uint16_t height, const statmc_combine_entry *entries, int n_entries, void *stream) {
+    NEED_READY();
+    if (n_entries < 0 || n_entries > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_entries must be in [0,%d]", statmc::kMaxStatTypes);
+    if (n_entries == 0) return STATMC_OK;
+    if (!entries) return fail(STATMC_ERR_INVALID, "null entries");
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    statmc::CombineArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_px = (long long)width * height;
+    int slot = 0;
+    for (int pass = 0; pass < 2; pass++)   // borrowing entries, then the count owners
+        for (int i = 0; i < n_entries; i++)
+            if ((entries[i].count_of != -1) == (pass == 0))
+                if (int rc = fill_combine_entry(dstate, entries, n_entries, i, k.e[slot++])) return rc;
+    k.n_entries = slot;
+    k.vec = 1;
+    for (int i = 0; i < k.n_entries; i++) {
+        const statmc::CombineEntry &e = k.e[i];
+        k.vec &= aligned16(e.cnt_dst) && aligned16(e.cnt_src) && aligned16(e.mean_corr) && aligned16(e.disc);
+        for (int f = 0; f < statmc::kCombFields; f++) k.vec &= aligned16(e.d[f]) && aligned16(e.s[f]);
+    }
+    HIP_TRY(statmc::launch_combine(k, S(stream)));
     return STATMC_OK;
 }
 

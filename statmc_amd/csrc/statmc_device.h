@@ -75,6 +75,26 @@ struct AccumulateTilesArgs {
     int dma_first;                   // A/B (statmc_debug_accumulate_launch): the first rows of the LDS-DMA ring requested before the state loads
 };
 
+// statmc_combine_statistics: one entry per pair of states.  The counts are read from cnt_dst / cnt_src: the entry's own
+// count images, or those of the entry it borrows them from.  The ABI puts borrowing entries first, so that they read the
+// counts before their owner (later in the same lane) writes n = nA + nB.
+enum { kCombMean = 0, kCombM2, kCombM3, kCombFilmMean, kCombFilmM2, kCombFields };
+struct CombineEntry {
+    int32_t *cnt_dst;
+    const int32_t *cnt_src;
+    float *d[kCombFields];           // dst planes (NULL: not combined)
+    const float *s[kCombFields];     // the matching src planes
+    float *mean_corr, *disc;         // optional pre-pass epilogue (own counts, max_moment 3)
+    int channels, write_n, pre_table, pre_flags;
+};
+struct CombineArgs {
+    CombineEntry e[kMaxStatTypes];
+    int n_entries;
+    int vec;                         // every plane 16-byte aligned: whole 4-pixel groups move as dwordx4
+    long long n_px;
+};
+hipError_t launch_combine(const CombineArgs &a, hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

@@ -1088,4 +1088,186 @@ hipError_t launch_tile_moments(const TileMomentsArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ combine
+// Two independently accumulated states of the same pixels -> the state of the union of their samples (Chan et al. 1979,
+// Pebay 2008); part A is dst, part B src.  The fp32 operation order, per element, is the one stated in include/statmc.h
+// (statmc_combine_statistics).  One lane owns 4 consecutive pixels, as in the accumulation, and runs every entry of the
+// call over them in entry order: the ABI puts the entries that borrow counts first, so they read the counts before the
+// owning entry -- later in the same lane -- writes n = nA + nB.  HBM-bound: C float4 per plane and one int4 of counts per
+// lane when every plane is 16-byte aligned (the last, partial group and unaligned planes take the scalar path).
+template <int C, bool VEC>
+__device__ __forceinline__ void comb_load(const float *p, long long px0, int npx, float (&v)[4 * C]) {
+    if (VEC) {
+#pragma unroll
+        for (int k = 0; k < C; k++) {
+            const float4 x = reinterpret_cast<const float4 *>(p + px0 * C)[k];
+            v[4 * k] = x.x;
+            v[4 * k + 1] = x.y;
+            v[4 * k + 2] = x.z;
+            v[4 * k + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4 * C; j++) v[j] = j < npx * C ? p[px0 * C + j] : 0.f;
+    }
+}
+template <int C, bool VEC>
+__device__ __forceinline__ void comb_store(float *p, long long px0, int npx, const float (&v)[4 * C]) {
+    if (VEC) {
+#pragma unroll
+        for (int k = 0; k < C; k++)
+            reinterpret_cast<float4 *>(p + px0 * C)[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4 * C; j++)
+            if (j < npx * C) p[px0 * C + j] = v[j];
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void comb_load_n(const int32_t *p, long long px0, int npx, int (&v)[4]) {
+    if (VEC) {
+        const int4 x = *reinterpret_cast<const int4 *>(p + px0);
+        v[0] = x.x;
+        v[1] = x.y;
+        v[2] = x.z;
+        v[3] = x.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) v[j] = j < npx ? p[px0 + j] : 0;
+    }
+}
+
+// per pixel: nB == 0 keeps A's bits, otherwise nA == 0 takes B's, otherwise the formula
+__device__ __forceinline__ float comb_pick(int nA, int nB, float a, float b, float f) { return nB == 0 ? a : (nA == 0 ? b : f); }
+
+// mean (and m2) of one chain: the mean / m2 lines of the formula.  t, q and u (u only with WANT_U) are kept for m3.
+template <int C, bool VEC, bool M2, bool WANT_U>
+__device__ __forceinline__ void comb_chain(float *dm, const float *sm, float *dm2, const float *sm2, long long px0, int npx,
+                                           const int (&nA)[4], const int (&nB)[4], const float (&fA)[4], const float (&fB)[4],
+                                           const float (&nf)[4], const float (&r)[4], float (&mA)[4 * C], float (&m2A)[4 * C],
+                                           float (&m2B)[4 * C], float (&q)[4 * C], float (&t)[4 * C], float (&u)[4 * C]) {
+    float mB[4 * C];
+    comb_load<C, VEC>(dm, px0, npx, mA);
+    comb_load<C, VEC>(sm, px0, npx, mB);
+    if (M2) {
+        comb_load<C, VEC>(dm2, px0, npx, m2A);
+        comb_load<C, VEC>(sm2, px0, npx, m2B);
+    }
+#pragma unroll
+    for (int j = 0; j < 4 * C; j++) {
+        const int p = j / C;
+        const float d = mB[j] - mA[j];
+        t[j] = div_by_count(d * fB[p], nf[p], r[p]);   // delta nB / n
+        q[j] = d * fA[p];                              // delta nA
+        if (WANT_U) u[j] = div_by_count(d, nf[p], r[p]);   // delta / n
+        mA[j] = comb_pick(nA[p], nB[p], mA[j], mB[j], mA[j] + t[j]);
+    }
+    comb_store<C, VEC>(dm, px0, npx, mA);
+    if (M2) {
+        float o[4 * C];
+#pragma unroll
+        for (int j = 0; j < 4 * C; j++) {
+            const int p = j / C;
+            o[j] = comb_pick(nA[p], nB[p], m2A[j], m2B[j], (m2A[j] + m2B[j]) + q[j] * t[j]);
+        }
+        comb_store<C, VEC>(dm2, px0, npx, o);
+        if (!WANT_U) {   // no m3 to come: the combined m2 is what the caller keeps
+#pragma unroll
+            for (int j = 0; j < 4 * C; j++) m2A[j] = o[j];
+        }
+    }
+}
+
+template <int C, bool VEC>
+__device__ __forceinline__ void combine_entry(const CombineEntry &e, long long px0, int npx) {
+    int nA[4], nB[4];
+    comb_load_n<VEC>(e.cnt_dst, px0, npx, nA);
+    comb_load_n<VEC>(e.cnt_src, px0, npx, nB);
+    float fA[4], fB[4], nf[4], r[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        fA[p] = (float)nA[p];
+        fB[p] = (float)nB[p];
+        nf[p] = (float)(nA[p] + nB[p]);
+        r[p] = refined_rcp(nf[p]);
+    }
+    float mA[4 * C], m2A[4 * C], m2B[4 * C], q[4 * C], t[4 * C], u[4 * C];
+    if (e.d[kCombM3]) {
+        comb_chain<C, VEC, true, true>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, nA, nB, fA, fB, nf, r,
+                                       mA, m2A, m2B, q, t, u);
+        float m3A[4 * C], m3B[4 * C];
+        comb_load<C, VEC>(e.d[kCombM3], px0, npx, m3A);
+        comb_load<C, VEC>(e.s[kCombM3], px0, npx, m3B);
+#pragma unroll
+        for (int j = 0; j < 4 * C; j++) {
+            const int p = j / C;
+            const float f = ((m3A[j] + m3B[j]) + (q[j] * t[j]) * ((fA[p] - fB[p]) * u[j])) + (3.f * u[j]) * (fA[p] * m2B[j] - fB[p] * m2A[j]);
+            const float m2 = comb_pick(nA[p], nB[p], m2A[j], m2B[j], (m2A[j] + m2B[j]) + q[j] * t[j]);
+            m3A[j] = comb_pick(nA[p], nB[p], m3A[j], m3B[j], f);
+            m2A[j] = m2;
+        }
+        comb_store<C, VEC>(e.d[kCombM3], px0, npx, m3A);
+        if (e.mean_corr) {   // the pre-pass of the combined moments: prepass_kernel's prepass_elem, the same bits
+            float mc[4 * C], dc[4 * C];
+#pragma unroll
+            for (int j = 0; j < 4 * C; j++) {
+                const int p = j / C, ni = nA[p] + nB[p];
+                prepass_elem(ni, (e.pre_flags & 1) ? 1.f : t_quantile(e.pre_table, ni - 1), mA[j], m2A[j], m3A[j], mc[j], dc[j],
+                             (e.pre_flags & 2) != 0);
+            }
+            comb_store<C, VEC>(e.mean_corr, px0, npx, mc);
+            comb_store<C, VEC>(e.disc, px0, npx, dc);
+        }
+    } else if (e.d[kCombM2]) {
+        comb_chain<C, VEC, true, false>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, nA, nB, fA, fB, nf, r,
+                                        mA, m2A, m2B, q, t, u);
+    } else {
+        comb_chain<C, VEC, false, false>(e.d[kCombMean], e.s[kCombMean], nullptr, nullptr, px0, npx, nA, nB, fA, fB, nf, r, mA, m2A,
+                                         m2B, q, t, u);
+    }
+    if (e.d[kCombFilmM2])
+        comb_chain<C, VEC, true, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], e.d[kCombFilmM2], e.s[kCombFilmM2], px0, npx, nA, nB, fA,
+                                        fB, nf, r, mA, m2A, m2B, q, t, u);
+    else if (e.d[kCombFilmMean])
+        comb_chain<C, VEC, false, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], nullptr, nullptr, px0, npx, nA, nB, fA, fB, nf, r, mA,
+                                         m2A, m2B, q, t, u);
+    if (e.write_n) {
+        if (VEC) {
+            *reinterpret_cast<int4 *>(e.cnt_dst + px0) = make_int4(nA[0] + nB[0], nA[1] + nB[1], nA[2] + nB[2], nA[3] + nB[3]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+                if (p < npx) e.cnt_dst[px0 + p] = nA[p] + nB[p];
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void combine_stats_kernel(CombineArgs a) {
+    const long long n_groups = (a.n_px + 3) >> 2;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (long long)gridDim.x * kBlock) {
+        const long long px0 = g << 2;
+        const int npx = a.n_px - px0 < 4 ? (int)(a.n_px - px0) : 4;
+        for (int i = 0; i < a.n_entries; i++) {
+            const CombineEntry &e = a.e[i];
+            if (VEC && npx == 4) {
+                if (e.channels == 3) combine_entry<3, true>(e, px0, 4);
+                else combine_entry<1, true>(e, px0, 4);
+            } else {
+                if (e.channels == 3) combine_entry<3, false>(e, px0, npx);
+                else combine_entry<1, false>(e, px0, npx);
+            }
+        }
+    }
+}
+
+hipError_t launch_combine(const CombineArgs &a, hipStream_t s) {
+    const int grid = grid_for((a.n_px + 3) / 4);
+    if (a.vec)
+        hipLaunchKernelGGL(combine_stats_kernel<true>, dim3(grid), dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL(combine_stats_kernel<false>, dim3(grid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace statmc

@@ -76,6 +76,27 @@ class FilmStats:
         api.accumulate(self.width, self.height, sts, rows=rows)
         self._prepass_current = self._prepass_key() if fuse else None
 
+    def combine_(self, other):
+        """Combines the statistics of `other` -- the same film, its own samples -- into self, so that self holds the
+        statistics of the union of both sample sets (statmc_combine_statistics: one launch).  Every stat type is weighed
+        with its own counts; the colour image `film` with the radiance counts.  With fused_prepass the launch's epilogue
+        writes mean-corr / discriminator of the combined radiance moments (the bits of statmc_prepass)."""
+        if (other.width, other.height) != (self.width, self.height) or other.device != self.device:
+            raise ValueError("combine_: both films must have the same size and device")
+        if set(other.types) != set(self.types):
+            raise ValueError("combine_: both films must carry the same stat types (%s / %s)" % (self.types, other.types))
+        fuse = self.fused_prepass and "radiance" in self.types
+        entries = []
+        for t in self.types:
+            cfg = STAT_TYPES[t]
+            entries.append(api.make_combine_entry(self.state[t], other.state[t], cfg["channels"], cfg["max_moment"],
+                                                  prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None))
+        if "radiance" in self.types and self.film is not None and other.film is not None:
+            owner = self.types.index("radiance")
+            entries.append(api.make_combine_entry({"mean": self.film}, {"mean": other.film}, 3, 1, count_of=owner))
+        api.combine_statistics(self.width, self.height, entries)
+        self._prepass_current = self._prepass_key() if fuse else None
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

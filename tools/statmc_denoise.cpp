@@ -9,6 +9,7 @@
 //                  [--spec gate=sym|asym,channels=and|joint,sides=two|one,dof=pixel|welch,border=clip|clamp,small_n=accept|exclude]
 //                  [--grid GXxGY [--devices 0,1,..]]   the denoise pass over film blocks with a halo exchange (C++ only)
 //                  [--placed]                          device images from statmc_malloc_placed (statmc::usePlacedMemory())
+//                  [--combine S1[,S2,..] --output-stem O [--write-combined]]   dumps of independent renders, combined
 //   statmc_denoise --catalogue [--config denoise|acrr|smis|proden|ours] [--width W --height H]
 //
 // Per iteration it reads "<stem>-<spp>-film.pfm" and every "<stem>-<spp>-t<i>-b<j>-<suffix>.pfm"
@@ -22,6 +23,12 @@
 // StatMC) and the relative L2 error per channel is printed -- the check BASELINE's 1e-5 parity
 // bound is stated in.  --tquantiles loads whitespace-separated t quantiles for dof 1..n into the
 // selected significance slot (for users who have the reference's own tables).
+// --combine S1,S2,..: the dumps "<Sk>-<spp>-*" of renders of the same scene with other samples (pbrt --baseseed) are combined
+// with "<stem>-<spp>-*" on the device before the denoise pass (Estimator::CombineStatistics, a left fold); every stem must
+// carry the same set of buffer files.  Types without an n file (the G-buffer means of a for-ours dump) are weighed with
+// t0-b0-n; input mean-corr / discriminator dumps are not read (Denoise recomputes them).  The outputs go to
+// "<O>-<spp * (1 + k)>-<buffer>.pfm"; --write-combined also writes every combined statistics buffer that was read under the
+// same names: a dump `statmc_denoise --stem O --spp <total>` (or pbrt --denoise) reads like any other.
 #include <chrono>
 #include <memory>
 #include <cmath>
@@ -116,7 +123,8 @@ static StatPathParams shippedConfig(const std::string &name) {
 int main(int argc, char **argv) {
     try {
         std::string stem, sppList, output = "film-f", config = "denoise", compareStem, tqFile, specText, gridText, devicesText;
-        bool noWrite = false;
+        bool noWrite = false, writeCombined = false;
+        std::string combineText, outputStem;
         int forceParts = 0, bands = 0;
         std::string kernel, sweep, sweepSignificance = "0,1,2";
         int significance = 0;
@@ -154,9 +162,21 @@ int main(int argc, char **argv) {
             else if (a == "--parts") forceParts = std::stoi(next());
             else if (a == "--kernel") kernel = next();   // "general": window_filter_generic for every call (one arithmetic for every spec)
             else if (a == "--bands") bands = std::stoi(next());  // Upload / Denoise / Download as a pipeline of row bands (0 = automatic, 1 = off)
+            else if (a == "--combine") combineText = next();
+            else if (a == "--output-stem") outputStem = next();
+            else if (a == "--write-combined") writeCombined = true;
             else if (a == "--width") width = std::stoi(next());
             else if (a == "--height") height = std::stoi(next());
             else throw std::runtime_error("unknown option " + a);
+        }
+        const std::vector<std::string> combineStems = split(combineText);
+        if (!combineText.empty() && combineStems.empty()) throw std::runtime_error("--combine wants a list of stems");
+        if (!combineStems.empty()) {
+            if (outputStem.empty()) throw std::runtime_error("--combine needs --output-stem (where the combined results go)");
+            if (!gridText.empty()) throw std::runtime_error("--combine cannot be used with --grid (the combine runs on one device)");
+            if (!sweep.empty()) throw std::runtime_error("--combine cannot be used with --sweep");
+        } else if (!outputStem.empty() || writeCombined) {
+            throw std::runtime_error("--output-stem and --write-combined go with --combine");
         }
         if (configGiven) {
             StatPathParams c = shippedConfig(config);
@@ -207,7 +227,19 @@ int main(int argc, char **argv) {
         BufferRegistry reg(film);
         Estimator est(film, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr, params.smis, reg);
         est.AllocateBuffers(reg);
-        est.SetPipelineBands(bands);
+        // --combine: the combine sits between the uploads and Denoise, so the row-band pipeline is off
+        est.SetPipelineBands(combineStems.empty() ? bands : 1);
+        std::unique_ptr<Buffer> otherFilm;
+        std::unique_ptr<BufferRegistry> otherReg;
+        std::unique_ptr<Estimator> other;   // --combine: the dump of one other stem at a time
+        if (!combineStems.empty()) {
+            otherFilm.reset(new Buffer("film", HostImage(height, width, F32C3)));
+            otherReg.reset(new BufferRegistry(*otherFilm));
+            other.reset(new Estimator(*otherFilm, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr,
+                                      params.smis, *otherReg));
+            other->AllocateBuffers(*otherReg);
+            other->SetPipelineBands(1);
+        }
         std::cout << "pipeline bands: " << est.PipelineBands() << std::endl;
         std::vector<float> tq;
         if (!tqFile.empty()) {
@@ -255,26 +287,84 @@ int main(int argc, char **argv) {
             shards.reset(new FilmShards(est, std::stoi(gridText.substr(0, x)), std::stoi(gridText.substr(x + 1)), devs));
         }
 
-        auto iteration = [&](const std::string &spp, bool write) {
-            using clk = std::chrono::steady_clock;
-            auto t0 = clk::now();
-            const std::string prefix = stem + "-" + spp + "-";
-            if (fileExists(prefix + "film.pfm")) readInto(prefix + "film.pfm", est.filmBuffer);
+        // reads the buffers of one dump into `e`; returns the names of the buffers read.  Under --combine the statistics only:
+        // mean-corr / discriminator are results of the denoise pass, which recomputes them from the combined moments.
+        bool notedPrepassInputs = false;
+        auto readDump = [&](const std::string &prefix, Estimator &e) {
+            std::vector<std::string> names;
+            if (fileExists(prefix + "film.pfm")) {
+                readInto(prefix + "film.pfm", e.filmBuffer);
+                names.push_back("film");
+            }
             struct Slot { const char *suffix; std::vector<std::vector<Buffer>> *bufs; };
-            const Slot slots[] = {{"n", &est.nBuffers}, {"mean", &est.meanBuffers}, {"m2", &est.m2Buffers},
-                                  {"m3", &est.m3Buffers}, {"film-m2", &est.filmM2Buffers},
-                                  {"mean-corr", &est.meanCorrBuffers}, {"discriminator", &est.discriminatorBuffers},
-                                  {"film-mean", &est.filmBuffers}};
+            const Slot slots[] = {{"n", &e.nBuffers}, {"mean", &e.meanBuffers}, {"m2", &e.m2Buffers},
+                                  {"m3", &e.m3Buffers}, {"film-m2", &e.filmM2Buffers},
+                                  {"mean-corr", &e.meanCorrBuffers}, {"discriminator", &e.discriminatorBuffers},
+                                  {"film-mean", &e.filmBuffers}};
             for (const Slot &s : slots)
                 for (auto &perType : *s.bufs)
                     for (Buffer &b : perType) {
                         const std::string path = prefix + b.name + ".pfm";
-                        if (fileExists(path)) readInto(path, b);
+                        if (!fileExists(path)) continue;
+                        if (!combineStems.empty() && (s.bufs == &e.meanCorrBuffers || s.bufs == &e.discriminatorBuffers)) {
+                            if (!notedPrepassInputs)
+                                std::cout << "note: " << path << " and other mean-corr / discriminator dumps are not combined; "
+                                          << "the denoise pass recomputes them from the combined moments" << std::endl;
+                            notedPrepassInputs = true;
+                            continue;
+                        }
+                        readInto(path, b);
+                        names.push_back(b.name);
                     }
+            return names;
+        };
+        // --combine: the buffers the denoise pass uploads and every buffer read, on the device (on e's stream)
+        auto uploadAll = [&](Estimator &e, BufferRegistry &r, const std::vector<std::string> &names) {
+            std::vector<Buffer *> bufs(e.uploadBuffers.begin(), e.uploadBuffers.end());
+            for (const auto &name : names) {
+                Buffer *b = const_cast<Buffer *>(r.find(name));
+                if (b && std::find(bufs.begin(), bufs.end(), b) == bufs.end()) bufs.push_back(b);
+            }
+            for (Buffer *b : bufs) b->upload(e.stream);
+        };
+        std::vector<std::string> combinedNames;   // the statistics buffers the last iteration combined
+        auto iteration = [&](const std::string &spp, bool write) {
+            using clk = std::chrono::steady_clock;
+            auto t0 = clk::now();
+            const std::string prefix = stem + "-" + spp + "-";
+            std::string outPrefix = prefix;
+            combinedNames = readDump(prefix, est);
+            if (!combineStems.empty()) {
+                uploadAll(est, reg, combinedNames);
+                // a type whose counts are not in the dump (G-buffer means of a for-ours dump) is weighed with t0-b0-n
+                std::vector<unsigned char> borrow;
+                for (unsigned char i = 1; i < est.statTypeConfigs.nEnabled; i++)
+                    if (!est.nBuffers[i].empty() && !fileExists(prefix + est.nBuffers[i][0].name + ".pfm")) borrow.push_back(i);
+                // the buffer files every stem must carry: the ones of the first
+                std::vector<std::string> candidates{"film"};
+                for (const auto &r : reg.buffers) candidates.push_back(r.name);
+                for (const auto &s : combineStems) {
+                    const std::string op = s + "-" + spp + "-";
+                    for (const auto &name : candidates) {
+                        if (name.find("mean-corr") != std::string::npos || name.find("discriminator") != std::string::npos) continue;
+                        const bool mine = fileExists(prefix + name + ".pfm"), theirs = fileExists(op + name + ".pfm");
+                        if (mine != theirs)
+                            throw std::runtime_error("--combine: " + (mine ? op : prefix) + name + ".pfm is missing (" +
+                                                     (mine ? prefix : op) + name + ".pfm exists)");
+                    }
+                    readDump(op, *other);
+                    uploadAll(*other, *otherReg, combinedNames);
+                    est.CombineStatistics(*other, borrow);
+                    // the next stem's dump goes into the same host and device images
+                    est.Synchronize();
+                    other->Synchronize();
+                }
+                outPrefix = outputStem + "-" + std::to_string(std::stoll(spp) * (long long)(1 + combineStems.size())) + "-";
+            }
             auto t1 = clk::now();
             std::cout << "I/O time [ns]: " << std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() << std::endl;
             t0 = clk::now();
-            est.Upload();
+            if (combineStems.empty()) est.Upload();   // (--combine: uploaded and combined above)
             const auto tu = clk::now();
             if (shards) shards->Denoise();   // film blocks + halo exchange (statmc_halo_exchange), same result bit for bit
             else est.Denoise();
@@ -309,10 +399,28 @@ int main(int argc, char **argv) {
                 }
                 // compare first, and never write over the file a comparison reads (--compare with the dumps' own stem: the
                 // CUDA build's outputs sit next to its inputs, tools/pin_from_dumps.sh)
-                const std::string mine = prefix + name + ".pfm", other = compareStem + "-" + spp + "-" + name + ".pfm";
-                const bool comparing = !compareStem.empty() && fileExists(other);
-                if (comparing) compareImages(name, readPfm(other), width, height, host.channels(), pixels);
-                if (!noWrite && !(comparing && other == mine)) writePfm(mine, width, height, host.channels(), pixels);
+                const std::string mine = outPrefix + name + ".pfm", theirs = compareStem + "-" + spp + "-" + name + ".pfm";
+                const bool comparing = !compareStem.empty() && fileExists(theirs);
+                if (comparing) compareImages(name, readPfm(theirs), width, height, host.channels(), pixels);
+                if (!noWrite && !(comparing && theirs == mine)) writePfm(mine, width, height, host.channels(), pixels);
+            }
+            if (writeCombined && !noWrite) {   // the combined statistics: a dump of the union of the renders' samples
+                est.DownloadStatistics();
+                est.filmBuffer.download(est.stream);
+                est.Synchronize();
+                for (const auto &name : combinedNames) {
+                    const Buffer *b = reg.find(name);
+                    if (!b) throw std::runtime_error("no buffer named " + name);
+                    const HostImage &host = b->mat;
+                    std::vector<float> tmp;
+                    const float *pixels = host.type == I32C1 ? nullptr : host.ptr<float>();
+                    if (host.type == I32C1) {
+                        tmp.resize((size_t)width * height);
+                        for (size_t i = 0; i < tmp.size(); i++) tmp[i] = (float)host.ptr<int32_t>()[i];
+                        pixels = tmp.data();
+                    }
+                    writePfm(outPrefix + name + ".pfm", width, height, host.channels(), pixels);
+                }
             }
         };
         for (const auto &run : runs) {

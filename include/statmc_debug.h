@@ -29,15 +29,13 @@ int statmc_debug_last_filter_tail(int *parts_hi, int *tail_rows);
 int statmc_debug_accumulate_resident_blocks(int n);
 /* Workgroups of the calling thread's last statmc_accumulate launch (which launch shape the sizes chose: DESIGN.md 4.1). */
 int statmc_debug_last_accumulate_grid(void);
-/* 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers (same bits). */
+/* 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers (same bits).  Any other value:
+ * STATMC_ERR_INVALID. */
 int statmc_debug_accumulate_dma(int on);
 /* Film-major launch shape: grid_mode -1 = chosen by the batch length (default); 1 = one pass per workgroup, stat types
  * round-robin; 0 = capped grid with slots per type and a grid-stride walk.  dma_first 1 = the first rows of the LDS-DMA
  * ring are requested before the state loads (A/B; default 0). */
 int statmc_debug_accumulate_launch(int grid_mode, int dma_first);
-/* Experiment builds (-DSTATMC_ACC_OCC_AB=1): 3 = the film-major kernel compiled for three waves per SIMD (168 VGPRs; default 2
- * waves, 202 VGPRs).  Other builds ignore it. */
-int statmc_debug_accumulate_occupancy(int waves_per_simd);
 /* 2: the mean-only feature types of the film-major kernel prefetch twice as deep (default 1). */
 int statmc_debug_accumulate_umul(int umul);
 /* Tile-fed accumulation: prefetch depth of the mean-only types (1 | 2, default 2), item order, workgroups per CU. */
@@ -54,14 +52,11 @@ int statmc_debug_placement_role(const void *ptr);
  * itself (0 = unknown): what its class thresholds are multiples of.  Pure arithmetic, no device call (tests/test_abi_cpu.py). */
 float statmc_debug_placement_fast_level(const float *probes_ms, int n, float self_ms);
 
-/* Non-zero: the library was built with a timing-only / diagnostic switch (statmc_sym_experiments.h); its results are
- * not the product's and statmc_amd.api refuses to load it. */
-int statmc_debug_diagnostic_build(void);
 /* Welch degrees of freedom on the pair-symmetric kernel: the number of work items of the calling thread's last launch
  * that left their band of the quantile table and were computed again from the table in global memory (0 for a film of
  * uniform sample count; -1: the last pair-symmetric launch was not a Welch one).  Waits for the device. */
 int statmc_debug_welch_far_items(void);
-/* Largest filter workspace of the current device (diagnostic builds read their counters back from it). */
+/* Largest filter workspace of the current device (bench.py reports where it lives). */
 int statmc_debug_last_workspace(void **ptr, size_t *bytes);
 
 #ifdef __cplusplus

@@ -40,7 +40,6 @@ struct DeviceState {
     // device's dispatch does not reach a second Estimator on another device
     int force_variant = 0;                                    // statmc_debug_force_filter_variant
     int acc_resident_blocks = 0, acc_umul = 1, acc_dma = 1;   // film-major accumulation
-    int acc_occ = 0;                                          // experiment builds: 3 = the accumulate kernel compiled for three waves per SIMD
     int acc_grid_mode = -1, acc_dma_first = 0;                // launch shape: -1 automatic (by batch length), 0 capped grid, 1 one pass per workgroup; A/B: ring rows requested before the state
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
@@ -1337,7 +1336,7 @@ int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_s
     k.dma = dstate.acc_dma;
     k.grid_mode = dstate.acc_grid_mode;
     k.dma_first = dstate.acc_dma_first;
-    k.occ = dstate.acc_occ;
+    k.occ = 0;   // (unused)
     // every type's samples in a STREAM block and its moments in a STATE block of the placed allocator: apart by construction
     k.apart = 1;
     for (int i = 0; i < k.n_types && k.apart; i++)
@@ -1565,11 +1564,9 @@ int statmc_debug_accumulate_resident_blocks(int n) {  // 0 by shape (default), n
     STATMC_DEBUG_SET(d.acc_resident_blocks = n < 0 ? -1 : n);
 }
 int statmc_debug_last_accumulate_grid(void) { return (int)statmc::last_accumulate_grid(); }
-int statmc_debug_accumulate_dma(int on) {   // 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers; 3 .. 6: that ring depth (experiment builds)
-    STATMC_DEBUG_SET(d.acc_dma = on < 0 ? 1 : on > 6 ? 6 : on == 2 ? 1 : on);
-}
-int statmc_debug_accumulate_occupancy(int waves_per_simd) {   // experiment builds (-DSTATMC_ACC_OCC_AB=1): 3 = the 168-VGPR build
-    STATMC_DEBUG_SET(d.acc_occ = waves_per_simd == 3 ? 3 : 0);
+int statmc_debug_accumulate_dma(int on) {   // 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers
+    if (on != 0 && on != 1) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_dma(%d): 0 or 1", on);
+    STATMC_DEBUG_SET(d.acc_dma = on);
 }
 int statmc_debug_accumulate_launch(int grid_mode, int dma_first) {   // A/B of the film-major launch shape (round 4)
     STATMC_DEBUG_SET(d.acc_grid_mode = grid_mode < 0 ? -1 : grid_mode == 1 ? 1 : 0; d.acc_dma_first = dma_first ? 1 : 0);
@@ -1581,8 +1578,6 @@ int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu) { 
     STATMC_DEBUG_SET(d.tiles_umul = umul == 2 ? 2 : 1; d.tiles_order = order < 0 || order > 2 ? 0 : order; d.tiles_wg_per_cu = wg_per_cu < 0 ? 0 : wg_per_cu);
 }
 int statmc_debug_force_filter_parts(int k) { return statmc_set_filter_split(k < 0 ? 0 : k); }   // the older name of the pin
-// non-zero: the library was built with an experiment switch of statmc_sym_experiments.h (never the product build)
-int statmc_debug_diagnostic_build(void) { return statmc::sym_diagnostic_bits() | statmc::acc_diagnostic_bits(); }
 int statmc_debug_last_filter_parts(void) { return g_last_parts; }
 // the tail split of the calling thread's last pair-symmetric launch: parts of the last `*tail_rows` tile rows (0: uniform)
 int statmc_debug_last_filter_tail(int *parts_hi, int *tail_rows) {
@@ -1602,7 +1597,7 @@ int statmc_debug_welch_far_items(void) {
     for (int v : f) n += v != 0;
     return n;
 }
-// the partial-sum / patch workspace of the calling thread's current device and stream 0 (diagnostic builds read it back)
+// the partial-sum / patch workspace of the calling thread's current device and stream 0 (bench.py reports where it lives)
 int statmc_debug_last_workspace(void **ptr, size_t *bytes) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));

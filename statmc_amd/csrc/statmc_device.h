@@ -52,7 +52,7 @@ struct AccumulateArgs {
     int dma;              // RGB sample planes arrive by LDS-DMA (default 1; 0: loads into registers, A/B)
     int grid_mode;        // -1: by batch length (default); 0: capped grid, slots per type in proportion to cost, grid-stride; 1: one pass per workgroup, types round-robin
     int dma_first;        // the first rows of the LDS-DMA ring are requested before the state loads
-    int occ;              // experiment builds (STATMC_ACC_OCC_AB): 3 = the build for three waves per SIMD
+    int occ;              // unused: kept so that the fields behind it keep their kernel-argument offsets
     int apart;            // 1: samples and moments are known to lie in different interference classes (statmc_malloc_placed blocks)
     // large grid: workgroup b serves slot b % n_slots; slots are dealt to types in proportion to cost
     int n_slots;
@@ -247,8 +247,6 @@ void sym_apply_split(FilterArgs &a);                        // n_lo_tiles / n_lo
 long long sym_items(const FilterArgs &a);
 size_t sym_patch_floats(const FilterArgs &a, int n_parts);
 hipError_t launch_sym(FilterArgs a, hipStream_t s);
-int sym_diagnostic_bits();   // non-zero: built with a STATMC_SYM_* experiment switch (statmc_sym_experiments.h)
-int acc_diagnostic_bits();   // non-zero: the accumulation was built with a timing-only switch (STATMC_ACC_SKIP_STORES: bit 7)
 hipError_t launch_border_virtual(const FilterArgs &a, hipStream_t s);   // the clamped border's taps beyond the image (RGB)
 int choose_parts(int tiles, int n_rows, int n_cus);
 // statmc_placement.hip (device memory placed by HBM rank)

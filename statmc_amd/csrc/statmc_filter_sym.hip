@@ -64,19 +64,9 @@
 #include "statmc_device.h"
 #include "statmc_filter_common.h"
 
-#include "statmc_sym_experiments.h"   // the STATMC_SYM_* diagnostic / experiment switches: all zero in the product build
-
 namespace statmc {
 namespace sym {
 
-constexpr int kHkAtEndForced = STATMC_SYM_HK_END;   // -1: per build (hk_at_end below); 0 / 1: every build (A/B)
-constexpr bool kStamps = STATMC_SYM_STAMPS;    // diagnostic: per-wave clock sums per step (tools/experiments/stamps_sym.py)
-constexpr bool kPipe = STATMC_SYM_PIPE;        // experiment: hand-placed LDS reads one phase ahead of the arithmetic
-constexpr int kPrio = STATMC_SYM_PRIO;         // experiment (s_setprio)
-constexpr int kSplit = STATMC_SYM_SPLIT;       // window half 0 sweeps dx <= kSplit, half 1 the rest
-constexpr int kGSplitForced = STATMC_SYM_GSPLIT;    // -1: per build (gsplit_of below); 0: the window split at dx = kSplit (rounds 2 - 5); G > 0: every build
-constexpr bool kGroupSplitRT = STATMC_SYM_GSPLIT_RT != 0;   // the runtime-radius builds: split at a read-group boundary too
-constexpr int kAblate = STATMC_SYM_ABLATE;     // timing only: 1 no q side, 2 no row staging, 4 no flush, 8 no sweep arithmetic, 16 no barrier
 // membership / buffer mode of a launch: one RGB buffer, every channel passes (default spec) | two float buffers
 // (filter<float>) | one RGB buffer, channels pooled (STATMC_CHANNELS_JOINT: sum_c fma(d_c, d_c, -(D_p,c + D_q,c)) <= 0,
 // as symmetric in (p, q) as the default test)
@@ -124,11 +114,10 @@ constexpr bool mode_pair(int m) { return m == 1 /* kModePair */ || m == kModeWel
 // exactly two RGB images -- the shipped normal + albedo -- runs a six-plane build whether it filters the whole film or a 15-channel block +
 // halo image, so those calls may have a G of their own: 7 under the default and the pooled test (G7 builds; 1.603 - 1.611 against 1.641 -
 // 1.650 ms in the step at 1080p, three A/B pairs, profiles/r06_ab_g7_step.log).  Every other set keeps 6 in every build.
-constexpr int gsplit_of(int, int, bool g7 = false) { return kGSplitForced >= 0 ? kGSplitForced : g7 ? 7 : 6; }
-constexpr bool hk_at_end(int mode, int ng) {
-    if (kHkAtEndForced >= 0) return kHkAtEndForced != 0;
-    return ng == 6 && !mode_pair(mode);
-}
+// (G itself, 1080p RGB, back to back, one box: 1.440 ms with the dx = 0 split | G = 5 1.42 | 6 1.383 | 7 1.340 | 8 1.442;
+// profiles/r06_ab*.log.)
+constexpr int gsplit_of(bool g7) { return g7 ? 7 : 6; }
+constexpr bool hk_at_end(int mode, int ng) { return ng == 6 && !mode_pair(mode); }
 constexpr int kR = 20;
 constexpr int kPx = 4;                    // pixels per lane
 constexpr int kW = 32 * kPx;              // 128 tile columns: half a wave per row
@@ -147,7 +136,7 @@ constexpr int kPatchP = kRows * kW;       // float4 per patch: p-side piece
 // of a row, five RGB images (or one 15-float AoS image) = 165 / 150 pieces of 16 B per wave and row, landing in a
 // wave-private raw area.  Half 0 because its waves are the older ones of every SIMD pair: they win the issue
 // arbitration, finish their sweep first and would otherwise idle at the barrier; while they wait for their fetches
-// and LDS reads the half-1 wave of the SIMD sweeps (tools/experiments/stamps_sym.py).
+// and LDS reads the half-1 wave of the SIMD sweeps (per-wave clocks, HISTORY.md 4.3).
 constexpr int kWaveCols = 44;
 __host__ __device__ inline int wave_col0(int wave) { return wave < 2 ? 44 * wave : 88 + 40 * (wave - 2); }
 __host__ __device__ inline int wave_cols(int wave) { return wave < 2 ? 44 : wave < 4 ? 40 : 0; }
@@ -199,9 +188,6 @@ struct Lane : std::conditional<W, LaneWelch, LaneNoWelch>::type {
     v2f pc[kPx][2];    // colour (r, g), (b, -)
     v2f acc[kPx][3];   // .x even taps, .y odd taps of every read group
     v2f sw[kPx];
-#if STATMC_SYM_COUNT
-    unsigned n_groups = 0, n_empty = 0, n_empty_halves = 0;
-#endif
 };
 // The three packed instructions that take a broadcast half of a pair, spelled out: written as shuffles the
 // broadcasts are loop-invariant, get hoisted out of the sweep and come back as (x, x) register pairs of their own.
@@ -343,16 +329,11 @@ __device__ __forceinline__ void gate_weight(LaneT &st, const v4f *mcn, const v4f
                 const v2f sn = rsub_bc(pair_of<H>(mcn[3 + ch]), st.ms[k][ch], 1);      // -(v_p + v_q)
                 const v2f den = add_bc(st.pe[k][ch >> 1], ch & 1, pair_of<H>(en[ch]));   // E_p + E_q
                 const v2f s2 = sn * sn;
-                v2f nu;
-                if constexpr ((STATMC_SYM_WELCH_ABLATE & 4) != 0) {   // timing only
-                    nu = s2 + den;
-                } else {
-                    const v2f r = v2f{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-                    const v2f p = s2 * r;
-                    const v2f q0 = v2f{min_finite(p.x), min_finite(p.y)};
-                    const v2f er = __builtin_elementwise_fma(-q0, den, s2);
-                    nu = __builtin_elementwise_fma(er, r, q0);
-                }
+                const v2f r = v2f{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+                const v2f p = s2 * r;
+                const v2f q0 = v2f{min_finite(p.x), min_finite(p.y)};
+                const v2f er = __builtin_elementwise_fma(-q0, den, s2);
+                const v2f nu = __builtin_elementwise_fma(er, r, q0);
                 // v_cvt_u32_f32 truncates, sends a NaN and everything below 1 to 0 and saturates above (spelled out: the C++
                 // conversion of such values is undefined); entry 0 of the table is entry 1, which finishes the oracle's
                 // `nu >= 1 ? min((int)nu, 4096) : 1` but for the upper clamp -- that is in the band's fill
@@ -360,8 +341,6 @@ __device__ __forceinline__ void gate_weight(LaneT &st, const v4f *mcn, const v4f
                 dy[ch] = cvt_u32(nu.y);
                 if constexpr (mode_welch_far(MODE)) {
                     out[ch] = v2f{tq2.table[min(dx[ch], 4096u)], tq2.table[min(dy[ch], 4096u)]};
-                } else if constexpr ((STATMC_SYM_WELCH_ABLATE & 1) != 0) {   // timing only: no gather
-                    out[ch] = v2f{(float)dx[ch] * 1e-3f + 9.f, (float)dy[ch] * 1e-3f + 9.f};
                 } else {
                     // byte offset in the band: the table's upper clamp, one shift-and-add, one minimum.  A dof beyond the band's
                     // end reads its LAST entry (and flags the item, below: the far build computes it again from the whole
@@ -541,153 +520,52 @@ __device__ __forceinline__ void accumulate(LaneT &st, const v4f *col, const v2f 
     }
 }
 
-// LDS byte address of a pointer into the workgroup's shared array
-__device__ __forceinline__ unsigned lds_addr(const float *p) {
-    return (unsigned)(unsigned long long)(const __attribute__((address_space(3))) float *)p;
-}
-// ds_read_b128 placed by hand: the compiler sinks its own loads next to their first use, which leaves the LDS
-// latency of every phase exposed (a wave is mostly alone on its SIMD while it sweeps: the older wave of a pair wins
-// the issue arbitration, runs ahead and waits at the barrier -- tools/experiments/stamps_sym.py).  The register
-// is written when the data lands: every use sits behind an lds_wait that names it.
-template <int OFF>
-__device__ __forceinline__ v4f lds_read128(unsigned addr) {
-    v4f v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-// wait until at most N LDS operations issued after the named registers' loads are outstanding (in-order return)
-template <int N>
-__device__ __forceinline__ void lds_wait(v4f &a, v4f &b, v4f &c) {
-    asm volatile("s_waitcnt lgkmcnt(%3)" : "+v"(a), "+v"(b), "+v"(c) : "n"(N) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(v4f &a, v4f &b, v4f &c, v4f &d) {
-    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
-}
-
 // One read group (4 taps) against the lane's 4 pixels.  Every LDS operand is one ds_read_b128 of a channel plane
 // (consecutive lanes read consecutive 16 B: conflict-free); the group runs in three phases -- range exponents
 // (6 feature planes), gates and weights (6 statistics planes), accumulation (3 colour planes + the 4 accumulator
-// planes of the taps).  PIPE: the statistics planes are requested before the feature planes and the colour /
-// accumulator planes before the gates, by hand-placed reads, so that two of the three phases find their operands
-// in registers; otherwise the compiler's own loads (each phase waits for its operands).
-template <unsigned MASK, bool SYM, bool PIPE, int MODE, int NG, class LaneT>
+// planes of the taps), each behind the compiler's own loads of its operands.  (Hand-placed reads one phase ahead of
+// the arithmetic were slower: 1.57 ms against 1.43, HISTORY.md 4.3.)
+template <unsigned MASK, bool SYM, int MODE, int NG, class LaneT>
 __device__ __forceinline__ void chunk(LaneT &st, const float *__restrict__ row, const float *__restrict__ tab, float *__restrict__ qrow, int j,
                                       const WelchTab &tq2) {
     using M0 = Taps<0, MASK>;
     using M1 = Taps<1, MASK>;
     constexpr bool PAIR = mode_pair(MODE);
     constexpr bool W = mode_welch(MODE);
-    static_assert(!(W && PIPE), "the Welch modes use the compiler-placed reads");
     constexpr int C_MC = Planes<NG, W>::cMC, C_COL = Planes<NG, W>::cCOL;
     const float *r = row + 4 * j;
     v4f g[NG], mcn[6], col[3], q4[4], en[3];
     v2f e0[kPx], e1[kPx], w0[kPx], w1[kPx], wb0[kPx], wb1[kPx];   // wb*: second buffer's weights (PAIR)
-    unsigned ra = 0, qa = 0;
-    if constexpr ((kAblate & 32) != 0) {   // timing only: operands from nowhere (no LDS reads in the sweep)
-#pragma unroll
-        for (int ch = 0; ch < NG; ch++) asm volatile("" : "=v"(g[ch]));
-#pragma unroll
-        for (int ch = 0; ch < 6; ch++) asm volatile("" : "=v"(mcn[ch]));
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) asm volatile("" : "=v"(col[ch]));
-#pragma unroll
-        for (int v = 0; v < 4; v++) asm volatile("" : "=v"(q4[v]));
-        if constexpr (M0::any()) range_exponent<0, MASK, NG>(st, g, tab, j, e0);
-        if constexpr (M1::any()) range_exponent<1, MASK, NG>(st, g, tab, j, e1);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) asm volatile("" : "=v"(en[ch]));
-        if constexpr (M0::any()) gate_weight<0, MASK, MODE, NG>(st, mcn, en, tq2, e0, w0, wb0);
-        if constexpr (M1::any()) gate_weight<1, MASK, MODE, NG>(st, mcn, en, tq2, e1, w1, wb1);
-        v2f qa2[4], qb2[4];
-#pragma unroll
-        for (int v = 0; v < 4; v++) { qa2[v] = pair_of<0>(q4[v]); qb2[v] = pair_of<1>(q4[v]); }
-        if constexpr (M0::any()) accumulate<0, MASK, SYM, MODE, NG>(st, col, w0, wb0, qa2);
-        if constexpr (M1::any()) accumulate<1, MASK, SYM, MODE, NG>(st, col, w1, wb1, qb2);
-        if constexpr (SYM) {
-#pragma unroll
-            for (int v = 0; v < 4; v++) asm volatile("" ::"v"(qa2[v]), "v"(qb2[v]));
-        }
-        return;
-    }
-    if constexpr (PIPE) {
-        ra = lds_addr(r);
-        qa = lds_addr(qrow + 4 * j);
-        mcn[0] = lds_read128<(C_MC + 0) * kP * 4>(ra);
-        mcn[1] = lds_read128<(C_MC + 1) * kP * 4>(ra);
-        mcn[2] = lds_read128<(C_MC + 2) * kP * 4>(ra);
-        mcn[3] = lds_read128<(C_MC + 3) * kP * 4>(ra);
-        mcn[4] = lds_read128<(C_MC + 4) * kP * 4>(ra);
-        mcn[5] = lds_read128<(C_MC + 5) * kP * 4>(ra);
-    }
 #pragma unroll
     for (int ch = 0; ch < NG; ch++) g[ch] = *reinterpret_cast<const v4f *>(r + ch * kP);
     if constexpr (M0::any()) range_exponent<0, MASK, NG>(st, g, tab, j, e0);
     if constexpr (M1::any()) range_exponent<1, MASK, NG>(st, g, tab, j, e1);
-    if constexpr (PIPE) {
-        col[0] = lds_read128<(C_COL + 0) * kP * 4>(ra);
-        col[1] = lds_read128<(C_COL + 1) * kP * 4>(ra);
-        col[2] = lds_read128<(C_COL + 2) * kP * 4>(ra);
-        if constexpr (SYM) {
-            q4[0] = lds_read128<0 * kP * 4>(qa);
-            q4[1] = lds_read128<1 * kP * 4>(qa);
-            q4[2] = lds_read128<2 * kP * 4>(qa);
-            q4[3] = lds_read128<3 * kP * 4>(qa);
-        }
-        // the statistics planes were requested before the feature planes, which phase 1 has consumed
-        lds_wait<SYM ? 7 : 3>(mcn[0], mcn[1], mcn[2]);
-        lds_wait<SYM ? 7 : 3>(mcn[3], mcn[4], mcn[5]);
-    } else {
-        // (PAIR: the third channel's planes hold nothing and are not read)
+    // (PAIR: the third channel's planes hold nothing and are not read)
 #pragma unroll
-        for (int ch = 0; ch < 6; ch++)
-            if (!(PAIR && ch % 3 == 2)) mcn[ch] = *reinterpret_cast<const v4f *>(r + (C_MC + ch) * kP);
-        if constexpr (W && NG == 8) {
-            // eight feature planes: the ring holds n - 1 and the taps divide -- the oracle's own expression, Dp * Dp / ((float)n - 1.f),
-            // an IEEE division each (12 per read group; a reciprocal with a correction is a last bit off now and then, which
-            // moves nu across an integer exactly where one side's variance is 0).  A pixel that takes no part has -D = 0 and a
-            // NaN mean: whatever E comes out, its weight is 0.  PAIR: the second buffer's n - 1 sits in the (otherwise unread)
-            // third channel's mean plane.
-            const v4f nm1 = *reinterpret_cast<const v4f *>(r + Planes<NG, W>::cE * kP);
-            const v4f nm1b = PAIR ? *reinterpret_cast<const v4f *>(r + (C_MC + 2) * kP) : nm1;
-            en[0] = (mcn[3] * mcn[3]) / nm1;
-            en[1] = (mcn[4] * mcn[4]) / nm1b;
-            if constexpr (!PAIR) en[2] = (mcn[5] * mcn[5]) / nm1;
-        } else if constexpr (W) {
+    for (int ch = 0; ch < 6; ch++)
+        if (!(PAIR && ch % 3 == 2)) mcn[ch] = *reinterpret_cast<const v4f *>(r + (C_MC + ch) * kP);
+    if constexpr (W && NG == 8) {
+        // eight feature planes: the ring holds n - 1 and the taps divide -- the oracle's own expression, Dp * Dp / ((float)n - 1.f),
+        // an IEEE division each (12 per read group; a reciprocal with a correction is a last bit off now and then, which
+        // moves nu across an integer exactly where one side's variance is 0).  A pixel that takes no part has -D = 0 and a
+        // NaN mean: whatever E comes out, its weight is 0.  PAIR: the second buffer's n - 1 sits in the (otherwise unread)
+        // third channel's mean plane.
+        const v4f nm1 = *reinterpret_cast<const v4f *>(r + Planes<NG, W>::cE * kP);
+        const v4f nm1b = PAIR ? *reinterpret_cast<const v4f *>(r + (C_MC + 2) * kP) : nm1;
+        en[0] = (mcn[3] * mcn[3]) / nm1;
+        en[1] = (mcn[4] * mcn[4]) / nm1b;
+        if constexpr (!PAIR) en[2] = (mcn[5] * mcn[5]) / nm1;
+    } else if constexpr (W) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ch++) en[ch] = *reinterpret_cast<const v4f *>(r + (Planes<NG, W>::cE + ch) * kP);
-        }
+        for (int ch = 0; ch < 3; ch++) en[ch] = *reinterpret_cast<const v4f *>(r + (Planes<NG, W>::cE + ch) * kP);
     }
     if constexpr (M0::any()) gate_weight<0, MASK, MODE, NG>(st, mcn, en, tq2, e0, w0, wb0);
     if constexpr (M1::any()) gate_weight<1, MASK, MODE, NG>(st, mcn, en, tq2, e1, w1, wb1);
-#if STATMC_SYM_COUNT
-    if constexpr (MASK == 0xFFFFu && SYM && MODE == kModeRgb) {   // full read groups of the default mode
-        bool any0 = false, any1 = false;
 #pragma unroll
-        for (int k = 0; k < kPx; k++) {
-            any0 = any0 || w0[k].x != 0.f || w0[k].y != 0.f;
-            any1 = any1 || w1[k].x != 0.f || w1[k].y != 0.f;
-        }
-        const bool e0w = __builtin_amdgcn_ballot_w64(any0) == 0, e1w = __builtin_amdgcn_ballot_w64(any1) == 0;
-        st.n_groups++;
-        st.n_empty += (e0w && e1w) ? 1u : 0u;
-        st.n_empty_halves += (e0w ? 1u : 0u) + (e1w ? 1u : 0u);
-    }
-#endif
-    if constexpr (PIPE) {
-        // ... and the colour / accumulator planes before the gates; the wait names the weights too, so that it stays
-        // behind the arithmetic that produced them (plain arithmetic may otherwise be scheduled after the wait)
-        if constexpr (M0::any()) asm volatile("" : "+v"(w0[0]), "+v"(w0[1]), "+v"(w0[2]), "+v"(w0[3]));
-        if constexpr (M1::any()) asm volatile("" : "+v"(w1[0]), "+v"(w1[1]), "+v"(w1[2]), "+v"(w1[3]));
-        lds_wait<0>(col[0], col[1], col[2]);
-        if constexpr (SYM) lds_wait<0>(q4[0], q4[1], q4[2], q4[3]);
-    } else {
+    for (int ch = 0; ch < (PAIR ? 2 : 3); ch++) col[ch] = *reinterpret_cast<const v4f *>(r + (C_COL + ch) * kP);
+    if constexpr (SYM) {
 #pragma unroll
-        for (int ch = 0; ch < (PAIR ? 2 : 3); ch++) col[ch] = *reinterpret_cast<const v4f *>(r + (C_COL + ch) * kP);
-        if constexpr (SYM) {
-#pragma unroll
-            for (int v = 0; v < 4; v++) q4[v] = *reinterpret_cast<const v4f *>(qrow + 4 * j + v * kP);
-        }
+        for (int v = 0; v < 4; v++) q4[v] = *reinterpret_cast<const v4f *>(qrow + 4 * j + v * kP);
     }
     v2f qa2[4], qb2[4];
     if constexpr (SYM) {
@@ -697,14 +575,9 @@ __device__ __forceinline__ void chunk(LaneT &st, const float *__restrict__ row, 
     if constexpr (M0::any()) accumulate<0, MASK, SYM, MODE, NG>(st, col, w0, wb0, qa2);
     if constexpr (M1::any()) accumulate<1, MASK, SYM, MODE, NG>(st, col, w1, wb1, qb2);
     if constexpr (SYM) {
-        if constexpr ((kAblate & 64) != 0) {   // timing only: no write-back of the accumulators
 #pragma unroll
-            for (int v = 0; v < 4; v++) asm volatile("" ::"v"(qa2[v]), "v"(qb2[v]));
-        } else {
-#pragma unroll
-            for (int v = 0; v < 4; v++)
-                *reinterpret_cast<v4f *>(qrow + 4 * j + v * kP) = v4f{qa2[v].x, qa2[v].y, qb2[v].x, qb2[v].y};
-        }
+        for (int v = 0; v < 4; v++)
+            *reinterpret_cast<v4f *>(qrow + 4 * j + v * kP) = v4f{qa2[v].x, qa2[v].y, qb2[v].x, qb2[v].y};
     }
 }
 
@@ -738,67 +611,62 @@ __device__ __forceinline__ void sweep_range(LaneT &st, const float *row, const f
     constexpr bool has_full = f0 <= f1;
     constexpr int lo_end = has_full ? f0 : j1 + 1;      // masked groups j0 .. lo_end-1, full f0 .. f1, masked f1+1 .. j1
     static_assert(lo_end - j0 <= 2 && (!has_full || j1 - f1 <= 2), "more than two cut groups at an end");
-    if constexpr (j0 < lo_end) chunk<R::m(j0), SYM, kPipe && !mode_welch(MODE), MODE, NG>(st, row, tab, qrow, j0, tq2);
-    if constexpr (j0 + 1 < lo_end) chunk<R::m(j0 + 1), SYM, kPipe && !mode_welch(MODE), MODE, NG>(st, row, tab, qrow, j0 + 1, tq2);
+    if constexpr (j0 < lo_end) chunk<R::m(j0), SYM, MODE, NG>(st, row, tab, qrow, j0, tq2);
+    if constexpr (j0 + 1 < lo_end) chunk<R::m(j0 + 1), SYM, MODE, NG>(st, row, tab, qrow, j0 + 1, tq2);
     if constexpr (has_full) {
 #pragma unroll 1
-        for (int j = f0; j <= f1; j++) chunk<R::kFull, SYM, kPipe && !mode_welch(MODE), MODE, NG>(st, row, tab, qrow, j, tq2);
-        if constexpr (f1 + 1 <= j1) chunk<R::m(f1 + 1 <= j1 ? f1 + 1 : 0), SYM, kPipe && !mode_welch(MODE), MODE, NG>(st, row, tab, qrow, f1 + 1, tq2);
-        if constexpr (f1 + 2 <= j1) chunk<R::m(f1 + 2 <= j1 ? f1 + 2 : 0), SYM, kPipe && !mode_welch(MODE), MODE, NG>(st, row, tab, qrow, f1 + 2, tq2);
+        for (int j = f0; j <= f1; j++) chunk<R::kFull, SYM, MODE, NG>(st, row, tab, qrow, j, tq2);
+        if constexpr (f1 + 1 <= j1) chunk<R::m(f1 + 1 <= j1 ? f1 + 1 : 0), SYM, MODE, NG>(st, row, tab, qrow, f1 + 1, tq2);
+        if constexpr (f1 + 2 <= j1) chunk<R::m(f1 + 2 <= j1 ? f1 + 2 : 0), SYM, MODE, NG>(st, row, tab, qrow, f1 + 2, tq2);
     }
 }
 
-// Read groups [J0, J1] of one window row, whole (experiment kGSplit): the two end groups of the window carry their static masks
+// Read groups [J0, J1] of one window row, whole (the r = 20 split, gsplit_of): the two end groups of the window carry their static masks
 template <int J0, int J1, bool SYM, int MODE, int NG, class LaneT>
 __device__ __forceinline__ void sweep_groups(LaneT &st, const float *row, const float *tab, float *qrow, const WelchTab &tq2) {
     using R = Range<-kR, kR>;
-    constexpr bool pipe = kPipe && !mode_welch(MODE);
     constexpr int f0 = J0 == 0 ? 1 : J0, f1 = J1 == kChunks - 1 ? kChunks - 2 : J1;
     static_assert(R::m(1) == R::kFull && R::m(kChunks - 2) == R::kFull, "only the end groups are cut by the window");
-    if constexpr (J0 == 0) chunk<R::m(0), SYM, pipe, MODE, NG>(st, row, tab, qrow, 0, tq2);
+    if constexpr (J0 == 0) chunk<R::m(0), SYM, MODE, NG>(st, row, tab, qrow, 0, tq2);
 #pragma unroll 1
-    for (int j = f0; j <= f1; j++) chunk<R::kFull, SYM, pipe, MODE, NG>(st, row, tab, qrow, j, tq2);
-    if constexpr (J1 == kChunks - 1) chunk<R::m(kChunks - 1), SYM, pipe, MODE, NG>(st, row, tab, qrow, kChunks - 1, tq2);
+    for (int j = f0; j <= f1; j++) chunk<R::kFull, SYM, MODE, NG>(st, row, tab, qrow, j, tq2);
+    if constexpr (J1 == kChunks - 1) chunk<R::m(kChunks - 1), SYM, MODE, NG>(st, row, tab, qrow, kChunks - 1, tq2);
 }
 
-// The window columns of one window row, split between the two waves of a row at dx = kSplit: wave half 0 sweeps
-// dx in [-20, kSplit], half 1 dx in [kSplit + 1, 20], every pair feeding both its pixels.  kSplit = 0: the middle.
-// (The per-wave clocks -- tools/experiments/stamps_sym.py -- show the older wave of every SIMD pair finishing its
-// half well before the younger one and idling at the barrier, which suggests giving it more columns; measured, any
-// uneven split is slower: 1.43 ms at kSplit = 0; 1.46 at 4 and 1.48 at -4, which like 0 cut only one read group;
-// 1.56 at 7 and 1.75 at 11, which cut two.  The SIMD is busy either way.)
-// dy = 0: the pairs inside a row are the taps dx >= 1 (the accumulator row is the wave's own row); the pixel's own
-// tap dx = 0 feeds the p side only.
-// RT (runtime radius r < 20): the same staging geometry (20 halo columns) and the same split of the window at dx = 0; the
-// read groups a half sweeps are groups [j_lo, 4] + the cut group 5 (half 0) and the cut group 5 + groups [6, j_hi] (half 1),
+// The window columns of one window row, split between the two waves of a row at a read-group boundary: r = 20, half 0
+// sweeps the groups [0, G), half 1 the groups [G, 11), G = gsplit_of(G7), every pair feeding both its pixels.  (Rounds 2 - 5
+// split the window at dx = 0; splits by columns away from the middle were all slower -- 1.43 ms at dx = 0, 1.46 at 4 and
+// 1.48 at -4, 1.56 at 7 and 1.75 at 11, the last two cutting a second read group; HISTORY.md 4.3.)
+// dy = 0: the pairs inside a row are the taps dx >= 1, all with half 1 (the accumulator row is the wave's own row); the
+// pixel's own tap dx = 0 feeds the p side only, with half 0.
+// RT (runtime radius r < 20, and the Welch builds): the same staging geometry (20 halo columns); below nine read groups the
+// window is split at dx = 0 -- groups [j_lo, 4] + the cut group 5 (half 0) and the cut group 5 + groups [6, j_hi] (half 1),
 // where j_lo / j_hi are the outermost groups that hold a tap with |dx| <= r; taps of those groups beyond r carry a
 // spatial exponent of -inf in the table (weight 0).
 template <int HF, int MODE, int NG, bool RT, bool G7, class LaneT>
 __device__ __forceinline__ void eval_half_row(LaneT &st, const float *row, const float *tab, float *qrow, bool dy0, int j_lo, int j_hi, const WelchTab &tq2) {
-    constexpr bool kPipe = sym::kPipe && !mode_welch(MODE);
     if constexpr (RT) {
-        static_assert(kSplit == 0, "the runtime-radius build splits the window in the middle");
         // From nine read groups up (r >= 16), in every build (ONE rule for all of them: see gsplit_of): whole read groups
         // [j_lo, g) to half 0, [g, j_hi] to half 1, g = j_lo + 9/14 of the groups; taps beyond the radius carry -inf in the table, so
         // no group needs a mask.  1080p, r = 19: 1.436 ms with the middle split and the housekeeping first, 1.377 with it last, 1.322
         // with this share on top (a 6/11 share: 1.372); Welch r = 20 3.48 -> 3.39 (pooled 3.47 -> 3.30).  Below nine groups the middle
         // split is as good or better (r = 10 0.58 | 0.60 ms, Welch r = 6 0.70 | 0.72; profiles/r06_rt.log, r06_modes_product*.log).
-        if (kGroupSplitRT && j_hi - j_lo + 1 >= 9) {
+        if (j_hi - j_lo + 1 >= 9) {
             const int g = j_lo + ((j_hi - j_lo + 1) * 9 + 7) / 14;
             if (dy0) {
                 if constexpr (HF == 0) {
                     sweep_range<0, 0, false, MODE, NG>(st, row, tab, qrow, tq2);
                 } else {
-                    chunk<Range<1, kR>::m(kMid), true, kPipe, MODE, NG>(st, row, tab, qrow, kMid, tq2);
+                    chunk<Range<1, kR>::m(kMid), true, MODE, NG>(st, row, tab, qrow, kMid, tq2);
 #pragma unroll 1
-                    for (int j = kMid + 1; j <= j_hi; j++) chunk<0xFFFFu, true, kPipe, MODE, NG>(st, row, tab, qrow, j, tq2);
+                    for (int j = kMid + 1; j <= j_hi; j++) chunk<0xFFFFu, true, MODE, NG>(st, row, tab, qrow, j, tq2);
                 }
             } else if constexpr (HF == 0) {
 #pragma unroll 1
-                for (int j = j_lo; j < g; j++) chunk<0xFFFFu, true, kPipe, MODE, NG>(st, row, tab, qrow, j, tq2);
+                for (int j = j_lo; j < g; j++) chunk<0xFFFFu, true, MODE, NG>(st, row, tab, qrow, j, tq2);
             } else {
 #pragma unroll 1
-                for (int j = g; j <= j_hi; j++) chunk<0xFFFFu, true, kPipe, MODE, NG>(st, row, tab, qrow, j, tq2);
+                for (int j = g; j <= j_hi; j++) chunk<0xFFFFu, true, MODE, NG>(st, row, tab, qrow, j, tq2);
             }
             return;
         }
@@ -807,42 +675,24 @@ __device__ __forceinline__ void eval_half_row(LaneT &st, const float *row, const
                 sweep_range<0, 0, false, MODE, NG>(st, row, tab, qrow, tq2);
             } else {
 #pragma unroll 1
-                for (int j = j_lo; j < kMid; j++) chunk<0xFFFFu, true, kPipe, MODE, NG>(st, row, tab, qrow, j, tq2);
-                chunk<Range<-kR, 0>::m(kMid), true, kPipe, MODE, NG>(st, row, tab, qrow, kMid, tq2);
+                for (int j = j_lo; j < kMid; j++) chunk<0xFFFFu, true, MODE, NG>(st, row, tab, qrow, j, tq2);
+                chunk<Range<-kR, 0>::m(kMid), true, MODE, NG>(st, row, tab, qrow, kMid, tq2);
             }
         } else {
-            chunk<Range<1, kR>::m(kMid), true, kPipe, MODE, NG>(st, row, tab, qrow, kMid, tq2);
+            chunk<Range<1, kR>::m(kMid), true, MODE, NG>(st, row, tab, qrow, kMid, tq2);
 #pragma unroll 1
-            for (int j = kMid + 1; j <= j_hi; j++) chunk<0xFFFFu, true, kPipe, MODE, NG>(st, row, tab, qrow, j, tq2);
+            for (int j = kMid + 1; j <= j_hi; j++) chunk<0xFFFFu, true, MODE, NG>(st, row, tab, qrow, j, tq2);
         }
         return;
     }
-    constexpr int kGSplit = gsplit_of(MODE, NG, G7);
-    if constexpr (kGSplit > 0) {   // the split at a read-group boundary (dy = 0: the pairs inside the row stay with half 1)
-        static_assert(kSplit == 0 && kGSplit < kChunks - 1, "one split at a time");
-        if (dy0) {
-            if constexpr (HF == 0) sweep_range<0, 0, false, MODE, NG>(st, row, tab, qrow, tq2);
-            else sweep_range<1, kR, true, MODE, NG>(st, row, tab, qrow, tq2);
-        } else {
-            if constexpr (HF == 0) sweep_groups<0, kGSplit - 1, true, MODE, NG>(st, row, tab, qrow, tq2);
-            else sweep_groups<kGSplit, kChunks - 1, true, MODE, NG>(st, row, tab, qrow, tq2);
-        }
-        return;
-    }
-    if constexpr (HF == 0) {
-        if (dy0) {
-            sweep_range<0, 0, false, MODE, NG>(st, row, tab, qrow, tq2);
-            if constexpr (kSplit >= 1) sweep_range<1, kSplit, true, MODE, NG>(st, row, tab, qrow, tq2);
-        } else {
-            sweep_range<-kR, kSplit, true, MODE, NG>(st, row, tab, qrow, tq2);
-        }
+    constexpr int kGSplit = gsplit_of(G7);
+    static_assert(kGSplit > 0 && kGSplit < kChunks - 1, "a split between two read groups of the window");
+    if (dy0) {
+        if constexpr (HF == 0) sweep_range<0, 0, false, MODE, NG>(st, row, tab, qrow, tq2);
+        else sweep_range<1, kR, true, MODE, NG>(st, row, tab, qrow, tq2);
     } else {
-        if constexpr (kSplit >= 1) {
-            sweep_range<kSplit + 1, kR, true, MODE, NG>(st, row, tab, qrow, tq2);
-        } else {
-            if (dy0) sweep_range<1, kR, true, MODE, NG>(st, row, tab, qrow, tq2);
-            else sweep_range<kSplit + 1, kR, true, MODE, NG>(st, row, tab, qrow, tq2);
-        }
+        if constexpr (HF == 0) sweep_groups<0, kGSplit - 1, true, MODE, NG>(st, row, tab, qrow, tq2);
+        else sweep_groups<kGSplit, kChunks - 1, true, MODE, NG>(st, row, tab, qrow, tq2);
     }
 }
 
@@ -1062,9 +912,6 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
         (void)n_short;
     }
 
-    unsigned long long t_start = 0, t_swept = 0, c_pro = 0, s_hk = 0, s_ev = 0, s_bar = 0;
-    unsigned long long rt_start = 0;     // (the 100 MHz counter every XCD shares: when, within the launch, the item started)
-    if constexpr (kStamps) { t_start = __builtin_amdgcn_s_memtime(); rt_start = __builtin_amdgcn_s_memrealtime(); }
     int part, tile, n_parts;
     if (!a.sym.parts_hi || u < a.sym.n_lo_items) {
         n_parts = a.n_parts;
@@ -1097,7 +944,6 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
     const int trow = (wave & 3) + 4 * (lane >> 5);      // lower / upper half of the wave: rows t and t + 4
     const int half = wave >> 2;
     constexpr int tw = kTabW;
-    if constexpr (kPrio == 1) { if (half == 1) __builtin_amdgcn_s_setprio(2); }
 
     // ---- the lane's own 4 pixels (loads clamped into the image; outside it the pixel takes no part)
     Lane<NG, W> st;
@@ -1173,7 +1019,7 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
             // quotient's last-bit errors; a computed nu below even that -- possible only where E_p + E_q is denormal --
             // wraps around in the unsigned offset and reads the band's last entry, like a dof beyond the band: gate_weight.)
             // The band is addressed from LDS address 0 (lds_at0): `smem` is the kernel's only LDS allocation, which the
-            // compiler places at 0; the diagnostic builds (STATMC_SYM_STAMPS) check it.
+            // compiler places at 0.
             float *band = smem;
             int *nrange = reinterpret_cast<int *>(band + kWelchBand);   // {least n, item flag}
             if (threadIdx.x == 0) { nrange[0] = 0x7fffffff; nrange[1] = 0; }
@@ -1201,7 +1047,7 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
             // (the barrier after the prologue's staging comes before the first look-up)
         }
         if constexpr (DMA) {   // the first row the sweep will need beyond the prologue: on its way during the prologue
-            if (s_a + 1 < s_b && !(kAblate & 2)) dma_row<NG>(a, F, raw_w, lane, x0 - kR + wcol0, y0 + s_a + kRows, ncols);
+            if (s_a + 1 < s_b) dma_row<NG>(a, F, raw_w, lane, x0 - kR + wcol0, y0 + s_a + kRows, ncols);
         }
         // ---- prologue: rows rel = s_a .. s_a+7 (image rows y0 + rel) into slots rel % 9.  All of a thread's fetches
         // are issued before the first is staged: one memory latency per item instead of three.
@@ -1231,13 +1077,10 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
         __syncthreads();
 
         // ---- sweep
-        unsigned long long tk0 = 0, c_hk = 0, c_ev = 0, c_bar = 0;
-        if constexpr (kStamps) c_pro = __builtin_amdgcn_s_memtime() - t_start;
         for (int s = s_a; s < s_b; s++) {
-            if constexpr (kStamps) tk0 = __builtin_amdgcn_s_memtime();
             const int i = DMA ? wcol0 + lane : (int)threadIdx.x;             // the staged column this thread looks after
             const bool mine = DMA ? lane < ncols : i < kP;
-            const bool stage = s + 1 < s_b && mine && !(kAblate & 2);
+            const bool stage = s + 1 < s_b && mine;
             Staged nxt;
             nxt.p.valid = false;
             if constexpr (!DMA) {
@@ -1249,10 +1092,10 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
             // the two waves of a SIMD, the other wave of the pair, or both waves in turn were all slower: HISTORY.md 4.3 / 4.3d).
             auto housekeeping = [&]() {
                 const int dead = s - 1;
-                if (mine && dead >= q_first && y0 + dead >= 0 && !(kAblate & 4))
+                if (mine && dead >= q_first && y0 + dead >= 0)
                     flush_q<NG, W>(lds + (dead % kSlots) * kSlotFloats, i, patch_q + (long long)(dead - q_first) * kP);
                 if constexpr (DMA) {
-                    if (s + 1 < s_b && !(kAblate & 2)) {
+                    if (s + 1 < s_b) {
                         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's own transfers
                         if (stage) {
                             const Staged sp = raw_pixel<NG>(a, F, raw_w, lane, ncols, x0 - kR + i, y0 + s + kRows);
@@ -1265,10 +1108,7 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
                     }
                 }
             };
-            if constexpr (kPrio == 2) { if (half == 0) __builtin_amdgcn_s_setprio(3); }
             if (!DMA || (!kHkAtEnd && half == 0)) housekeeping();
-            if constexpr (kPrio == 2) { if (half == 0) __builtin_amdgcn_s_setprio(0); }
-            if constexpr (kStamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); c_hk += t - tk0; tk0 = t; }
             const int ti = (int)threadIdx.x - (kThreads - 64);
             const bool tstage = s + 1 < s_b && ti >= 0 && ti < tw;
             v2f tnext = v2f{0.f, 0.f};
@@ -1281,25 +1121,18 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
             const float *row = slot + kPx * lane32;
             float *qrow = slot + (kIn + 4 * half) * kP + kPx * lane32;
             const float *tab = tab_lds + ((s - s_a) & 1) * kTabPad;
-            if (kAblate & 8) {
-            } else if (half == 0) {
+            if (half == 0) {
                 eval_half_row<0, MODE, NG, RT, G7>(st, row, tab, qrow, s == 0, j_lo, j_hi, tq2);
             } else {
                 eval_half_row<1, MODE, NG, RT, G7>(st, row, tab, qrow, s == 0, j_lo, j_hi, tq2);
             }
 
-            if constexpr (kStamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); c_ev += t - tk0; tk0 = t; }
             if (DMA && kHkAtEnd && half == 0) housekeeping();
             if (tstage) *reinterpret_cast<v2f *>(tab_lds + ((s - s_a + 1) & 1) * kTabPad + 2 * ti) = tnext;
             if constexpr (!DMA) {
                 if (stage) stage_store<NG, W>(lds + ((s + kRows) % kSlots) * kSlotFloats, i, nxt, F, !PAIR);
             }
-            if (!(kAblate & 16)) __syncthreads();
-            if constexpr (kStamps) { const unsigned long long t = __builtin_amdgcn_s_memtime(); c_bar += t - tk0; tk0 = t; }
-        }
-        if constexpr (kStamps) {
-            t_swept = __builtin_amdgcn_s_memtime();
-            s_hk = c_hk; s_ev = c_ev; s_bar = c_bar;
+            __syncthreads();
         }
         // ---- the rows still in the ring: rel = s_b-1 .. s_b+6
         for (int idx2 = threadIdx.x; idx2 < kRows * kP; idx2 += kThreads) {
@@ -1337,26 +1170,6 @@ __global__ __launch_bounds__(kThreads, 2) void window_filter_sym(FilterArgs a) {
             patch[trow * kW + kPx * lane32 + k] =
                 make_float4((st.acc[k][0].x + st.acc[k][0].y) + e[0 * kW], (st.acc[k][1].x + st.acc[k][1].y) + e[1 * kW],
                             (st.acc[k][2].x + st.acc[k][2].y) + e[2 * kW], (st.sw[k].x + st.sw[k].y) + e[3 * kW]);
-        }
-    }
-#if STATMC_SYM_COUNT
-    __syncthreads();
-    if (lane == 0 && s_a < s_b)
-        patch[a.sym.item_stride4 - 8 + wave] = make_float4((float)st.n_groups, (float)st.n_empty, (float)st.n_empty_halves, 0.f);
-#endif
-    if constexpr (kStamps) {
-        // the item's last 16 float4 (columns of its last accumulator row: the results of a stamps build are wrong):
-        // per wave (housekeeping, sweep, barrier clocks summed over the steps, steps) and (before the first step,
-        // after the last step, whole item)
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        __syncthreads();
-        if (lane == 0 && s_a < s_b) {
-            patch[a.sym.item_stride4 - 8 + wave] = make_float4((float)s_hk, (float)s_ev, (float)s_bar, (float)(s_b - s_a));
-            patch[a.sym.item_stride4 - 16 + wave] = make_float4((float)c_pro, (float)(t_end - t_swept), (float)(t_end - t_start), (float)(rt_start & 0xFFFFFFull));
-            unsigned xcc = 0, hw = 0;      // where the wave ran (tools/experiments/stamps_roi.py)
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            patch[a.sym.item_stride4 - 24 + wave] = make_float4(__uint_as_float(xcc), __uint_as_float(hw), __uint_as_float(blockIdx.x), 0.f);
         }
     }
 }
@@ -1432,8 +1245,6 @@ static int floordiv_h(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b
 
 }  // namespace sym
 
-int sym_diagnostic_bits() { return STATMC_SYM_DIAGNOSTIC_BITS; }
-
 // Tile range of a launch: every tile of the film grid that holds a pixel whose upper half-window reaches the
 // ROI (rows ry0-20 .. ry1-1, columns rx0-20 .. rx1+19, clipped to the local image).
 void sym_geometry(FilterArgs &a) {
@@ -1451,7 +1262,7 @@ int sym_tiles(const FilterArgs &a) { return a.sym.ntx * a.sym.nty; }
 
 // Parts per tile: the grid runs one workgroup per CU, so its makespan is ceil(items / CUs) rounds of the longest part,
 // ceil(21 / parts) steps, plus what a further item costs: 0.95 steps before its first and after its last step
-// (stamps_sym.py), 7 more accumulator rows to flush and to gather in the combine.  Fitted at 1.35 steps on 1080p runs
+// (per-wave clocks, HISTORY.md 4.3), 7 more accumulator rows to flush and to gather in the combine.  Fitted at 1.35 steps on 1080p runs
 // with 1 .. 4 parts (1.46 / 1.61 / 1.62 / 1.92 ms); the same model orders the parts of a 1920 x 135 / 270 / 540 block
 // (tools/experiments/block_parts.py: 3 parts best for all three).
 int sym_choose_parts(int tiles, int n_cus, int steps) {
@@ -1642,13 +1453,13 @@ hipError_t launch_sym(FilterArgs a, hipStream_t s) {
     // float buffers have one channel: pooled == per channel
     const bool joint = a.channel_rule == STATMC_CHANNELS_JOINT, asym = a.gate == STATMC_GATE_ASYMMETRIC, centre = a.gate == STATMC_GATE_CENTRE;
     const int mode = pair ? kModePair : centre ? (joint ? kModeCentreJoint : kModeCentre) : asym ? (joint ? kModeAsymJoint : kModeAsym) : joint ? kModeJoint : kModeRgb;
-#define STATMC_SYM_K(D, M, G, R) reinterpret_cast<const void *>(&window_filter_sym<D, M, G, R>)
-#define STATMC_SYM_ROW(D, G, R) {STATMC_SYM_K(D, kModeRgb, G, R), STATMC_SYM_K(D, kModePair, G, R), STATMC_SYM_K(D, kModeJoint, G, R), STATMC_SYM_K(D, kModeAsym, G, R), STATMC_SYM_K(D, kModeAsymJoint, G, R), STATMC_SYM_K(D, kModeCentre, G, R), STATMC_SYM_K(D, kModeCentreJoint, G, R)}
+#define SYM_KERNEL(D, M, G, R) reinterpret_cast<const void *>(&window_filter_sym<D, M, G, R>)
+#define SYM_ROW(D, G, R) {SYM_KERNEL(D, kModeRgb, G, R), SYM_KERNEL(D, kModePair, G, R), SYM_KERNEL(D, kModeJoint, G, R), SYM_KERNEL(D, kModeAsym, G, R), SYM_KERNEL(D, kModeAsymJoint, G, R), SYM_KERNEL(D, kModeCentre, G, R), SYM_KERNEL(D, kModeCentreJoint, G, R)}
     // [runtime radius][eight feature planes][LDS-DMA staging][mode]
-    const void *kernels[2][2][2][kModes] = {{{STATMC_SYM_ROW(false, 6, false), STATMC_SYM_ROW(true, 6, false)}, {STATMC_SYM_ROW(false, 8, false), STATMC_SYM_ROW(true, 8, false)}},
-                                            {{STATMC_SYM_ROW(false, 6, true), STATMC_SYM_ROW(true, 6, true)}, {STATMC_SYM_ROW(false, 8, true), STATMC_SYM_ROW(true, 8, true)}}};
-#undef STATMC_SYM_ROW
-#undef STATMC_SYM_K
+    const void *kernels[2][2][2][kModes] = {{{SYM_ROW(false, 6, false), SYM_ROW(true, 6, false)}, {SYM_ROW(false, 8, false), SYM_ROW(true, 8, false)}},
+                                            {{SYM_ROW(false, 6, true), SYM_ROW(true, 6, true)}, {SYM_ROW(false, 8, true), SYM_ROW(true, 8, true)}}};
+#undef SYM_ROW
+#undef SYM_KERNEL
     const void *kernel = kernels[rt ? 1 : 0][g8 ? 1 : 0][dma ? 1 : 0][mode];
     // exactly two RGB G-buffers (whole film, or its 15-channel block + halo image), r = 20, the symmetric gate on one RGB buffer: the G7 builds
     if (!rt && !g8 && !welch && a.n_g == 2 && a.g[0].channels == 3 && a.g[1].channels == 3 && (mode == kModeRgb || mode == kModeJoint)) {
@@ -1658,10 +1469,10 @@ hipError_t launch_sym(FilterArgs a, hipStream_t s) {
     const void *kernel_far = nullptr;
     if (welch) {   // (the gate field has no meaning under Welch: there is one test, symmetric in the pair)
         if (a.sym.redo == nullptr) return hipErrorInvalidValue;
-#define STATMC_SYM_W(M) (g8 ? reinterpret_cast<const void *>(&window_filter_sym<false, M, 8, true>) : reinterpret_cast<const void *>(&window_filter_sym<false, M, 6, true>))
-        kernel = pair ? STATMC_SYM_W(kModeWelchPair) : joint ? STATMC_SYM_W(kModeWelchJoint) : STATMC_SYM_W(kModeWelch);
-        kernel_far = pair ? STATMC_SYM_W(kModeWelchPairFar) : joint ? STATMC_SYM_W(kModeWelchJointFar) : STATMC_SYM_W(kModeWelchFar);
-#undef STATMC_SYM_W
+#define SYM_WELCH(M) (g8 ? reinterpret_cast<const void *>(&window_filter_sym<false, M, 8, true>) : reinterpret_cast<const void *>(&window_filter_sym<false, M, 6, true>))
+        kernel = pair ? SYM_WELCH(kModeWelchPair) : joint ? SYM_WELCH(kModeWelchJoint) : SYM_WELCH(kModeWelch);
+        kernel_far = pair ? SYM_WELCH(kModeWelchPairFar) : joint ? SYM_WELCH(kModeWelchJointFar) : SYM_WELCH(kModeWelchFar);
+#undef SYM_WELCH
     }
     static std::mutex mu;
     static std::set<std::pair<int, const void *>> done;

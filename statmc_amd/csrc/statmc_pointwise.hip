@@ -22,62 +22,29 @@
 
 #include "statmc_device.h"
 
-// sample rows in flight per lane (x2: current + next group) per kind of stat type; the defaults are
-// the measured optimum (tools/experiments/build_variant.sh sweeps them)
-#ifndef STATMC_ACC_U_RGB_T
-#define STATMC_ACC_U_RGB_T 3
-#endif
-#ifndef STATMC_ACC_U_RGB
-#define STATMC_ACC_U_RGB 3
-#endif
-#ifndef STATMC_ACC_U_F
-#define STATMC_ACC_U_F 6
-#endif
-// RGB sample planes stream through LDS-DMA (global_load_lds_dwordx4, non-temporal): a wave's sample row is 3 KiB of
-// contiguous memory, three 1-KiB transfers land it in a wave-private ring of STATMC_ACC_DMA_D rows, every lane reads its own
-// 48 B back.  tools/microbench/hbm_read_ldsdma.hip: 7.0 TB/s against 6.26 for the same walk with loads into registers
-// (which for a 48-B lane stride coalesce only through the cache and must not be non-temporal); 1-channel planes keep
-// their non-temporal register loads (6.8 TB/s against 6.3 - 6.6 through LDS-DMA).  Ring depth (STATMC_ACC_DMA_D, below): 3 rows --
-// 240 VGPRs, two waves per SIMD; with 5 the compiler hoists all five row reads (256 VGPRs + AGPR copies), occupancy
-// drops to one wave per SIMD and every type loses.
-// element pairs folded stage by stage together (RGB types: 6 pairs per lane and sample)
-#ifndef STATMC_ACC_PAIR_GROUP
-#define STATMC_ACC_PAIR_GROUP 3
-#endif
-// timing experiment only (variant builds): the walk without its state stores -- what the stores cost
-#ifndef STATMC_ACC_SKIP_STORES
-#define STATMC_ACC_SKIP_STORES 0
-#elif defined(STATMC_PRODUCT_BUILD) && STATMC_ACC_SKIP_STORES
-#error "STATMC_ACC_SKIP_STORES is a timing experiment: the results are wrong"
-#endif
-// the state planes are written once per launch and not read again before the next one: non-temporal stores
-// (tools/microbench/acc_model.hip: the stores are 1 % of the bytes and 9 % of the time of a one-type walk, streaming ones cost a
-// quarter less there; in the kernel the radiance type alone gains 3 %, the full mix nothing: off)
-#ifndef STATMC_ACC_NT_STORES
-#define STATMC_ACC_NT_STORES 0
-#endif
-#ifndef STATMC_ACC_WAVES
-#define STATMC_ACC_WAVES 2   // waves per SIMD the film-major kernel is compiled for (3: 168 VGPRs, 346 spills, slower)
-#endif
-#ifndef STATMC_ACC_DMA_D
-#define STATMC_ACC_DMA_D 3
-#endif
-#ifndef STATMC_ACC_TILES_DMA_D
-#define STATMC_ACC_TILES_DMA_D 3     // ring depth of the tile-fed kernel
-#endif
-#ifndef STATMC_ACC_OCC_AB
-#define STATMC_ACC_OCC_AB 0
-#endif
-#ifndef STATMC_ACC_DMA_DEPTHS
-#define STATMC_ACC_DMA_DEPTHS 0      // 1 (experiment builds): the film-major kernel at ring depths 3 .. 6, chosen by statmc_debug_accumulate_dma
-#endif
 #include "t_quantiles.h"
 
 namespace statmc {
 
-constexpr int kAccDmaD = STATMC_ACC_DMA_D;                 // sample rows in flight per wave (RGB types): the default ring depth
-constexpr int kAccTilesDmaD = STATMC_ACC_TILES_DMA_D;
-constexpr int kAccDmaMaxD = 6;                              // 2 workgroups x 4 waves x D rows x 3 KiB <= 160 KiB of LDS
+// Sample rows in flight per lane (x2: current + next group) per kind of stat type: RGB with the Box-Cox transform, RGB,
+// 1-channel.  The measured optimum (tools/experiments/build_variant.sh A/Bs source revisions).
+constexpr int kAccURgbT = 3, kAccURgb = 3, kAccUF = 6;
+// element pairs folded stage by stage together (RGB types: 6 pairs per lane and sample)
+constexpr int kAccPairGroup = 3;
+// waves per SIMD the film-major kernel is compiled for (3: 168 VGPRs, 346 spills, slower)
+constexpr int kAccWaves = 2;
+// RGB sample planes stream through LDS-DMA (global_load_lds_dwordx4, non-temporal): a wave's sample row is 3 KiB of
+// contiguous memory, three 1-KiB transfers land it in a wave-private ring of kAccDmaD rows, every lane reads its own
+// 48 B back.  tools/microbench/hbm_read_ldsdma.hip: 7.0 TB/s against 6.26 for the same walk with loads into registers
+// (which for a 48-B lane stride coalesce only through the cache and must not be non-temporal); 1-channel planes keep
+// their non-temporal register loads (6.8 TB/s against 6.3 - 6.6 through LDS-DMA).  Ring depth: 3 rows -- 240 VGPRs, two
+// waves per SIMD; with 5 the compiler hoists all five row reads (256 VGPRs + AGPR copies), occupancy drops to one wave
+// per SIMD and every type loses.
+constexpr int kAccDmaD = 3;                 // sample rows in flight per wave (RGB types)
+constexpr int kAccTilesDmaD = 3;            // ring depth of the tile-fed kernel
+// (The state planes are written once per launch and not read again before the next one, but non-temporal stores do not
+// pay: tools/microbench/acc_model.hip -- the stores are 1 % of the bytes and 9 % of the time of a one-type walk, streaming
+// ones cost a quarter less there; in the kernel the radiance type alone gains 3 %, the full mix nothing.)
 constexpr int acc_ring_floats(int d) { return d * 3 * 256; }                                  // per wave: D rows of 64 lanes x 12 floats
 constexpr size_t acc_lds_bytes(int d) { return (size_t)4 * acc_ring_floats(d) * sizeof(float); }   // four waves per workgroup
 template <int N> __device__ __forceinline__ void acc_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -463,7 +430,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     // they only coalesce through the cache, so they must be plain loads (non-temporal ones
     // re-fetch the shared lines: 4.8 vs 6.4 TB/s, tools/microbench/hbm_read.hip).  C = 1
     // streams with non-temporal loads.
-    constexpr int U = UMUL * (C == 3 ? (TRANSFORM ? STATMC_ACC_U_RGB_T : STATMC_ACC_U_RGB) : STATMC_ACC_U_F);
+    constexpr int U = UMUL * (C == 3 ? (TRANSFORM ? kAccURgbT : kAccURgb) : kAccUF);
     auto load_sample = [&](vfloat4 (&dst)[C], const float *src) {
 #pragma unroll
         for (int k = 0; k < C; k++)
@@ -484,7 +451,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
                 rc2[i] = v2f{rc0, rc0};
                 smp2[i] = v2f{q[i >> 1][2 * (i & 1)], q[i >> 1][2 * (i & 1) + 1]};
             }
-            constexpr int G = C == 3 ? STATMC_ACC_PAIR_GROUP : 2;
+            constexpr int G = C == 3 ? kAccPairGroup : 2;
 #pragma unroll
             for (int g = 0; g < NE / 2; g += G) add_sample2<G, MAXM, TRANSFORM>(st + g, nf2 + g, rc2 + g, smp2 + g);
         } else {
@@ -582,9 +549,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     if (enabled) {                                                               \
         _Pragma("unroll") for (int k = 0; k < C; k++) {                          \
             const vfloat4 v = {st[2 * k].field.x, st[2 * k].field.y, st[2 * k + 1].field.x, st[2 * k + 1].field.y}; \
-            if (STATMC_ACC_SKIP_STORES && v.x != 12345.678f) continue;  /* the arithmetic stays alive, the store never happens */ \
-            if (STATMC_ACC_NT_STORES) __builtin_nontemporal_store(v, reinterpret_cast<vfloat4 *>((ptr) + e0 + 4 * k)); \
-            else *reinterpret_cast<vfloat4 *>((ptr) + e0 + 4 * k) = v;            \
+            *reinterpret_cast<vfloat4 *>((ptr) + e0 + 4 * k) = v;                \
         }                                                                        \
     }
     STATMC_STORE_PLANE(t.mean, mean, true)
@@ -596,8 +561,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     // Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
     typedef int vint4 __attribute__((ext_vector_type(4)));
     const vint4 n_out = {n0[0] + S, n0[1] + S, n0[2] + S, n0[3] + S};
-    if (STATMC_ACC_NT_STORES) __builtin_nontemporal_store(n_out, reinterpret_cast<vint4 *>(t.n + p0));
-    else *reinterpret_cast<vint4 *>(t.n + p0) = n_out;
+    *reinterpret_cast<vint4 *>(t.n + p0) = n_out;
     // Optional epilogue (round 6): the pre-pass of the moments just written, from the registers that hold them -- the same
     // prepass_elem as prepass_kernel, hence the same bits -- instead of a launch that reads 40 B per pixel back.
     if constexpr (MAXM >= 3) {
@@ -704,21 +668,17 @@ __device__ __forceinline__ void accumulate_dispatch(const AccumulateType &t, lon
 // running this bandwidth-bound kernel beside the VALU-bound window filter of the previous
 // iteration on a second stream gains <= 15 % (the two contend for VALU issue), so bench.py
 // keeps the kernels back to back.
-template <bool VEC, int UMUL, int DMA, int OCC = STATMC_ACC_WAVES>
+template <bool VEC, int UMUL, int DMA, int OCC = kAccWaves>
 __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs a) {
     extern __shared__ __attribute__((aligned(16))) float acc_lds[];
     // the wave's LDS-DMA ring (RGB types, vector path); DMA = false (debug hook, A/B) keeps every type on register loads
     float *ring = DMA ? acc_lds + (threadIdx.x >> 6) * acc_ring_floats(DMA) : nullptr;
     if (a.resident_blocks > 0) {
         for (int i = 0; i < a.n_types; i++) {
-#ifndef STATMC_ACC_RESIDENT_START
-#define STATMC_ACC_RESIDENT_START 0
-#endif
-            // (which type a workgroup starts with: 0 = its index, so that every type is walked by a fifth of the grid at any time; experiment
-            // builds: 1 = every workgroup the same type -- 3.92 against 3.75 ms --, 2 = the eight workgroups of a dispatch round -- one per
-            // XCD -- the same type: no difference; profiles/r06_ab_resident_start.log)
-            const int first = STATMC_ACC_RESIDENT_START == 1 ? 0 : STATMC_ACC_RESIDENT_START == 2 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-            const AccumulateType t = a.t[(first + i) % a.n_types];   // (by value: see below)
+            // (workgroup b starts with type b % n_types, so that every type is walked by a fifth of the grid at any time; every workgroup
+            // starting with the same type: 3.92 against 3.75 ms; the eight workgroups of a dispatch round -- one per XCD -- with the same
+            // type: no difference; profiles/r06_ab_resident_start.log)
+            const AccumulateType t = a.t[((int)blockIdx.x + i) % a.n_types];   // (by value: see below)
             if (t.channels == 3) accumulate_dispatch<3, VEC, UMUL, DMA>(t, blockIdx.x, gridDim.x, ring, a.dma_first != 0);
             else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blockIdx.x, gridDim.x, ring, a.dma_first != 0);
         }
@@ -749,8 +709,6 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
     if (t.channels == 3) accumulate_dispatch<3, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
     else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
 }
-
-int acc_diagnostic_bits() { return STATMC_ACC_SKIP_STORES ? 128 : 0; }
 
 static thread_local unsigned g_last_acc_grid = 0;
 unsigned last_accumulate_grid() { return g_last_acc_grid; }   // workgroups of the calling thread's last film-major launch (tests)
@@ -824,23 +782,11 @@ hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
     }
     const dim3 grid(a.resident_blocks > 0 ? a.resident_blocks : a.grid_mode == 1 ? (unsigned)(units * a.n_types) : rounds * a.n_slots);
     g_last_acc_grid = grid.x;
-    // a.dma: 0 = loads into registers (A/B), 1 = the default ring depth, 3 .. 6 = that depth where the build holds it
-    // (STATMC_ACC_DMA_DEPTHS: experiment builds instantiate every depth, the product build the default one)
-    const int depth = a.dma == 1 ? kAccDmaD : a.dma;
-#define STATMC_LAUNCH_DEPTH(D) \
-    if (vec && depth == D) { hipLaunchKernelGGL((accumulate_kernel<true, 1, D>), grid, dim3(kBlock), acc_lds_bytes(D), s, a); return hipGetLastError(); }
-#if STATMC_ACC_OCC_AB       // experiment builds: the default depth compiled for three waves per SIMD as well (statmc_debug_accumulate_occupancy)
-    if (vec && depth == kAccDmaD && a.occ == 3) {
-        hipLaunchKernelGGL((accumulate_kernel<true, 1, kAccDmaD, 3>), grid, dim3(kBlock), acc_lds_bytes(kAccDmaD), s, a);
+    // a.dma: 1 = the LDS-DMA ring (default), 0 = loads into registers (A/B)
+    if (vec && a.dma) {
+        hipLaunchKernelGGL((accumulate_kernel<true, 1, kAccDmaD>), grid, dim3(kBlock), acc_lds_bytes(kAccDmaD), s, a);
         return hipGetLastError();
     }
-#endif
-    STATMC_LAUNCH_DEPTH(kAccDmaD)
-#if STATMC_ACC_DMA_DEPTHS
-    STATMC_LAUNCH_DEPTH(3) STATMC_LAUNCH_DEPTH(4) STATMC_LAUNCH_DEPTH(5) STATMC_LAUNCH_DEPTH(6)
-#endif
-#undef STATMC_LAUNCH_DEPTH
-    if (vec && depth != 0) return hipErrorInvalidValue;      // a ring depth this build does not hold
     if (vec && a.umul == 2)
         hipLaunchKernelGGL((accumulate_kernel<true, 2, 0>), grid, dim3(kBlock), 0, s, a);
     else if (vec)

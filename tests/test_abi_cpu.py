@@ -133,6 +133,8 @@ def test_per_device_state_needs_setup(lib):
     assert lib.statmc_get_significance() == 0
     q = (C.c_float * 4)(1, 2, 3, 4)
     assert lib.statmc_set_t_quantiles(0, q, 4) == api.ERR_NO_DEVICE
+    assert lib.statmc_debug_accumulate_dma(1) == api.ERR_NO_DEVICE
+    assert lib.statmc_debug_accumulate_dma(3) == api.ERR_INVALID     # 0 or 1: the library holds one ring depth
 
 
 def test_filter_spec_struct_layout(lib):

@@ -12,7 +12,6 @@ VAR = os.path.join(ROOT, "tools", "experiments", "variants")
 
 def one(name, out_path):
     from statmc_amd import build
-    os.environ.setdefault("STATMC_ALLOW_DIAGNOSTIC_BUILD", "1")
     build.SO = os.path.join(VAR, name + ".so")
     import torch
     from statmc_amd import api, film, synthetic

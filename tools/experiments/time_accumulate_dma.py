@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch
 from statmc_amd import build
 if os.environ.get("STATMC_VARIANT"):
-    os.environ.setdefault("STATMC_ALLOW_DIAGNOSTIC_BUILD", "1"); build.SO = os.path.abspath(os.environ["STATMC_VARIANT"])
+    build.SO = os.path.abspath(os.environ["STATMC_VARIANT"])
 from statmc_amd import api, film, synthetic
 dev = torch.device("cuda:0"); api.setup(0)
 lib = api.load()

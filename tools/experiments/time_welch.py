@@ -1,13 +1,12 @@
 """Welch degrees of freedom on the pair-symmetric kernel at 1080p (round 4): against the default spec on the same film, with
 LDS-DMA staging (width 1920) and with register staging (width 1922: what the Welch build always uses).
-python tools/experiments/time_welch.py [variant.so]     (a variant library: the timing-only ablations STATMC_SYM_WELCH_ABLATE;
+python tools/experiments/time_welch.py [variant.so]     (a variant library, tools/experiments/build_variant.sh;
                                                           QUICK=1: the first shape only -- what tools/profile_variants.sh counts)"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from statmc_amd import build
 if len(sys.argv) > 1:
-    os.environ.setdefault("STATMC_ALLOW_DIAGNOSTIC_BUILD", "1")
     build.SO = os.path.abspath(sys.argv[1])
 import torch
 from statmc_amd import api, film, synthetic

@@ -4,7 +4,6 @@ import os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from statmc_amd import build
-os.environ.setdefault("STATMC_ALLOW_DIAGNOSTIC_BUILD", "1")
 build.SO = os.path.join(ROOT, "tools", "experiments", "variants", sys.argv[1] + ".so")
 assert os.path.exists(build.SO), build.SO
 script = sys.argv[2]

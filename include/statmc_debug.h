@@ -15,7 +15,8 @@ extern "C" {
 #endif
 
 /* Window-filter kernel of the device: 0 automatic; 1 window_filter_generic (global memory); 2 the one-sided LDS kernel's
- * runtime-radius build; 3 its compile-time r = 20 build (the kernel the pair-symmetric one replaced). */
+ * runtime-radius build; 3 its compile-time r = 20 build (the kernel the pair-symmetric one replaced).  Any other value:
+ * STATMC_ERR_INVALID. */
 int statmc_debug_force_filter_variant(int variant);
 /* Older name of statmc_set_filter_split (include/statmc.h). */
 int statmc_debug_force_filter_parts(int parts);

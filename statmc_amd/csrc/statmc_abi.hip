@@ -21,7 +21,7 @@
 namespace {
 
 thread_local char g_err[512] = "";
-thread_local const char *g_variant = "none";
+thread_local char g_variant[96] = "none";
 thread_local int g_last_parts = 0, g_last_parts_hi = 0, g_last_tail_rows = 0;
 thread_local const int *g_last_redo = nullptr;   // the item flags of the calling thread's last Welch launch (device memory)
 thread_local int g_last_redo_n = 0;
@@ -173,8 +173,6 @@ void apply_spec(const DeviceState &d, statmc::FilterArgs &k, const statmc_filter
     k.channel_rule = d.spec.channel_rule;
     k.dof = d.spec.dof;
     k.border = d.spec.border;
-    k.force_variant = d.force_variant;
-    k.force_parts = d.split;
     k.n = nullptr;
     k.tq = nullptr;
     k.tq2 = nullptr;
@@ -184,61 +182,6 @@ void apply_spec(const DeviceState &d, statmc::FilterArgs &k, const statmc_filter
         k.tq2 = statmc::t_table_sq_device_ptr(table);   // indexed by dof = 0 .. 4096 (entry 0 = entry 1)
     }
     (void)a;
-}
-// pair-symmetric kernel: tile range, parts and the patch workspace of this launch
-// Window-sweep parts per tile are chosen for the whole local image, whatever output region a call asks for: the parts
-// decide how a pixel's sums are grouped, so a pixel filtered as part of a band of rows (Estimator's Upload / Denoise /
-// Download pipeline) gets the same bits as in a whole-image call.
-int parts_for_whole_image(const statmc::FilterArgs &k, int cus, bool sym) {
-    statmc::FilterArgs w = k;
-    w.rx0 = 0;
-    w.ry0 = 0;
-    w.rx1 = k.width;
-    w.ry1 = k.height;
-    if (!sym) return statmc::lds_filter_parts(w, cus);
-    statmc::sym_geometry(w);
-    return statmc::sym_filter_parts(w, cus);
-}
-
-// pair: filter<float> on the pair-symmetric kernel -- the workspace also holds the three RGB-shaped images every
-// launch packs its two buffers into (behind the patches, 16-byte aligned).
-int prepare_sym(const DeviceState &d, statmc::FilterArgs &k, const statmc_filter_args *a, bool pair = false) {
-    k.sym.fx0 = a->film_x0;
-    k.sym.fy0 = a->film_y0;
-    k.sym.tab_rt = nullptr;
-    if (k.radius != 20 || k.dof == STATMC_DOF_WELCH) {   // (the Welch modes run the runtime-radius build at r = 20 too)
-        if (int rc = spatial_table(k.radius, k.ds, &k.sym.tab_rt, true)) return rc;
-    }
-    // parts -- and the tail split, if the whole image's tile count leaves its last round mostly empty -- are chosen for
-    // the WHOLE local image whatever region this call filters; so is the workspace: the bands of the Upload / Denoise /
-    // Download pipeline then share one allocation (growing it mid-pipeline means a stream synchronisation and a hipFree
-    // between two bands)
-    statmc::FilterArgs whole = k;
-    whole.rx0 = 0; whole.ry0 = 0; whole.rx1 = k.width; whole.ry1 = k.height;
-    statmc::sym_geometry(whole);
-    statmc::sym_choose_split(whole, d.cus);
-    statmc::sym_apply_split(whole);
-    k.n_parts = whole.n_parts;
-    k.sym.parts_hi = whole.sym.parts_hi;
-    k.sym.split_ty = whole.sym.split_ty;
-    statmc::sym_geometry(k);
-    statmc::sym_apply_split(k);
-    float *ws = nullptr;
-    const size_t patch_floats = (statmc::sym_patch_floats(whole, k.n_parts) + 3) & ~(size_t)3;
-    const size_t image_floats = pair ? (size_t)9 * k.width * k.height : 0;
-    const size_t extra_floats = k.border == STATMC_BORDER_CLAMP ? (size_t)4 * k.width * k.height : 0;
-    const size_t redo_floats = k.dof == STATMC_DOF_WELCH ? ((size_t)statmc::sym_items(whole) + 3) & ~(size_t)3 : 0;
-    if (int rc = partial_workspace((patch_floats + image_floats + extra_floats + redo_floats) * sizeof(float), a->stream, &ws)) return rc;
-    k.sym.patch = reinterpret_cast<float4 *>(ws);
-    k.sym.pair = pair ? 1 : 0;
-    k.sym.pair_images = pair ? ws + patch_floats : nullptr;
-    k.sym.border_extra = extra_floats ? reinterpret_cast<float4 *>(ws + patch_floats + image_floats) : nullptr;
-    k.sym.redo = redo_floats ? reinterpret_cast<int *>(ws + patch_floats + image_floats + extra_floats) : nullptr;
-    g_last_redo = k.sym.redo;
-    g_last_redo_n = k.sym.redo ? (int)statmc::sym_items(k) : 0;
-    g_last_parts_hi = whole.sym.parts_hi;
-    g_last_tail_rows = whole.sym.parts_hi ? whole.sym.ty0 + whole.sym.nty - whole.sym.split_ty : 0;
-    return STATMC_OK;
 }
 int prepass_table(const DeviceState &d) { return d.alpha_index + STATMC_TQ_N_ALPHAS * (d.spec.sides ? 1 : 0); }
 
@@ -589,8 +532,8 @@ static int window_filter_impl(const statmc_filter_args *a, int channels) {
     NEED_READY();
     if (int rc = check_common(a, channels)) return rc;
     const int W = a->width, H = a->height;
-    const bool packed_in = a->packed_inputs.data != nullptr;
-    if (!packed_in) {
+    const bool packed = a->packed_inputs.data != nullptr;
+    if (!packed) {
         if (a->n_buffers && (!a->mean_corr || !a->discriminator)) return fail(STATMC_ERR_INVALID, "null buffer table");
         if (a->n_g_buffers && (!a->g_buffers || !a->g_channel_counts || !a->g_dr_factors))
             return fail(STATMC_ERR_INVALID, "null G-buffer table");
@@ -610,143 +553,71 @@ static int window_filter_impl(const statmc_filter_args *a, int channels) {
     k.radius = a->filter_radius;
     k.ds = a->filter_ds_factor;
     k.n_g = (int)a->n_g_buffers;
+    k.sym.fx0 = a->film_x0;
+    k.sym.fy0 = a->film_y0;
     apply_spec(dstate, k, a);
     if (k.dof == STATMC_DOF_WELCH) {
         if (!k.tq) return fail(STATMC_ERR_HIP, "quantile table of the device not found");
-        if (packed_in ? !packed_has_counts(packed_channels(a->packed_inputs)) : !a->n)
+        if (packed ? !packed_has_counts(packed_channels(a->packed_inputs)) : !a->n)
             return fail(STATMC_ERR_INVALID, "Welch dof: the window filter reads the sample counts (args->n, or the last channel of a 16- or 18-channel block + halo image)");
     }
-    const bool packed = a->packed_inputs.data != nullptr;
     if (packed) {
-        // block + halo path: everything the window filter reads comes from one 15- or 17-channel image
+        // block + halo path: everything the window filter reads comes from one 15- to 18-channel image
         const int pch = packed_channels(a->packed_inputs);
         if (channels != 3 || a->n_buffers != 1 || !a->g_dr_factors || pch == 0)
             return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs: needs T = float3, n_buffers = 1 and a packed 15-, 16-, 17- or 18-channel image");
         CHECK_IMG(a->packed_inputs, pch, "packed_inputs", 0);
         if (!a->film_filtered) return fail(STATMC_ERR_INVALID, "null film_filtered table");
         CHECK_IMG(a->film_filtered[0], 3, "film_filtered", 0);
-        if (pch == 15 || pch == 16) {
-            if (a->n_g_buffers != 2) return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (15 / 16 channels): two RGB G-buffers");
-            for (int g = 0; g < 2; g++) {
-                k.g[g].data = nullptr;
-                k.g[g].channels = 3;
-                k.g[g].dr = a->g_dr_factors[g];
-            }
-        } else {
-            if (a->n_g_buffers > 4 || !a->g_channel_counts)
-                return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): up to two RGB and two 1-channel G-buffers, g_channel_counts needed");
-            for (int g = 0; g < k.n_g; g++) {
-                k.g[g].data = nullptr;
-                k.g[g].channels = a->g_channel_counts[g];
-                k.g[g].dr = a->g_dr_factors[g];
-            }
-        }
+        if (pch <= 16 && a->n_g_buffers != 2) return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (15 / 16 channels): two RGB G-buffers");
+        if (pch >= 17 && (a->n_g_buffers > 4 || !a->g_channel_counts))
+            return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): up to two RGB and two 1-channel G-buffers, g_channel_counts needed");
+        for (int g = 0; g < k.n_g; g++) k.g[g] = statmc::GBufferDesc{nullptr, pch <= 16 ? 3 : a->g_channel_counts[g], a->g_dr_factors[g]};
         k.packed = static_cast<const float *>(a->packed_inputs.data);
         k.packed_ch = pch;
         k.out = static_cast<float *>(a->film_filtered[0].data);
-        if (pch == 17 || pch == 18) {
-            // eight feature planes: the pair-symmetric kernel only (the one-sided kernel has six feature slots); 18 channels: its
-            // eight-plane Welch builds, and only they
-            if ((pch == 18 && k.dof != STATMC_DOF_WELCH) || !statmc::sym_eligible(k, 3))
-                return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): runs on the pair-symmetric kernel only -- radius 1..20, DR factors "
-                                                    "finite and <= 0, at most two RGB and two 1-channel G-buffers; 17 channels under STATMC_DOF_PIXEL, "
-                                                    "18 under STATMC_DOF_WELCH");
-            if (int rc = spatial_table(k.radius, k.ds, &k.spatial_tab)) return rc;
-            if (!statmc::sym_path_selected(k, 3)) return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): the forced kernel variant cannot read them");
-            statmc::sym_feature_slots(k);
-            if (int rc = prepare_sym(dstate, k, a)) return rc;
-        } else if (pch == 16) {
-            // + the sample counts: the Welch builds of the pair-symmetric kernel, and only they
-            if (k.dof != STATMC_DOF_WELCH || !statmc::sym_eligible(k, 3))
-                return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (16 channels): for STATMC_DOF_WELCH on the pair-symmetric kernel -- radius 1..20, DR "
-                                                    "factors finite and <= 0, two RGB G-buffers");
-            if (int rc = spatial_table(k.radius, k.ds, &k.spatial_tab)) return rc;
-            k.gscale0 = sqrtf(-k.g[0].dr * 1.44269504088896340736f);
-            k.gscale1 = sqrtf(-k.g[1].dr * 1.44269504088896340736f);
-            if (!statmc::sym_path_selected(k, 3)) return fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (16 channels): the forced kernel variant cannot read them");
-            if (int rc = prepare_sym(dstate, k, a)) return rc;
-        } else {
-            if (!statmc::fast_path_eligible(k, 3))
-                return fail(STATMC_ERR_UNSUPPORTED,
-                            "packed_inputs: radius must be 1..20, DR factors finite and <= 0, and the discriminator's degrees "
-                            "of freedom per pixel (STATMC_DOF_PIXEL)");
-            if (int rc = spatial_table(k.radius, k.ds, &k.spatial_tab)) return rc;
-            k.gscale0 = sqrtf(-k.g[0].dr * 1.44269504088896340736f);
-            k.gscale1 = sqrtf(-k.g[1].dr * 1.44269504088896340736f);
-            // (k.packed is set before the kernel is chosen: sym_eligible looks at it; the one-sided kernel takes what the
-            // pair-symmetric one does not -- a forced variant)
-            if (statmc::sym_path_selected(k, 3)) {
-                if (int rc = prepare_sym(dstate, k, a)) return rc;
-            } else {
-                k.n_parts = parts_for_whole_image(k, dstate.cus, false);
-                if (k.n_parts > 1) {
-                    if (int rc = partial_workspace((size_t)k.n_parts * W * H * 4 * sizeof(float), a->stream, &k.partial)) return rc;
-                }
-            }
+    } else {
+        for (int g = 0; g < k.n_g; g++) {
+            const int gc = a->g_channel_counts[g];
+            if (gc != 1 && gc != 3) return fail(STATMC_ERR_UNSUPPORTED, "g_buffers[%d]: %d channels", g, gc);
+            CHECK_IMG(a->g_buffers[g], gc, "g_buffers", g);
+            k.g[g] = statmc::GBufferDesc{static_cast<const float *>(a->g_buffers[g].data), gc, a->g_dr_factors[g]};
         }
-        const char *variant = "none";
-        HIP_TRY(statmc::launch_lds_packed(k, S(a->stream), &variant));
-        g_variant = variant;
+    }
+    statmc::FilterPlan plan;
+    if (int rc = statmc::plan_window_filter(k, channels, a->n_buffers, dstate.cus, dstate.force_variant, dstate.split, plan)) return rc;
+    if (plan.spatial_tab) {
+        if (int rc = spatial_table(k.radius, k.ds, &k.spatial_tab)) return rc;
+    }
+    if (plan.sym_rt_tab) {
+        if (int rc = spatial_table(k.radius, k.ds, &k.sym.tab_rt, true)) return rc;
+    }
+    const size_t patch = plan.patch_floats, image = plan.image_floats, extra = plan.extra_floats;
+    if (const size_t floats = plan.partial_floats + patch + image + extra + plan.redo_floats) {
+        float *ws = nullptr;
+        if (int rc = partial_workspace(floats * sizeof(float), a->stream, &ws)) return rc;
+        if (plan.kernel != statmc::kFilterSym) {
+            k.partial = ws;
+        } else {
+            k.sym.patch = reinterpret_cast<float4 *>(ws);
+            k.sym.pair_images = image ? ws + patch : nullptr;
+            k.sym.border_extra = extra ? reinterpret_cast<float4 *>(ws + patch + image) : nullptr;
+            k.sym.redo = plan.redo_floats ? reinterpret_cast<int *>(ws + patch + image + extra) : nullptr;
+            g_last_redo = k.sym.redo;
+            g_last_redo_n = k.sym.redo ? plan.redo_items : 0;
+            g_last_parts_hi = k.sym.parts_hi;
+            g_last_tail_rows = plan.tail_rows;
+        }
+    }
+    if (packed) {
+        HIP_TRY(statmc::launch_window_filter(plan, false, k, 3, S(a->stream)));
+        snprintf(g_variant, sizeof(g_variant), "%s", plan.variant);
         g_last_parts = k.n_parts;
         return STATMC_OK;
     }
-    for (int g = 0; g < k.n_g; g++) {
-        const int gc = a->g_channel_counts[g];
-        if (gc != 1 && gc != 3) return fail(STATMC_ERR_UNSUPPORTED, "g_buffers[%d]: %d channels", g, gc);
-        CHECK_IMG(a->g_buffers[g], gc, "g_buffers", g);
-        k.g[g].data = static_cast<const float *>(a->g_buffers[g].data);
-        k.g[g].channels = gc;
-        k.g[g].dr = a->g_dr_factors[g];
-    }
-    const bool lds_ok = statmc::fast_path_eligible(k, channels);   // one-sided LDS kernel: at most six feature channels
-    if (lds_ok || statmc::sym_eligible(k, channels)) {
-        if (int rc = spatial_table(k.radius, k.ds, &k.spatial_tab)) return rc;
-        if (lds_ok) {
-            statmc::set_feature_layout(k);
-            k.n_parts = parts_for_whole_image(k, dstate.cus, false);
-        } else {
-            // pair-symmetric kernel only: eight feature planes (their factors come from sym_feature_slots) or the Welch
-            // build, whose six planes take the two-RGB-image factors like every six-plane build
-            if (k.dof == STATMC_DOF_WELCH) statmc::set_feature_layout(k);
-            k.n_parts = 1;
-        }
-    } else {
-        k.n_parts = 1;
-    }
-    // (the one-sided kernel's view of the call, before the pair-symmetric preparation below changes parts and workspace: an odd number
-    // of float buffers ends with three of them on that kernel -- see the loop)
-    const statmc::FilterArgs k_lds = k;
-    // the pair-symmetric kernel (r = 20) also takes G-buffer sets the one-sided kernel has no slots for: two RGB + two
-    // 1-channel images (normal, albedo, depth, material id)
-    const bool sym = statmc::sym_path_selected(k, channels);
-    const bool fast = sym || statmc::lds_path_selected(k, channels);
-    if (sym) {
-        statmc::sym_feature_slots(k);
-        if (int rc = prepare_sym(dstate, k, a, channels == 1)) return rc;
-    } else if (fast) {
-        const int per_px = channels == 3 ? 4 : 8;
-        if (k.n_parts > 1) {
-            if (int rc = partial_workspace((size_t)k.n_parts * W * H * per_px * sizeof(float), a->stream, &k.partial)) return rc;
-        }
-    }
-    // float buffers share the range weight of a launch: two per launch on the pair-symmetric kernel, three on the
-    // one-sided LDS kernel
-    const int pair_group = (fast && channels == 1) ? (sym ? 2 : 3) : 1;
-    // An ODD number of float buffers (ACRR's five: estimator.cpp:434-460) would end with a launch of the pair-symmetric kernel that
-    // carries one buffer at the price of two (1.39 ms at 1080p).  Where the one-sided kernel can take the call as well -- it shares the
-    // range weight over THREE buffers, 2.47 ms -- the last three go to it: 5 buffers 1.40 + 2.47 instead of 1.40 + 1.40 + 1.39 ms
-    // (round 6).  Only with the whole window sweep in one part there (no partial-sum workspace to share with the patches) and no forced
-    // variant; the two kernels agree to 5e-7, each within 1e-5 of the oracle.
-    static const bool mix_allowed = [] { const char *e = getenv("STATMC_FLOAT_MIX"); return !(e && e[0] == '0'); }();   // (A/B: tools/experiments/time_float.py)
-    const bool mix = mix_allowed && sym && channels == 1 && lds_ok && dstate.force_variant == 0 && (a->n_buffers & 1) && a->n_buffers >= 3 && k_lds.n_parts == 1 &&
-                     statmc::lds_path_selected(k_lds, channels);
-    statmc::FilterArgs k_tail = k_lds;
-    statmc::FilterArgs &k_pairs = k;
-    for (int b0 = 0, group = pair_group; b0 < a->n_buffers; b0 += group) {
-        const char *variant = "none";
-        const bool tail = mix && a->n_buffers - b0 == 3;
+    for (int b0 = 0, group = plan.per_launch; b0 < a->n_buffers; b0 += group) {
+        const bool tail = plan.lds_tail && a->n_buffers - b0 == 3;
         if (tail) group = 3;
-        statmc::FilterArgs &k = tail ? k_tail : k_pairs;
         if (group > 1) {
             k.f_active = a->n_buffers - b0 < group ? a->n_buffers - b0 : group;
             if (!a->film || !a->film_filtered) return fail(STATMC_ERR_INVALID, "null film table");
@@ -767,40 +638,31 @@ static int window_filter_impl(const statmc_filter_args *a, int channels) {
                 }
                 if (k.f_out[j] == k.f_colour[j]) return fail(STATMC_ERR_INVALID, "filter cannot run in place (buffer %d)", b);
             }
-            HIP_TRY(statmc::launch_window_filter(k, channels, S(a->stream), &variant));
-            // (a call that ran both kernels names both: "sym_r20_f+lds_r20_f")
-            if (tail && b0 > 0) {
-                static thread_local char both[96];
-                snprintf(both, sizeof(both), "%s+%s", g_variant, variant);
-                variant = both;
+        } else {
+            const int b = b0;
+            // buffer 0 filters the "film" image into "film-f" when denoiseFilm is set
+            // (estimator.cpp:143-146,168-172; argument positions 12 and 20 of filter<T>)
+            const bool film = a->denoise_film && b == 0 && channels == 3;
+            const statmc_image &colour = film ? a->film_buffer : a->film[b];
+            const statmc_image &out = film ? a->film_filtered_buffer : a->film_filtered[b];
+            if (!film && (!a->film || !a->film_filtered)) return fail(STATMC_ERR_INVALID, "null film table");
+            CHECK_IMG(a->mean_corr[b], channels, "mean_corr", b);
+            CHECK_IMG(a->discriminator[b], channels, "discriminator", b);
+            CHECK_IMG(colour, channels, film ? "film_buffer" : "film", b);
+            CHECK_IMG(out, channels, film ? "film_filtered_buffer" : "film_filtered", b);
+            k.mean_corr = static_cast<const float *>(a->mean_corr[b].data);
+            k.disc = static_cast<const float *>(a->discriminator[b].data);
+            k.colour = static_cast<const float *>(colour.data);
+            k.out = static_cast<float *>(out.data);
+            if (k.dof == STATMC_DOF_WELCH) {
+                CHECK_IMG(a->n[b], 1, "n", b);
+                k.n = static_cast<const int32_t *>(a->n[b].data);
             }
-            g_variant = variant;
-            g_last_parts = k.n_parts;
-            continue;
+            if (k.out == k.colour) return fail(STATMC_ERR_INVALID, "filter cannot run in place (buffer %d)", b);
         }
-        const int b = b0;
-        // buffer 0 filters the "film" image into "film-f" when denoiseFilm is set
-        // (estimator.cpp:143-146,168-172; argument positions 12 and 20 of filter<T>)
-        const bool film = a->denoise_film && b == 0 && channels == 3;
-        const statmc_image &colour = film ? a->film_buffer : a->film[b];
-        const statmc_image &out = film ? a->film_filtered_buffer : a->film_filtered[b];
-        if (!film && (!a->film || !a->film_filtered)) return fail(STATMC_ERR_INVALID, "null film table");
-        CHECK_IMG(a->mean_corr[b], channels, "mean_corr", b);
-        CHECK_IMG(a->discriminator[b], channels, "discriminator", b);
-        CHECK_IMG(colour, channels, film ? "film_buffer" : "film", b);
-        CHECK_IMG(out, channels, film ? "film_filtered_buffer" : "film_filtered", b);
-        k.mean_corr = static_cast<const float *>(a->mean_corr[b].data);
-        k.disc = static_cast<const float *>(a->discriminator[b].data);
-        k.colour = static_cast<const float *>(colour.data);
-        k.out = static_cast<float *>(out.data);
-        if (k.dof == STATMC_DOF_WELCH) {
-            CHECK_IMG(a->n[b], 1, "n", b);
-            k.n = static_cast<const int32_t *>(a->n[b].data);
-        }
-        if (k.out == k.colour) return fail(STATMC_ERR_INVALID, "filter cannot run in place (buffer %d)", b);
-        HIP_TRY(statmc::launch_window_filter(k, channels, S(a->stream), &variant));
-        g_variant = variant;
-        g_last_parts = k.n_parts;
+        HIP_TRY(statmc::launch_window_filter(plan, tail, k, channels, S(a->stream)));
+        snprintf(g_variant, sizeof(g_variant), "%s", tail ? plan.tail_variant : plan.variant);
+        g_last_parts = tail ? 1 : k.n_parts;   // (the tail sweeps the window in one part: the plan's rule)
     }
     return STATMC_OK;
 }
@@ -1538,11 +1400,8 @@ int statmc_filter_split_auto(int width, int height, int radius) {
     memset(&k, 0, sizeof(k));
     k.width = width;
     k.height = height;
-    k.rx1 = width;
-    k.ry1 = height;
     k.radius = radius;
-    statmc::sym_geometry(k);
-    return statmc::sym_filter_parts(k, dstate.cus);
+    return statmc::whole_image_parts(k, true, dstate.cus, 0);
 }
 
 // ---- test / A-B switches (include/statmc_debug.h; not part of the reference surface).  Per device: they act on the calling
@@ -1558,6 +1417,7 @@ int statmc_filter_split_auto(int width, int height, int radius) {
         return STATMC_OK;                                            \
     } while (0)
 int statmc_debug_force_filter_variant(int v) {  // 0 auto, 1 generic, 2 runtime-radius one-sided LDS, 3 one-sided r = 20
+    if (v < 0 || v > 3) return fail(STATMC_ERR_INVALID, "statmc_debug_force_filter_variant(%d): 0 .. 3", v);
     STATMC_DEBUG_SET(d.force_variant = v);
 }
 int statmc_debug_accumulate_resident_blocks(int n) {  // 0 by shape (default), n > 0: n resident workgroups, -1: never a resident grid

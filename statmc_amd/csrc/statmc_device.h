@@ -123,10 +123,7 @@ struct FilterArgs {
     float *out;
     // filter spec (statmc_filter_spec): every field but dof = Welch has an LDS kernel (statmc_filter.hip, statmc_filter_sym.hip)
     int gate, channel_rule, dof, border;
-    // dispatch overrides of the device (statmc_abi.hip DeviceState): force_variant 0 auto, 1 generic, 2 lds_rt (one-sided,
-    // runtime radius), 3 lds_r20 (one-sided, compile-time radius 20); force_parts 0 automatic, k >= 1: window-sweep parts
-    // per tile (statmc_set_filter_split)
-    int force_variant, force_parts;
+    int force_variant, force_parts;   // unused: kept so that the fields behind them keep their kernel-argument offsets
     const int32_t *n;            // Welch mode: sample counts
     const float *tq;             // Welch mode: this device's quantile table (4096 entries)
     const float *tq2;            // ... and its squares: tq2[dof] = fl(t_dof * t_dof), dof = 0 .. 4096, entry 0 = entry 1 (pair-symmetric kernel)
@@ -171,7 +168,7 @@ struct FilterArgs {
         float4 *border_extra;     // border rule "clamp": per pixel, the sums over the taps beyond the image (border_virtual_kernel)
         int *redo;                // Welch: one flag per work item, set by the band build for the items the far build computes again
         // eight feature planes (NG = 8 build): up to two RGB and up to two 1-channel G-buffers of the argument list, sorted
-        // into slots by sym_feature_slots(); scale = sqrt(-dr * log2 e), 0 = empty slot (never read)
+        // into slots by the planner; scale = sqrt(-dr * log2 e), 0 = empty slot (never read)
         // Tail split (round 4): the tiles of the film's tile rows >= split_ty sweep with parts_hi workgroups each instead of
         // n_parts, so that the launch's last round of workgroups is full (1280 x 720: 900 tiles = 3.5 rounds of 256).  The
         // work items of the n_parts-tiles come first (n_lo_items of them: the launch's tile rows below split_ty), then
@@ -222,33 +219,34 @@ hipError_t launch_merge_tiles(const MergeTilesArgs &a, int n_tiles, int max_tile
 hipError_t launch_tile_moments(const TileMomentsArgs &a, hipStream_t s);
 hipError_t launch_film_update(const void *pixels, long long n, float splat_scale, float scale, float *rgb, hipStream_t s);
 
-// Returns the variant name through *variant.  channels = 1 or 3.
-hipError_t launch_window_filter(const FilterArgs &a, int channels, hipStream_t s, const char **variant);
-hipError_t launch_lds_packed(const FilterArgs &a, hipStream_t s, const char **variant);
+// What one window-filter call runs (plan_window_filter, statmc_filter.hip): the kernel and build of its launches, how its
+// buffers are grouped into launches, and the tables and workspace the C-ABI layer provides for them.
+enum { kFilterGeneric, kFilterLds, kFilterSym };
+struct FilterPlan {
+    int kernel;                 // of the main launches: kFilterGeneric (global memory), kFilterLds (one-sided), kFilterSym (pair-symmetric)
+    bool lds_r20;               // the one-sided kernel's launches run its compile-time r = 20 build
+    int per_launch;             // float buffers per main launch: 1, 2 (pair-symmetric) or 3 (one-sided)
+    bool lds_tail;              // an odd number of float buffers ends with three of them on the one-sided kernel, in one part
+    bool spatial_tab, sym_rt_tab;   // the launches read FilterArgs::spatial_tab / sym.tab_rt
+    // workspace in floats: the one-sided kernel's partial sums (n_parts > 1), or the pair-symmetric kernel's patches, pair
+    // images, clamped-border sums and Welch redo flags, in this order, each a multiple of 4
+    size_t partial_floats, patch_floats, image_floats, extra_floats, redo_floats;
+    int redo_items;             // pair-symmetric: work items of the launch (one redo flag each)
+    int tail_rows;              // ... tile rows the tail split sweeps with sym.parts_hi parts (0: uniform)
+    char variant[48], tail_variant[96];   // names of the main launches and of the tail launch
+};
+// STATMC_OK, or STATMC_ERR_UNSUPPORTED (with the message recorded) for a block + halo image no kernel can read.  Fills the
+// layout fields of k: feature scales and slots, parts, the pair-symmetric kernel's tile range and split.
+int plan_window_filter(FilterArgs &k, int channels, int n_buffers, int n_cus, int force_variant, int split, FilterPlan &p);
+hipError_t launch_window_filter(const FilterPlan &p, bool tail, const FilterArgs &a, int channels, hipStream_t s);
+// window-sweep parts per tile for the whole local image (statmc_filter_split_auto: sym, split 0)
+int whole_image_parts(const FilterArgs &a, bool sym, int n_cus, int split);
 // Size in floats of the spatial table the fast path wants for radius r (0 if r unsupported).
 size_t spatial_table_floats(int radius);
 size_t sym_rt_table_floats(int radius);                   // pair-symmetric kernel, radius < 20
 void fill_sym_rt_table(float *host_tab, int radius, float ds);
 void fill_spatial_table(float *host_tab, int radius, float ds);
-bool fast_path_eligible(const FilterArgs &a, int channels);
-void set_feature_layout(FilterArgs &a);   // gscale0/1, feat[] of an eligible G-buffer set
-bool lds_path_selected(const FilterArgs &a, int channels);
 
-// pair-symmetric kernel
-bool sym_eligible(const FilterArgs &a, int channels);
-void sym_feature_slots(FilterArgs &a);                       // fills a.sym.g8 / rgb / sc from a.g[] (eligible sets only)
-bool sym_path_selected(const FilterArgs &a, int channels);   // eligible and not overridden
-void sym_geometry(FilterArgs &a);                            // fills a.sym.tx0 .. nty from the ROI and film origin
-int sym_tiles(const FilterArgs &a);
-int sym_choose_parts(int tiles, int n_cus, int steps);
-int sym_filter_parts(const FilterArgs &a, int n_cus);
-void sym_choose_split(FilterArgs &whole, int n_cus);        // n_parts, sym.parts_hi, sym.split_ty for the whole local image (a.sym geometry filled)
-void sym_apply_split(FilterArgs &a);                        // n_lo_tiles / n_lo_items of this launch's tile range
-long long sym_items(const FilterArgs &a);
-size_t sym_patch_floats(const FilterArgs &a, int n_parts);
-hipError_t launch_sym(FilterArgs a, hipStream_t s);
-hipError_t launch_border_virtual(const FilterArgs &a, hipStream_t s);   // the clamped border's taps beyond the image (RGB)
-int choose_parts(int tiles, int n_rows, int n_cus);
 // statmc_placement.hip (device memory placed by HBM rank)
 int abi_fail(int code, const char *fmt, ...);   // records the calling thread's statmc_last_error() text, returns `code` (statmc_abi.hip)
 int placement_role_of(const void *ptr);         // STATMC_MEM_STATE / _STREAM when `ptr` lies in a block dealt with the wanted class, else -1
@@ -256,7 +254,5 @@ int placement_free(void *ptr);                  // 1: `ptr` was a statmc_malloc_
 hipError_t workspace_alloc(void **p, size_t bytes);   // the library's own read-and-written workspaces: STATE role where the device's caller uses placed memory, hipMalloc otherwise
 hipError_t workspace_free(void *p);
 hipError_t placement_grant_peer(int owner_device, int peer_device);   // blocks of `owner`'s placed allocator become valid operands of copies device `peer` executes
-// parts per tile the LDS kernel would use for this ROI on a device with n_cus compute units
-int lds_filter_parts(const FilterArgs &a, int n_cus);
 
 }  // namespace statmc

@@ -59,9 +59,8 @@
 
 namespace statmc {
 
-// (dispatch overrides -- forced kernel variant, pinned window-sweep split -- are per-device state of the C-ABI layer
-// and reach this file in FilterArgs::force_variant / force_parts)
-
+// (which kernel runs a call is decided in one place, plan_window_filter at the end of this file; the dispatch overrides --
+// forced kernel variant, pinned window-sweep split -- are per-device state of the C-ABI layer and arrive as its arguments)
 
 // ====================================================================== generic kernel
 // Every option of statmc_filter_spec, one lane per pixel, straight from global memory; the statements
@@ -819,11 +818,12 @@ hipError_t launch_pack_inputs(const PackArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ====================================================================== dispatch (host)
 // The LDS kernel covers T = float3 (one RGB buffer) and T = float (three buffers per launch)
 // under G-buffers of 1 or 3 channels whose channel counts add up to at most six (the kernel's feature
 // slots; written for two RGB images, an absent one is a slot with factor 0 that is never read), finite
 // non-positive DR factors and radius 1..20.
-bool fast_path_eligible(const FilterArgs &a, int channels) {
+static bool lds_eligible(const FilterArgs &a, int channels) {
     if (channels != 3 && channels != 1) return false;
     // the LDS kernels know both gates, both channel rules and both border rules; a per-pair Welch lookup runs the
     // general kernel
@@ -839,17 +839,17 @@ bool fast_path_eligible(const FilterArgs &a, int channels) {
     return true;
 }
 
-// Feature layout of the LDS kernel for an eligible G-buffer set: up to two RGB images keep the vector
-// loads (k0, k1 per image); anything else is spread over the six slots, one channel each.
-void set_feature_layout(FilterArgs &a) {
-    constexpr float kL2e = 1.44269504088896340736f;
+// Feature layout of the LDS kernel (and of the pair-symmetric kernel's six-plane builds) for a G-buffer set of at most six
+// channels: up to two RGB images keep the vector loads (k0, k1 per image); anything else is spread over the six slots, one
+// channel each.
+static void set_feature_layout(FilterArgs &a) {
     bool rgb_pair = a.n_g <= 2;
     for (int g = 0; g < a.n_g; g++) rgb_pair = rgb_pair && a.g[g].channels == 3;
     for (int f = 0; f < 6; f++) a.feat[f] = FilterArgs::FeatSlot{nullptr, 0, 0, 0.f};
     if (rgb_pair) {
         a.feat_generic = 0;
-        a.gscale0 = a.n_g > 0 ? sqrtf(-a.g[0].dr * kL2e) : 0.f;
-        a.gscale1 = a.n_g > 1 ? sqrtf(-a.g[1].dr * kL2e) : 0.f;
+        a.gscale0 = a.n_g > 0 ? gbuffer_scale(a.g[0].dr) : 0.f;
+        a.gscale1 = a.n_g > 1 ? gbuffer_scale(a.g[1].dr) : 0.f;
         return;
     }
     a.feat_generic = 1;
@@ -857,14 +857,63 @@ void set_feature_layout(FilterArgs &a) {
     int f = 0;
     for (int g = 0; g < a.n_g; g++)
         for (int c = 0; c < a.g[g].channels; c++, f++)
-            a.feat[f] = FilterArgs::FeatSlot{a.g[g].data, a.g[g].channels, c, sqrtf(-a.g[g].dr * kL2e)};
+            a.feat[f] = FilterArgs::FeatSlot{a.g[g].data, a.g[g].channels, c, gbuffer_scale(a.g[g].dr)};
+}
+
+// filter<float3> and filter<float> (two buffers per launch), radius 1..20, every spec: Welch degrees of freedom run the Welch builds
+// (six or eight feature planes, like the others).
+// G-buffers: up to two RGB images (six feature planes, the shipped normal + albedo), or up to two RGB and up to two
+// 1-channel images in any order (eight feature planes: + depth + material id; block + halo calls carry them in a
+// 17-channel packed image)
+static bool sym_eligible(const FilterArgs &a, int channels) {
+    if (a.radius < 1 || a.radius > kMaxR || (channels != 1 && channels != 3)) return false;
+    // Welch degrees of freedom: the pair needs the sample counts -- from their own images (one RGB buffer, or two float
+    // buffers per launch), or from the last channel of a 16- / 18-channel block + halo image (and those images are for the Welch builds only)
+    if (a.dof != STATMC_DOF_PIXEL && a.packed && a.packed_ch != 16 && a.packed_ch != 18) return false;
+    if (a.packed && (a.packed_ch == 16 || a.packed_ch == 18) && a.dof != STATMC_DOF_WELCH) return false;
+    // the pair-symmetric kernel implements both gates and both channel rules; the clamped border's taps beyond the image
+    // are added by border_virtual_kernel
+    // float buffers with the one-sided gate (four weights per pair for two buffers): one-sided kernel
+    if (a.gate != STATMC_GATE_SYMMETRIC && channels != 3 && a.dof == STATMC_DOF_PIXEL) return false;   // (Welch: one test, no gate form)
+    // (a clamped border on a block + halo image: the border kernel reads the packed image -- round 5; before, such calls ran the
+    // one-sided kernel and a block decomposition was not bit-identical to the whole film, which runs this kernel)
+    int n_rgb = 0, n_sc = 0;
+    for (int g = 0; g < a.n_g; g++) {
+        if (a.g[g].channels == 3) n_rgb++;
+        else if (a.g[g].channels == 1) n_sc++;
+        else return false;
+        if (!(a.g[g].dr <= 0.f) || !isfinite(a.g[g].dr)) return false;
+    }
+    if (n_rgb > 2 || n_sc > 2) return false;
+    if (a.packed && n_sc > 0 && a.packed_ch != 17 && a.packed_ch != 18) return false;   // 1-channel features travel in the 17- / 18-channel block + halo image
+    // (a 17-channel image with no 1-channel feature -- FilmShards packs every set other than exactly two RGB G-buffers that way --
+    // runs the eight-plane build with its 1-channel slots at scale 0; the pack kernel writes zeros there)
+    // (Welch with 1-channel features: the eight-plane Welch builds -- from the separate images, or from an 18-channel block + halo
+    // image, which carries the 1-channel features AND the sample counts)
+    return true;
+}
+
+// The pair-symmetric kernel's eight feature planes: up to two RGB and up to two 1-channel G-buffers of the argument list,
+// sorted into slots (eligible sets only; the six-plane builds read gscale0/1 instead)
+static void sym_feature_slots(FilterArgs &a) {
+    for (int i = 0; i < 2; i++) {
+        a.sym.rgb[i] = a.sym.sc[i] = nullptr;
+        a.sym.rgb_scale[i] = a.sym.sc_scale[i] = 0.f;
+    }
+    int n_rgb = 0, n_sc = 0;
+    for (int g = 0; g < a.n_g; g++) {
+        const float scale = gbuffer_scale(a.g[g].dr);
+        if (a.g[g].channels == 3 && n_rgb < 2) { a.sym.rgb[n_rgb] = a.g[g].data; a.sym.rgb_scale[n_rgb++] = scale; }
+        else if (a.g[g].channels == 1 && n_sc < 2) { a.sym.sc[n_sc] = a.g[g].data; a.sym.sc_scale[n_sc++] = scale; }
+    }
+    a.sym.g8 = n_sc > 0 || (a.packed && (a.packed_ch == 17 || a.packed_ch == 18));
 }
 
 // Number of window-sweep parts per tile: the grid runs one workgroup per CU (LDS-bound), so its
 // makespan is ceil(tiles*parts / CUs) rounds of 1/parts tile-time each (+ a prologue per part
 // that stages 8 rows without compute to overlap, measured at about one window row of time).
 // Pick the part count with the smallest estimate.
-int choose_parts(int tiles, int n_rows, int n_cus) {
+static int choose_parts(int tiles, int n_rows, int n_cus) {
     int best = 1;
     double best_cost = 1e30;
     for (int k = 1; k <= 8 && k <= n_rows; k++) {
@@ -879,13 +928,23 @@ int choose_parts(int tiles, int n_rows, int n_cus) {
     return best;
 }
 
-bool sym_path_selected(const FilterArgs &a, int channels) {
-    return sym_eligible(a, channels) && a.spatial_tab != nullptr && a.force_variant == 0;
-}
-int sym_filter_parts(const FilterArgs &a, int n_cus) {
-    const int forced = a.force_parts;
-    if (forced > 0) return forced < a.radius + 1 ? forced : a.radius + 1;
-    return sym_choose_parts(sym_tiles(a), n_cus, a.radius + 1);
+// The same for the pair-symmetric kernel: its makespan is ceil(items / CUs) rounds of the longest part, ceil(21 / parts) steps,
+// plus what a further item costs: 0.95 steps before its first and after its last step (per-wave clocks, HISTORY.md 4.3), 7 more
+// accumulator rows to flush and to gather in the combine.  Fitted at 1.35 steps on 1080p runs with 1 .. 4 parts
+// (1.46 / 1.61 / 1.62 / 1.92 ms); the same model orders the parts of a 1920 x 135 / 270 / 540 block
+// (tools/experiments/block_parts.py: 3 parts best for all three).
+static int sym_choose_parts(int tiles, int n_cus, int steps) {
+    int best = 1;
+    double best_cost = 1e30;
+    for (int k = 1; k <= 8 && k <= steps; k++) {
+        const double rounds = (double)(((long long)tiles * k + n_cus - 1) / n_cus);
+        const double cost = rounds * ((double)((steps + k - 1) / k) + 1.35);
+        if (cost < best_cost * 0.98) {
+            best_cost = cost;
+            best = k;
+        }
+    }
+    return best;
 }
 
 // Where the ROI is cut: columns [rx0, split) go to regular 256-wide tiles, [split, rx1) -- at most half
@@ -901,14 +960,32 @@ static int lds_tiles(const FilterArgs &a) {
     return tiles;
 }
 
+// Window-sweep parts per tile are chosen for the WHOLE local image, whatever output region a call asks for: the parts decide
+// how a pixel's sums are grouped, so a pixel filtered as part of a band of rows (Estimator's Upload / Denoise / Download
+// pipeline) gets the same bits as in a whole-image call.  split > 0: the pinned count (statmc_set_filter_split), at most the
+// window rows a tile sweeps; 0: the count fitted to the kernel's tile grid (sym: the pair-symmetric kernel, before the tail
+// split sym_choose_split may add; otherwise the one-sided kernel).
+int whole_image_parts(const FilterArgs &a, bool sym, int n_cus, int split) {
+    FilterArgs w = a;
+    w.rx0 = 0;
+    w.ry0 = 0;
+    w.rx1 = a.width;
+    w.ry1 = a.height;
+    const int rows = sym ? a.radius + 1 : 2 * a.radius + 1;
+    if (split > 0) return split < rows ? split : rows;
+    if (!sym) return choose_parts(lds_tiles(w), rows, n_cus);
+    sym_geometry(w);
+    return sym_choose_parts(w.sym.ntx * w.sym.nty, n_cus, rows);
+}
+
 template <bool DUAL>
 static size_t lds_bytes_for(int rp) {
     using G = Geo<DUAL>;
     return ((size_t)G::SLOTS * kCh * (G::W + 2 * rp) + 4 * (2 * rp + 8)) * sizeof(float);
 }
 
-// The 160 KB dynamic-LDS attribute is a property of (kernel, device): set once for each pair.
-static hipError_t allow_full_lds(const void *kernel) {
+// The 160 KB dynamic-LDS attribute is a property of (kernel, device): set once for each pair (both LDS kernels).
+hipError_t allow_full_lds(const void *kernel) {
     static std::mutex mu;
     static std::set<std::pair<int, const void *>> done;
     int dev = 0;
@@ -941,85 +1018,116 @@ static hipError_t launch_lds(FilterArgs a, hipStream_t s) {
     return hipGetLastError();
 }
 
-int lds_filter_parts(const FilterArgs &a, int n_cus) {
-    const int forced = a.force_parts;
-    if (forced > 0) return forced < 2 * a.radius + 1 ? forced : 2 * a.radius + 1;
-    return choose_parts(lds_tiles(a), 2 * a.radius + 1, n_cus);
-}
-
-// True when launch_window_filter will run the LDS kernel for these arguments (the C-ABI layer
-// groups float buffers three per launch only then).
-bool lds_path_selected(const FilterArgs &a, int channels) {
-    return fast_path_eligible(a, channels) && a.spatial_tab != nullptr && a.force_variant != 1;
-}
-
-// "sym_r20|sym_rt[_f][_g8][_asym][_joint][_clamp]": compile-time / runtime radius, float buffers, eight feature planes, then the spec's non-default choices
-static const char *sym_variant_name(const FilterArgs &a, int channels) {
-    static thread_local char name[64];
-    const bool joint = a.channel_rule == STATMC_CHANNELS_JOINT && channels == 3;
-    const bool welch = a.dof == STATMC_DOF_WELCH;   // (one build for every radius; the gate field has no meaning under Welch)
-    snprintf(name, sizeof(name), "%s%s%s%s%s%s", welch ? "sym_welch" : a.radius == 20 ? "sym_r20" : "sym_rt", channels == 1 ? "_f" : "", a.sym.g8 ? "_g8" : "",
-             welch ? "" : a.gate == STATMC_GATE_ASYMMETRIC ? "_asym" : a.gate == STATMC_GATE_CENTRE ? "_centre" : "", joint ? "_joint" : "",
-             a.border == STATMC_BORDER_CLAMP ? "_clamp" : "");
-    return name;
-}
-
-// Launch of the one-sided LDS kernel for the arguments' spec.  The default membership test has a compile-time-radius
-// build for r = 20; the other tests (one-sided gate, pooled channels) run the runtime-radius build.
+// The one-sided LDS kernel's build for the arguments' spec.  The default membership test has a compile-time-radius
+// build for r = 20 (r20); the other tests (one-sided gate, pooled channels) run the runtime-radius build.
 static int lds_spec_of(const FilterArgs &a, bool rgb) {
     // (STATMC_GATE_CENTRE runs the one-sided-gate build on rows staged with -D_q = 0)
     return (a.gate != STATMC_GATE_SYMMETRIC ? kSpecAsym : 0) | (rgb && a.channel_rule == STATMC_CHANNELS_JOINT ? kSpecJoint : 0);
 }
 
 template <int K>
-static hipError_t launch_lds_spec(const FilterArgs &a, hipStream_t s, const char **variant) {
+static hipError_t launch_lds_spec(const FilterArgs &a, bool r20, hipStream_t s) {
     constexpr bool rgb = K == 0;
     switch (lds_spec_of(a, rgb)) {
     case 0:
-        if (a.radius == 20 && a.force_variant != 2) {
-            *variant = rgb ? "lds_r20" : "lds_r20_f";
-            return launch_lds<20, K>(a, s);
-        }
-        *variant = rgb ? "lds_rt" : "lds_rt_f";
-        return launch_lds<0, K>(a, s);
+        return r20 ? launch_lds<20, K>(a, s) : launch_lds<0, K>(a, s);
     case kSpecAsym:
-        *variant = a.gate == STATMC_GATE_CENTRE ? (rgb ? "lds_rt_centre" : "lds_rt_f_centre") : (rgb ? "lds_rt_asym" : "lds_rt_f_asym");
         return launch_lds<0, K, kSpecAsym>(a, s);
     case kSpecJoint:
-        *variant = "lds_rt_joint";
         return launch_lds<0, K, rgb ? kSpecJoint : 0>(a, s);
     default:
-        *variant = a.gate == STATMC_GATE_CENTRE ? "lds_rt_centre_joint" : "lds_rt_asym_joint";
         return launch_lds<0, K, rgb ? (kSpecAsym | kSpecJoint) : kSpecAsym>(a, s);
     }
 }
 
-// Window filter reading the 15-channel block + halo image (multi-GPU path): LDS kernels only.
-hipError_t launch_lds_packed(const FilterArgs &a, hipStream_t s, const char **variant) {
-    if (a.sym.patch != nullptr) {
-        *variant = sym_variant_name(a, 3);
+// One launch of the plan: the kernel and build it chose for the call's buffers (tail: for the last three float buffers).
+hipError_t launch_window_filter(const FilterPlan &p, bool tail, const FilterArgs &a, int channels, hipStream_t s) {
+    switch (tail ? kFilterLds : p.kernel) {
+    case kFilterSym:
         return launch_sym(a, s);
+    case kFilterLds:
+        if (channels == 3) return launch_lds_spec<0>(a, p.lds_r20, s);
+        return a.f_active >= 3 ? launch_lds_spec<3>(a, p.lds_r20, s) : a.f_active == 2 ? launch_lds_spec<2>(a, p.lds_r20, s) : launch_lds_spec<1>(a, p.lds_r20, s);
     }
-    return launch_lds_spec<0>(a, s, variant);
-}
-
-hipError_t launch_window_filter(const FilterArgs &a, int channels, hipStream_t s, const char **variant) {
-    if (a.sym.patch != nullptr) {   // the C-ABI layer prepared the pair-symmetric kernel's workspace: that kernel was chosen
-        *variant = sym_variant_name(a, channels);
-        return launch_sym(a, s);
-    }
-    const bool fast = lds_path_selected(a, channels);
-    if (fast) {
-        if (channels == 3) return launch_lds_spec<0>(a, s, variant);
-        return a.f_active >= 3 ? launch_lds_spec<3>(a, s, variant) : a.f_active == 2 ? launch_lds_spec<2>(a, s, variant) : launch_lds_spec<1>(a, s, variant);
-    }
-    *variant = "generic";
     const dim3 grid((a.rx1 - a.rx0 + 31) / 32, (a.ry1 - a.ry0 + 7) / 8);
     if (channels == 3)
         hipLaunchKernelGGL(window_filter_generic<3>, grid, dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL(window_filter_generic<1>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+// The variant names (statmc_last_filter_variant): "generic"; "lds_r20|lds_rt[_f][_centre|_asym][_joint]" for the one-sided
+// kernel; "sym_r20|sym_rt|sym_welch[_f][_g8][_centre|_asym][_joint][_clamp]" for the pair-symmetric one: compile-time / runtime
+// radius / Welch build, float buffers, eight feature planes, then the spec's non-default choices (the gate field has no meaning
+// under Welch; float buffers have one channel: pooled == per channel).
+static void variant_name(char *out, size_t size, int kernel, bool lds_r20, const FilterArgs &a, int channels) {
+    if (kernel == kFilterGeneric) {
+        snprintf(out, size, "generic");
+        return;
+    }
+    const bool sym = kernel == kFilterSym, welch = a.dof == STATMC_DOF_WELCH;
+    const char *build = sym ? (welch ? "sym_welch" : a.radius == 20 ? "sym_r20" : "sym_rt") : lds_r20 ? "lds_r20" : "lds_rt";
+    snprintf(out, size, "%s%s%s%s%s%s", build, channels == 1 ? "_f" : "", sym && a.sym.g8 ? "_g8" : "",
+             welch ? "" : a.gate == STATMC_GATE_ASYMMETRIC ? "_asym" : a.gate == STATMC_GATE_CENTRE ? "_centre" : "",
+             a.channel_rule == STATMC_CHANNELS_JOINT && channels == 3 ? "_joint" : "", sym && a.border == STATMC_BORDER_CLAMP ? "_clamp" : "");
+}
+
+// Which kernel runs a window-filter call, with which build, parts and workspace.  k: the call's arguments as the C-ABI layer
+// marshalled them; the planner fills in their layout fields (feature scales and slots, parts, the pair-symmetric kernel's
+// tile range and split).  force_variant: statmc_debug_force_filter_variant; split: statmc_set_filter_split.
+int plan_window_filter(FilterArgs &k, int channels, int n_buffers, int n_cus, int force_variant, int split, FilterPlan &p) {
+    p = FilterPlan();
+    const bool lds_ok = lds_eligible(k, channels), sym_ok = sym_eligible(k, channels);
+    // a block + halo image has no generic kernel: 15 channels run either LDS kernel, 16 - 18 the pair-symmetric one only (eight
+    // feature planes: the one-sided kernel has six feature slots; the sample counts: its Welch builds, and only they)
+    const int pch = k.packed ? k.packed_ch : 0;
+    if (pch >= 17 && !sym_ok)
+        return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): runs on the pair-symmetric kernel only -- radius 1..20, DR factors "
+                                                "finite and <= 0, at most two RGB and two 1-channel G-buffers; 17 channels under STATMC_DOF_PIXEL, "
+                                                "18 under STATMC_DOF_WELCH");
+    if (pch == 16 && !sym_ok)
+        return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (16 channels): for STATMC_DOF_WELCH on the pair-symmetric kernel -- radius 1..20, DR "
+                                                "factors finite and <= 0, two RGB G-buffers");
+    if (pch == 15 && !lds_ok)
+        return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs: radius must be 1..20, DR factors finite and <= 0, and the discriminator's degrees "
+                                                "of freedom per pixel (STATMC_DOF_PIXEL)");
+    if (pch >= 16 && force_variant != 0)
+        return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (%s channels): the forced kernel variant cannot read them", pch == 16 ? "16" : "17 / 18");
+    // the pair-symmetric kernel unless a variant is forced; the one-sided LDS kernel takes the rest it covers (a block + halo
+    // image even under a forced generic kernel)
+    const bool sym = sym_ok && force_variant == 0;
+    const bool lds = !sym && lds_ok && (force_variant != 1 || pch != 0);
+    p.kernel = sym ? kFilterSym : lds ? kFilterLds : kFilterGeneric;
+    p.lds_r20 = k.radius == 20 && lds_spec_of(k, channels == 3) == 0 && force_variant != 2;
+    p.spatial_tab = lds_ok || sym_ok;
+    int slots = 0;
+    for (int g = 0; g < k.n_g; g++) slots += k.g[g].channels;
+    if (p.spatial_tab && slots <= 6) set_feature_layout(k);
+    k.n_parts = lds_ok ? whole_image_parts(k, false, n_cus, split) : 1;
+    // An ODD number of float buffers (ACRR's five: estimator.cpp:434-460) would end with a launch of the pair-symmetric kernel that
+    // carries one buffer at the price of two (1.39 ms at 1080p).  Where the one-sided kernel can take the call as well -- it shares the
+    // range weight over THREE buffers, 2.47 ms -- the last three go to it: 5 buffers 1.40 + 2.47 instead of 1.40 + 1.40 + 1.39 ms
+    // (round 6).  Only with the whole window sweep in one part there (no partial-sum workspace to share with the patches) and no forced
+    // variant; the two kernels agree to 5e-7, each within 1e-5 of the oracle.
+    p.lds_tail = sym && channels == 1 && lds_ok && n_buffers >= 3 && (n_buffers & 1) && k.n_parts == 1;
+    // float buffers share the range weight of a launch: two per launch on the pair-symmetric kernel, three on the one-sided one
+    p.per_launch = channels == 1 && p.kernel != kFilterGeneric ? (sym ? 2 : 3) : 1;
+    if (sym) {
+        sym_feature_slots(k);
+        k.sym.pair = channels == 1;
+        p.sym_rt_tab = k.radius != 20 || k.dof == STATMC_DOF_WELCH;   // (the Welch modes run the runtime-radius build at r = 20 too)
+        sym_layout(k, n_cus, split, p);
+    } else if (lds && k.n_parts > 1) {
+        p.partial_floats = (size_t)k.n_parts * k.width * k.height * (channels == 3 ? 4 : 8);
+    }
+    variant_name(p.variant, sizeof(p.variant), p.kernel, p.lds_r20, k, channels);
+    if (p.lds_tail) {   // (a call that ran both kernels names both: "sym_r20_f+lds_r20_f")
+        char lds_name[sizeof(p.variant)];
+        variant_name(lds_name, sizeof(lds_name), kFilterLds, p.lds_r20, k, channels);
+        snprintf(p.tail_variant, sizeof(p.tail_variant), "%s%s%s", n_buffers > 3 ? p.variant : "", n_buffers > 3 ? "+" : "", lds_name);
+    }
+    return STATMC_OK;
 }
 
 }  // namespace statmc

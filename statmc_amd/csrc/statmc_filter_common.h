@@ -1,6 +1,7 @@
 // statmc_filter_common.h -- device helpers shared by the window-filter translation units
 // (statmc_filter.hip: general + row-per-wave LDS kernels; statmc_filter_sym.hip: pair-symmetric LDS kernel):
-// the 15-float staging of a pixel, which pixels take part in windows (spec v2), the LDS channel planes.
+// the 15-float staging of a pixel, which pixels take part in windows (spec v2), the LDS channel planes; and the host
+// functions one of the two files calls in the other.
 #pragma once
 
 #include "statmc_device.h"
@@ -8,6 +9,8 @@
 namespace statmc {
 
 constexpr float kLog2e = 1.44269504088896340736f;
+// A G-buffer's factor in the staged features, sqrt(-DR * log2 e): the range weight is then one exp2 of a sum of squares.
+inline float gbuffer_scale(float dr) { return sqrtf(-dr * kLog2e); }
 
 // LDS row layout of the LDS kernels: 15 channel planes of `pitch` floats.
 enum { C_G0 = 0, C_G1 = 3, C_MC = 6, C_ND = 9, C_COL = 12 };
@@ -131,5 +134,11 @@ __device__ __forceinline__ void store_pixel(float *slot, int pitch, int i, const
     p[(C_COL + 2) * pitch] = ok.z ? s.col.z : 0.f;
 }
 
+// ---- host
+hipError_t allow_full_lds(const void *kernel);                          // statmc_filter.hip: the 160 KB LDS attribute, once per (device, kernel)
+hipError_t launch_border_virtual(const FilterArgs &a, hipStream_t s);   // ... the clamped border's taps beyond the image
+void sym_geometry(FilterArgs &a);                                       // statmc_filter_sym.hip: a.sym.tx0 .. nty from the ROI and film origin
+void sym_layout(FilterArgs &k, int n_cus, int split, FilterPlan &p);    // ... parts, tail split, tile range and workspace of a plan
+hipError_t launch_sym(FilterArgs a, hipStream_t s);
 
 }  // namespace statmc

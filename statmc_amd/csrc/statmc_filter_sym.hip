@@ -57,7 +57,6 @@
 #include <map>
 #include <mutex>
 #include <vector>
-#include <set>
 #include <type_traits>
 #include <utility>
 
@@ -1258,32 +1257,14 @@ void sym_geometry(FilterArgs &a) {
     a.sym.ntx = floordiv_h(ex1 - 1 + a.sym.fx0, kW) - a.sym.tx0 + 1;
     a.sym.nty = floordiv_h(ey1 - 1 + a.sym.fy0, kRows) - a.sym.ty0 + 1;
 }
-int sym_tiles(const FilterArgs &a) { return a.sym.ntx * a.sym.nty; }
+static int sym_tiles(const FilterArgs &a) { return a.sym.ntx * a.sym.nty; }
 
-// Parts per tile: the grid runs one workgroup per CU, so its makespan is ceil(items / CUs) rounds of the longest part,
-// ceil(21 / parts) steps, plus what a further item costs: 0.95 steps before its first and after its last step
-// (per-wave clocks, HISTORY.md 4.3), 7 more accumulator rows to flush and to gather in the combine.  Fitted at 1.35 steps on 1080p runs
-// with 1 .. 4 parts (1.46 / 1.61 / 1.62 / 1.92 ms); the same model orders the parts of a 1920 x 135 / 270 / 540 block
-// (tools/experiments/block_parts.py: 3 parts best for all three).
-int sym_choose_parts(int tiles, int n_cus, int steps) {
-    int best = 1;
-    double best_cost = 1e30;
-    for (int k = 1; k <= 8 && k <= steps; k++) {
-        const double rounds = (double)(((long long)tiles * k + n_cus - 1) / n_cus);
-        const double cost = rounds * ((double)((steps + k - 1) / k) + 1.35);
-        if (cost < best_cost * 0.98) {
-            best_cost = cost;
-            best = k;
-        }
-    }
-    return best;
-}
 // Work items of a launch (sym geometry and split applied)
-long long sym_items(const FilterArgs &a) {
+static long long sym_items(const FilterArgs &a) {
     if (!a.sym.parts_hi) return (long long)sym_tiles(a) * a.n_parts;
     return (long long)a.sym.n_lo_items + (long long)(sym_tiles(a) - a.sym.n_lo_tiles) * a.sym.parts_hi;
 }
-void sym_apply_split(FilterArgs &a) {
+static void sym_apply_split(FilterArgs &a) {
     if (!a.sym.parts_hi) {
         a.sym.n_lo_tiles = sym_tiles(a);
         a.sym.n_lo_items = a.sym.n_lo_tiles * a.n_parts;
@@ -1294,7 +1275,7 @@ void sym_apply_split(FilterArgs &a) {
     a.sym.n_lo_items = a.sym.n_lo_tiles * a.n_parts;
 }
 // (n_parts: the smaller part count of the launch -- its items have the most accumulator rows and set the item stride)
-size_t sym_patch_floats(const FilterArgs &a, int n_parts) {
+static size_t sym_patch_floats(const FilterArgs &a, int n_parts) {
     return (size_t)sym_items(a) * (sym::kPatchP + (size_t)sym::q_rows_max(n_parts, a.radius + 1) * sym::kP) * 4;
 }
 
@@ -1313,24 +1294,22 @@ static double sym_makespan(long long n_long, double c_long, long long n_short, d
     return *std::max_element(cu.begin(), cu.end());
 }
 
-// Parts for the whole local image: the uniform choice of sym_choose_parts, or -- when that leaves the last round of
-// workgroups mostly empty -- the same with the last tile rows swept by more parts (a "tail split"): their short items fill
-// the end of the launch.  1280 x 720 (900 tiles): 4 rounds of 21 steps -> 3 rounds + half-length items.  Cost of an item as in
-// sym_choose_parts: ceil(steps / parts) + 1.35 steps.  Results are cached per (tile grid, CUs, steps): the search simulates
-// the dispatch.  A pinned split (statmc_set_filter_split) is uniform: no tail.
-void sym_choose_split(FilterArgs &w, int n_cus) {
+// Parts for the whole local image (w: its geometry filled): the uniform choice of whole_image_parts, or -- when that leaves the
+// last round of workgroups mostly empty -- the same with the last tile rows swept by more parts (a "tail split"): their short
+// items fill the end of the launch.  1280 x 720 (900 tiles): 4 rounds of 21 steps -> 3 rounds + half-length items.  Cost of an
+// item as in sym_choose_parts: ceil(steps / parts) + 1.35 steps.  Results are cached per (tile grid, CUs, steps): the search
+// simulates the dispatch.  A pinned split (statmc_set_filter_split) is uniform: no tail.
+static void sym_choose_split(FilterArgs &w, int n_cus, int split) {
+    w.n_parts = whole_image_parts(w, true, n_cus, split);
     w.sym.parts_hi = 0;
     w.sym.split_ty = 0;
-    if (w.force_parts > 0) {
-        w.n_parts = sym_filter_parts(w, n_cus);
-        return;
-    }
+    if (split > 0) return;
     struct Choice { int lo, hi, tail_rows; };
     static std::mutex mu;
     static std::map<std::array<int, 4>, Choice> cache;
     const int steps = w.radius + 1, ntx = w.sym.ntx, nty = w.sym.nty;
     const std::array<int, 4> key = {ntx, nty, n_cus, steps};
-    Choice c{1, 0, 0};
+    Choice c{w.n_parts, 0, 0};
     {
         std::lock_guard<std::mutex> lk(mu);
         auto it = cache.find(key);
@@ -1339,7 +1318,6 @@ void sym_choose_split(FilterArgs &w, int n_cus) {
         } else {
             const long long tiles = (long long)ntx * nty;
             auto cost = [&](int k) { return (double)((steps + k - 1) / k) + 1.35; };
-            c.lo = sym_choose_parts((int)tiles, n_cus, steps);
             double best = sym_makespan(tiles * c.lo, cost(c.lo), 0, 0.0, n_cus);
             for (int lo = 1; lo <= 3 && lo <= steps; lo++)
                 for (int hi = 2 * lo; hi <= 4 * lo && hi <= steps && hi <= 8; hi += lo) {
@@ -1367,52 +1345,27 @@ void sym_choose_split(FilterArgs &w, int n_cus) {
     }
 }
 
-// filter<float3> and filter<float> (two buffers per launch), radius 1..20, every spec: Welch degrees of freedom run the Welch builds
-// (six or eight feature planes, like the others).
-// G-buffers: up to two RGB images (six feature planes, the shipped normal + albedo), or up to two RGB and up to two
-// 1-channel images in any order (eight feature planes: + depth + material id; block + halo calls carry them in a
-// 17-channel packed image)
-bool sym_eligible(const FilterArgs &a, int channels) {
-    if (a.radius < 1 || a.radius > sym::kR || (channels != 1 && channels != 3)) return false;
-    // Welch degrees of freedom: the pair needs the sample counts -- from their own images (one RGB buffer, or two float
-    // buffers per launch), or from the last channel of a 16- / 18-channel block + halo image (and those images are for the Welch builds only)
-    if (a.dof != STATMC_DOF_PIXEL && a.packed && a.packed_ch != 16 && a.packed_ch != 18) return false;
-    if (a.packed && (a.packed_ch == 16 || a.packed_ch == 18) && a.dof != STATMC_DOF_WELCH) return false;
-    // the pair-symmetric kernel implements both gates and both channel rules; the clamped border's taps beyond the image
-    // are added by border_virtual_kernel
-    // float buffers with the one-sided gate (four weights per pair for two buffers): one-sided kernel
-    if (a.gate != STATMC_GATE_SYMMETRIC && channels != 3 && a.dof == STATMC_DOF_PIXEL) return false;   // (Welch: one test, no gate form)
-    // (a clamped border on a block + halo image: the border kernel reads the packed image -- round 5; before, such calls ran the
-    // one-sided kernel and a block decomposition was not bit-identical to the whole film, which runs this kernel)
-    int n_rgb = 0, n_sc = 0;
-    for (int g = 0; g < a.n_g; g++) {
-        if (a.g[g].channels == 3) n_rgb++;
-        else if (a.g[g].channels == 1) n_sc++;
-        else return false;
-        if (!(a.g[g].dr <= 0.f) || !std::isfinite(a.g[g].dr)) return false;
-    }
-    if (n_rgb > 2 || n_sc > 2) return false;
-    if (a.packed && n_sc > 0 && a.packed_ch != 17 && a.packed_ch != 18) return false;   // 1-channel features travel in the 17- / 18-channel block + halo image
-    // (a 17-channel image with no 1-channel feature -- FilmShards packs every set other than exactly two RGB G-buffers that way --
-    // runs the eight-plane build with its 1-channel slots at scale 0; the pack kernel writes zeros there)
-    // (Welch with 1-channel features: the eight-plane Welch builds -- from the separate images, or from an 18-channel block + halo
-    // image, which carries the 1-channel features AND the sample counts)
-    return true;
-}
-
-void sym_feature_slots(FilterArgs &a) {
-    a.sym.g8 = 0;
-    for (int i = 0; i < 2; i++) {
-        a.sym.rgb[i] = a.sym.sc[i] = nullptr;
-        a.sym.rgb_scale[i] = a.sym.sc_scale[i] = 0.f;
-    }
-    int n_rgb = 0, n_sc = 0;
-    for (int g = 0; g < a.n_g; g++) {
-        const float scale = sqrtf(-a.g[g].dr * kLog2e);
-        if (a.g[g].channels == 3 && n_rgb < 2) { a.sym.rgb[n_rgb] = a.g[g].data; a.sym.rgb_scale[n_rgb++] = scale; }
-        else if (a.g[g].channels == 1 && n_sc < 2) { a.sym.sc[n_sc] = a.g[g].data; a.sym.sc_scale[n_sc++] = scale; }
-    }
-    a.sym.g8 = n_sc > 0 || (a.packed && (a.packed_ch == 17 || a.packed_ch == 18));
+// The pair-symmetric kernel's share of a plan: parts -- and the tail split -- are chosen for the WHOLE local image whatever
+// region the call filters; so is the workspace: the bands of the Upload / Denoise / Download pipeline then share one allocation
+// (growing it mid-pipeline means a stream synchronisation and a hipFree between two bands).  Then the launch's own tile range.
+void sym_layout(FilterArgs &k, int n_cus, int split, FilterPlan &p) {
+    FilterArgs whole = k;
+    whole.rx0 = 0; whole.ry0 = 0; whole.rx1 = k.width; whole.ry1 = k.height;
+    sym_geometry(whole);
+    sym_choose_split(whole, n_cus, split);
+    sym_apply_split(whole);
+    k.n_parts = whole.n_parts;
+    k.sym.parts_hi = whole.sym.parts_hi;
+    k.sym.split_ty = whole.sym.split_ty;
+    sym_geometry(k);
+    sym_apply_split(k);
+    const size_t px = (size_t)k.width * k.height;
+    p.patch_floats = (sym_patch_floats(whole, k.n_parts) + 3) & ~(size_t)3;
+    p.image_floats = k.sym.pair ? 9 * px : 0;   // filter<float>: the three RGB-shaped images every launch packs its two buffers into
+    p.extra_floats = k.border == STATMC_BORDER_CLAMP ? 4 * px : 0;
+    p.redo_floats = k.dof == STATMC_DOF_WELCH ? ((size_t)sym_items(whole) + 3) & ~(size_t)3 : 0;
+    p.redo_items = (int)sym_items(k);
+    p.tail_rows = whole.sym.parts_hi ? whole.sym.ty0 + whole.sym.nty - whole.sym.split_ty : 0;
 }
 
 hipError_t launch_sym(FilterArgs a, hipStream_t s) {
@@ -1474,17 +1427,9 @@ hipError_t launch_sym(FilterArgs a, hipStream_t s) {
         kernel_far = pair ? SYM_WELCH(kModeWelchPairFar) : joint ? SYM_WELCH(kModeWelchJointFar) : SYM_WELCH(kModeWelchFar);
 #undef SYM_WELCH
     }
-    static std::mutex mu;
-    static std::set<std::pair<int, const void *>> done;
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (const void *kf : {kernel, kernel_far}) {
-            if (kf == nullptr || done.count({dev, kf})) continue;
-            if (hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); e != hipSuccess) return e;
-            done.insert({dev, kf});
-        }
+    for (const void *kf : {kernel, kernel_far}) {
+        if (kf == nullptr) continue;
+        if (hipError_t e = allow_full_lds(kf); e != hipSuccess) return e;
     }
     const dim3 grid((unsigned)sym_items(a));
     void *kargs[] = {&a};

@@ -135,6 +135,9 @@ def test_per_device_state_needs_setup(lib):
     assert lib.statmc_set_t_quantiles(0, q, 4) == api.ERR_NO_DEVICE
     assert lib.statmc_debug_accumulate_dma(1) == api.ERR_NO_DEVICE
     assert lib.statmc_debug_accumulate_dma(3) == api.ERR_INVALID     # 0 or 1: the library holds one ring depth
+    assert lib.statmc_debug_force_filter_variant(1) == api.ERR_NO_DEVICE
+    assert lib.statmc_debug_force_filter_variant(4) == api.ERR_INVALID     # 0 .. 3: no value quietly means another
+    assert lib.statmc_debug_force_filter_variant(-1) == api.ERR_INVALID
 
 
 def test_filter_spec_struct_layout(lib):

@@ -7,7 +7,7 @@ import torch
 from statmc_amd import api, film, synthetic
 
 W, H = 1920, 1080
-RADIUS = int(sys.argv[1]) if len(sys.argv) > 1 else 20      # (STATMC_FLOAT_MIX=0: odd counts stay on the pair-symmetric kernel)
+RADIUS = int(sys.argv[1]) if len(sys.argv) > 1 else 20      # (odd counts end with three buffers on the one-sided kernel; to time them without that tail, build a variant: README.md)
 dev = torch.device("cuda:0")
 api.setup(0)
 scene = synthetic.Scene(W, H, seed=1, device=dev)

@@ -152,9 +152,9 @@ int statmc_free(void *dev_ptr);   /* blocks of statmc_malloc and of statmc_mallo
  * sample arenas in the others the 1080p / 256-spp launch of all stat types runs at 0.85 of the HBM peak instead of 0.76
  * (4K / 64 spp: 0.79 instead of 0.68; DESIGN.md section 4.1a, tools/experiments/acc_pool.py fastslow) -- the same kernel, the
  * same bits.  The class travels with the physical memory and HIP does not expose it, so the allocator MEASURES it: one reserved address range per device, backed GiB by GiB, every GiB probed
- * against two GiB of the allocator's own (0.2 ms each; statmc_amd/csrc/statmc_placement.hip).
+ * against two GiB of the allocator's own, the reference and a second target (0.2 ms each; statmc_amd/csrc/statmc_placement.hip).
  *   role STATMC_MEM_STATE   images a kernel reads AND writes per launch: n, mean, m2, m3, film-mean, film-m2 (the first 960 MiB in
- *                           the very GiB every other one is probed against, the rest in slots of its class, A)
+ *                           the reference, the very GiB every other one is probed against, the rest in slots of its class, A)
  *   role STATMC_MEM_STREAM  read-once inputs: the sample arenas of statmc_accumulate / statmc_accumulate_tiles (all in ONE of the
  *                           other two classes while the card has room: arenas spread over both cost 2 - 3 % of the gain)
  * Blocks are 2-MiB aligned, contiguous in the address space (a block above 2 GiB is GiB slots of one class from anywhere on the
@@ -168,8 +168,9 @@ int statmc_free(void *dev_ptr);   /* blocks of statmc_malloc and of statmc_mallo
  * the call still succeeds with memory as it comes (statmc_placement_info says so); STATMC_PLACEMENT=0 in the environment
  * makes it hipMalloc.  Not to be called while a kernel of the caller's runs (the probe competes for the memory system).
  * (ROCm 7.2 / gfx950: hipMemUnmap leaves the shaders' address translation in place -- memory mapped at an address that was mapped
- * before is not what kernels see until the driver rewrites the page tables; the allocator forces that after every unmap, so addresses
- * it uses again -- windows, filled holes -- reach their own memory: tools/microbench/vmm_remap.hip) */
+ * before is not what kernels see there.  The allocator never maps an address twice: a freed window's addresses and the holes
+ * statmc_placement_trim leaves are not used again, and a full range is followed by a fresh one: tools/microbench/vmm_remap.hip,
+ * DESIGN.md section 4.1a.) */
 #define STATMC_MEM_STATE 0
 #define STATMC_MEM_STREAM 1
 int statmc_malloc_placed(void **dev_ptr, size_t bytes, int role);
@@ -182,7 +183,7 @@ typedef struct statmc_placement_info_t {
     int32_t active;          /* 1: slots are told apart and dealt by class */
     int32_t virtual_memory;  /* 1: the device maps physical allocations into reserved ranges (hipMemCreate / hipMemMap) */
     int32_t slots, probes;   /* GiB slots backed (the allocator's own included), probes run */
-    int32_t slots_a, slots_b, slots_c, slots_unclear;   /* by class: A = the allocator's first slot's (STATE), B = its second probe target's (STREAM), C */
+    int32_t slots_a, slots_b, slots_c, slots_unclear;   /* by class: A = the reference's (STATE), B = the second probe target's (STREAM), C */
     int32_t slots_idle;      /* backed, probed, dealt to no role (yet) */
     int32_t slots_as_they_came[2];   /* per role: slots dealt without the wanted class (no room for better) */
     float fast_probe_ms, slow_probe_ms;
@@ -190,17 +191,17 @@ typedef struct statmc_placement_info_t {
     int32_t slots_released;  /* holes statmc_placement_trim left in the range (not counted in `slots`) */
     int32_t peer_devices;    /* devices besides the owner that the blocks are mapped for (statmc_copy_rect / statmc_halo_exchange operands) */
     int32_t peak_slots;      /* most GiB slots backed at any one time (what the class searches held before statmc_placement_trim) */
-    int32_t rebased;         /* 1: the allocator's reference slot traded places with a slot of another class, because the card's first
-                                slots were mostly of the first one's (the moments' home should be the class the card has least of) */
+    int32_t rebased;         /* 1: the reference moved to a slot of another class, because the card's first slots were mostly of the
+                                first reference's (the moments' home should be the class the card has least of) */
 } statmc_placement_info_t;
 int statmc_placement_info(statmc_placement_info_t *out);   /* current device */
 /* Gives the memory of the idle slots of the current device (backed and probed, dealt to no role: the classes nobody asked for)
  * back to the driver; returns how many, or a negative error.  Synchronises the device.  Later statmc_malloc_placed calls back
- * and probe new slots as they need them (the released addresses first). */
+ * and probe new slots as they need them (new slots behind the holes: released addresses are not mapped again). */
 int statmc_placement_trim(void);
-/* One character per GiB slot of the current device, NUL-terminated: '#' the allocator's own, a / b / c an idle slot of
- * that class, A / B / C one dealt to a role, S / T one dealt to the state / stream role without the wanted class, '?' unclear,
- * '_' released by statmc_placement_trim. */
+/* One character per GiB slot of the current device, NUL-terminated: '#' the allocator's own (the reference -- slot 0 unless
+ * `rebased` -- and the second probe target), a / b / c an idle slot of that class, A / B / C one dealt to a role, S / T one dealt
+ * to the state / stream role without the wanted class, '?' unclear, '_' released by statmc_placement_trim (a hole for good). */
 int statmc_placement_map(char *out, int capacity);
 /* Page-locked host memory for the staging side of statmc_upload / statmc_download (sample arenas
  * of the tile path, dump buffers): copies from it run at the full PCIe rate and stay asynchronous. */

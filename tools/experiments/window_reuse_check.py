@@ -1,5 +1,5 @@
-"""A window block at the addresses a freed window left: do the two live blocks share memory?  (statmc_placement.hip, flush_translations;
-tests/test_placement_gpu.py::test_a_window_at_addresses_another_window_left_reaches_its_own_memory runs the same steps.)
+"""A window block made after another window was freed: do the two live blocks share memory?  (statmc_placement.hip, map_fresh: the
+new window takes fresh addresses; tests/test_placement_gpu.py::test_windows_take_fresh_addresses_and_reach_their_own_memory runs the same steps.)
 python tools/experiments/window_reuse_check.py [library.so]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -21,7 +21,7 @@ pa = a.data_ptr()
 torch.cuda.synchronize()
 del a
 b = api.empty_placed((G,), torch.float32, dev, api.MEM_STREAM)          # takes the first slot the window gave back
-c = api.empty_placed((3 * G,), torch.float32, dev, api.MEM_STREAM)      # a window again: other slots, the first window's addresses
+c = api.empty_placed((3 * G,), torch.float32, dev, api.MEM_STREAM)      # a window again: other slots, fresh addresses
 print("second window at the first one's addresses:", c.data_ptr() == pa, api.placement_info()["map"])
 b.fill_(2.0)
 c.fill_(3.0)

@@ -1,5 +1,6 @@
-// Does a physical allocation mapped at a virtual address another one has just left reach the shaders?  (statmc_placement.hip: the
-// reference slot's trade, holes of the range filled again after statmc_placement_trim, window slots used again.)
+// Does a physical allocation mapped at a virtual address another one has just left reach the shaders?  On ROCm 7.2 / gfx950 it does
+// not (profiles/r06_vmm_remap.log), which is why statmc_placement.hip never maps an address twice (map_fresh) and never gives a
+// range back.
 // hipcc --offload-arch=gfx950 -O2 -o vmm_remap tools/microbench/vmm_remap.hip && ./vmm_remap
 #include <hip/hip_runtime.h>
 #include <stdio.h>

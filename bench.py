@@ -24,6 +24,12 @@ Two ways to run N > 1, same step order, same JSON line (`backend` says which):
                      statmc_prepass_pack_rows -> statmc_halo_exchange (device-to-device copies, peer access over
                      xGMI) -> statmc_window_filter.  No torch.distributed, no RCCL.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: the headline
+figure and what the timed steps' own events give (per-stage times, rooflines).  Everything that takes runs of its own
+-- the shader clock held behind the kernels, the CPU baseline, the secondary legs (other configurations, schedules,
+feeds, buffer sets, host copies), the N > 1 gather time, overlap self-check and eight-feature filter -- runs only
+with --full (--no-cpu-baseline / --no-host-legs leave parts of it out).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -107,7 +113,11 @@ def parse():
     ap.add_argument("--grid", default="rows", choices=("rows", "blocks"),
                     help="N > 1: rows = 1xN strips of full-width blocks (contiguous halo rows, default); "
                          "blocks = 2x1 / 2x2 / 4x2 grid")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline figure does not need: the shader clock "
+                         "behind the kernels, the CPU baseline and the secondary legs (N = 1), the gather time, the overlap "
+                         "self-check and the eight-feature filter (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (N = 1)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo", "peer"),
                     help="N > 1: nccl = one process per GPU, halo exchange over torch.distributed / RCCL (default; if it gives no "
                          "result, the peer leg runs in a fresh process and the line says so); peer = ONE process drives all N devices "
@@ -126,7 +136,8 @@ def parse():
                          "two builds run with the same arguments can be compared output for output")
     ap.add_argument("--share-device", action="store_true", help="debug: every rank uses cuda:0")
     ap.add_argument("--cpu-acc-rows", type=int, default=32, help="rows of the film the CPU baseline accumulates")
-    ap.add_argument("--no-host-legs", action="store_true", help="skip the secondary host-side measurements (N = 1)")
+    ap.add_argument("--no-host-legs", action="store_true", help="--full: skip the secondary measurements (N = 1: host-side legs and other "
+                                                                 "configurations; N > 1: the eight-feature filter)")
     ap.add_argument("--feed", choices=("film", "tiles"), default="film",
                     help="how the timed step's samples reach the accumulation: film-major planes through statmc_accumulate (default), or "
                          "16 x 16 tile blocks through statmc_accumulate_tiles, the way Render<T> hands them over (N = 1, --schedule single)")
@@ -1366,10 +1377,10 @@ def main():
     # per-STEP totals of every stage (a reference-schedule step launches each stage n_iter times)
     ms = {k: (sum(a.elapsed_time(b) for a, b in v) / args.steps) for k, v in k_events.items()}
 
-    # ---- outside the timed region: film-f assembled on rank 0 (SURVEY 8e "final gather", 12 B/px), and the shader
-    # clock the chip holds right behind the two big kernels (one wave counting shader cycles against the 100 MHz clock)
+    # ---- outside the timed region, --full only: film-f assembled on rank 0 (SURVEY 8e "final gather", 12 B/px), and the
+    # shader clock the chip holds right behind the two big kernels (one wave counting shader cycles against the 100 MHz clock)
     gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         block = pipe.window_filter()
         times = []
         for _ in range(5):
@@ -1381,63 +1392,64 @@ def main():
         t = torch.tensor([sorted(times)[len(times) // 2]], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         gather_ms = float(t.item())
-    # The shader clock the chip HOLDS while a kernel runs: one wave on a side stream counts shader clocks (s_memtime) against
-    # the constant 100 MHz clock (s_memrealtime) beside the kernel -- released together with it by an event recorded in
-    # front of the kernel, it gets a CU as soon as one of the kernel's workgroups retires and counts for about the
-    # kernel's duration.  (A probe enqueued BEHIND the kernel reads the idle clock: 2.3 - 2.4 GHz whatever ran before.)
-    clocks = {}
-    slots = torch.zeros(2 * 8, 2, dtype=torch.int64, device=dev)
-    idx = {"accumulate": 0, "filter": 0}
-    side = torch.cuda.Stream(device=dev)
-    main_stream = torch.cuda.current_stream()
     n_acc_launches = sum(len(pool_slices(sum(batches[:i]), b, pool)) for i, b in enumerate(batches))
-    acc_ms_total = ms["interior_accumulate"] if border else ms["accumulate"]
-    est_ms = {"accumulate": acc_ms_total / max(1, n_acc_launches), "filter": ms["filter"] / n_iter}
-    import ctypes
-    C_void = ctypes.c_void_p
+    clocks = None
+    if args.full:
+        # The shader clock the chip HOLDS while a kernel runs: one wave on a side stream counts shader clocks (s_memtime) against
+        # the constant 100 MHz clock (s_memrealtime) beside the kernel -- released together with it by an event recorded in
+        # front of the kernel, it gets a CU as soon as one of the kernel's workgroups retires and counts for about the
+        # kernel's duration.  (A probe enqueued BEHIND the kernel reads the idle clock: 2.3 - 2.4 GHz whatever ran before.)
+        slots = torch.zeros(2 * 8, 2, dtype=torch.int64, device=dev)
+        idx = {"accumulate": 0, "filter": 0}
+        side = torch.cuda.Stream(device=dev)
+        main_stream = torch.cuda.current_stream()
+        acc_ms_total = ms["interior_accumulate"] if border else ms["accumulate"]
+        est_ms = {"accumulate": acc_ms_total / max(1, n_acc_launches), "filter": ms["filter"] / n_iter}
+        import ctypes
+        C_void = ctypes.c_void_p
 
-    def probed(name, fn, *a):
-        i = idx[name]
-        if rank != 0 or i >= 8:
+        def probed(name, fn, *a):
+            i = idx[name]
+            if rank != 0 or i >= 8:
+                return fn(*a)
+            idx[name] = i + 1
+            go = torch.cuda.Event()
+            go.record(main_stream)
+            side.wait_event(go)
+            cycles = int(min(max(est_ms[name] * 0.8 * 2.0e6, 5e4), 1.6e7))       # ~80 % of the kernel's time at 2 GHz
+            api.clock_probe(slots[(0 if name == "accumulate" else 8) + i], cycles=cycles, stream=C_void(side.cuda_stream))
             return fn(*a)
-        idx[name] = i + 1
-        go = torch.cuda.Event()
-        go.record(main_stream)
-        side.wait_event(go)
-        cycles = int(min(max(est_ms[name] * 0.8 * 2.0e6, 5e4), 1.6e7))       # ~80 % of the kernel's time at 2 GHz
-        api.clock_probe(slots[(0 if name == "accumulate" else 8) + i], cycles=cycles, stream=C_void(side.cuda_stream))
-        return fn(*a)
 
-    def probe_step():
-        if args.schedule == "reference":
-            fs.reset()
-        pos = 0
-        for b in batches:
-            probed("accumulate", accumulate_range, pos, b)
-            pos += b
-            pipe.prepass()
-            if world > 1:
-                pipe.exchange()
-            block = probed("filter", pipe.window_filter)
-            if world > 1 and args.gather:
-                pipe.gather_film(block, film_f)
-    for _ in range(max(1, 8 // n_iter)):     # every rank steps (the halo exchange is collective); rank 0 probes
-        probe_step()
-    torch.cuda.synchronize()
-    if rank == 0:
-        clocks = read_clock_slots(slots, idx)
-    if world > 1:
-        barrier()
+        def probe_step():
+            if args.schedule == "reference":
+                fs.reset()
+            pos = 0
+            for b in batches:
+                probed("accumulate", accumulate_range, pos, b)
+                pos += b
+                pipe.prepass()
+                if world > 1:
+                    pipe.exchange()
+                block = probed("filter", pipe.window_filter)
+                if world > 1 and args.gather:
+                    pipe.gather_film(block, film_f)
+        for _ in range(max(1, 8 // n_iter)):     # every rank steps (the halo exchange is collective); rank 0 probes
+            probe_step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            clocks = read_clock_slots(slots, idx)
+        if world > 1:
+            barrier()
 
     # ---- the overlapped order against the plain one, on this run's own backend (the asynchronous nccl branch
     # -- border chain on this stream, interior on the side stream, sends and receives in flight until the join -- is
     # otherwise never compared with anything): from empty statistics, three steps each way, the filtered blocks must be
-    # the same bits on every rank.
+    # the same bits on every rank.  --full; without it, --dump-film-f alone still runs the overlapped order's three steps.
     self_check = None
     dump_block = None
     if world > 1:
         outs = []
-        for overlapped in (True, False):
+        for overlapped in (True, False) if args.full else (True,) if args.dump_film_f else ():
             fs.reset()
             blk = None
             for _ in range(1 if args.schedule == "reference" else 3):
@@ -1446,15 +1458,16 @@ def main():
             outs.append(blk.clone())
             if overlapped:
                 dump_block = outs[0]
-        same = torch.tensor([1.0 if torch.equal(outs[0], outs[1]) else 0.0], device=cdev)
-        dist.all_reduce(same, op=dist.ReduceOp.MIN)
-        self_check = {"overlapped_vs_plain_order": "bit-identical" if float(same.item()) == 1.0 else "DIFFERENT",
-                      "ranks": world, "backend": args.backend, "overlapped_order_used": bool(border),
-                      "steps_each": 1 if args.schedule == "reference" else 3}
+        if len(outs) == 2:
+            same = torch.tensor([1.0 if torch.equal(outs[0], outs[1]) else 0.0], device=cdev)
+            dist.all_reduce(same, op=dist.ReduceOp.MIN)
+            self_check = {"overlapped_vs_plain_order": "bit-identical" if float(same.item()) == 1.0 else "DIFFERENT",
+                          "ranks": world, "backend": args.backend, "overlapped_order_used": bool(border),
+                          "steps_each": 1 if args.schedule == "reference" else 3}
     # secondary, N > 1: the block's window filter with all four feature types as G-buffers (eight feature planes: a
     # 17-channel block + halo image through the same pack / exchange / filter path), on 8 samples of the pool
     eight = None
-    if world > 1 and args.channels == 11 and not args.no_host_legs:
+    if world > 1 and args.channels == 11 and args.full and not args.no_host_legs:
         # (no collective inside the try: a rank that fails here must not leave the others waiting; the halo of the 17-channel
         # image stays zero -- the filter's time does not depend on what the halo holds)
         names = ("materialid", "depth", "normal", "albedo")
@@ -1521,12 +1534,12 @@ def main():
         if eight is not None:
             result["filter_8_feature_channels"] = eight
         # (before the host-side legs: their page-locked staging buffers and band pipelines keep threads and memory busy)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 result["cpu_baseline"] = cpu_baseline(args, fs, samples, types)
             except Exception as e:          # noqa: BLE001
                 result["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, str(e)[-300:])}
-        if world == 1 and not args.no_host_legs:
+        if world == 1 and args.full and not args.no_host_legs:
             # secondary measurements, outside `value`: the reference's own `CUDA time` bracket through the C++ host
             # side, the tile-fed accumulation, and the raw host <-> device copy rates
             # (a failure in one of them must not cost the headline line: it is reported in place)
@@ -1759,7 +1772,7 @@ def build_result(c):
         "metric": "denoised_mpixels_per_s", "value": round(value, 3), "unit": "Mpixels/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling if world > 1 else "strong",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
         "n_ranks_seen": c["n_ranks_seen"], "backend": c["backend"] if world > 1 else "single",
         "config": {
             # (the driver keeps 120 characters of this string: the facts that must survive come first and are keys of their own below)
@@ -1820,9 +1833,9 @@ def build_result(c):
         result["experiment"] = {k: os.environ[k] for k in ("STATMC_VARIANT", "STATMC_BENCH_ACC_RESIDENT", "STATMC_BENCH_ACC_DMA") if k in os.environ}
     if world > 1:
         g = c["gather_ms"]
-        result["gather_ms"] = round(g, 4)
-        result["gather"] = {"ms": round(g, 4), "in_step": bool(args.gather), "bytes": 12 * fw * fh,
-                            "what": "film-f blocks assembled on rank 0 / device 0 (median of 5)"}
+        result["gather_ms"] = None if g is None else round(g, 4)
+        result["gather"] = {"ms": result["gather_ms"], "in_step": bool(args.gather), "bytes": 12 * fw * fh,
+                            "what": "film-f blocks assembled on rank 0 / device 0 (median of 5; measured with --full)"}
         if args.gather:
             result["kernels"]["gather"] = {"ms_per_step": round(ms["gather"], 4)}
         result["block_step_prediction"] = pred
@@ -1938,19 +1951,22 @@ def main_peer(args):
         ms["prepass"] = span("accumulated", "border")
         ms["halo"] = span("border", "exchange")
         ms["filter"] = span("exchange", "filter")
-    # film-f assembled on device 0 (SURVEY 8e "final gather")
-    film_f = torch.empty(fh, fw, 3, dtype=torch.float32, device=pf.blocks[0].dev)
-    times = []
-    for _ in range(5):
-        pf.synchronize()
-        g0 = time.perf_counter()
-        pf.gather(film_f)
-        pf.synchronize()
-        times.append((time.perf_counter() - g0) * 1e3)
-    gather_ms = sorted(times)[len(times) // 2]
-    # overlapped against plain order, from empty statistics (same bits)
+    # --full: film-f assembled on device 0 (SURVEY 8e "final gather")
+    gather_ms = None
+    if args.full:
+        film_f = torch.empty(fh, fw, 3, dtype=torch.float32, device=pf.blocks[0].dev)
+        times = []
+        for _ in range(5):
+            pf.synchronize()
+            g0 = time.perf_counter()
+            pf.gather(film_f)
+            pf.synchronize()
+            times.append((time.perf_counter() - g0) * 1e3)
+        gather_ms = sorted(times)[len(times) // 2]
+    # --full: overlapped against plain order, from empty statistics (same bits); --dump-film-f alone: the first of them
     self_check, outs = None, []
-    for pl in ([plans, make_plans(overlap=False)] if pf.overlap else [plans]):
+    orders = ([plans, make_plans(overlap=False)] if pf.overlap else [plans]) if args.full else [plans] if args.dump_film_f else []
+    for pl in orders:
         pf.reset()
         for _ in range(1 if args.schedule == "reference" else 3):
             if args.schedule == "reference":
@@ -1967,7 +1983,7 @@ def main_peer(args):
         import numpy as np
         np.save(args.dump_film_f, outs[0].cpu().numpy())
     eight = None
-    if n > 1 and args.channels == 11 and not args.no_host_legs:
+    if n > 1 and args.channels == 11 and args.full and not args.no_host_legs:
         try:
             names = ("materialid", "depth", "normal", "albedo")
             pf8 = peer.PeerFilm(n, W, H, r, devices, types, filter_sd=args.filtersd, grid=grid, overlap=False, g_buffers=names)

@@ -38,3 +38,13 @@ def test_outputs_over_the_limit_are_a_fixed_sample_of_pixels(tmp_path, monkeypat
 def test_steps_must_be_positive():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 2 and "--steps must be at least 1" in out.stderr
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and (args.steps, args.warmup) == (5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    args = bench.parse()
+    assert args.full is True and args.no_cpu_baseline

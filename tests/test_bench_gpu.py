@@ -5,6 +5,7 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -20,7 +21,7 @@ def _line(out):
 
 
 def test_single_gpu_line(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + COMMON + ["--cpu-acc-rows", "8"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + COMMON + ["--cpu-acc-rows", "8"],
                          capture_output=True, text=True, timeout=360)
     assert out.returncode == 0, out.stderr[-2000:]
     r = _line(out)
@@ -70,7 +71,7 @@ def test_placement_check_can_hand_the_step_to_the_allocators_memory(gpu):
     """bench.py runs the step on the placed buffers and on copies from torch's allocator before it times, and the faster set goes on
     (one card in six gives the placed allocator little to choose from).  The other branch, forced: the line says
     which set ran, the placed blocks are gone, every later leg runs on plain memory."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + COMMON + ["--no-cpu-baseline"], capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + COMMON + ["--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=360, env=dict(os.environ, STATMC_BENCH_CHECK_PICKS="allocator"))
     assert out.returncode == 0, out.stderr[-2000:]
     r = _line(out)
@@ -117,12 +118,51 @@ def test_dump_outputs_holds_the_last_timed_step(gpu, tmp_path):
     assert np.array_equal(got, np.load(fresh))
 
 
+SECONDARY_KEYS = ("cpu_baseline", "accumulate_placement_ab", "reference_schedule", "config1_1280x720_64spp", "cuda_time_bracket",
+                  "tile_fed_accumulate", "accumulate_by_batch", "accumulate_by_batch_3840x2160", "config4_3840x2160_64spp_one_gpu",
+                  "host_copies", "filter_8_feature_channels", "filter_float_buffers", "pcie_inclusive")
+
+
+def test_plain_default_run_is_lean(gpu, tmp_path):
+    """Without --full, the default workload (1920 x 1080, 256 spp) sets up, warms up, times its steps, writes --dump-outputs and
+    prints the line -- the headline figure and what the timed steps' own events give, none of the legs that take runs of their
+    own -- and spends well under 30 s outside its steps."""
+    steps, warmup = 3, 1
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=360)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = _line(out)
+    assert r["metric"] == "denoised_mpixels_per_s" and r["unit"] == "Mpixels/s" and r["higher_is_better"] and r["dtype"] == "f32"
+    assert r["full"] is False and r["steps"] == steps and r["config"]["film"] == "1920x1080" and r["config"]["spp"] == 256
+    assert abs(r["value"] - 1920 * 1080 / r["ms_per_step"] / 1e3) < 1e-2 * r["value"]
+    assert r["kernels"]["accumulate"]["ms_per_step"] > 0 and r["kernels"]["filter"]["ms_per_step"] > 0 and r["roofline"]["frac"] > 0
+    assert r["shader_clock"] is None and not any(k in r for k in SECONDARY_KEYS), sorted(r)
+    assert r["dumped_outputs"]["arrays"]["film_f"]["shape"] == [1080, 1920, 3]
+    assert wall - (steps + warmup) * r["ms_per_step"] / 1e3 < 30.0, wall
+
+
+@pytest.mark.parametrize("backend", ["gloo", "peer"])
+def test_plain_two_block_run_leaves_the_checks_to_full(gpu, backend):
+    """N > 1 without --full: the timed step and its own per-stage times; no gather timing, overlap self-check or eight-feature filter."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend, "--share-device"] + COMMON
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=360, env=_clean_env())
+    assert out.returncode == 0, out.stderr[-3000:]
+    r = _line(out)
+    assert r["full"] is False and r["backend"] == backend and r["n_ranks_seen"] == 2 and r["value"] > 0
+    assert abs(r["value"] - 512 * 256 / r["ms_per_step"] / 1e3) < 1e-2 * r["value"]
+    assert r["kernels"]["border_chain"]["ms_per_step"] > 0 and r["kernels"]["filter"]["ms_per_step"] > 0
+    assert r["overlap_self_check"] is None and r["gather_ms"] is None and r["gather"]["ms"] is None
+    assert "filter_8_feature_channels" not in r
+
+
 @pytest.mark.parametrize("grid,blocks", [("rows", "1x2"), ("blocks", "2x1")])
 def test_strong_scaling_two_ranks_share_the_device(gpu, grid, blocks):
     """`python bench.py --gpus 2` with NO launcher around it: bench.py starts its own ranks (fresh processes, before
     any GPU call in the parent) and relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--share-device",
            "--grid", grid] + COMMON
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=360, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -150,7 +190,7 @@ def test_two_ranks_with_placed_buffers(gpu):
     here two ranks share the box's GPU, each with its own slots): same self-checks as the plain two-rank run."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["STATMC_BENCH_PLACED_ON_SHARED_DEVICE"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device"] + COMMON
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--share-device"] + COMMON
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=360, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)
@@ -206,7 +246,7 @@ def test_peer_leg_one_process_all_blocks_and_same_bits_as_the_rank_leg(gpu, tmp_
     dumps = {}
     for backend in ("peer", "gloo"):
         dumps[backend] = str(tmp_path / ("film_f_%s.npy" % backend))
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", backend, "--share-device",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", backend, "--share-device",
                "--dump-film-f", dumps[backend], "--dump-outputs", str(tmp_path / backend)] + COMMON
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=360, env=_clean_env())
         assert out.returncode == 0, out.stderr[-3000:]

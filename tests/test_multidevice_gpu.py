@@ -79,7 +79,7 @@ def test_peer_film_on_two_devices_equals_the_whole_film(gpu, grid, bw, bh):
 
 def test_bench_two_gpus_nccl_leg(gpu, tmp_path):
     dump = str(tmp_path / "nccl.npy")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-fallback", "--dump-film-f", dump] + COMMON,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--no-fallback", "--dump-film-f", dump] + COMMON,
                          capture_output=True, text=True, timeout=900, env=_env())
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)
@@ -90,7 +90,7 @@ def test_bench_two_gpus_nccl_leg(gpu, tmp_path):
 
 
 def test_bench_two_gpus_forced_nccl_failure_lands_on_the_peer_leg(gpu):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + COMMON, capture_output=True, text=True, timeout=900,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2"] + COMMON, capture_output=True, text=True, timeout=900,
                          env=_env(STATMC_BENCH_FAIL_NCCL="1"))
     assert out.returncode == 0, out.stderr[-3000:]
     r = _line(out)

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 for round in 1 2; do
 for n in ${NS:-0 256}; do
-  STATMC_BENCH_ACC_RESIDENT=$n python bench.py --no-cpu-baseline --no-host-legs --steps 200 2> /dev/null | python -c "
+  STATMC_BENCH_ACC_RESIDENT=$n python bench.py --full --no-cpu-baseline --no-host-legs --steps 200 2> /dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('resident', $n, 'step', d['ms_per_step'], 'acc', d['kernels']['accumulate']['ms_per_step'], 'filter', d['kernels']['filter']['ms_per_step'], d['shader_clock']['during_accumulate_GHz'], d['shader_clock']['during_filter_GHz'], d['placement'].get('map'), flush=True)

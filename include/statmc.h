@@ -391,6 +391,24 @@ typedef struct statmc_stat_type {
 
 int statmc_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                       void *stream);
+
+/* ---- accumulating inside the renderer's own kernel (include/statmc_device_api.hpp: statmc::device::PixelStats folds a sample
+ * held in registers into a statmc_stat_type's images -- the bits of statmc_accumulate, no sample arena).  Its pre-pass store
+ * needs what the accumulation's epilogue reads from the library's per-device state; a user's code object cannot see the
+ * library's symbols, so the state is handed over as a value:
+ *   t_table  device pointer to the current device's Student-t table of its significance level and sides (statmc_filter_spec.sides):
+ *            4096 quantiles for dof = 1 .. 4096, indexed by dof - 1 (larger dof reuse the last entry)
+ *   flags    the epilogue's encoding: 1 = STATMC_DOF_WELCH (the pre-pass multiplies with t = 1), 2 = STATMC_SMALL_N_EXCLUDE
+ * Valid for the current device until its significance level or filter spec changes (statmc_set_significance,
+ * statmc_set_filter_spec, statmc_reset_filter_spec, statmc_copy_device_settings): query again after those.  The table's
+ * address stays put: statmc_set_t_quantiles rewrites it in place, so kernels enqueued after that call read the new quantiles.
+ * Returns STATMC_ERR_NO_DEVICE before statmc_setup of the current device. */
+typedef struct statmc_prepass_context {
+    const float *t_table;
+    int32_t flags;
+    int32_t reserved;   /* 0 */
+} statmc_prepass_context;
+int statmc_get_prepass_context(statmc_prepass_context *out);
 /* The same for rows [y0, y1) of the film only (the descriptors still describe the whole film: samples
  * [n_samples][height][width][channels], whole state images).  Per-pixel work, so any split of a batch into row ranges
  * leaves the same bits; the multi-GPU step accumulates the rows next to a neighbour first and the rest while their

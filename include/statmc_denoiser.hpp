@@ -1071,6 +1071,35 @@ class Estimator {
         std::unique_lock<std::mutex> lk(acc.mu);
         flushLocked(lk);
     }
+    // ---- accumulating inside the renderer's own kernel (include/statmc_device_api.hpp)
+    // The device images of (statTypeIndex, bounceIndex) as a statmc_stat_type, with channels / transform / max_moment of its
+    // configuration (samples and n_samples are not set): what statmc::device::PixelStats loads from and stores to.  withPrepass
+    // also sets mean_corr / discriminator to the type's "-mean-corr" / "-discriminator" images, for the pre-pass store
+    // (max_moment 3; its statmc_prepass_context comes from statmc_get_prepass_context).  Needs EnableDeviceAccumulation(); samples
+    // staged by Merge*Tile(s) so far are flushed first, so that a kernel enqueued on DeviceStream() afterwards folds its samples
+    // behind them.  After such a kernel Upload / Denoise / Download and DownloadStatistics behave as after a flush.
+    statmc_stat_type DeviceStatistics(unsigned char statTypeIndex, unsigned char bounceIndex, bool withPrepass = false) {
+        {
+            std::lock_guard<std::mutex> lk(acc.mu);
+            if (!acc.enabled || acc.dry)
+                throw Error(STATMC_ERR_INVALID, "DeviceStatistics: call EnableDeviceAccumulation() first (the statistics must live on the device)");
+        }
+        if (statTypeIndex >= statTypeConfigs.nEnabled || bounceIndex >= statTypeConfigs.configs[statTypeIndex].nBounces)
+            throw Error(STATMC_ERR_INVALID, "DeviceStatistics: no such buffer");
+        const StatTypeConfig &cfg = statTypeConfigs.configs[statTypeIndex];
+        if (withPrepass && cfg.maxMoment < 3) throw Error(STATMC_ERR_INVALID, "DeviceStatistics: the pre-pass needs max_moment 3");
+        FlushSamples();
+        statmc_stat_type t = statTypeFor(statTypeIndex, bounceIndex, nullptr);   // (film_mean / film_m2: transform types only)
+        if (withPrepass) {
+            t.mean_corr = static_cast<float *>(meanCorrBuffers[statTypeIndex][bounceIndex].gpuMat.data());
+            t.discriminator = static_cast<float *>(discriminatorBuffers[statTypeIndex][bounceIndex].gpuMat.data());
+        }
+        return t;
+    }
+    // The stream (hipStream_t) this Estimator enqueues on: a renderer launches its accumulating kernel there, between
+    // DeviceStatistics and Upload / Denoise / Download, or orders it against this stream with events.
+    void *DeviceStream() const { return stream.handle(); }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     size_t flushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nFlushes; }

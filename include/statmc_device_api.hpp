@@ -1,0 +1,187 @@
+// statmc_device_api.hpp -- StatMC's per-sample update as device code a renderer can call inside its own kernel (HIP, gfx950).
+//
+// statmc_accumulate reads every sample back from a film-major arena ([S][H][W][C] fp32) that the renderer wrote.  A renderer
+// that holds a sample in registers right after it traced the path can instead fold it into the statistics on the spot:
+//
+//   statmc::device::PixelStats<C, MAXM, TRANSFORM> ps;
+//   ps.load(t, pixel);                 // t: the (type, bounce)'s statmc_stat_type (samples / n_samples are ignored)
+//   for (...) ps.add(sample);          // C floats per sample, in sample order
+//   ps.store(t, pixel);                // moments and n; store(t, pixel, ctx) also writes mean_corr / discriminator
+//
+// The result is bit for bit what statmc_accumulate leaves after the same samples (one launch or several: the state is the
+// same), and store(t, pixel, ctx) writes what the accumulation's pre-pass epilogue writes.  This header is the one
+// definition of that arithmetic: libstatmc_hip.so's kernels include it too.
+//
+// The bits do not depend on the including translation unit's floating-point flags: every function body starts with
+// `#pragma clang fp contract(off)` (HIP's default -ffp-contract=fast-honor-pragmas would otherwise fuse d * (d - dN) + m2 and
+// change m2), and fast-math / finite-math-only builds are refused below (the pre-pass writes inf and NaN on purpose).  A
+// build that replaces the correctly rounded fp32 division (-fno-hip-fp32-correctly-rounded-divide-sqrt) changes the
+// pre-pass's variance and is not supported either.
+#ifndef STATMC_DEVICE_API_HPP
+#define STATMC_DEVICE_API_HPP
+
+#if defined(__FAST_MATH__) || (defined(__FINITE_MATH_ONLY__) && __FINITE_MATH_ONLY__)
+#error "statmc_device_api.hpp needs IEEE fp32 semantics: compile without -ffast-math / -ffinite-math-only (the pre-pass relies on inf and NaN)"
+#endif
+
+#include <hip/hip_runtime.h>
+
+#include "statmc.h"
+
+namespace statmc {
+namespace device {
+
+// d / n for an integer-valued divisor n in [1, 2^24): `r` is 1/n refined from v_rcp_f32 by one
+// Newton step (shared by every division by the same count: all channels, both Welford chains),
+// then one residual correction of the quotient (Markstein).  Bit-identical to the IEEE
+// quotient for the operand ranges of this path (tests/test_gpu_parity.py::test_exact_division
+// sweeps n = 1..4096 against `/`); 3 + 3 instructions instead of ~10 per division.
+__device__ __forceinline__ float refined_rcp(float nf) {
+#pragma clang fp contract(off)
+    const float y0 = __builtin_amdgcn_rcpf(nf);
+    const float e = __builtin_fmaf(-nf, y0, 1.f);
+    return __builtin_fmaf(e, y0, y0);
+}
+__device__ __forceinline__ float div_by_count(float d, float nf, float r) {
+#pragma clang fp contract(off)
+    const float q0 = d * r;
+    const float rem = __builtin_fmaf(-q0, nf, d);
+    return __builtin_fmaf(rem, r, q0);
+}
+
+// The running state of one element (pixel x channel): Box-Cox moments and the raw-sample chain (transform types).
+struct ElemState {
+    float mean, m2, m3, fmean, fm2;
+};
+
+// One sample into one element; nf = the element's count INCLUDING this sample, r = refined_rcp(nf).
+template <int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void add_sample(ElemState &st, float nf, float r, float smp) {
+#pragma clang fp contract(off)
+    // estimator.h:215 -- boxCox(sample, .5f) = (pow(v, .5) - 1) / .5; v_sqrt_f32 (1 ulp) stands
+    // in for pow(v, .5), itself only faithfully rounded in the reference's libm.
+    const float v = TRANSFORM ? (__builtin_amdgcn_sqrtf(smp) - 1.f) / .5f : smp;
+    const float d = v - st.mean;
+    const float dN = div_by_count(d, nf, r);
+    if (MAXM >= 3) {
+        const float d2 = d * d;
+        const float dN2 = dN * dN;
+        st.mean += dN;
+        st.m2 += d * (d - dN);
+        st.m3 += -3.f * dN * st.m2 + d * (d2 - dN2);
+    } else if (MAXM == 2) {
+        st.mean += dN;
+        st.m2 += d * (d - dN);
+    } else {
+        st.mean += dN;
+    }
+    if (TRANSFORM) {  // estimator.h:217-225
+        const float fd = smp - st.fmean;
+        const float fdN = div_by_count(fd, nf, r);
+        st.fmean += fdN;
+        st.fm2 += fd * (fd - fdN);
+    }
+}
+
+// ------------------------------------------------------------------ pre-pass
+// t = 1 in Welch mode (the pair looks its quantile up itself); exclude: n < 2 takes the pixel out of every window
+__device__ __forceinline__ void prepass_elem(int ni, float t, float mu, float s2sum, float s3sum,
+                                             float &mc, float &dc, bool exclude_small_n = false) {
+#pragma clang fp contract(off)
+    const float nf = (float)ni;
+    if (ni >= 2 && s2sum > 0.f) {
+        const float var = s2sum / (nf - 1.f);
+        const float mu3 = s3sum / nf;
+        mc = mu + mu3 / (6.f * var * nf);
+        dc = (t * t) * (var / nf);
+    } else if (ni < 2 && exclude_small_n) {
+        mc = __builtin_nanf("");
+        dc = __builtin_nanf("");
+    } else {
+        mc = mu;
+        dc = ni >= 2 ? 0.f : __builtin_inff();
+    }
+}
+
+// The quantile the pre-pass multiplies with: the context's table (statmc_get_prepass_context) indexed by dof - 1, larger dof
+// reusing the last of its 4096 entries, +inf for dof < 1 -- the lookup of the library's own pre-pass.
+__device__ __forceinline__ float t_quantile(const statmc_prepass_context &ctx, int dof) {
+#pragma clang fp contract(off)
+    if (dof < 1) return __builtin_inff();
+    if (dof > 4096) dof = 4096;
+    return ctx.t_table[dof - 1];
+}
+
+// ------------------------------------------------------------------ one pixel of one (type, bounce), one thread
+// The semantics of statmc_accumulate for one pixel: load its state, fold samples in order, store.  C = channels (1 or 3),
+// MAXM = max_moment (1..3), TRANSFORM = the type's Box-Cox flag -- the three fields of the statmc_stat_type, fixed at
+// compile time here.  Plain scalar loads and stores: any pixel, any alignment.  One thread owns a pixel between load() and
+// store(); two threads folding into the same pixel at once lose samples (combine partial states with
+// statmc_combine_statistics instead).
+template <int C, int MAXM, bool TRANSFORM>
+struct PixelStats {
+    static_assert(C == 1 || C == 3, "a stat type has 1 or 3 channels");
+    static_assert(MAXM >= 1 && MAXM <= 3, "max_moment is 1, 2 or 3");
+    ElemState st[C];
+    int n;
+
+    __device__ __forceinline__ void load(const statmc_stat_type &t, long long pixel) {
+#pragma clang fp contract(off)
+        n = t.n[pixel];
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const long long e = pixel * C + c;
+            st[c].mean = t.mean[e];
+            st[c].m2 = MAXM >= 2 ? t.m2[e] : 0.f;
+            st[c].m3 = MAXM >= 3 ? t.m3[e] : 0.f;
+            st[c].fmean = TRANSFORM ? t.film_mean[e] : 0.f;
+            st[c].fm2 = TRANSFORM ? t.film_m2[e] : 0.f;
+        }
+    }
+    // one sample: sample[0 .. C)
+    __device__ __forceinline__ void add(const float *sample) {
+#pragma clang fp contract(off)
+        n += 1;
+        const float nf = (float)n;
+        const float r = refined_rcp(nf);
+#pragma unroll
+        for (int c = 0; c < C; c++) add_sample<MAXM, TRANSFORM>(st[c], nf, r, sample[c]);
+    }
+    // the moments and n (Merge*Tile casts the tile's count to int32 as well, estimator.cpp:347,380)
+    __device__ __forceinline__ void store(const statmc_stat_type &t, long long pixel) const {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const long long e = pixel * C + c;
+            t.mean[e] = st[c].mean;
+            if (MAXM >= 2) t.m2[e] = st[c].m2;
+            if (MAXM >= 3) t.m3[e] = st[c].m3;
+            if (TRANSFORM) {
+                t.film_mean[e] = st[c].fmean;
+                t.film_m2[e] = st[c].fm2;
+            }
+        }
+        t.n[pixel] = n;
+    }
+    // ... and the pre-pass of the stored moments into t.mean_corr / t.discriminator (both required; max_moment 3), under the
+    // spec and significance level `ctx` was queried for: the bits of the accumulation's epilogue and of statmc_prepass.
+    __device__ __forceinline__ void store(const statmc_stat_type &t, long long pixel, const statmc_prepass_context &ctx) const {
+#pragma clang fp contract(off)
+        static_assert(MAXM >= 3, "the pre-pass reads m2 and m3: max_moment 3");
+        store(t, pixel);
+        const float tq = (ctx.flags & 1) ? 1.f : t_quantile(ctx, n - 1);
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const long long e = pixel * C + c;
+            float m, d;
+            prepass_elem(n, tq, st[c].mean, st[c].m2, st[c].m3, m, d, (ctx.flags & 2) != 0);
+            t.mean_corr[e] = m;
+            t.discriminator[e] = d;
+        }
+    }
+};
+
+}  // namespace device
+}  // namespace statmc
+
+#endif  // STATMC_DEVICE_API_HPP

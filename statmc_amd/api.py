@@ -75,6 +75,13 @@ class StatType(C.Structure):
     ]
 
 
+class PrepassContext(C.Structure):
+    """statmc_prepass_context: what a renderer's own kernel needs for the pre-pass store of statmc::device::PixelStats
+    (include/statmc_device_api.hpp): the current device's t table (device pointer) and the epilogue's flags (1 Welch, 2 small n
+    excluded)."""
+    _fields_ = [("t_table", C.c_void_p), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CombineEntry(C.Structure):
     """statmc_combine_entry: part A (dst, updated in place) and part B (src) of one set of statistics."""
     _fields_ = [("dst", StatType), ("src", StatType), ("count_of", C.c_int32)]
@@ -88,7 +95,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -164,6 +171,7 @@ def load():
     lib.statmc_accumulate_row_ranges.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
     lib.statmc_accumulate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]
+    lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
@@ -523,6 +531,13 @@ def make_combine_entry(dst, src, channels, max_moment, count_of=-1, prepass_into
     if prepass_into is not None:
         e.dst.mean_corr, e.dst.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
     return e
+
+
+def prepass_context():
+    """statmc_get_prepass_context of the current device: query again after set_significance / set_filter_spec."""
+    ctx = PrepassContext()
+    check(load().statmc_get_prepass_context(C.byref(ctx)))
+    return ctx
 
 
 def combine_statistics(width, height, entries, stream=None):

@@ -10,7 +10,7 @@ SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip"]
 HEADERS = ["statmc_device.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
-           os.path.join("..", "..", "include", "statmc_pinned_spec.h")]
+           os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]
@@ -90,8 +90,15 @@ ROOT = os.path.dirname(HERE)
 DENOISE_BIN = os.path.join(ROOT, "tools", "bin", "statmc_denoise")
 RENDER_SIM_BIN = os.path.join(ROOT, "tools", "bin", "statmc_render_sim")
 CV_ADAPTOR_BIN = os.path.join(ROOT, "tools", "bin", "test_cv_adaptor")   # tests/cpp/test_cv_adaptor.cpp: include/statmc_cv.hpp in use
+DEVICE_ACC_BIN = os.path.join(ROOT, "tools", "bin", "test_device_accumulate")   # tests/cpp/test_device_accumulate.cpp: Estimator::DeviceStatistics
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
-         CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp")}
+         CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
+         DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp")}
+# A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
+# hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
+DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")
+DEVICE_EXAMPLE_SRC = "device_accumulate_example.hip"
+DEVICE_EXAMPLE_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared"]
 
 
 TOOLS_STAMP = os.path.join(os.path.dirname(DENOISE_BIN), ".src")
@@ -102,7 +109,7 @@ def tools_hash():
     import hashlib
     h = hashlib.sha256()
     inc = os.path.join(ROOT, "include")
-    files = [os.path.join(ROOT, "tools", src) for src in TOOLS.values()]
+    files = [os.path.join(ROOT, "tools", src) for src in list(TOOLS.values()) + [DEVICE_EXAMPLE_SRC]]
     files += [os.path.join(inc, f) for f in sorted(os.listdir(inc))]
     for path in files:
         with open(path, "rb") as f:
@@ -119,20 +126,26 @@ def tools_stale():
 
 def build_tools(force=False):
     """g++ build of the C++ host side (include/statmc_denoiser.hpp + tools/*.cpp: the offline
-    denoise driver and the render-loop harness), linked against libstatmc_hip.so."""
+    denoise driver and the render-loop harness), linked against libstatmc_hip.so, and the hipcc build of the
+    device-side accumulation example (tools/bin/libstatmc_device_example.so)."""
     # Binaries built from other sources than the ones in the tree are rebuilt (content hash: mtimes do not survive a
     # snapshot copy of the tree); each goes to a temporary file and is renamed into place.
-    if not force and all(os.path.exists(b) for b in TOOLS) and not tools_stale():
+    if not force and all(os.path.exists(b) for b in list(TOOLS) + [DEVICE_EXAMPLE_SO]) and not tools_stale():
         return DENOISE_BIN
     if not os.path.exists(SO):
         build()
     os.makedirs(os.path.dirname(DENOISE_BIN), exist_ok=True)
     rocm_lib = os.path.join(os.path.dirname(os.path.dirname(_hipcc())), "lib")
+    tmp = DEVICE_EXAMPLE_SO + ".tmp%d" % os.getpid()
+    subprocess.check_call([_hipcc()] + DEVICE_EXAMPLE_FLAGS + ["-I", os.path.join(ROOT, "include"),
+                                                             os.path.join(ROOT, "tools", DEVICE_EXAMPLE_SRC), "-o", tmp])
+    os.replace(tmp, DEVICE_EXAMPLE_SO)
     for binary, src in TOOLS.items():
         tmp = binary + ".tmp%d" % os.getpid()
+        extra = ["-L", os.path.dirname(DEVICE_EXAMPLE_SO), "-lstatmc_device_example", "-Wl,-rpath,$ORIGIN"] if binary == DEVICE_ACC_BIN else []
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread",
                                "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", src), "-o", tmp,
-                               "-L", HERE, "-lstatmc_hip", "-L", rocm_lib, "-Wl,-rpath,$ORIGIN/../../statmc_amd",
+                               "-L", HERE, "-lstatmc_hip"] + extra + ["-L", rocm_lib, "-Wl,-rpath,$ORIGIN/../../statmc_amd",
                                "-Wl,-rpath," + rocm_lib])
         os.replace(tmp, binary)
     with open(TOOLS_STAMP, "w") as f:

@@ -1146,6 +1146,19 @@ static int fill_stat_type(const DeviceState &ds, const statmc_stat_type &t, int 
     return STATMC_OK;
 }
 
+// what the epilogue of fill_stat_type hands the accumulation kernel, for device code outside the library
+// (include/statmc_device_api.hpp: PixelStats::store with a context)
+int statmc_get_prepass_context(statmc_prepass_context *out) {
+    if (!out) return fail(STATMC_ERR_INVALID, "null context");
+    NEED_READY();
+    const float *table = statmc::t_table_device_ptr(prepass_table(dstate));
+    if (!table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
+    out->t_table = table;
+    out->flags = (dstate.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (dstate.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0);
+    out->reserved = 0;
+    return STATMC_OK;
+}
+
 int statmc_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, void *stream) {
     return statmc_accumulate_rows(width, height, types, n_types, 0, height, stream);
 }

@@ -22,9 +22,17 @@
 
 #include "statmc_device.h"
 
+#include "../../include/statmc_device_api.hpp"
 #include "t_quantiles.h"
 
 namespace statmc {
+
+// the per-sample arithmetic and the pre-pass of one element: one definition, shared with device code outside the library
+using device::ElemState;
+using device::add_sample;
+using device::div_by_count;
+using device::prepass_elem;
+using device::refined_rcp;
 
 // Sample rows in flight per lane (x2: current + next group) per kind of stat type: RGB with the Box-Cox transform, RGB,
 // 1-channel.  The measured optimum (tools/experiments/build_variant.sh A/Bs source revisions).
@@ -103,24 +111,7 @@ static inline int grid_for(long long work_items, int cap = 256 * 16) {
 }
 
 // ------------------------------------------------------------------ pre-pass
-// t = 1 in Welch mode (the pair looks its quantile up itself); exclude: n < 2 takes the pixel out of every window
-__device__ __forceinline__ void prepass_elem(int ni, float t, float mu, float s2sum, float s3sum,
-                                             float &mc, float &dc, bool exclude_small_n = false) {
-    const float nf = (float)ni;
-    if (ni >= 2 && s2sum > 0.f) {
-        const float var = s2sum / (nf - 1.f);
-        const float mu3 = s3sum / nf;
-        mc = mu + mu3 / (6.f * var * nf);
-        dc = (t * t) * (var / nf);
-    } else if (ni < 2 && exclude_small_n) {
-        mc = __builtin_nanf("");
-        dc = __builtin_nanf("");
-    } else {
-        mc = mu;
-        dc = ni >= 2 ? 0.f : __builtin_inff();
-    }
-}
-
+// (prepass_elem: include/statmc_device_api.hpp)
 template <bool VEC4>
 __global__ __launch_bounds__(kBlock) void prepass_kernel(PrepassArgs a) {
     const long long n_groups = (a.n_elems + 3) >> 2;
@@ -237,52 +228,8 @@ hipError_t launch_mean_vars(const MeanVarsArgs &a, hipStream_t s) {
 // of pixel p, channel c is at samples[s*n_elems + p*C + c]), so the update sequence per element
 // is the reference's (estimator.h:162-226).  Owning whole pixels keeps the count n private to
 // the lane (no cross-lane read/write race on n).  blockIdx.y selects the stat type.
-struct ElemState {
-    float mean, m2, m3, fmean, fm2;
-};
-
-// d / n for an integer-valued divisor n in [1, 2^24): `r` is 1/n refined from v_rcp_f32 by one
-// Newton step (shared by every division by the same count: all channels, both Welford chains),
-// then one residual correction of the quotient (Markstein).  Bit-identical to the IEEE
-// quotient for the operand ranges of this path (tests/test_gpu_parity.py::test_exact_division
-// sweeps n = 1..4096 against `/`); 3 + 3 instructions instead of ~10 per division.
-__device__ __forceinline__ float refined_rcp(float nf) {
-    const float y0 = __builtin_amdgcn_rcpf(nf);
-    const float e = __builtin_fmaf(-nf, y0, 1.f);
-    return __builtin_fmaf(e, y0, y0);
-}
-__device__ __forceinline__ float div_by_count(float d, float nf, float r) {
-    const float q0 = d * r;
-    const float rem = __builtin_fmaf(-q0, nf, d);
-    return __builtin_fmaf(rem, r, q0);
-}
-
-template <int MAXM, bool TRANSFORM>
-__device__ __forceinline__ void add_sample(ElemState &st, float nf, float r, float smp) {
-    // estimator.h:215 -- boxCox(sample, .5f) = (pow(v, .5) - 1) / .5; v_sqrt_f32 (1 ulp) stands
-    // in for pow(v, .5), itself only faithfully rounded in the reference's libm.
-    const float v = TRANSFORM ? (__builtin_amdgcn_sqrtf(smp) - 1.f) / .5f : smp;
-    const float d = v - st.mean;
-    const float dN = div_by_count(d, nf, r);
-    if (MAXM >= 3) {
-        const float d2 = d * d;
-        const float dN2 = dN * dN;
-        st.mean += dN;
-        st.m2 += d * (d - dN);
-        st.m3 += -3.f * dN * st.m2 + d * (d2 - dN2);
-    } else if (MAXM == 2) {
-        st.mean += dN;
-        st.m2 += d * (d - dN);
-    } else {
-        st.mean += dN;
-    }
-    if (TRANSFORM) {  // estimator.h:217-225
-        const float fd = smp - st.fmean;
-        const float fdN = div_by_count(fd, nf, r);
-        st.fmean += fdN;
-        st.fm2 += fd * (fd - fdN);
-    }
-}
+// (ElemState, refined_rcp, div_by_count, add_sample: include/statmc_device_api.hpp, the definition a renderer's own kernel
+// includes as well)
 
 // The same update on two elements at once (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: one issue slot for two lanes'
 // worth of IEEE fp32 arithmetic, each component rounded exactly like the scalar instruction, so the bits are those of

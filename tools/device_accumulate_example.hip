@@ -1,0 +1,224 @@
+// device_accumulate_example.hip -- a renderer's kernel folding its samples into StatMC's statistics itself
+// (include/statmc_device_api.hpp), built into tools/bin/libstatmc_device_example.so with hipcc's DEFAULT floating-point flags
+// (-ffp-contract=fast-honor-pragmas): the header's bits must not depend on them.  Three launchers, extern "C":
+//
+//   fold_arena  one thread per pixel folds a film-major arena ([S][H][W][C] fp32, statmc_accumulate's input) through
+//               PixelStats -- the bits of statmc_accumulate on the same arena (tests/test_device_api_gpu.py)
+//   gen_arena   a stand-in for a path tracer: one counter-based hash per (pixel, sample) gives the five G-buffer / radiance
+//               values of the flagship configuration (film.STAT_TYPES: radiance, normal, albedo, depth, material id; 11
+//               channels), written to one arena per type -- what feeds statmc_accumulate today
+//   gen_fold    the same values, folded straight into the statistics in registers: no arena
+//
+// Every launcher returns 0 or a negative STATMC_ERR_* (include/statmc.h), and only enqueues on `stream`.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "statmc.h"
+#include "statmc_device_api.hpp"
+
+using statmc::device::PixelStats;
+
+namespace {
+
+constexpr int kBlock = 256;
+
+inline int grid_for(long long n_px) { return (int)((n_px + kBlock - 1) / kBlock); }
+
+int launched() { return hipGetLastError() == hipSuccess ? STATMC_OK : STATMC_ERR_HIP; }
+
+// ------------------------------------------------------------------ fold_arena
+template <int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(kBlock) void fold_arena_kernel(statmc_stat_type t, long long n_px, const float *arena, int n_samples,
+                                                            statmc_prepass_context ctx, int with_prepass) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_px) return;
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    ps.load(t, p);
+    for (int s = 0; s < n_samples; s++) {
+        const float *q = arena + ((long long)s * n_px + p) * C;
+        float smp[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) smp[c] = q[c];
+        ps.add(smp);
+    }
+    if constexpr (MAXM >= 3) {
+        if (with_prepass) {
+            ps.store(t, p, ctx);
+            return;
+        }
+    }
+    ps.store(t, p);
+}
+
+template <int C, int MAXM, bool TRANSFORM>
+int launch_fold(const statmc_stat_type &t, long long n_px, const float *arena, int n_samples, const statmc_prepass_context *ctx,
+                hipStream_t s) {
+    const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
+    hipLaunchKernelGGL((fold_arena_kernel<C, MAXM, TRANSFORM>), dim3(grid_for(n_px)), dim3(kBlock), 0, s, t, n_px, arena, n_samples, c,
+                       ctx ? 1 : 0);
+    return launched();
+}
+
+template <int C>
+int fold_dispatch(const statmc_stat_type &t, long long n_px, const float *arena, int n_samples, const statmc_prepass_context *ctx,
+                  hipStream_t s) {
+    if (t.transform) {
+        if (t.max_moment == 3) return launch_fold<C, 3, true>(t, n_px, arena, n_samples, ctx, s);
+        if (t.max_moment == 2) return launch_fold<C, 2, true>(t, n_px, arena, n_samples, ctx, s);
+        return launch_fold<C, 1, true>(t, n_px, arena, n_samples, ctx, s);
+    }
+    if (t.max_moment == 3) return launch_fold<C, 3, false>(t, n_px, arena, n_samples, ctx, s);
+    if (t.max_moment == 2) return launch_fold<C, 2, false>(t, n_px, arena, n_samples, ctx, s);
+    return launch_fold<C, 1, false>(t, n_px, arena, n_samples, ctx, s);
+}
+
+// ------------------------------------------------------------------ the sample generator
+// One 32-bit hash of (seed, pixel, sample) seeds a short PCG-style stream that yields the sample's 11 values.  Written with
+// contraction off, so that gen_arena and gen_fold produce the same bits whatever the optimiser does around them.
+__device__ __forceinline__ uint32_t mix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x7feb352du;
+    h ^= h >> 15;
+    h *= 0x846ca68bu;
+    h ^= h >> 16;
+    return h;
+}
+struct Rng {
+    uint32_t state;
+    __device__ __forceinline__ float next() {   // [0, 1), 24 bits
+        state = state * 747796405u + 2891336453u;
+        const uint32_t w = ((state >> ((state >> 28) + 4u)) ^ state) * 277803737u;
+        return (float)((w ^ (w >> 22)) >> 8) * (1.f / 16777216.f);
+    }
+};
+struct Sample {
+    float radiance[3], normal[3], albedo[3], depth, material;
+};
+__device__ __forceinline__ void gen_sample(uint32_t seed, long long px, int s, Sample &o) {
+#pragma clang fp contract(off)
+    Rng r{mix32(seed ^ mix32((uint32_t)px * 0x9e3779b9u ^ mix32((uint32_t)s + 0x632be5abu)))};
+    const float scale = r.next() < 1.f / 64.f ? 64.f : 1.f;   // the odd firefly
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float u = r.next();
+        o.radiance[c] = (0.01f + u * u) * scale;               // positive radiance
+    }
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = 2.f * r.next() - 1.f;
+    const float len2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+    const float inv = len2 > 1e-6f ? 1.f / __builtin_sqrtf(len2) : 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; c++) o.normal[c] = len2 > 1e-6f ? v[c] * inv : (c == 2 ? 1.f : 0.f);   // unit normals
+#pragma unroll
+    for (int c = 0; c < 3; c++) o.albedo[c] = r.next();                                              // [0, 1)
+    o.depth = 1.f + 9.f * r.next();
+    o.material = __builtin_floorf(8.f * r.next());
+}
+
+__global__ __launch_bounds__(kBlock) void gen_arena_kernel(uint32_t seed, long long n_px, int sample0, int n_samples, float *rad,
+                                                           float *nrm, float *alb, float *dep, float *mat) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_px) return;
+    for (int s = 0; s < n_samples; s++) {
+        Sample o;
+        gen_sample(seed, p, sample0 + s, o);
+        const long long e = (long long)s * n_px + p;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            rad[3 * e + c] = o.radiance[c];
+            nrm[3 * e + c] = o.normal[c];
+            alb[3 * e + c] = o.albedo[c];
+        }
+        dep[e] = o.depth;
+        mat[e] = o.material;
+    }
+}
+
+struct FiveTypes {
+    statmc_stat_type t[5];
+};
+
+__global__ __launch_bounds__(kBlock) void gen_fold_kernel(uint32_t seed, long long n_px, int sample0, int n_samples, FiveTypes ft,
+                                                          statmc_prepass_context ctx, int with_prepass) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_px) return;
+    PixelStats<3, 3, true> rad;
+    PixelStats<3, 1, false> nrm, alb;
+    PixelStats<1, 1, false> dep, mat;
+    rad.load(ft.t[0], p);
+    nrm.load(ft.t[1], p);
+    alb.load(ft.t[2], p);
+    dep.load(ft.t[3], p);
+    mat.load(ft.t[4], p);
+    for (int s = 0; s < n_samples; s++) {
+        Sample o;
+        gen_sample(seed, p, sample0 + s, o);
+        rad.add(o.radiance);
+        nrm.add(o.normal);
+        alb.add(o.albedo);
+        dep.add(&o.depth);
+        mat.add(&o.material);
+    }
+    if (with_prepass) rad.store(ft.t[0], p, ctx);
+    else rad.store(ft.t[0], p);
+    nrm.store(ft.t[1], p);
+    alb.store(ft.t[2], p);
+    dep.store(ft.t[3], p);
+    mat.store(ft.t[4], p);
+}
+
+}  // namespace
+
+extern "C" {
+
+// t: one stat type's device images (its samples / n_samples fields are not read); arena: [n_samples][height][width][channels];
+// ctx != NULL: the pre-pass store (max_moment 3 and t.mean_corr / t.discriminator only).
+int fold_arena(const statmc_stat_type *t, int width, int height, const float *arena, int n_samples, const statmc_prepass_context *ctx,
+               void *stream) {
+    if (!t || width <= 0 || height <= 0 || n_samples < 0 || (n_samples > 0 && !arena)) return STATMC_ERR_INVALID;
+    if ((t->channels != 1 && t->channels != 3) || t->max_moment < 1 || t->max_moment > 3 || !t->n || !t->mean) return STATMC_ERR_INVALID;
+    if ((t->max_moment >= 2 && !t->m2) || (t->max_moment >= 3 && !t->m3) || (t->transform && (!t->film_mean || !t->film_m2)))
+        return STATMC_ERR_INVALID;
+    if (ctx && (t->max_moment < 3 || !t->mean_corr || !t->discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    const long long n_px = (long long)width * height;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return t->channels == 3 ? fold_dispatch<3>(*t, n_px, arena, n_samples, ctx, s) : fold_dispatch<1>(*t, n_px, arena, n_samples, ctx, s);
+}
+
+// arenas[5]: radiance, normal, albedo ([n_samples][height][width][3]), depth, material id ([n_samples][height][width]); samples
+// sample0 .. sample0 + n_samples - 1 of every pixel.
+int gen_arena(uint32_t seed, int width, int height, int sample0, int n_samples, float *const *arenas, void *stream) {
+    if (!arenas || width <= 0 || height <= 0 || n_samples < 0 || sample0 < 0) return STATMC_ERR_INVALID;
+    for (int k = 0; k < 5; k++)
+        if (!arenas[k]) return STATMC_ERR_INVALID;
+    const long long n_px = (long long)width * height;
+    hipLaunchKernelGGL(gen_arena_kernel, dim3(grid_for(n_px)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), seed, n_px, sample0,
+                       n_samples, arenas[0], arenas[1], arenas[2], arenas[3], arenas[4]);
+    return launched();
+}
+
+// types[5] in gen_arena's order, with the configurations of film.STAT_TYPES: radiance (3 channels, transform, max_moment 3),
+// normal / albedo (3, no transform, 1), depth / material id (1, no transform, 1); ctx != NULL: radiance is stored with its
+// pre-pass (types[0].mean_corr / discriminator).
+int gen_fold(uint32_t seed, int width, int height, int sample0, int n_samples, const statmc_stat_type *types,
+             const statmc_prepass_context *ctx, void *stream) {
+    if (!types || width <= 0 || height <= 0 || n_samples < 0 || sample0 < 0) return STATMC_ERR_INVALID;
+    static const int want[5][3] = {{3, 1, 3}, {3, 0, 1}, {3, 0, 1}, {1, 0, 1}, {1, 0, 1}};   // channels, transform, max_moment
+    FiveTypes ft;
+    for (int k = 0; k < 5; k++) {
+        const statmc_stat_type &t = types[k];
+        if (t.channels != want[k][0] || (t.transform != 0) != (want[k][1] != 0) || t.max_moment != want[k][2] || !t.n || !t.mean)
+            return STATMC_ERR_INVALID;
+        if (k == 0 && (!t.m2 || !t.m3 || !t.film_mean || !t.film_m2)) return STATMC_ERR_INVALID;
+        ft.t[k] = t;
+    }
+    if (ctx && (!types[0].mean_corr || !types[0].discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
+    const long long n_px = (long long)width * height;
+    hipLaunchKernelGGL(gen_fold_kernel, dim3(grid_for(n_px)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), seed, n_px, sample0,
+                       n_samples, ft, c, ctx ? 1 : 0);
+    return launched();
+}
+
+}  // extern "C"

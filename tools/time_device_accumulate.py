@@ -1,0 +1,112 @@
+"""Times accumulation inside the renderer's kernel (include/statmc_device_api.hpp) against the arena path it replaces, at the
+flagship configuration: 1920 x 1080, 256 samples per pixel, the five stat types of film.STAT_TYPES (11 channels), moments
+and arenas from statmc_malloc_placed as bench.py places them.  The renderer is tools/device_accumulate_example.hip's
+counter-based hash generator:
+
+  arena  gen_arena writes one film-major arena per type, statmc_accumulate reads them back (what bench.py times)
+  fused  gen_fold folds the same values into the moments in registers (statmc::device::PixelStats): no arena
+
+Prints one JSON line per path: milliseconds per step (hipEvent timing, after warm-up; the arena path also split into its two
+launches), the algorithmic bytes computed from the shapes, and the share of the 8 TB/s HBM peak they imply.
+
+    python tools/time_device_accumulate.py [--width 1920 --height 1080 --spp 256 --iters 10 --warmup 3]
+
+Algorithmic bytes: the arena written once and read once (4 B per channel and sample), and the moments read and written once
+per step (n, mean, m2, m3, film-mean, film-m2 of radiance; n and mean of the four feature types: 112 B per pixel each way)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from statmc_amd import api, build, film  # noqa: E402
+
+PEAK = 8.0e12
+TYPES = ("radiance", "normal", "albedo", "depth", "materialid")   # gen_arena / gen_fold order
+
+
+def state_bytes_per_pixel():
+    b = 0
+    for t in TYPES:
+        cfg = film.STAT_TYPES[t]
+        planes = cfg["max_moment"] + (2 if cfg["transform"] else 0)
+        b += 4 + 4 * cfg["channels"] * planes
+    return b
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(iters):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--spp", type=int, default=256)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    W, H, S = a.width, a.height, a.spp
+    dev = torch.device("cuda:0")
+    api.setup(0)
+    build.build_tools()
+    lib = C.CDLL(build.DEVICE_EXAMPLE_SO)
+    lib.gen_arena.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    lib.gen_fold.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(api.StatType), C.POINTER(api.PrepassContext),
+                             C.c_void_p]
+    ch = {t: film.STAT_TYPES[t]["channels"] for t in TYPES}
+    api.placement_expect(api.MEM_STREAM, sum(4 * S * H * W * ch[t] for t in TYPES), dev)
+    arenas = {t: api.empty_placed((S, H, W, ch[t]), torch.float32, dev, api.MEM_STREAM) for t in TYPES}
+    api.placement_expect(api.MEM_STREAM, 0, dev)
+    ptrs = (C.c_void_p * 5)(*[arenas[t].data_ptr() for t in TYPES])
+    fs = film.FilmStats(W, H, dev, types=TYPES, placed=True)
+    sts = (api.StatType * 5)(*[api.make_stat_type(arenas[t], fs.state[t], film.STAT_TYPES[t]["transform"], film.STAT_TYPES[t]["max_moment"])
+                               for t in TYPES])
+    stream = api.current_stream_handle()
+    step = [0]
+
+    def gen():
+        api.check(lib.gen_arena(1, W, H, step[0] * S, S, ptrs, stream))
+
+    def acc():
+        api.accumulate(W, H, list(sts), stream=stream)
+
+    def arena_step():
+        gen()
+        acc()
+        step[0] += 1
+
+    def fused_step():
+        api.check(lib.gen_fold(1, W, H, step[0] * S, S, sts, None, stream))
+        step[0] += 1
+
+    arena_b = 4 * S * H * W * sum(ch.values())
+    state_b = 2 * state_bytes_per_pixel() * H * W
+    common = {"width": W, "height": H, "spp": S, "channels": sum(ch.values()), "placed": api.placement_info()["active"] == 1}
+    gen_ms, acc_ms = timed(gen, a.iters, a.warmup), timed(acc, a.iters, a.warmup)
+    fs.reset()
+    arena_ms = timed(arena_step, a.iters, a.warmup)
+    b = 2 * arena_b + state_b
+    print(json.dumps(dict(path="arena", ms=round(arena_ms, 4), gen_arena_ms=round(gen_ms, 4), accumulate_ms=round(acc_ms, 4),
+                          bytes=b, of_peak=round(b / (arena_ms * 1e-3) / PEAK, 3),
+                          accumulate_of_peak=round((arena_b + state_b) / (acc_ms * 1e-3) / PEAK, 3), **common)))
+    fs.reset()
+    fused_ms = timed(fused_step, a.iters, a.warmup)
+    print(json.dumps(dict(path="fused", ms=round(fused_ms, 4), bytes=state_b, of_peak=round(state_b / (fused_ms * 1e-3) / PEAK, 3),
+                          speedup=round(arena_ms / fused_ms, 2), **common)))
+
+
+if __name__ == "__main__":
+    main()

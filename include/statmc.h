@@ -482,6 +482,35 @@ typedef struct statmc_combine_entry {
 int statmc_combine_statistics(uint16_t width, uint16_t height, const statmc_combine_entry *entries, int n_entries,
                               void *stream);
 
+/* ---- the same for K parts: dst (part 0) and n_sources further parts, one pass over memory.  The call leaves in every dst
+ * exactly the bits that this sequence leaves:
+ *     for k = 0 .. n_sources - 1: one statmc_combine_statistics call whose entries are (dst, srcs[k], count_of)
+ * -- a left fold in array order, per pixel and channel -- where that sequence moves 3 (K - 1) B bytes for K = n_sources + 1
+ * parts of B bytes per pixel and this call (K + 1) B: every part read once, dst written once.  Everything said above holds
+ * per source, so:
+ *   - per source, nB == 0 keeps the running bits and nA == 0 takes the source's bits; n becomes the integer sum;
+ *   - source k of an entry that borrows counts is weighed with its owner's running count, dst.n plus the counts of sources
+ *     0 .. k - 1, and with the owner's srcs[k].n: source k of every entry belongs to the same part k.  The owner's dst.n is
+ *     written once, at the end;
+ *   - film planes that alias the moments are combined once; the dst.mean_corr / dst.discriminator epilogue runs once, on the
+ *     final moments;
+ *   - every srcs[k] agrees with dst on channels and max_moment; no dst image may be an image of one of its sources; no two
+ *     entries may own the same count image (STATMC_ERR_INVALID, before anything is launched).
+ * n_sources = 0 or n_entries = 0 is a no-op; n_sources <= STATMC_MAX_COMBINE_SOURCES, n_entries <= 16, every pair works.
+ * `srcs` is a host array that the call has read when it returns.  The source tables travel as kernel arguments, so a call
+ * whose tables do not fit one launch (more than 90 / n_sources chains, a chain being an entry's moments or its film images
+ * of their own) becomes several launches on `stream`, the chains that only read counts first.  Asynchronous on `stream`;
+ * all states on the current device. */
+#define STATMC_MAX_COMBINE_SOURCES 15
+typedef struct statmc_combine_many_entry {
+    statmc_stat_type dst;         /* part 0, updated in place; as statmc_combine_entry::dst */
+    const statmc_stat_type *srcs; /* host array of n_sources read-only parts, in fold order */
+    int32_t count_of;             /* as in statmc_combine_entry */
+} statmc_combine_many_entry;
+
+int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_many_entry *entries, int n_entries,
+                        int n_sources, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

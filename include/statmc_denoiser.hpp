@@ -1122,32 +1122,63 @@ class Estimator {
     // `other`'s stream.  Asynchronous on this Estimator's stream; mean-corr / discriminator are left to Denoise().
     // (Not "Merge": Merge*Tile(s) is the reference's tile scatter, estimator.cpp:341-407.)
     void CombineStatistics(Estimator &other, const std::vector<unsigned char> &borrowCounts = {}) {
-        if (&other == this) throw Error(STATMC_ERR_INVALID, "CombineStatistics: an Estimator cannot be combined with itself");
-        if (!allocateDevice || !other.allocateDevice) throw Error(STATMC_ERR_INVALID, "CombineStatistics needs device images");
-        if (other.device != device) throw Error(STATMC_ERR_INVALID, "CombineStatistics: both Estimators must be on one device");
-        if (other.width != width || other.height != height) throw Error(STATMC_ERR_INVALID, "CombineStatistics: film sizes differ");
-        const auto &a = statTypeConfigs, &b = other.statTypeConfigs;
-        bool same = a.nEnabled == b.nEnabled;
-        for (unsigned char i = 0; same && i < a.nEnabled; i++)
-            same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
-                   a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
-        if (!same) throw Error(STATMC_ERR_INVALID, "CombineStatistics: the Estimators have different stat type configurations");
+        combineChecks({&other}, borrowCounts);
+        combineParts({&other}, borrowCounts, false);
+    }
+    // ... and of several others, folded into this Estimator in the order of `others` (statmc_combine_many): the bits of one
+    // CombineStatistics(*others[k], borrowCounts) after the other, with every part read once and this Estimator's images
+    // written once per group of STATMC_MAX_COMBINE_SOURCES parts.  The same checks and ordering, per part.
+    void CombineStatistics(const std::vector<Estimator *> &others, const std::vector<unsigned char> &borrowCounts = {}) {
+        combineChecks(others, borrowCounts);
+        for (size_t g = 0; g < others.size(); g += STATMC_MAX_COMBINE_SOURCES)
+            combineParts(std::vector<Estimator *>(others.begin() + g, others.begin() + std::min(others.size(), g + (size_t)STATMC_MAX_COMBINE_SOURCES)),
+                         borrowCounts, true);
+    }
+
+  private:
+    void combineChecks(const std::vector<Estimator *> &others, const std::vector<unsigned char> &borrowCounts) const {
+        const auto &a = statTypeConfigs;
+        for (size_t k = 0; k < others.size(); k++) {
+            if (!others[k]) throw Error(STATMC_ERR_INVALID, "CombineStatistics: null Estimator");
+            const Estimator &other = *others[k];
+            if (&other == this) throw Error(STATMC_ERR_INVALID, "CombineStatistics: an Estimator cannot be combined with itself");
+            for (size_t j = 0; j < k; j++)
+                if (others[j] == others[k]) throw Error(STATMC_ERR_INVALID, "CombineStatistics: an Estimator is listed twice");
+            if (!allocateDevice || !other.allocateDevice) throw Error(STATMC_ERR_INVALID, "CombineStatistics needs device images");
+            if (other.device != device) throw Error(STATMC_ERR_INVALID, "CombineStatistics: both Estimators must be on one device");
+            if (other.width != width || other.height != height) throw Error(STATMC_ERR_INVALID, "CombineStatistics: film sizes differ");
+            const auto &b = other.statTypeConfigs;
+            bool same = a.nEnabled == b.nEnabled;
+            for (unsigned char i = 0; same && i < a.nEnabled; i++)
+                same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
+                       a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
+            if (!same) throw Error(STATMC_ERR_INVALID, "CombineStatistics: the Estimators have different stat type configurations");
+        }
         if (a.nEnabled == 0 || nBuffers.empty() || nBuffers[0].empty())
             throw Error(STATMC_ERR_INVALID, "CombineStatistics: no statistics (call AllocateBuffers first)");
         for (unsigned char t : borrowCounts)
             if (t == 0 || t >= a.nEnabled) throw Error(STATMC_ERR_INVALID, "CombineStatistics: borrowCounts names type " + std::to_string(t));
+    }
+
+    // one call per chunk of <= 16 entries: statmc_combine_many over all of `others` (many), or the two-part call for one
+    void combineParts(const std::vector<Estimator *> &others, const std::vector<unsigned char> &borrowCounts, bool many) {
+        if (others.empty()) return;
+        const auto &a = statTypeConfigs;
         check(statmc_set_device(device));
         if (acc.enabled) FlushSamples();
-        if (other.acc.enabled) other.FlushSamples();
-        other.joinUploads();
+        for (Estimator *o : others)
+            if (o->acc.enabled) o->FlushSamples();
+        for (Estimator *o : others) o->joinUploads();
         joinUploads();
         if (!combineEvent) {
             void *ev = nullptr;
             check(statmc_event_create(&ev));
             combineEvent.reset(ev, [](void *e) { statmc_event_destroy(e); });
         }
-        check(statmc_event_record(combineEvent.get(), other.stream.handle()));
-        check(statmc_stream_wait_event(stream.handle(), combineEvent.get()));
+        for (Estimator *o : others) {   // behind every part's stream (a recorded event may be recorded again once it is waited on)
+            check(statmc_event_record(combineEvent.get(), o->stream.handle()));
+            check(statmc_stream_wait_event(stream.handle(), combineEvent.get()));
+        }
 
         auto side = [](const StatTypeConfig &c, Buffer &n, Buffer &mean, Buffer &m2, Buffer &m3, Buffer &fm, Buffer &fm2, bool own) {
             statmc_stat_type s;
@@ -1163,16 +1194,21 @@ class Estimator {
             s.film_m2 = static_cast<float *>(fm2.gpuMat.data());
             return s;
         };
-        // the owner of the borrowed counts and everything that borrows them go into the first call: a later call would see
-        // the counts already summed
-        std::vector<statmc_combine_entry> first, rest;
+        // an entry: dst, one src per part, count_of.  The owner of the borrowed counts and everything that borrows them go into
+        // the first call: a later call would see the counts already summed
+        struct Entry {
+            statmc_stat_type dst;
+            std::vector<statmc_stat_type> srcs;
+            int32_t count_of;
+        };
+        std::vector<Entry> first, rest;
         auto entry = [&](unsigned char i, unsigned char j, bool own) {
             const StatTypeConfig &c = a[i];
-            statmc_combine_entry e;
-            std::memset(&e, 0, sizeof(e));
+            Entry e;
             e.dst = side(c, nBuffers[i][j], meanBuffers[i][j], m2Buffers[i][j], m3Buffers[i][j], filmBuffers[i][j], filmM2Buffers[i][j], own);
-            e.src = side(c, other.nBuffers[i][j], other.meanBuffers[i][j], other.m2Buffers[i][j], other.m3Buffers[i][j],
-                         other.filmBuffers[i][j], other.filmM2Buffers[i][j], own);
+            for (Estimator *o : others)
+                e.srcs.push_back(side(c, o->nBuffers[i][j], o->meanBuffers[i][j], o->m2Buffers[i][j], o->m3Buffers[i][j], o->filmBuffers[i][j],
+                                      o->filmM2Buffers[i][j], own));
             e.count_of = own ? -1 : 0;
             return e;
         };
@@ -1185,13 +1221,19 @@ class Estimator {
                 else rest.push_back(entry(i, j, true));
             }
         }
-        if (filmBuffer.gpuMat.data() && other.filmBuffer.gpuMat.data()) {   // the colour image: an M1 mean weighted by t0-b0-n
-            statmc_combine_entry e;
-            std::memset(&e, 0, sizeof(e));
-            e.dst.channels = e.src.channels = 3;
-            e.dst.max_moment = e.src.max_moment = 1;
+        bool film = filmBuffer.gpuMat.data() != nullptr;
+        for (Estimator *o : others) film = film && o->filmBuffer.gpuMat.data();
+        if (film) {   // the colour image: an M1 mean weighted by t0-b0-n
+            Entry e;
+            std::memset(&e.dst, 0, sizeof(e.dst));
+            e.dst.channels = 3;
+            e.dst.max_moment = 1;
             e.dst.mean = static_cast<float *>(filmBuffer.gpuMat.data());
-            e.src.mean = static_cast<float *>(other.filmBuffer.gpuMat.data());
+            for (Estimator *o : others) {
+                statmc_stat_type s = e.dst;
+                s.mean = static_cast<float *>(o->filmBuffer.gpuMat.data());
+                e.srcs.push_back(s);
+            }
             e.count_of = 0;
             first.push_back(e);
         }
@@ -1201,11 +1243,31 @@ class Estimator {
             first.push_back(rest.back());
             rest.pop_back();
         }
-        check(statmc_combine_statistics(width, height, first.data(), (int)first.size(), stream.handle()));
-        for (size_t k = 0; k < rest.size(); k += cap)
-            check(statmc_combine_statistics(width, height, rest.data() + k, (int)std::min(cap, rest.size() - k), stream.handle()));
+        auto call = [&](const Entry *es, size_t n) {
+            if (many) {
+                std::vector<statmc_combine_many_entry> v(n);
+                for (size_t k = 0; k < n; k++) {
+                    v[k].dst = es[k].dst;
+                    v[k].srcs = es[k].srcs.data();
+                    v[k].count_of = es[k].count_of;
+                }
+                check(statmc_combine_many(width, height, v.data(), (int)n, (int)others.size(), stream.handle()));
+            } else {
+                std::vector<statmc_combine_entry> v(n);
+                for (size_t k = 0; k < n; k++) {
+                    std::memset(&v[k], 0, sizeof(v[k]));
+                    v[k].dst = es[k].dst;
+                    v[k].src = es[k].srcs[0];
+                    v[k].count_of = es[k].count_of;
+                }
+                check(statmc_combine_statistics(width, height, v.data(), (int)n, stream.handle()));
+            }
+        };
+        call(first.data(), first.size());
+        for (size_t k = 0; k < rest.size(); k += cap) call(rest.data() + k, std::min(cap, rest.size() - k));
     }
 
+  public:
     const unsigned short width, height;
     const float filterDSFactor;
     const unsigned char filterRadius;

@@ -8,6 +8,7 @@
 //   for (...) ps.add(sample);          // C floats per sample, in sample order
 //   ps.store(t, pixel);                // moments and n; store(t, pixel, ctx) also writes mean_corr / discriminator
 //
+// and put the states of several slots of one pixel together before the store (ps.merge(other), below).
 // The result is bit for bit what statmc_accumulate leaves after the same samples (one launch or several: the state is the
 // same), and store(t, pixel, ctx) writes what the accumulation's pre-pass epilogue writes.  This header is the one
 // definition of that arithmetic: libstatmc_hip.so's kernels include it too.
@@ -112,12 +113,84 @@ __device__ __forceinline__ float t_quantile(const statmc_prepass_context &ctx, i
     return ctx.t_table[dof - 1];
 }
 
+// ------------------------------------------------------------------ combine
+// Two independently accumulated states of one element -> the state of the union of their samples: part B (nB samples) into
+// part A (nA samples).  The formulas, their exact cases and the fp32 operation order are the ones stated in include/statmc.h
+// (statmc_combine_statistics); this is their one definition: statmc_combine_statistics, statmc_combine_many and
+// PixelStats::merge all run it.
+struct CombineCounts {
+    int nA, nB;
+    float fA, fB, nf, r;   // (float)nA, (float)nB, (float)(nA + nB) and its refined reciprocal
+};
+__device__ __forceinline__ CombineCounts combine_counts(int nA, int nB) {
+#pragma clang fp contract(off)
+    CombineCounts w;
+    w.nA = nA;
+    w.nB = nB;
+    w.fA = (float)nA;
+    w.fB = (float)nB;
+    w.nf = (float)(nA + nB);
+    w.r = refined_rcp(w.nf);
+    return w;
+}
+// per element: nB == 0 keeps A's bits, otherwise nA == 0 takes B's, otherwise the formula
+__device__ __forceinline__ float combine_pick(const CombineCounts &w, float a, float b, float f) {
+    return w.nB == 0 ? a : (w.nA == 0 ? b : f);
+}
+// The mean (and, with M2, the m2) line of one chain -- the moments, or the raw-sample chain film_mean / film_m2.  qt = q * t
+// and, with WANT_U, u = delta / n are what the m3 line needs.
+template <bool M2, bool WANT_U>
+__device__ __forceinline__ void combine_mean_m2(const CombineCounts &w, float mA, float mB, float m2A, float m2B, float &mean,
+                                                float &m2, float &qt, float &u) {
+#pragma clang fp contract(off)
+    const float d = mB - mA;
+    const float t = div_by_count(d * w.fB, w.nf, w.r);   // delta nB / n
+    const float q = d * w.fA;                            // delta nA
+    if (WANT_U) u = div_by_count(d, w.nf, w.r);          // delta / n
+    qt = q * t;
+    mean = combine_pick(w, mA, mB, mA + t);
+    if (M2) m2 = combine_pick(w, m2A, m2B, (m2A + m2B) + qt);
+}
+// The m3 line: m2A / m2B are both sides' m2 from BEFORE the combine, qt and u come from combine_mean_m2<true, true>.
+__device__ __forceinline__ float combine_m3(const CombineCounts &w, float m2A, float m2B, float m3A, float m3B, float qt, float u) {
+#pragma clang fp contract(off)
+    const float f = ((m3A + m3B) + qt * ((w.fA - w.fB) * u)) + (3.f * u) * (w.fA * m2B - w.fB * m2A);
+    return combine_pick(w, m3A, m3B, f);
+}
+// Part B into part A for one element: the first MAXM moments and the first FILM (0..2) fields of the raw-sample chain.
+template <int MAXM, int FILM>
+__device__ __forceinline__ void combine_elem(ElemState &a, const ElemState &b, const CombineCounts &w) {
+#pragma clang fp contract(off)
+    float mean, m2 = a.m2, qt, u;
+    if (MAXM >= 3) {
+        combine_mean_m2<true, true>(w, a.mean, b.mean, a.m2, b.m2, mean, m2, qt, u);
+        a.m3 = combine_m3(w, a.m2, b.m2, a.m3, b.m3, qt, u);
+    } else if (MAXM == 2) {
+        combine_mean_m2<true, false>(w, a.mean, b.mean, a.m2, b.m2, mean, m2, qt, u);
+    } else {
+        combine_mean_m2<false, false>(w, a.mean, b.mean, 0.f, 0.f, mean, m2, qt, u);
+    }
+    a.mean = mean;
+    a.m2 = m2;
+    if (FILM >= 2) {
+        combine_mean_m2<true, false>(w, a.fmean, b.fmean, a.fm2, b.fm2, mean, m2, qt, u);
+        a.fmean = mean;
+        a.fm2 = m2;
+    } else if (FILM == 1) {
+        combine_mean_m2<false, false>(w, a.fmean, b.fmean, 0.f, 0.f, mean, m2, qt, u);
+        a.fmean = mean;
+    }
+}
+
 // ------------------------------------------------------------------ one pixel of one (type, bounce), one thread
 // The semantics of statmc_accumulate for one pixel: load its state, fold samples in order, store.  C = channels (1 or 3),
 // MAXM = max_moment (1..3), TRANSFORM = the type's Box-Cox flag -- the three fields of the statmc_stat_type, fixed at
 // compile time here.  Plain scalar loads and stores: any pixel, any alignment.  One thread owns a pixel between load() and
-// store(); two threads folding into the same pixel at once lose samples (combine partial states with
-// statmc_combine_statistics instead).
+// store(); two threads folding into the same pixel at once lose samples.  A kernel that keeps several samples of a pixel in
+// flight gives every slot a PixelStats of its own (a default state: n = 0, all moments 0 -- clear()) and merges them before
+// the store: a.merge(b) is statmc_combine_statistics for this pixel, bit for bit, with a as part A and b as part B.  The
+// bits of a reduction depend on the order of its merges (fp32 addition is not associative): a left fold in slot order,
+// s[0].merge(s[1]); s[0].merge(s[2]); ..., leaves what statmc_combine_many leaves from the same parts in that order.
 template <int C, int MAXM, bool TRANSFORM>
 struct PixelStats {
     static_assert(C == 1 || C == 3, "a stat type has 1 or 3 channels");
@@ -137,6 +210,21 @@ struct PixelStats {
             st[c].fmean = TRANSFORM ? t.film_mean[e] : 0.f;
             st[c].fm2 = TRANSFORM ? t.film_m2[e] : 0.f;
         }
+    }
+    // the state of no samples
+    __device__ __forceinline__ void clear() {
+        n = 0;
+#pragma unroll
+        for (int c = 0; c < C; c++) st[c].mean = st[c].m2 = st[c].m3 = st[c].fmean = st[c].fm2 = 0.f;
+    }
+    // `other` -- the same pixel, samples of its own -- into this state: *this is part A, other part B, n becomes the sum.
+    // other.n == 0 keeps this state's bits, otherwise n == 0 takes other's.  Counts must sum below 2^24.
+    __device__ __forceinline__ void merge(const PixelStats &other) {
+#pragma clang fp contract(off)
+        const CombineCounts w = combine_counts(n, other.n);
+#pragma unroll
+        for (int c = 0; c < C; c++) combine_elem<MAXM, TRANSFORM ? 2 : 0>(st[c], other.st[c], w);
+        n += other.n;
     }
     // one sample: sample[0 .. C)
     __device__ __forceinline__ void add(const float *sample) {

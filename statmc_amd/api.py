@@ -87,6 +87,13 @@ class CombineEntry(C.Structure):
     _fields_ = [("dst", StatType), ("src", StatType), ("count_of", C.c_int32)]
 
 
+class CombineManyEntry(C.Structure):
+    """statmc_combine_many_entry: part 0 (dst, updated in place) and a host array of further parts, in fold order."""
+    _fields_ = [("dst", StatType), ("srcs", C.POINTER(StatType)), ("count_of", C.c_int32)]
+
+
+MAX_COMBINE_SOURCES = 15
+
 EXPORTS = [
     "statmc_last_error", "statmc_setup", "statmc_device_cus", "statmc_set_device", "statmc_set_significance", "statmc_get_significance", "statmc_set_t_quantiles",
     "statmc_set_filter_spec", "statmc_get_filter_spec", "statmc_reset_filter_spec", "statmc_pinned_from", "statmc_copy_device_settings",
@@ -95,7 +102,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -173,6 +180,7 @@ def load():
                                             C.c_void_p, C.c_int, C.c_void_p]
     lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
+    lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -545,6 +553,34 @@ def combine_statistics(width, height, entries, stream=None):
     arr = (CombineEntry * max(len(entries), 1))(*entries)
     check(load().statmc_combine_statistics(int(width), int(height), arr, len(entries),
                                            stream if stream is not None else current_stream_handle()))
+
+
+def make_combine_many_entry(dst, srcs, channels, max_moment, count_of=-1, prepass_into=None):
+    """One statmc_combine_many_entry: dst and every element of `srcs` are state dicts as for make_combine_entry; srcs is
+    the fold order.  The entry keeps its array of source descriptors alive (`_srcs`, `_n_sources` of them)."""
+    e = CombineManyEntry()
+    own = count_of < 0
+    e.dst = _state_side(dst, channels, max_moment, own)
+    arr = (StatType * max(len(srcs), 1))(*[_state_side(s, channels, max_moment, own) for s in srcs])
+    e._srcs, e._n_sources = arr, len(srcs)
+    e.srcs = C.cast(arr, C.POINTER(StatType))
+    e.count_of = -1 if own else int(count_of)
+    if prepass_into is not None:
+        e.dst.mean_corr, e.dst.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
+    return e
+
+
+def combine_many(width, height, entries, n_sources=None, stream=None):
+    """statmc_combine_many: every entry's sources into its dst, a left fold in source order, in one pass over memory
+    (include/statmc.h).  n_sources defaults to the length of the entries' source lists, which must agree."""
+    if n_sources is None:
+        counts = set(getattr(e, "_n_sources", 0) for e in entries)
+        if len(counts) > 1:
+            raise ValueError("combine_many: the entries have different numbers of sources (%s)" % sorted(counts))
+        n_sources = counts.pop() if counts else 0
+    arr = (CombineManyEntry * max(len(entries), 1))(*entries)
+    check(load().statmc_combine_many(int(width), int(height), arr, len(entries), int(n_sources),
+                                     stream if stream is not None else current_stream_handle()))
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):

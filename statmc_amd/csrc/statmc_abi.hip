@@ -1,6 +1,7 @@
 // statmc_abi.hip -- the extern "C" surface declared in include/statmc.h.
 // Validation + argument marshalling only; kernels live in statmc_pointwise.hip / statmc_filter.hip.
 
+#include <algorithm>
 #include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
@@ -1314,6 +1315,96 @@ int statmc_combine_statistics(uint16_t width, uint16_t height, const statmc_comb
         for (int f = 0; f < statmc::kCombFields; f++) k.vec &= aligned16(e.d[f]) && aligned16(e.s[f]);
     }
     HIP_TRY(statmc::launch_combine(k, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_combine_many: every (entry, source) pair passes the validation of the two-part call it stands for, then each entry
+// becomes one or two chains of the kernel -- its moments, and its raw-sample chain when it has film images of its own (at most
+// two planes, weighed with the same counts).  Chains that do not write counts go first, launch after launch in stream order,
+// so they read the owner's counts before the owner's chain -- last -- writes the sum.
+int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_many_entry *entries, int n_entries, int n_sources,
+                        void *stream) {
+    NEED_READY();
+    if (n_entries < 0 || n_entries > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_entries must be in [0,%d]", statmc::kMaxStatTypes);
+    if (n_sources < 0 || n_sources > STATMC_MAX_COMBINE_SOURCES)
+        return fail(STATMC_ERR_INVALID, "n_sources must be in [0,%d]", STATMC_MAX_COMBINE_SOURCES);
+    if (n_entries == 0 || n_sources == 0) return STATMC_OK;
+    if (!entries) return fail(STATMC_ERR_INVALID, "null entries");
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    for (int i = 0; i < n_entries; i++)
+        if (!entries[i].srcs) return fail(STATMC_ERR_INVALID, "entries[%d]: null srcs", i);
+    // pairs[k][i]: the two-part entry (dst, srcs[k]) of entry i, as the kernel's descriptor
+    std::vector<statmc::CombineEntry> pairs((size_t)n_sources * n_entries);
+    std::vector<statmc_combine_entry> two(n_entries);
+    for (int k = 0; k < n_sources; k++) {
+        for (int i = 0; i < n_entries; i++) {
+            two[i].dst = entries[i].dst;
+            two[i].src = entries[i].srcs[k];
+            two[i].count_of = entries[i].count_of;
+        }
+        for (int i = 0; i < n_entries; i++)
+            if (int rc = fill_combine_entry(dstate, two.data(), n_entries, i, pairs[(size_t)k * n_entries + i])) return rc;
+    }
+    // no dst image may be an image of one of its sources: the same plane is refused above, any other plane here
+    for (int i = 0; i < n_entries; i++) {
+        const statmc::CombineEntry &d = pairs[i];
+        for (int k = 0; k < n_sources; k++) {
+            const statmc::CombineEntry &p = pairs[(size_t)k * n_entries + i];
+            for (int f = 0; f < statmc::kCombFields; f++)
+                for (int g = 0; g < statmc::kCombFields; g++)
+                    if (d.d[f] && d.d[f] == p.s[g]) return fail(STATMC_ERR_INVALID, "entries[%d]: a dst image is an image of source %d", i, k);
+        }
+    }
+    struct Chain { int entry, first, planes, writes; };
+    std::vector<Chain> chains;
+    for (int pass = 0; pass < 2; pass++)   // the chains that only read counts, then the count owners' moments
+        for (int i = 0; i < n_entries; i++) {
+            const statmc::CombineEntry &d = pairs[i];
+            if (pass == 0 && d.d[statmc::kCombFilmMean]) chains.push_back({i, statmc::kCombFilmMean, d.d[statmc::kCombFilmM2] ? 2 : 1, 0});
+            if ((pass == 1) == (d.write_n != 0))
+                chains.push_back({i, statmc::kCombMean, d.d[statmc::kCombM3] ? 3 : d.d[statmc::kCombM2] ? 2 : 1, d.write_n});
+        }
+    const size_t per_launch = std::min<size_t>(statmc::kMaxStatTypes, statmc::kCombManySlots / n_sources);
+    for (size_t c0 = 0; c0 < chains.size(); c0 += per_launch) {
+        statmc::CombineManyArgs k;
+        memset(&k, 0, sizeof(k));
+        k.n_px = (long long)width * height;
+        k.n_sources = n_sources;
+        k.n_entries = (int)std::min(per_launch, chains.size() - c0);
+        k.vec = 1;
+        for (int c = 0; c < k.n_entries; c++) {
+            const Chain &ch = chains[c0 + c];
+            const statmc::CombineEntry &d = pairs[ch.entry];
+            statmc::CombineManyEntry &e = k.e[c];
+            e.cnt_dst = d.cnt_dst;
+            e.channels = d.channels;
+            e.moments = ch.planes;
+            e.write_n = ch.writes;
+            k.vec &= aligned16(e.cnt_dst);
+            for (int m = 0; m < ch.planes; m++) {
+                e.d[m] = d.d[ch.first + m];
+                k.vec &= aligned16(e.d[m]);
+            }
+            if (ch.first == statmc::kCombMean && d.mean_corr) {
+                e.mean_corr = d.mean_corr;
+                e.disc = d.disc;
+                e.pre = d.pre_table | (d.pre_flags << 8);
+                k.vec &= aligned16(e.mean_corr) && aligned16(e.disc);
+            }
+            for (int s = 0; s < n_sources; s++) {
+                const statmc::CombineEntry &p = pairs[(size_t)s * n_entries + ch.entry];
+                const void **slot = k.src + ((size_t)c * n_sources + s) * statmc::kCombManySrcPtrs;
+                slot[0] = p.cnt_src;
+                k.vec &= aligned16(slot[0]);
+                for (int m = 0; m < ch.planes; m++) {
+                    slot[1 + m] = p.s[ch.first + m];
+                    k.vec &= aligned16(slot[1 + m]);
+                }
+            }
+        }
+        HIP_TRY(statmc::launch_combine_many(k, S(stream)));
+    }
     return STATMC_OK;
 }
 

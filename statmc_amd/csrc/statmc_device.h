@@ -95,6 +95,30 @@ struct CombineArgs {
 };
 hipError_t launch_combine(const CombineArgs &a, hipStream_t s);
 
+// statmc_combine_many: one chain of up to three planes per kernel entry -- an ABI entry's moments, or its raw-sample chain
+// (film_mean / film_m2 of their own), which is a chain of at most two planes weighed with the same counts -- folded over
+// n_sources parts.  src holds kCombManySrcPtrs pointers per (entry, source): the part's counts, then its planes; entry i's
+// source k starts at (i * n_sources + k) * kCombManySrcPtrs.  The whole argument stays below the 4-KB kernel-argument
+// limit, so a launch takes min(kMaxStatTypes, kCombManySlots / n_sources) entries; the ABI splits a call into launches,
+// entries that do not write counts first (launches of one stream run in order).
+enum { kCombManyPlanes = 3, kCombManySrcPtrs = 1 + kCombManyPlanes, kCombManySlots = 90 };
+struct CombineManyEntry {
+    int32_t *cnt_dst;
+    float *d[kCombManyPlanes];       // dst planes, the first `moments` of them
+    float *mean_corr, *disc;         // optional pre-pass epilogue (own counts, moments 3)
+    int channels, moments, write_n, pre;   // pre: pre_table | pre_flags << 8
+};
+struct CombineManyArgs {
+    long long n_px;
+    int n_entries, n_sources;
+    int vec;                         // every plane 16-byte aligned: whole 4-pixel groups move as dwordx4
+    int reserved;
+    CombineManyEntry e[kMaxStatTypes];
+    const void *src[kCombManySlots * kCombManySrcPtrs];
+};
+static_assert(sizeof(CombineManyArgs) <= 4096, "CombineManyArgs is passed by value: the kernel-argument limit");
+hipError_t launch_combine_many(const CombineManyArgs &a, hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

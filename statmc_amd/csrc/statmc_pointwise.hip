@@ -28,6 +28,7 @@
 namespace statmc {
 
 // the per-sample arithmetic and the pre-pass of one element: one definition, shared with device code outside the library
+using device::CombineCounts;
 using device::ElemState;
 using device::add_sample;
 using device::div_by_count;
@@ -1030,16 +1031,15 @@ __device__ __forceinline__ void comb_load_n(const int32_t *p, long long px0, int
     }
 }
 
-// per pixel: nB == 0 keeps A's bits, otherwise nA == 0 takes B's, otherwise the formula
-__device__ __forceinline__ float comb_pick(int nA, int nB, float a, float b, float f) { return nB == 0 ? a : (nA == 0 ? b : f); }
+// (combine_counts, combine_mean_m2, combine_m3: include/statmc_device_api.hpp -- the per-element arithmetic, the definition a
+// renderer's own kernel merges with as well)
 
-// mean (and m2) of one chain: the mean / m2 lines of the formula.  t, q and u (u only with WANT_U) are kept for m3.
+// mean (and m2) of one chain: the mean / m2 lines of the formula.  qt and u (u only with WANT_U) are kept for m3.
 template <int C, bool VEC, bool M2, bool WANT_U>
 __device__ __forceinline__ void comb_chain(float *dm, const float *sm, float *dm2, const float *sm2, long long px0, int npx,
-                                           const int (&nA)[4], const int (&nB)[4], const float (&fA)[4], const float (&fB)[4],
-                                           const float (&nf)[4], const float (&r)[4], float (&mA)[4 * C], float (&m2A)[4 * C],
-                                           float (&m2B)[4 * C], float (&q)[4 * C], float (&t)[4 * C], float (&u)[4 * C]) {
-    float mB[4 * C];
+                                           const CombineCounts (&w)[4], float (&mA)[4 * C], float (&m2A)[4 * C], float (&m2B)[4 * C],
+                                           float (&qt)[4 * C], float (&u)[4 * C]) {
+    float mB[4 * C], o[4 * C];
     comb_load<C, VEC>(dm, px0, npx, mA);
     comb_load<C, VEC>(sm, px0, npx, mB);
     if (M2) {
@@ -1047,22 +1047,10 @@ __device__ __forceinline__ void comb_chain(float *dm, const float *sm, float *dm
         comb_load<C, VEC>(sm2, px0, npx, m2B);
     }
 #pragma unroll
-    for (int j = 0; j < 4 * C; j++) {
-        const int p = j / C;
-        const float d = mB[j] - mA[j];
-        t[j] = div_by_count(d * fB[p], nf[p], r[p]);   // delta nB / n
-        q[j] = d * fA[p];                              // delta nA
-        if (WANT_U) u[j] = div_by_count(d, nf[p], r[p]);   // delta / n
-        mA[j] = comb_pick(nA[p], nB[p], mA[j], mB[j], mA[j] + t[j]);
-    }
+    for (int j = 0; j < 4 * C; j++)
+        device::combine_mean_m2<M2, WANT_U>(w[j / C], mA[j], mB[j], m2A[j], m2B[j], mA[j], o[j], qt[j], u[j]);
     comb_store<C, VEC>(dm, px0, npx, mA);
     if (M2) {
-        float o[4 * C];
-#pragma unroll
-        for (int j = 0; j < 4 * C; j++) {
-            const int p = j / C;
-            o[j] = comb_pick(nA[p], nB[p], m2A[j], m2B[j], (m2A[j] + m2B[j]) + q[j] * t[j]);
-        }
         comb_store<C, VEC>(dm2, px0, npx, o);
         if (!WANT_U) {   // no m3 to come: the combined m2 is what the caller keeps
 #pragma unroll
@@ -1076,28 +1064,20 @@ __device__ __forceinline__ void combine_entry(const CombineEntry &e, long long p
     int nA[4], nB[4];
     comb_load_n<VEC>(e.cnt_dst, px0, npx, nA);
     comb_load_n<VEC>(e.cnt_src, px0, npx, nB);
-    float fA[4], fB[4], nf[4], r[4];
+    CombineCounts w[4];
 #pragma unroll
-    for (int p = 0; p < 4; p++) {
-        fA[p] = (float)nA[p];
-        fB[p] = (float)nB[p];
-        nf[p] = (float)(nA[p] + nB[p]);
-        r[p] = refined_rcp(nf[p]);
-    }
-    float mA[4 * C], m2A[4 * C], m2B[4 * C], q[4 * C], t[4 * C], u[4 * C];
+    for (int p = 0; p < 4; p++) w[p] = device::combine_counts(nA[p], nB[p]);
+    float mA[4 * C], m2A[4 * C], m2B[4 * C], qt[4 * C], u[4 * C];
     if (e.d[kCombM3]) {
-        comb_chain<C, VEC, true, true>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, nA, nB, fA, fB, nf, r,
-                                       mA, m2A, m2B, q, t, u);
+        comb_chain<C, VEC, true, true>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, w, mA, m2A, m2B, qt, u);
         float m3A[4 * C], m3B[4 * C];
         comb_load<C, VEC>(e.d[kCombM3], px0, npx, m3A);
         comb_load<C, VEC>(e.s[kCombM3], px0, npx, m3B);
 #pragma unroll
         for (int j = 0; j < 4 * C; j++) {
-            const int p = j / C;
-            const float f = ((m3A[j] + m3B[j]) + (q[j] * t[j]) * ((fA[p] - fB[p]) * u[j])) + (3.f * u[j]) * (fA[p] * m2B[j] - fB[p] * m2A[j]);
-            const float m2 = comb_pick(nA[p], nB[p], m2A[j], m2B[j], (m2A[j] + m2B[j]) + q[j] * t[j]);
-            m3A[j] = comb_pick(nA[p], nB[p], m3A[j], m3B[j], f);
-            m2A[j] = m2;
+            const CombineCounts &wp = w[j / C];
+            m3A[j] = device::combine_m3(wp, m2A[j], m2B[j], m3A[j], m3B[j], qt[j], u[j]);
+            m2A[j] = device::combine_pick(wp, m2A[j], m2B[j], (m2A[j] + m2B[j]) + qt[j]);
         }
         comb_store<C, VEC>(e.d[kCombM3], px0, npx, m3A);
         if (e.mean_corr) {   // the pre-pass of the combined moments: prepass_kernel's prepass_elem, the same bits
@@ -1112,18 +1092,15 @@ __device__ __forceinline__ void combine_entry(const CombineEntry &e, long long p
             comb_store<C, VEC>(e.disc, px0, npx, dc);
         }
     } else if (e.d[kCombM2]) {
-        comb_chain<C, VEC, true, false>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, nA, nB, fA, fB, nf, r,
-                                        mA, m2A, m2B, q, t, u);
+        comb_chain<C, VEC, true, false>(e.d[kCombMean], e.s[kCombMean], e.d[kCombM2], e.s[kCombM2], px0, npx, w, mA, m2A, m2B, qt, u);
     } else {
-        comb_chain<C, VEC, false, false>(e.d[kCombMean], e.s[kCombMean], nullptr, nullptr, px0, npx, nA, nB, fA, fB, nf, r, mA, m2A,
-                                         m2B, q, t, u);
+        comb_chain<C, VEC, false, false>(e.d[kCombMean], e.s[kCombMean], nullptr, nullptr, px0, npx, w, mA, m2A, m2B, qt, u);
     }
     if (e.d[kCombFilmM2])
-        comb_chain<C, VEC, true, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], e.d[kCombFilmM2], e.s[kCombFilmM2], px0, npx, nA, nB, fA,
-                                        fB, nf, r, mA, m2A, m2B, q, t, u);
+        comb_chain<C, VEC, true, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], e.d[kCombFilmM2], e.s[kCombFilmM2], px0, npx, w, mA,
+                                        m2A, m2B, qt, u);
     else if (e.d[kCombFilmMean])
-        comb_chain<C, VEC, false, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], nullptr, nullptr, px0, npx, nA, nB, fA, fB, nf, r, mA,
-                                         m2A, m2B, q, t, u);
+        comb_chain<C, VEC, false, false>(e.d[kCombFilmMean], e.s[kCombFilmMean], nullptr, nullptr, px0, npx, w, mA, m2A, m2B, qt, u);
     if (e.write_n) {
         if (VEC) {
             *reinterpret_cast<int4 *>(e.cnt_dst + px0) = make_int4(nA[0] + nB[0], nA[1] + nB[1], nA[2] + nB[2], nA[3] + nB[3]);
@@ -1160,6 +1137,178 @@ hipError_t launch_combine(const CombineArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(combine_stats_kernel<true>, dim3(grid), dim3(kBlock), 0, s, a);
     else
         hipLaunchKernelGGL(combine_stats_kernel<false>, dim3(grid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ combine, K parts
+// statmc_combine_many: the left fold of n_sources combines, in one pass over memory.  One lane owns 4 consecutive pixels
+// and walks the entries in the ABI's order (the entries that do not write counts first), as above; per entry it loads the
+// dst planes and counts once, folds source after source in registers and stores once.  The source planes are read once and
+// never again, but they are plain loads: with the nt bit the same kernel streamed at 0.59-0.62 of the HBM peak instead of
+// 0.63-0.65.  The loads of the next sources are requested before the arithmetic on source k (a ring of
+// register sets, the loop unrolled by its size), so a lane has whole sources in flight behind the one it works on.
+typedef float cm_f32x4 __attribute__((ext_vector_type(4)));
+typedef int cm_i32x4 __attribute__((ext_vector_type(4)));
+
+template <int C, int M>
+struct CombManySrc {
+    int n[4];
+    float v[M][4 * C];
+};
+
+template <int C, int M, bool VEC>
+__device__ __forceinline__ void comb_many_load(const void *const *sp, long long px0, int npx, CombManySrc<C, M> &s) {
+    const int32_t *cn = static_cast<const int32_t *>(sp[0]);
+    if (VEC) {
+        const cm_i32x4 x = *reinterpret_cast<const cm_i32x4 *>(cn + px0);   // counts: read again by the entries that share them
+        s.n[0] = x.x;
+        s.n[1] = x.y;
+        s.n[2] = x.z;
+        s.n[3] = x.w;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const cm_f32x4 *p = reinterpret_cast<const cm_f32x4 *>(static_cast<const float *>(sp[1 + m]) + px0 * C);
+#pragma unroll
+            for (int k = 0; k < C; k++) {
+                const cm_f32x4 y = p[k];
+                s.v[m][4 * k] = y.x;
+                s.v[m][4 * k + 1] = y.y;
+                s.v[m][4 * k + 2] = y.z;
+                s.v[m][4 * k + 3] = y.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) s.n[j] = j < npx ? cn[px0 + j] : 0;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const float *p = static_cast<const float *>(sp[1 + m]) + px0 * C;
+#pragma unroll
+            for (int j = 0; j < 4 * C; j++) s.v[m][j] = j < npx * C ? p[j] : 0.f;
+        }
+    }
+}
+
+// source `s` (part B) into the running state (part A); nA becomes the running count
+template <int C, int M>
+__device__ __forceinline__ void comb_many_fold(int (&nA)[4], float (&A)[M][4 * C], const CombManySrc<C, M> &s) {
+#pragma unroll
+    for (int p = 0; p < 4; p++) {
+        const CombineCounts w = device::combine_counts(nA[p], s.n[p]);
+#pragma unroll
+        for (int c = 0; c < C; c++) {
+            const int j = p * C + c;
+            ElemState a, b;
+            a.mean = A[0][j];
+            b.mean = s.v[0][j];
+            a.m2 = M >= 2 ? A[1][j] : 0.f;
+            b.m2 = M >= 2 ? s.v[1][j] : 0.f;
+            a.m3 = M >= 3 ? A[2][j] : 0.f;
+            b.m3 = M >= 3 ? s.v[2][j] : 0.f;
+            a.fmean = a.fm2 = b.fmean = b.fm2 = 0.f;
+            device::combine_elem<M, 0>(a, b, w);
+            A[0][j] = a.mean;
+            if (M >= 2) A[1][j] = a.m2;
+            if (M >= 3) A[2][j] = a.m3;
+        }
+        nA[p] += s.n[p];
+    }
+}
+
+template <int C, int M, bool VEC>
+__device__ __forceinline__ void combine_many_entry(const CombineManyEntry &e, const void *const *src, int n_sources, long long px0,
+                                                   int npx) {
+    // D register sets: D - 1 sources in flight behind the one being folded.  A chain of one plane moves 64 B per lane and
+    // source, too little to keep a CU's share of HBM busy from one request: the fewer planes, the deeper the ring.
+    constexpr int D = M == 1 ? 4 : M == 2 ? 3 : 2;
+    CombManySrc<C, M> s[D];
+    int nA[4];
+    float A[M][4 * C];
+    comb_load_n<VEC>(e.cnt_dst, px0, npx, nA);
+#pragma unroll
+    for (int m = 0; m < M; m++) comb_load<C, VEC>(e.d[m], px0, npx, A[m]);
+#pragma unroll
+    for (int j = 0; j < D - 1; j++)
+        if (j < n_sources) comb_many_load<C, M, VEC>(src + j * kCombManySrcPtrs, px0, npx, s[j]);
+    // The steady state has no branch between a request and the fold before it: the wait in front of a fold then counts the
+    // loads requested after the ones it needs and leaves them in flight (a conditional request makes it a wait for all).
+    int k = 0;
+    for (; k + 2 * D - 1 <= n_sources; k += D) {
+#pragma unroll
+        for (int j = 0; j < D; j++) {
+            comb_many_load<C, M, VEC>(src + (k + j + D - 1) * kCombManySrcPtrs, px0, npx, s[(j + D - 1) % D]);
+            comb_many_fold<C, M>(nA, A, s[j]);
+        }
+    }
+    // the last sources, fewer than 2 D - 1: k .. k + D - 2 are requested already
+#pragma unroll
+    for (int j = 0; j < 2 * D - 2; j++) {
+        if (k + j < n_sources) {
+            if (k + j + D - 1 < n_sources)
+                comb_many_load<C, M, VEC>(src + (k + j + D - 1) * kCombManySrcPtrs, px0, npx, s[(j + D - 1) % D]);
+            comb_many_fold<C, M>(nA, A, s[j % D]);
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) comb_store<C, VEC>(e.d[m], px0, npx, A[m]);
+    if (M == 3 && e.mean_corr) {   // the pre-pass of the final moments: prepass_kernel's prepass_elem, the same bits
+        const int table = e.pre & 255, flags = e.pre >> 8;
+        float mc[4 * C], dc[4 * C];
+#pragma unroll
+        for (int j = 0; j < 4 * C; j++) {
+            const int ni = nA[j / C];
+            prepass_elem(ni, (flags & 1) ? 1.f : t_quantile(table, ni - 1), A[0][j], A[M >= 2 ? 1 : 0][j], A[M >= 3 ? 2 : 0][j], mc[j],
+                         dc[j], (flags & 2) != 0);
+        }
+        comb_store<C, VEC>(e.mean_corr, px0, npx, mc);
+        comb_store<C, VEC>(e.disc, px0, npx, dc);
+    }
+    if (e.write_n) {
+        if (VEC) {
+            *reinterpret_cast<int4 *>(e.cnt_dst + px0) = make_int4(nA[0], nA[1], nA[2], nA[3]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+                if (p < npx) e.cnt_dst[px0 + p] = nA[p];
+        }
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void combine_many_dispatch(const CombineManyEntry &e, const void *const *src, int n_sources, long long px0,
+                                                      int npx) {
+    if (e.channels == 3) {
+        if (e.moments == 3) combine_many_entry<3, 3, VEC>(e, src, n_sources, px0, npx);
+        else if (e.moments == 2) combine_many_entry<3, 2, VEC>(e, src, n_sources, px0, npx);
+        else combine_many_entry<3, 1, VEC>(e, src, n_sources, px0, npx);
+    } else {
+        if (e.moments == 3) combine_many_entry<1, 3, VEC>(e, src, n_sources, px0, npx);
+        else if (e.moments == 2) combine_many_entry<1, 2, VEC>(e, src, n_sources, px0, npx);
+        else combine_many_entry<1, 1, VEC>(e, src, n_sources, px0, npx);
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void combine_many_kernel(CombineManyArgs a) {
+    const long long n_groups = (a.n_px + 3) >> 2;
+    for (long long g = (long long)blockIdx.x * kBlock + threadIdx.x; g < n_groups; g += (long long)gridDim.x * kBlock) {
+        const long long px0 = g << 2;
+        const int npx = a.n_px - px0 < 4 ? (int)(a.n_px - px0) : 4;
+        for (int i = 0; i < a.n_entries; i++) {
+            const CombineManyEntry e = a.e[i];   // a copy, not a reference into the by-value argument
+            const void *const *src = a.src + (long long)i * a.n_sources * kCombManySrcPtrs;
+            if (VEC && npx == 4) combine_many_dispatch<true>(e, src, a.n_sources, px0, 4);
+            else combine_many_dispatch<false>(e, src, a.n_sources, px0, npx);
+        }
+    }
+}
+
+hipError_t launch_combine_many(const CombineManyArgs &a, hipStream_t s) {
+    const int grid = grid_for((a.n_px + 3) / 4);
+    if (a.vec)
+        hipLaunchKernelGGL(combine_many_kernel<true>, dim3(grid), dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL(combine_many_kernel<false>, dim3(grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -80,22 +80,37 @@ class FilmStats:
         """Combines the statistics of `other` -- the same film, its own samples -- into self, so that self holds the
         statistics of the union of both sample sets (statmc_combine_statistics: one launch).  Every stat type is weighed
         with its own counts; the colour image `film` with the radiance counts.  With fused_prepass the launch's epilogue
-        writes mean-corr / discriminator of the combined radiance moments (the bits of statmc_prepass)."""
-        if (other.width, other.height) != (self.width, self.height) or other.device != self.device:
-            raise ValueError("combine_: both films must have the same size and device")
-        if set(other.types) != set(self.types):
-            raise ValueError("combine_: both films must carry the same stat types (%s / %s)" % (self.types, other.types))
+        writes mean-corr / discriminator of the combined radiance moments (the bits of statmc_prepass).
+
+        `other` may also be a sequence of films: they are folded into self in that order by statmc_combine_many -- the bits
+        of one combine_ per film, every part read once and self written once (groups of api.MAX_COMBINE_SOURCES)."""
+        many = not isinstance(other, FilmStats)
+        others = list(other) if many else [other]
+        for o in others:
+            if (o.width, o.height) != (self.width, self.height) or o.device != self.device:
+                raise ValueError("combine_: both films must have the same size and device")
+            if set(o.types) != set(self.types):
+                raise ValueError("combine_: both films must carry the same stat types (%s / %s)" % (self.types, o.types))
         fuse = self.fused_prepass and "radiance" in self.types
-        entries = []
-        for t in self.types:
-            cfg = STAT_TYPES[t]
-            entries.append(api.make_combine_entry(self.state[t], other.state[t], cfg["channels"], cfg["max_moment"],
-                                                  prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None))
-        if "radiance" in self.types and self.film is not None and other.film is not None:
-            owner = self.types.index("radiance")
-            entries.append(api.make_combine_entry({"mean": self.film}, {"mean": other.film}, 3, 1, count_of=owner))
-        api.combine_statistics(self.width, self.height, entries)
-        self._prepass_current = self._prepass_key() if fuse else None
+        with_film = "radiance" in self.types and self.film is not None and all(o.film is not None for o in others)
+        for g in range(0, len(others), api.MAX_COMBINE_SOURCES):
+            group = others[g:g + api.MAX_COMBINE_SOURCES]
+            make = (lambda dst, srcs, *a, **kw: api.make_combine_many_entry(dst, srcs, *a, **kw)) if many else \
+                   (lambda dst, srcs, *a, **kw: api.make_combine_entry(dst, srcs[0], *a, **kw))
+            entries = []
+            for t in self.types:
+                cfg = STAT_TYPES[t]
+                entries.append(make(self.state[t], [o.state[t] for o in group], cfg["channels"], cfg["max_moment"],
+                                    prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None))
+            if with_film:
+                owner = self.types.index("radiance")
+                entries.append(make({"mean": self.film}, [{"mean": o.film} for o in group], 3, 1, count_of=owner))
+            if many:
+                api.combine_many(self.width, self.height, entries, n_sources=len(group))
+            else:
+                api.combine_statistics(self.width, self.height, entries)
+        if others:
+            self._prepass_current = self._prepass_key() if fuse else None
 
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())

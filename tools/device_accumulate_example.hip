@@ -1,9 +1,12 @@
 // device_accumulate_example.hip -- a renderer's kernel folding its samples into StatMC's statistics itself
 // (include/statmc_device_api.hpp), built into tools/bin/libstatmc_device_example.so with hipcc's DEFAULT floating-point flags
-// (-ffp-contract=fast-honor-pragmas): the header's bits must not depend on them.  Three launchers, extern "C":
+// (-ffp-contract=fast-honor-pragmas): the header's bits must not depend on them.  Four launchers, extern "C":
 //
 //   fold_arena  one thread per pixel folds a film-major arena ([S][H][W][C] fp32, statmc_accumulate's input) through
 //               PixelStats -- the bits of statmc_accumulate on the same arena (tests/test_device_api_gpu.py)
+//   fold_arena_slots  the same arena with every pixel's samples dealt to several slots: each slot folds its share, the slots
+//               are merged in slot order (PixelStats::merge) and the pixel is stored once -- the bits of the slots' states
+//               combined by statmc_combine_many (tests/test_combine_many_gpu.py)
 //   gen_arena   a stand-in for a path tracer: one counter-based hash per (pixel, sample) gives the five G-buffer / radiance
 //               values of the flagship configuration (film.STAT_TYPES: radiance, normal, albedo, depth, material id; 11
 //               channels), written to one arena per type -- what feeds statmc_accumulate today
@@ -50,10 +53,51 @@ __global__ __launch_bounds__(kBlock) void fold_arena_kernel(statmc_stat_type t, 
     ps.store(t, p);
 }
 
+// ------------------------------------------------------------------ fold_arena_slots
+// A renderer that keeps several samples of a pixel in flight: slot k of pixel p owns the samples bounds[k][p] .. bounds[k + 1][p]
+// - 1 of the arena (bounds: [n_slots + 1][n_px] int32, non-decreasing per pixel; a slot may own none).  Slot 0 folds into the
+// pixel's stored state, every other slot into a cleared state of its own; the slots are merged in slot order -- a left fold,
+// the bits of statmc_combine_many over the slots' states -- and the pixel is stored once.
+template <int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(kBlock) void fold_slots_kernel(statmc_stat_type t, long long n_px, const float *arena, const int32_t *bounds,
+                                                            int n_slots, statmc_prepass_context ctx, int with_prepass) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_px) return;
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    ps.load(t, p);
+    for (int k = 0; k < n_slots; k++) {
+        PixelStats<C, MAXM, TRANSFORM> slot;
+        slot.clear();
+        PixelStats<C, MAXM, TRANSFORM> &into = k == 0 ? ps : slot;
+        const int s1 = bounds[(long long)(k + 1) * n_px + p];
+        for (int s = bounds[(long long)k * n_px + p]; s < s1; s++) {
+            const float *q = arena + ((long long)s * n_px + p) * C;
+            float smp[C];
+#pragma unroll
+            for (int c = 0; c < C; c++) smp[c] = q[c];
+            into.add(smp);
+        }
+        if (k > 0) ps.merge(slot);
+    }
+    if constexpr (MAXM >= 3) {
+        if (with_prepass) {
+            ps.store(t, p, ctx);
+            return;
+        }
+    }
+    ps.store(t, p);
+}
+
+// bounds == NULL: fold_arena_kernel over n_samples; otherwise fold_slots_kernel over n_slots
 template <int C, int MAXM, bool TRANSFORM>
 int launch_fold(const statmc_stat_type &t, long long n_px, const float *arena, int n_samples, const statmc_prepass_context *ctx,
-                hipStream_t s) {
+                hipStream_t s, const int32_t *bounds = nullptr, int n_slots = 0) {
     const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
+    if (bounds) {
+        hipLaunchKernelGGL((fold_slots_kernel<C, MAXM, TRANSFORM>), dim3(grid_for(n_px)), dim3(kBlock), 0, s, t, n_px, arena, bounds,
+                           n_slots, c, ctx ? 1 : 0);
+        return launched();
+    }
     hipLaunchKernelGGL((fold_arena_kernel<C, MAXM, TRANSFORM>), dim3(grid_for(n_px)), dim3(kBlock), 0, s, t, n_px, arena, n_samples, c,
                        ctx ? 1 : 0);
     return launched();
@@ -61,15 +105,15 @@ int launch_fold(const statmc_stat_type &t, long long n_px, const float *arena, i
 
 template <int C>
 int fold_dispatch(const statmc_stat_type &t, long long n_px, const float *arena, int n_samples, const statmc_prepass_context *ctx,
-                  hipStream_t s) {
+                  hipStream_t s, const int32_t *bounds = nullptr, int n_slots = 0) {
     if (t.transform) {
-        if (t.max_moment == 3) return launch_fold<C, 3, true>(t, n_px, arena, n_samples, ctx, s);
-        if (t.max_moment == 2) return launch_fold<C, 2, true>(t, n_px, arena, n_samples, ctx, s);
-        return launch_fold<C, 1, true>(t, n_px, arena, n_samples, ctx, s);
+        if (t.max_moment == 3) return launch_fold<C, 3, true>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
+        if (t.max_moment == 2) return launch_fold<C, 2, true>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
+        return launch_fold<C, 1, true>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
     }
-    if (t.max_moment == 3) return launch_fold<C, 3, false>(t, n_px, arena, n_samples, ctx, s);
-    if (t.max_moment == 2) return launch_fold<C, 2, false>(t, n_px, arena, n_samples, ctx, s);
-    return launch_fold<C, 1, false>(t, n_px, arena, n_samples, ctx, s);
+    if (t.max_moment == 3) return launch_fold<C, 3, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
+    if (t.max_moment == 2) return launch_fold<C, 2, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
+    return launch_fold<C, 1, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
 }
 
 // ------------------------------------------------------------------ the sample generator
@@ -184,6 +228,22 @@ int fold_arena(const statmc_stat_type *t, int width, int height, const float *ar
     const long long n_px = (long long)width * height;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return t->channels == 3 ? fold_dispatch<3>(*t, n_px, arena, n_samples, ctx, s) : fold_dispatch<1>(*t, n_px, arena, n_samples, ctx, s);
+}
+
+// The same with every pixel's samples dealt to n_slots slots that are merged in slot order (fold_slots_kernel): bounds is a
+// device array [n_slots + 1][height][width] of sample indices into the arena, non-decreasing per pixel and within the arena
+// (the caller's to guarantee: it is not read here).
+int fold_arena_slots(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int n_slots,
+                     const statmc_prepass_context *ctx, void *stream) {
+    if (!t || width <= 0 || height <= 0 || !arena || !bounds || n_slots < 1) return STATMC_ERR_INVALID;
+    if ((t->channels != 1 && t->channels != 3) || t->max_moment < 1 || t->max_moment > 3 || !t->n || !t->mean) return STATMC_ERR_INVALID;
+    if ((t->max_moment >= 2 && !t->m2) || (t->max_moment >= 3 && !t->m3) || (t->transform && (!t->film_mean || !t->film_m2)))
+        return STATMC_ERR_INVALID;
+    if (ctx && (t->max_moment < 3 || !t->mean_corr || !t->discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    const long long n_px = (long long)width * height;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return t->channels == 3 ? fold_dispatch<3>(*t, n_px, arena, 0, ctx, s, bounds, n_slots)
+                            : fold_dispatch<1>(*t, n_px, arena, 0, ctx, s, bounds, n_slots);
 }
 
 // arenas[5]: radiance, normal, albedo ([n_samples][height][width][3]), depth, material id ([n_samples][height][width]); samples

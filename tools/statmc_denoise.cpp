@@ -9,7 +9,7 @@
 //                  [--spec gate=sym|asym,channels=and|joint,sides=two|one,dof=pixel|welch,border=clip|clamp,small_n=accept|exclude]
 //                  [--grid GXxGY [--devices 0,1,..]]   the denoise pass over film blocks with a halo exchange (C++ only)
 //                  [--placed]                          device images from statmc_malloc_placed (statmc::usePlacedMemory())
-//                  [--combine S1[,S2,..] --output-stem O [--write-combined]]   dumps of independent renders, combined
+//                  [--combine S1[,S2,..] --output-stem O [--write-combined] [--combine-mem GiB]]   dumps of independent renders, combined
 //   statmc_denoise --catalogue [--config denoise|acrr|smis|proden|ours] [--width W --height H]
 //
 // Per iteration it reads "<stem>-<spp>-film.pfm" and every "<stem>-<spp>-t<i>-b<j>-<suffix>.pfm"
@@ -24,7 +24,9 @@
 // bound is stated in.  --tquantiles loads whitespace-separated t quantiles for dof 1..n into the
 // selected significance slot (for users who have the reference's own tables).
 // --combine S1,S2,..: the dumps "<Sk>-<spp>-*" of renders of the same scene with other samples (pbrt --baseseed) are combined
-// with "<stem>-<spp>-*" on the device before the denoise pass (Estimator::CombineStatistics, a left fold); every stem must
+// with "<stem>-<spp>-*" on the device before the denoise pass (Estimator::CombineStatistics, a left fold in argument order:
+// the stems are uploaded and combined in groups of up to STATMC_MAX_COMBINE_SOURCES, fewer when a group's images would take
+// more than --combine-mem GiB, default 8; the grouping does not change a bit of the result); every stem must
 // carry the same set of buffer files.  Types without an n file (the G-buffer means of a for-ours dump) are weighed with
 // t0-b0-n; input mean-corr / discriminator dumps are not read (Denoise recomputes them).  The outputs go to
 // "<O>-<spp * (1 + k)>-<buffer>.pfm"; --write-combined also writes every combined statistics buffer that was read under the
@@ -125,6 +127,7 @@ int main(int argc, char **argv) {
         std::string stem, sppList, output = "film-f", config = "denoise", compareStem, tqFile, specText, gridText, devicesText;
         bool noWrite = false, writeCombined = false;
         std::string combineText, outputStem;
+        size_t combineMemBytes = 8ull << 30;   // --combine-mem GiB: the images of the other stems held at once
         int forceParts = 0, bands = 0;
         std::string kernel, sweep, sweepSignificance = "0,1,2";
         int significance = 0;
@@ -164,6 +167,7 @@ int main(int argc, char **argv) {
             else if (a == "--bands") bands = std::stoi(next());  // Upload / Denoise / Download as a pipeline of row bands (0 = automatic, 1 = off)
             else if (a == "--combine") combineText = next();
             else if (a == "--output-stem") outputStem = next();
+            else if (a == "--combine-mem") combineMemBytes = (size_t)(std::stod(next()) * (double)(1ull << 30));
             else if (a == "--write-combined") writeCombined = true;
             else if (a == "--width") width = std::stoi(next());
             else if (a == "--height") height = std::stoi(next());
@@ -229,16 +233,28 @@ int main(int argc, char **argv) {
         est.AllocateBuffers(reg);
         // --combine: the combine sits between the uploads and Denoise, so the row-band pipeline is off
         est.SetPipelineBands(combineStems.empty() ? bands : 1);
-        std::unique_ptr<Buffer> otherFilm;
-        std::unique_ptr<BufferRegistry> otherReg;
-        std::unique_ptr<Estimator> other;   // --combine: the dump of one other stem at a time
+        // --combine: the dumps of up to STATMC_MAX_COMBINE_SOURCES other stems at a time, as many as fit the memory bound
+        struct Part {
+            std::unique_ptr<Buffer> film;
+            std::unique_ptr<BufferRegistry> reg;
+            std::unique_ptr<Estimator> est;
+        };
+        std::vector<Part> parts;
         if (!combineStems.empty()) {
-            otherFilm.reset(new Buffer("film", HostImage(height, width, F32C3)));
-            otherReg.reset(new BufferRegistry(*otherFilm));
-            other.reset(new Estimator(*otherFilm, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr,
-                                      params.smis, *otherReg));
-            other->AllocateBuffers(*otherReg);
-            other->SetPipelineBands(1);
+            size_t partBytes = 0;   // host and device images of one part
+            for (const auto &b : reg.buffers) partBytes += b.mat.bytes();
+            const size_t fit = std::max<size_t>(1, combineMemBytes / std::max<size_t>(partBytes, 1));
+            parts.resize(std::min({combineStems.size(), (size_t)STATMC_MAX_COMBINE_SOURCES, fit}));
+            for (Part &p : parts) {
+                p.film.reset(new Buffer("film", HostImage(height, width, F32C3)));
+                p.reg.reset(new BufferRegistry(*p.film));
+                p.est.reset(new Estimator(*p.film, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr,
+                                          params.smis, *p.reg));
+                p.est->AllocateBuffers(*p.reg);
+                p.est->SetPipelineBands(1);
+            }
+            std::cout << "combine: " << combineStems.size() << " stems in groups of " << parts.size() << " (" << partBytes
+                      << " bytes per part)" << std::endl;
         }
         std::cout << "pipeline bands: " << est.PipelineBands() << std::endl;
         std::vector<float> tq;
@@ -352,12 +368,21 @@ int main(int argc, char **argv) {
                             throw std::runtime_error("--combine: " + (mine ? op : prefix) + name + ".pfm is missing (" +
                                                      (mine ? prefix : op) + name + ".pfm exists)");
                     }
-                    readDump(op, *other);
-                    uploadAll(*other, *otherReg, combinedNames);
-                    est.CombineStatistics(*other, borrow);
-                    // the next stem's dump goes into the same host and device images
+                }
+                // a left fold in argument order: one call per group of stems
+                for (size_t g = 0; g < combineStems.size(); g += parts.size()) {
+                    const size_t n = std::min(parts.size(), combineStems.size() - g);
+                    std::vector<Estimator *> group;
+                    for (size_t k = 0; k < n; k++) {
+                        readDump(combineStems[g + k] + "-" + spp + "-", *parts[k].est);
+                        uploadAll(*parts[k].est, *parts[k].reg, combinedNames);
+                        group.push_back(parts[k].est.get());
+                    }
+                    if (n == 1) est.CombineStatistics(*group[0], borrow);
+                    else est.CombineStatistics(group, borrow);
+                    // the next group's dumps go into the same host and device images
                     est.Synchronize();
-                    other->Synchronize();
+                    for (Estimator *e : group) e->Synchronize();
                 }
                 outPrefix = outputStem + "-" + std::to_string(std::stoll(spp) * (long long)(1 + combineStems.size())) + "-";
             }

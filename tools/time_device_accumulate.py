@@ -9,7 +9,12 @@ counter-based hash generator:
 Prints one JSON line per path: milliseconds per step (hipEvent timing, after warm-up; the arena path also split into its two
 launches), the algorithmic bytes computed from the shapes, and the share of the 8 TB/s HBM peak they imply.
 
-    python tools/time_device_accumulate.py [--width 1920 --height 1080 --spp 256 --iters 10 --warmup 3]
+    python tools/time_device_accumulate.py [--width 1920 --height 1080 --spp 256 --iters 10 --warmup 3] [--slots P]
+
+--slots P instead times a renderer with P samples of a pixel in flight, on the radiance type alone (one arena, every pixel's
+samples dealt evenly to P slots), and prints two lines:
+  merged  fold_arena_slots: every slot folds its share in the kernel, the slots are merged there (PixelStats::merge), one store
+  states  P sets of state images, one statmc_accumulate per slot over its share, then one statmc_combine_many
 
 Algorithmic bytes: the arena written once and read once (4 B per channel and sample), and the moments read and written once
 per step (n, mean, m2, m3, film-mean, film-m2 of radiance; n and mean of the four feature types: 112 B per pixel each way)."""
@@ -50,6 +55,43 @@ def timed(fn, iters, warmup):
     return t0.elapsed_time(t1) / iters
 
 
+def time_slots(a, dev):
+    """--slots: PixelStats::merge inside the kernel against P states + statmc_combine_many (radiance: 3 channels, max_moment 3)."""
+    W, H, S, P = a.width, a.height, a.spp, a.slots
+    lib = C.CDLL(build.DEVICE_EXAMPLE_SO)
+    lib.fold_arena_slots.argtypes = [C.POINTER(api.StatType), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.POINTER(api.PrepassContext), C.c_void_p]
+    cfg = film.STAT_TYPES["radiance"]
+    arena = torch.rand(S, H, W, 3, device=dev)
+    cuts = [k * S // P for k in range(P + 1)]
+    bounds = torch.tensor(cuts, dtype=torch.int32, device=dev)[:, None, None].expand(P + 1, H, W).contiguous()
+    states = [film.new_state(H, W, 3, dev, transform=True) for _ in range(P)]
+    t = api.make_stat_type(arena, states[0], cfg["transform"], cfg["max_moment"])
+    stream = api.current_stream_handle()
+    shares = [api.make_stat_type(arena[cuts[k]:cuts[k + 1]], states[k], cfg["transform"], cfg["max_moment"]) for k in range(P)]
+    many = [api.make_combine_many_entry(states[0], states[1:], 3, 3)]
+
+    def merged():
+        api.check(lib.fold_arena_slots(C.byref(t), W, H, arena.data_ptr(), bounds.data_ptr(), P, None, stream))
+
+    def by_states():
+        for k in range(1, P):
+            for v in states[k].values():
+                v.zero_()
+        for st in shares:
+            api.accumulate(W, H, [st], stream=stream)
+        api.combine_many(W, H, many, stream=stream)
+
+    common = {"width": W, "height": H, "spp": S, "slots": P}
+    m_ms = timed(merged, a.iters, a.warmup)
+    for st in states:
+        for v in st.values():
+            v.zero_()
+    s_ms = timed(by_states, a.iters, a.warmup)
+    print(json.dumps(dict(path="merged", ms=round(m_ms, 4), **common)))
+    print(json.dumps(dict(path="states", ms=round(s_ms, 4), merged_speedup=round(s_ms / m_ms, 2), **common)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -57,11 +99,16 @@ def main():
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--slots", type=int, default=0, help="P slots per pixel: in-kernel merge against P states + combine_many")
     a = ap.parse_args()
     W, H, S = a.width, a.height, a.spp
     dev = torch.device("cuda:0")
     api.setup(0)
     build.build_tools()
+    if a.slots:
+        if not 2 <= a.slots <= api.MAX_COMBINE_SOURCES + 1:
+            ap.error("--slots wants 2 .. %d" % (api.MAX_COMBINE_SOURCES + 1))
+        return time_slots(a, dev)
     lib = C.CDLL(build.DEVICE_EXAMPLE_SO)
     lib.gen_arena.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
     lib.gen_fold.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(api.StatType), C.POINTER(api.PrepassContext),

@@ -402,7 +402,10 @@ int statmc_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *t
  * Valid for the current device until its significance level or filter spec changes (statmc_set_significance,
  * statmc_set_filter_spec, statmc_reset_filter_spec, statmc_copy_device_settings): query again after those.  The table's
  * address stays put: statmc_set_t_quantiles rewrites it in place, so kernels enqueued after that call read the new quantiles.
- * Returns STATMC_ERR_NO_DEVICE before statmc_setup of the current device. */
+ * Returns STATMC_ERR_NO_DEVICE before statmc_setup of the current device.
+ * Where several lanes of a wave or several waves of a workgroup hold states of one pixel, the header's merge_lanes<G> and
+ * merge_waves<NW> put them together in a fixed tree of two-part statmc_combine_statistics steps; they use nothing of the
+ * library's state, so there is no C entry point for them. */
 typedef struct statmc_prepass_context {
     const float *t_table;
     int32_t flags;

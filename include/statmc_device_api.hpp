@@ -8,7 +8,8 @@
 //   for (...) ps.add(sample);          // C floats per sample, in sample order
 //   ps.store(t, pixel);                // moments and n; store(t, pixel, ctx) also writes mean_corr / discriminator
 //
-// and put the states of several slots of one pixel together before the store (ps.merge(other), below).
+// and put the states of several slots of one pixel together before the store: ps.merge(other) where one thread holds both,
+// merge_lanes<G>(ps) across the lanes of a wave and merge_waves<NW>(ps, lds) across the waves of a workgroup (all below).
 // The result is bit for bit what statmc_accumulate leaves after the same samples (one launch or several: the state is the
 // same), and store(t, pixel, ctx) writes what the accumulation's pre-pass epilogue writes.  This header is the one
 // definition of that arithmetic: libstatmc_hip.so's kernels include it too.
@@ -268,6 +269,121 @@ struct PixelStats {
         }
     }
 };
+
+// ------------------------------------------------------------------ reductions without global memory
+// The states of one pixel held by several lanes of a wave (merge_lanes) or by the same lane of several waves of a workgroup
+// (merge_waves), put together with PixelStats::merge -- combine_counts / combine_elem above: there is no second copy of the
+// formulas.  Both run the SAME balanced tree over the slots 0 .. K - 1, the lower slot always as part A:
+//
+//   for stride = 1, 2, 4, ... < K:
+//       for every slot j with j % (2 * stride) == 0:   slot[j].merge(slot[j + stride])      // A = slot j, B = slot j + stride
+//
+// and leave the result in slot 0.  That is the definition: the result is, bit for bit, K states combined by two-part
+// statmc_combine_statistics calls in exactly that order (dst = part j, src = part j + stride).  It is NOT the left fold in
+// slot order that statmc_combine_many computes (s[0].merge(s[1]); s[0].merge(s[2]); ...): fp32 addition is not associative,
+// and for K > 2 the two orders differ in the last bits.  A slot without samples holds clear(): it keeps the other side's bits.
+// Counts must sum below 2^24, as for merge.
+//
+// merge_lanes<G> and then merge_waves<NW> on the states the slot-0 lanes hold is one tree over NW * G slots, slot index
+// w * G + j (wave w, slot j of the lane group): the lane levels are the tree's first log2(G) levels, the wave levels the rest.
+
+// every dword of a state through f, in place -- n first, then per channel the fields the instantiation has: the one list of
+// what a state is made of when it travels
+template <int C, int MAXM, bool TRANSFORM, class F>
+__device__ __forceinline__ void map_state(PixelStats<C, MAXM, TRANSFORM> &ps, F f) {
+#pragma clang fp contract(off)
+    ps.n = f(ps.n);
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        ElemState &e = ps.st[c];
+        e.mean = __int_as_float(f(__float_as_int(e.mean)));
+        if (MAXM >= 2) e.m2 = __int_as_float(f(__float_as_int(e.m2)));
+        if (MAXM >= 3) e.m3 = __int_as_float(f(__float_as_int(e.m3)));
+        if (TRANSFORM) {
+            e.fmean = __int_as_float(f(__float_as_int(e.fmean)));
+            e.fm2 = __int_as_float(f(__float_as_int(e.fm2)));
+        }
+    }
+}
+
+// One level of merge_lanes: the state of lane (l ^ D) into this lane's.  The dwords cross the wave by __shfl_xor
+// (ds_bpermute_b32) at every distance: DPP quad_perm (1, 2) and ds_swizzle (4, 8) measured level with it and
+// v_permlane16_swap / v_permlane32_swap (16, 32) slower -- the merge behind each exchange is a few hundred VALU instructions,
+// the exchange sixteen dwords at most.
+template <int D, int C, int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void merge_lane_level(PixelStats<C, MAXM, TRANSFORM> &ps) {
+#pragma clang fp contract(off)
+    PixelStats<C, MAXM, TRANSFORM> other = ps;
+    map_state(other, [](int v) { return __shfl_xor(v, D, 64); });
+    ps.merge(other);
+}
+
+// The lanes of a wave.  The wave's 64 lanes form 64 / G groups of G consecutive lanes; lane l is slot l % G of group l / G,
+// and every slot holds a state of the group's pixel.  After the call SLOT 0 of every group holds the merged state (the tree
+// above with K = G); what the other slots hold is unspecified -- do not store it.
+// ALL 64 lanes of the wave execute the call, in uniform control flow: a cross-lane read from an inactive lane is undefined.  A
+// lane whose pixel lies past the film does not return early: it carries a cleared state and skips only its load and store.
+template <int G, int C, int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void merge_lanes(PixelStats<C, MAXM, TRANSFORM> &ps) {
+#pragma clang fp contract(off)
+    static_assert(G == 2 || G == 4 || G == 8 || G == 16 || G == 32 || G == 64, "G lanes per group: 2, 4, 8, 16, 32 or 64");
+    if constexpr (G > 1) merge_lane_level<1>(ps);
+    if constexpr (G > 2) merge_lane_level<2>(ps);
+    if constexpr (G > 4) merge_lane_level<4>(ps);
+    if constexpr (G > 8) merge_lane_level<8>(ps);
+    if constexpr (G > 16) merge_lane_level<16>(ps);
+    if constexpr (G > 32) merge_lane_level<32>(ps);
+}
+
+// The dwords of one state: n and, per channel, the fields the instantiation has.
+template <int C, int MAXM, bool TRANSFORM>
+constexpr int state_dwords() {
+    return 1 + C * (MAXM + (TRANSFORM ? 2 : 0));
+}
+// The LDS scratch merge_waves<NW> needs, in bytes: one plane of 64 dwords per field and staging wave (wave 0 never stages).
+template <int NW, int C, int MAXM, bool TRANSFORM>
+constexpr int merge_waves_lds_bytes() {
+    return state_dwords<C, MAXM, TRANSFORM>() * (NW - 1) * 64 * 4;
+}
+
+// The waves of a workgroup, through LDS.  A one-dimensional workgroup of NW waves (blockDim.x == 64 * NW): lane l of wave w
+// holds slot w of item l.  After the call WAVE 0 holds the merged states (the tree above with K = NW); what the other waves
+// hold is unspecified.  `scratch`: merge_waves_lds_bytes<NW, C, MAXM, TRANSFORM>() bytes of LDS, 4-byte aligned, laid out
+// [field][wave - 1][lane], one dword per lane and access: consecutive lanes, consecutive banks.
+// The call contains workgroup barriers: EVERY wave of the workgroup calls it, in uniform control flow, whether or not its items
+// lie inside the film.  It starts with a barrier, so the scratch may come straight from another use (a previous merge_waves
+// included); it does not end with one.
+template <int NW, int C, int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void merge_waves(PixelStats<C, MAXM, TRANSFORM> &ps, float *scratch) {
+#pragma clang fp contract(off)
+    static_assert(NW == 2 || NW == 4 || NW == 8 || NW == 16, "NW waves per workgroup: 2, 4, 8 or 16");
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    // A wave stages into its own planes at the one level where it is part B; the waves that read at that level are part A
+    // there and stage only at a later level, into other planes: one barrier per level, between the stores and the loads.
+    __syncthreads();
+#pragma unroll
+    for (int stride = 1; stride < NW; stride *= 2) {
+        if ((wave & (2 * stride - 1)) == stride) {
+            int *plane = reinterpret_cast<int *>(scratch) + (wave - 1) * 64 + lane;
+            map_state(ps, [&plane](int v) {
+                *plane = v;
+                plane += (NW - 1) * 64;
+                return v;
+            });
+        }
+        __syncthreads();
+        if ((wave & (2 * stride - 1)) == 0) {
+            const int *plane = reinterpret_cast<const int *>(scratch) + (wave + stride - 1) * 64 + lane;
+            PixelStats<C, MAXM, TRANSFORM> other = ps;
+            map_state(other, [&plane](int) {
+                const int v = *plane;
+                plane += (NW - 1) * 64;
+                return v;
+            });
+            ps.merge(other);
+        }
+    }
+}
 
 }  // namespace device
 }  // namespace statmc

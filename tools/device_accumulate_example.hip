@@ -1,6 +1,6 @@
 // device_accumulate_example.hip -- a renderer's kernel folding its samples into StatMC's statistics itself
 // (include/statmc_device_api.hpp), built into tools/bin/libstatmc_device_example.so with hipcc's DEFAULT floating-point flags
-// (-ffp-contract=fast-honor-pragmas): the header's bits must not depend on them.  Four launchers, extern "C":
+// (-ffp-contract=fast-honor-pragmas): the header's bits must not depend on them.  The launchers, extern "C":
 //
 //   fold_arena  one thread per pixel folds a film-major arena ([S][H][W][C] fp32, statmc_accumulate's input) through
 //               PixelStats -- the bits of statmc_accumulate on the same arena (tests/test_device_api_gpu.py)
@@ -11,6 +11,11 @@
 //               values of the flagship configuration (film.STAT_TYPES: radiance, normal, albedo, depth, material id; 11
 //               channels), written to one arena per type -- what feeds statmc_accumulate today
 //   gen_fold    the same values, folded straight into the statistics in registers: no arena
+//   fold_arena_lanes, fold_arena_waves, fold_arena_lanes_waves  fold_arena_slots with the slots of a pixel held by the lanes of
+//               a wave, by the waves of a workgroup, or both: merged by the header's merge_lanes / merge_waves -- the bits of
+//               the slots' states combined by two-part statmc_combine_statistics calls in the header's tree order
+//               (tests/test_device_reduce_gpu.py)
+//   gen_fold_lanes  gen_fold with G lanes per pixel
 //
 // Every launcher returns 0 or a negative STATMC_ERR_* (include/statmc.h), and only enqueues on `stream`.
 #include <hip/hip_runtime.h>
@@ -19,6 +24,9 @@
 #include "statmc.h"
 #include "statmc_device_api.hpp"
 
+using statmc::device::merge_lanes;
+using statmc::device::merge_waves;
+using statmc::device::merge_waves_lds_bytes;
 using statmc::device::PixelStats;
 
 namespace {
@@ -114,6 +122,129 @@ int fold_dispatch(const statmc_stat_type &t, long long n_px, const float *arena,
     if (t.max_moment == 3) return launch_fold<C, 3, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
     if (t.max_moment == 2) return launch_fold<C, 2, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
     return launch_fold<C, 1, false>(t, n_px, arena, n_samples, ctx, s, bounds, n_slots);
+}
+
+// ------------------------------------------------------------------ fold_arena_lanes / fold_arena_waves / fold_arena_lanes_waves
+// The slots of fold_slots_kernel held by different threads: slot k of pixel p still owns the samples bounds[k][p] ..
+// bounds[k + 1][p] - 1, slot 0 folds into the pixel's stored state and every other slot into a cleared state of its own.  The
+// slots then meet through the header's reductions -- a balanced tree, NOT fold_slots_kernel's left fold -- and slot 0 stores.
+// A thread whose pixel lies past the film takes part in the reduction with a cleared state: it skips its loads and its store
+// only (every lane executes merge_lanes, every wave merge_waves).
+template <int C, int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void fold_slot(PixelStats<C, MAXM, TRANSFORM> &ps, const statmc_stat_type &t, long long n_px, long long p,
+                                          int slot, const float *arena, const int32_t *bounds) {
+    ps.clear();
+    if (p >= n_px) return;
+    if (slot == 0) ps.load(t, p);
+    const int s1 = bounds[(long long)(slot + 1) * n_px + p];
+    for (int s = bounds[(long long)slot * n_px + p]; s < s1; s++) {
+        const float *q = arena + ((long long)s * n_px + p) * C;
+        float smp[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) smp[c] = q[c];
+        ps.add(smp);
+    }
+}
+
+template <int C, int MAXM, bool TRANSFORM>
+__device__ __forceinline__ void store_slot0(const PixelStats<C, MAXM, TRANSFORM> &ps, const statmc_stat_type &t, long long p,
+                                            const statmc_prepass_context &ctx, int with_prepass) {
+    if constexpr (MAXM >= 3) {
+        if (with_prepass) {
+            ps.store(t, p, ctx);
+            return;
+        }
+    }
+    ps.store(t, p);
+}
+
+// G consecutive lanes per pixel: thread i of the grid is slot i % G of pixel i / G
+template <int G, int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(kBlock) void fold_lanes_kernel(statmc_stat_type t, long long n_px, const float *arena, const int32_t *bounds,
+                                                            statmc_prepass_context ctx, int with_prepass) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const long long p = i / G;
+    const int slot = (int)(i % G);
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    fold_slot(ps, t, n_px, p, slot, arena, bounds);
+    merge_lanes<G>(ps);
+    if (p < n_px && slot == 0) store_slot0(ps, t, p, ctx, with_prepass);
+}
+
+// NW waves per workgroup share 64 pixels: lane l of wave w is slot w of pixel 64 * blockIdx.x + l
+template <int NW, int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(64 * NW) void fold_waves_kernel(statmc_stat_type t, long long n_px, const float *arena, const int32_t *bounds,
+                                                             statmc_prepass_context ctx, int with_prepass) {
+    __shared__ float scratch[merge_waves_lds_bytes<NW, C, MAXM, TRANSFORM>() / 4];
+    const long long p = (long long)blockIdx.x * 64 + (threadIdx.x & 63);
+    const int slot = (int)(threadIdx.x >> 6);
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    fold_slot(ps, t, n_px, p, slot, arena, bounds);
+    merge_waves<NW>(ps, scratch);
+    if (p < n_px && slot == 0) store_slot0(ps, t, p, ctx, with_prepass);
+}
+
+// Both: G lanes of each of NW waves per pixel, 64 / G pixels per workgroup; lane l of wave w is slot w * G + l % G
+template <int G, int NW, int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(64 * NW) void fold_lanes_waves_kernel(statmc_stat_type t, long long n_px, const float *arena,
+                                                                   const int32_t *bounds, statmc_prepass_context ctx, int with_prepass) {
+    __shared__ float scratch[merge_waves_lds_bytes<NW, C, MAXM, TRANSFORM>() / 4];
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const long long p = (long long)blockIdx.x * (64 / G) + lane / G;
+    const int slot = wave * G + lane % G;
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    fold_slot(ps, t, n_px, p, slot, arena, bounds);
+    merge_lanes<G>(ps);
+    merge_waves<NW>(ps, scratch);
+    if (p < n_px && slot == 0) store_slot0(ps, t, p, ctx, with_prepass);
+}
+
+enum class Meet { lanes, waves, lanes_waves };
+
+template <Meet M, int C, int MAXM, bool TRANSFORM>
+int launch_meet(const statmc_stat_type &t, long long n_px, const float *arena, const int32_t *bounds, int G, int NW,
+                const statmc_prepass_context *ctx, hipStream_t s) {
+    const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
+    const int pre = ctx ? 1 : 0;
+#define STATMC_LANES(g)                                                                                                       \
+    case g:                                                                                                                   \
+        hipLaunchKernelGGL((fold_lanes_kernel<g, C, MAXM, TRANSFORM>), dim3(grid_for(n_px * g)), dim3(kBlock), 0, s, t, n_px, \
+                           arena, bounds, c, pre);                                                                            \
+        return launched();
+#define STATMC_WAVES(nw)                                                                                                          \
+    case nw:                                                                                                                      \
+        hipLaunchKernelGGL((fold_waves_kernel<nw, C, MAXM, TRANSFORM>), dim3((unsigned)((n_px + 63) / 64)), dim3(64 * nw), 0, s, \
+                           t, n_px, arena, bounds, c, pre);                                                                       \
+        return launched();
+    if constexpr (M == Meet::lanes) {
+        switch (G) {
+            STATMC_LANES(2) STATMC_LANES(4) STATMC_LANES(8) STATMC_LANES(16) STATMC_LANES(32) STATMC_LANES(64)
+        }
+    } else if constexpr (M == Meet::waves) {
+        switch (NW) {
+            STATMC_WAVES(2) STATMC_WAVES(4) STATMC_WAVES(8) STATMC_WAVES(16)
+        }
+    } else if (G == 4 && NW == 4) {
+        hipLaunchKernelGGL((fold_lanes_waves_kernel<4, 4, C, MAXM, TRANSFORM>), dim3((unsigned)((n_px + 15) / 16)), dim3(256), 0, s, t,
+                           n_px, arena, bounds, c, pre);
+        return launched();
+    }
+#undef STATMC_LANES
+#undef STATMC_WAVES
+    return STATMC_ERR_INVALID;
+}
+
+template <Meet M, int C>
+int meet_dispatch(const statmc_stat_type &t, long long n_px, const float *arena, const int32_t *bounds, int G, int NW,
+                  const statmc_prepass_context *ctx, hipStream_t s) {
+    if (t.transform) {
+        if (t.max_moment == 3) return launch_meet<M, C, 3, true>(t, n_px, arena, bounds, G, NW, ctx, s);
+        if (t.max_moment == 2) return launch_meet<M, C, 2, true>(t, n_px, arena, bounds, G, NW, ctx, s);
+        return launch_meet<M, C, 1, true>(t, n_px, arena, bounds, G, NW, ctx, s);
+    }
+    if (t.max_moment == 3) return launch_meet<M, C, 3, false>(t, n_px, arena, bounds, G, NW, ctx, s);
+    if (t.max_moment == 2) return launch_meet<M, C, 2, false>(t, n_px, arena, bounds, G, NW, ctx, s);
+    return launch_meet<M, C, 1, false>(t, n_px, arena, bounds, G, NW, ctx, s);
 }
 
 // ------------------------------------------------------------------ the sample generator
@@ -212,6 +343,102 @@ __global__ __launch_bounds__(kBlock) void gen_fold_kernel(uint32_t seed, long lo
     mat.store(ft.t[4], p);
 }
 
+// gen_fold_kernel with G consecutive lanes per pixel: slot j folds the samples j, j + G, ... of the launch (slot 0 into the
+// pixel's stored state), the five states are merged across the lanes and slot 0 stores.
+template <int G>
+__global__ __launch_bounds__(kBlock) void gen_fold_lanes_kernel(uint32_t seed, long long n_px, int sample0, int n_samples, FiveTypes ft,
+                                                                statmc_prepass_context ctx, int with_prepass) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    const long long p = i / G;
+    const int slot = (int)(i % G);
+    const bool mine = p < n_px && slot == 0;
+    PixelStats<3, 3, true> rad;
+    PixelStats<3, 1, false> nrm, alb;
+    PixelStats<1, 1, false> dep, mat;
+    rad.clear();
+    nrm.clear();
+    alb.clear();
+    dep.clear();
+    mat.clear();
+    if (mine) {
+        rad.load(ft.t[0], p);
+        nrm.load(ft.t[1], p);
+        alb.load(ft.t[2], p);
+        dep.load(ft.t[3], p);
+        mat.load(ft.t[4], p);
+    }
+    if (p < n_px) {
+        for (int s = slot; s < n_samples; s += G) {
+            Sample o;
+            gen_sample(seed, p, sample0 + s, o);
+            rad.add(o.radiance);
+            nrm.add(o.normal);
+            alb.add(o.albedo);
+            dep.add(&o.depth);
+            mat.add(&o.material);
+        }
+    }
+    merge_lanes<G>(rad);   // every lane of the wave, pixels past the film included
+    merge_lanes<G>(nrm);
+    merge_lanes<G>(alb);
+    merge_lanes<G>(dep);
+    merge_lanes<G>(mat);
+    if (!mine) return;
+    if (with_prepass) rad.store(ft.t[0], p, ctx);
+    else rad.store(ft.t[0], p);
+    nrm.store(ft.t[1], p);
+    alb.store(ft.t[2], p);
+    dep.store(ft.t[3], p);
+    mat.store(ft.t[4], p);
+}
+
+int launch_gen_fold_lanes(uint32_t seed, long long n_px, int sample0, int n_samples, int G, const FiveTypes &ft,
+                          const statmc_prepass_context &c, int pre, hipStream_t s) {
+    switch (G) {
+#define STATMC_GEN_LANES(g)                                                                                                        \
+    case g:                                                                                                                        \
+        hipLaunchKernelGGL((gen_fold_lanes_kernel<g>), dim3(grid_for(n_px * g)), dim3(kBlock), 0, s, seed, n_px, sample0, n_samples, \
+                           ft, c, pre);                                                                                            \
+        return launched();
+        STATMC_GEN_LANES(2) STATMC_GEN_LANES(4) STATMC_GEN_LANES(8) STATMC_GEN_LANES(16) STATMC_GEN_LANES(32) STATMC_GEN_LANES(64)
+#undef STATMC_GEN_LANES
+    }
+    return STATMC_ERR_INVALID;
+}
+
+// gen_fold's checks of the five types (and of ctx): 0, or STATMC_ERR_INVALID
+int five_types_of(const statmc_stat_type *types, const statmc_prepass_context *ctx, FiveTypes &ft) {
+    static const int want[5][3] = {{3, 1, 3}, {3, 0, 1}, {3, 0, 1}, {1, 0, 1}, {1, 0, 1}};   // channels, transform, max_moment
+    for (int k = 0; k < 5; k++) {
+        const statmc_stat_type &t = types[k];
+        if (t.channels != want[k][0] || (t.transform != 0) != (want[k][1] != 0) || t.max_moment != want[k][2] || !t.n || !t.mean)
+            return STATMC_ERR_INVALID;
+        if (k == 0 && (!t.m2 || !t.m3 || !t.film_mean || !t.film_m2)) return STATMC_ERR_INVALID;
+        ft.t[k] = t;
+    }
+    if (ctx && (!types[0].mean_corr || !types[0].discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    return STATMC_OK;
+}
+
+// fold_arena_slots' checks of one type (and of ctx)
+bool fold_args_ok(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds,
+                  const statmc_prepass_context *ctx) {
+    if (!t || width <= 0 || height <= 0 || !arena || !bounds) return false;
+    if ((t->channels != 1 && t->channels != 3) || t->max_moment < 1 || t->max_moment > 3 || !t->n || !t->mean) return false;
+    if ((t->max_moment >= 2 && !t->m2) || (t->max_moment >= 3 && !t->m3) || (t->transform && (!t->film_mean || !t->film_m2))) return false;
+    return !ctx || (t->max_moment >= 3 && t->mean_corr && t->discriminator && ctx->t_table);
+}
+
+template <Meet M>
+int fold_meet(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int G, int NW,
+              const statmc_prepass_context *ctx, void *stream) {
+    if (!fold_args_ok(t, width, height, arena, bounds, ctx)) return STATMC_ERR_INVALID;
+    const long long n_px = (long long)width * height;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return t->channels == 3 ? meet_dispatch<M, 3>(*t, n_px, arena, bounds, G, NW, ctx, s)
+                            : meet_dispatch<M, 1>(*t, n_px, arena, bounds, G, NW, ctx, s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,11 +462,7 @@ int fold_arena(const statmc_stat_type *t, int width, int height, const float *ar
 // (the caller's to guarantee: it is not read here).
 int fold_arena_slots(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int n_slots,
                      const statmc_prepass_context *ctx, void *stream) {
-    if (!t || width <= 0 || height <= 0 || !arena || !bounds || n_slots < 1) return STATMC_ERR_INVALID;
-    if ((t->channels != 1 && t->channels != 3) || t->max_moment < 1 || t->max_moment > 3 || !t->n || !t->mean) return STATMC_ERR_INVALID;
-    if ((t->max_moment >= 2 && !t->m2) || (t->max_moment >= 3 && !t->m3) || (t->transform && (!t->film_mean || !t->film_m2)))
-        return STATMC_ERR_INVALID;
-    if (ctx && (t->max_moment < 3 || !t->mean_corr || !t->discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    if (!fold_args_ok(t, width, height, arena, bounds, ctx) || n_slots < 1) return STATMC_ERR_INVALID;
     const long long n_px = (long long)width * height;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return t->channels == 3 ? fold_dispatch<3>(*t, n_px, arena, 0, ctx, s, bounds, n_slots)
@@ -264,21 +487,46 @@ int gen_arena(uint32_t seed, int width, int height, int sample0, int n_samples, 
 int gen_fold(uint32_t seed, int width, int height, int sample0, int n_samples, const statmc_stat_type *types,
              const statmc_prepass_context *ctx, void *stream) {
     if (!types || width <= 0 || height <= 0 || n_samples < 0 || sample0 < 0) return STATMC_ERR_INVALID;
-    static const int want[5][3] = {{3, 1, 3}, {3, 0, 1}, {3, 0, 1}, {1, 0, 1}, {1, 0, 1}};   // channels, transform, max_moment
     FiveTypes ft;
-    for (int k = 0; k < 5; k++) {
-        const statmc_stat_type &t = types[k];
-        if (t.channels != want[k][0] || (t.transform != 0) != (want[k][1] != 0) || t.max_moment != want[k][2] || !t.n || !t.mean)
-            return STATMC_ERR_INVALID;
-        if (k == 0 && (!t.m2 || !t.m3 || !t.film_mean || !t.film_m2)) return STATMC_ERR_INVALID;
-        ft.t[k] = t;
-    }
-    if (ctx && (!types[0].mean_corr || !types[0].discriminator || !ctx->t_table)) return STATMC_ERR_INVALID;
+    if (five_types_of(types, ctx, ft) != STATMC_OK) return STATMC_ERR_INVALID;
     const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
     const long long n_px = (long long)width * height;
     hipLaunchKernelGGL(gen_fold_kernel, dim3(grid_for(n_px)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), seed, n_px, sample0,
                        n_samples, ft, c, ctx ? 1 : 0);
     return launched();
+}
+
+// fold_arena_slots with the slots held by different threads, merged by the header's reductions: a balanced tree over the
+// slots (statmc_device_api.hpp), not fold_arena_slots' left fold.  bounds: [slots + 1][height][width], as above.
+// G lanes per pixel (2, 4, 8, 16, 32 or 64 slots), merge_lanes<G>:
+int fold_arena_lanes(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int G,
+                     const statmc_prepass_context *ctx, void *stream) {
+    return fold_meet<Meet::lanes>(t, width, height, arena, bounds, G, 0, ctx, stream);
+}
+
+// one lane per pixel and wave, NW waves per workgroup share 64 pixels (2, 4, 8 or 16 slots), merge_waves<NW>:
+int fold_arena_waves(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int NW,
+                     const statmc_prepass_context *ctx, void *stream) {
+    return fold_meet<Meet::waves>(t, width, height, arena, bounds, 0, NW, ctx, stream);
+}
+
+// both: G lanes in each of NW waves per pixel, G * NW slots with slot index w * G + j; merge_lanes<G>, then merge_waves<NW>.
+// The example instantiates G = 4, NW = 4 (16 slots) only; every other pair is STATMC_ERR_INVALID.
+int fold_arena_lanes_waves(const statmc_stat_type *t, int width, int height, const float *arena, const int32_t *bounds, int G, int NW,
+                           const statmc_prepass_context *ctx, void *stream) {
+    return fold_meet<Meet::lanes_waves>(t, width, height, arena, bounds, G, NW, ctx, stream);
+}
+
+// gen_fold with the samples of a pixel dealt to G lanes (slot j takes samples j, j + G, ... of the launch), all five types
+// merged across the lanes (merge_lanes<G>): within the project's bound of gen_fold, not its bits (another merge order).
+int gen_fold_lanes(uint32_t seed, int width, int height, int sample0, int n_samples, int G, const statmc_stat_type *types,
+                   const statmc_prepass_context *ctx, void *stream) {
+    if (!types || width <= 0 || height <= 0 || n_samples < 0 || sample0 < 0) return STATMC_ERR_INVALID;
+    FiveTypes ft;
+    if (five_types_of(types, ctx, ft) != STATMC_OK) return STATMC_ERR_INVALID;
+    const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
+    return launch_gen_fold_lanes(seed, (long long)width * height, sample0, n_samples, G, ft, c, ctx ? 1 : 0,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

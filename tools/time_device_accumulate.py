@@ -9,12 +9,17 @@ counter-based hash generator:
 Prints one JSON line per path: milliseconds per step (hipEvent timing, after warm-up; the arena path also split into its two
 launches), the algorithmic bytes computed from the shapes, and the share of the 8 TB/s HBM peak they imply.
 
-    python tools/time_device_accumulate.py [--width 1920 --height 1080 --spp 256 --iters 10 --warmup 3] [--slots P]
+    python tools/time_device_accumulate.py [--width 1920 --height 1080 --spp 256 --iters 10 --warmup 3] [--slots P | --lanes G,G]
 
 --slots P instead times a renderer with P samples of a pixel in flight, on the radiance type alone (one arena, every pixel's
 samples dealt evenly to P slots), and prints two lines:
   merged  fold_arena_slots: every slot folds its share in the kernel, the slots are merged there (PixelStats::merge), one store
   states  P sets of state images, one statmc_accumulate per slot over its share, then one statmc_combine_many
+
+--lanes G[,G...] instead times the generator with several lanes per pixel (statmc::device::merge_lanes) against gen_fold's one
+thread per pixel, all five types, no arena, and prints one line per path:
+  gen_fold        five timings in this process: their mean is the yardstick, max - min its spread
+  gen_fold_lanes  per G: ms and the ratio to the yardstick
 
 Algorithmic bytes: the arena written once and read once (4 B per channel and sample), and the moments read and written once
 per step (n, mean, m2, m3, film-mean, film-m2 of radiance; n and mean of the four feature types: 112 B per pixel each way)."""
@@ -92,6 +97,41 @@ def time_slots(a, dev):
     print(json.dumps(dict(path="states", ms=round(s_ms, 4), merged_speedup=round(s_ms / m_ms, 2), **common)))
 
 
+def time_lanes(a, dev):
+    """--lanes: gen_fold_lanes at each G against gen_fold, placed moments, the five types"""
+    W, H, S = a.width, a.height, a.spp
+    lib = C.CDLL(build.DEVICE_EXAMPLE_SO)
+    gen = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(api.StatType), C.POINTER(api.PrepassContext), C.c_void_p]
+    lib.gen_fold.argtypes = gen
+    lib.gen_fold_lanes.argtypes = gen[:5] + [C.c_int] + gen[5:]
+    fs = film.FilmStats(W, H, dev, types=TYPES, placed=True)
+    dummy = {t: torch.empty(1, H, W, film.STAT_TYPES[t]["channels"], device=dev) for t in TYPES}   # make_stat_type wants a tensor
+    sts = (api.StatType * 5)(*[api.make_stat_type(dummy[t], fs.state[t], film.STAT_TYPES[t]["transform"], film.STAT_TYPES[t]["max_moment"])
+                               for t in TYPES])
+    stream = api.current_stream_handle()
+    step = [0]
+
+    def run(fn, *g):
+        def one():
+            api.check(fn(1, W, H, step[0] * S, S, *g, sts, None, stream))
+            step[0] += 1
+        fs.reset()          # counts stay far below 2^24
+        step[0] = 0
+        return timed(one, a.iters, a.warmup)
+
+    common = {"width": W, "height": H, "spp": S, "iters": a.iters, "warmup": a.warmup, "placed": api.placement_info()["active"] == 1}
+    base = [run(lib.gen_fold) for _ in range(5)]
+    yard, spread = sum(base) / len(base), max(base) - min(base)
+    print(json.dumps(dict(path="gen_fold", ms=round(yard, 4), spread_ms=round(spread, 4), runs_ms=[round(v, 4) for v in base], **common)),
+          flush=True)
+    for G in a.lanes:
+        ms = run(lib.gen_fold_lanes, G)
+        print(json.dumps(dict(path="gen_fold_lanes", lanes=G, ms=round(ms, 4), ratio_to_gen_fold=round(ms / yard, 3),
+                              beats_yardstick_by_more_than_its_spread=bool(yard - ms > spread), **common)), flush=True)
+    again = run(lib.gen_fold)    # the yardstick once more at the end: drift over the process
+    print(json.dumps(dict(path="gen_fold_again", ms=round(again, 4), **common)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -100,6 +140,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--slots", type=int, default=0, help="P slots per pixel: in-kernel merge against P states + combine_many")
+    ap.add_argument("--lanes", type=lambda v: [int(g) for g in v.split(",")], default=None,
+                    help="G[,G...] lanes per pixel (2 .. 64, powers of two): gen_fold_lanes against gen_fold")
     a = ap.parse_args()
     W, H, S = a.width, a.height, a.spp
     dev = torch.device("cuda:0")
@@ -109,6 +151,10 @@ def main():
         if not 2 <= a.slots <= api.MAX_COMBINE_SOURCES + 1:
             ap.error("--slots wants 2 .. %d" % (api.MAX_COMBINE_SOURCES + 1))
         return time_slots(a, dev)
+    if a.lanes:
+        if any(g not in (2, 4, 8, 16, 32, 64) for g in a.lanes):
+            ap.error("--lanes wants 2, 4, 8, 16, 32 or 64")
+        return time_lanes(a, dev)
     lib = C.CDLL(build.DEVICE_EXAMPLE_SO)
     lib.gen_arena.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
     lib.gen_fold.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(api.StatType), C.POINTER(api.PrepassContext),

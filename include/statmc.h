@@ -435,6 +435,40 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
                             const int32_t *tile_bounds, const int64_t *tile_offsets,
                             const int32_t *tile_samples, int n_tiles, void *stream);
 
+/* ---- samples that finish anywhere: unordered (pixel, sample) records (no counterpart in the reference, whose tiles own their
+ * pixels).  statmc_accumulate wants the same count for every pixel of the film, statmc_accumulate_tiles for every pixel of a
+ * tile, statmc::device::PixelStats one thread that owns the pixel.  A wavefront path tracer, per-pixel adaptive sampling or a
+ * sparse re-render have a queue of finished samples instead, and this entry takes that queue: 4 + 4 * channels bytes per
+ * sample that exists, not per slot of a dense arena.
+ *   pixels            device array of n_records entries.  Record i belongs to pixel pixels[i] = y * width + x.  Any value
+ *                     outside [0, width * height) -- negative ones included -- marks a skipped record (a terminated path,
+ *                     padding): it is never folded and never causes an access outside the images.
+ *   types[t].samples  device, fp32, record-major [n_records][channels].  Every type shares `pixels` and n_records, as every
+ *                     camera sample feeds every type in Render<T>; n_samples is ignored.  The state pointers, transform,
+ *                     max_moment and the optional mean_corr / discriminator mean what they mean for statmc_accumulate.
+ * The fold order is the definition: per pixel, its records are folded in ascending i, and they leave bit for bit what
+ * statmc_accumulate leaves after the same samples in that order -- n, the moments, the film chain and the pre-pass epilogue.
+ * So the result does not depend on how records of DIFFERENT pixels interleave, and one call over records [0, n) equals a call
+ * over [0, m) followed by a call over [m, n).  A pixel without a record keeps every bit of every image, mean_corr /
+ * discriminator included.  The same inputs give the same bits on every run: the records are grouped by a stable sort
+ * (pixel, record index) and each pixel's run is read back in that fixed order; nothing the hardware orders -- atomic
+ * arrival, wave scheduling -- reaches the fold order.
+ * Limits: n_records in [0, 2^31), n_types in [0, 16]; anything else is STATMC_ERR_INVALID before any launch.  Zero records or
+ * zero types is a no-op.  Counts stay below 2^24 as everywhere else; this is not checked.  Before statmc_setup:
+ * STATMC_ERR_NO_DEVICE, like every compute entry.
+ * Asynchronous on `stream`; nothing is read back to the host (it never learns how many pixels were touched).  The sorted
+ * pairs (8 bytes per record), the per-pixel runs (8 per pixel) and the sort's temporary live in a per-(device, stream)
+ * workspace that grows on demand (the only allocation on the call path, and only when a call needs more than any before it
+ * on that stream) and goes with statmc_stream_destroy; like the other library workspaces it never backs or probes a placed
+ * slot.
+ * Cost: the grouping is linear in the records whatever their distribution.  The fold gives a pixel to one lane, and the fold of
+ * one pixel is a sequential chain BY DEFINITION: the launch ends when its longest run ends, so a few pixels with tens of
+ * thousands of records end it on a few lanes.  Remedy: deal such a pixel's records to several states (several calls into
+ * several sets of images) and put them together with statmc_combine_many -- not the same bits as one fold, but the same
+ * statistics. */
+int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                              const int32_t *pixels, int64_t n_records, void *stream);
+
 /* ---- combining independently accumulated statistics (no counterpart in the reference, whose renders can only be split by
  * --baseseed and then not put back together: src/main/pbrt.cpp:71,165-168).  Per pixel and channel, part A in `dst`, part B
  * in `src`, n = nA + nB, delta = meanB - meanA (Chan et al. 1979, Pebay 2008):

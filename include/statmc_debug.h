@@ -42,6 +42,11 @@ int statmc_debug_accumulate_umul(int umul);
 /* Tile-fed accumulation: prefetch depth of the mean-only types (1 | 2, default 2), item order, workgroups per CU. */
 int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu);
 
+/* statmc_accumulate_records, for timing its two steps apart (tools/time_accumulate_records.py): 1 = the grouping only, 2 = the
+ * fold only, over the index that the last full or grouping-only call with the same pixels and record count left in the
+ * stream's workspace, 3 = both (default).  Any other value: STATMC_ERR_INVALID. */
+int statmc_debug_accumulate_records_phases(int phases);
+
 /* The placed allocator's probe (statmc_amd/csrc/statmc_placement.hip) on memory of the caller's: streams [stream_ptr, + stream_bytes)
  * while every fourth step read-modify-writes 16 bytes inside [rmw_ptr, + rmw_bytes) -- the words there change.  Best of five, ms.
  * Two buffers in the same interference class: ~ 9 % slower than two in different ones (1-GiB stream, 64-MiB window). */

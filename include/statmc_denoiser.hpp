@@ -1100,6 +1100,31 @@ class Estimator {
     // DeviceStatistics and Upload / Denoise / Download, or orders it against this stream with events.
     void *DeviceStream() const { return stream.handle(); }
 
+    // ---- samples that finish anywhere: unordered (pixel, sample) records (statmc_accumulate_records, include/statmc.h)
+    // A wavefront renderer's queue of finished samples: d_pixels[i] = y * width + x of record i (anything outside the film: a
+    // skipped record), and per listed (type, bounce) one sample per record at d_samples[i * channels], all on this
+    // Estimator's device.  Per pixel the records are folded in ascending i -- the bits Merge*Tile(s) leave for the same samples
+    // in that order -- and a pixel without a record keeps every bit.  Needs EnableDeviceAccumulation(); samples staged by
+    // Merge*Tile(s) so far are flushed first; the launch goes to DeviceStream(), so the arrays must stay valid and unchanged
+    // until work enqueued there behind this call has run.  withPrepass is DeviceStatistics' flag: the fold's epilogue also
+    // writes the "-mean-corr" / "-discriminator" images of the pixels it touched (max_moment 3).  Afterwards Upload / Denoise /
+    // Download and DownloadStatistics behave as after a flush.  At most 16 buffers per call.
+    struct RecordSamples {
+        unsigned char statTypeIndex, bounceIndex;
+        const float *d_samples;      // device, fp32, [n_records][channels of the type]
+        bool withPrepass = false;
+    };
+    void AccumulateRecords(const int32_t *d_pixels, int64_t n_records, const std::vector<RecordSamples> &buffers) {
+        std::vector<statmc_stat_type> types;
+        for (const RecordSamples &r : buffers) {
+            statmc_stat_type t = DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);   // validates, flushes staged samples
+            t.samples = r.d_samples;
+            types.push_back(t);
+        }
+        check(statmc_set_device(device));
+        check(statmc_accumulate_records(width, height, types.data(), (int)types.size(), d_pixels, n_records, stream.handle()));
+    }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     size_t flushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nFlushes; }

@@ -102,7 +102,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -178,6 +178,8 @@ def load():
     lib.statmc_accumulate_row_ranges.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
     lib.statmc_accumulate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]
+    lib.statmc_accumulate_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.statmc_debug_accumulate_records_phases.argtypes = [C.c_int]
     lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
@@ -612,6 +614,26 @@ def accumulate_tiles(width, height, stat_types, tile_bounds, tile_offsets, tile_
     check(load().statmc_accumulate_tiles(width, height, arr, len(stat_types), tile_bounds.data_ptr(),
                                          tile_offsets.data_ptr(), tile_samples.data_ptr(), tile_bounds.shape[0],
                                          stream if stream is not None else current_stream_handle()))
+
+
+def make_stat_type_records(samples, channels, state, transform, max_moment, prepass_into=None):
+    """Stat type whose samples arrive as records (accumulate_records): `samples` is a record-major fp32 device tensor,
+    [n_records, channels] or flat; record i's values are samples[i * channels : (i + 1) * channels]."""
+    if not samples.is_contiguous():   # the descriptor holds the address: a reshaped copy would be gone before the call
+        raise ValueError("make_stat_type_records: samples must be contiguous")
+    return make_stat_type_arena(samples.view(-1), channels, state, transform, max_moment, prepass_into=prepass_into)
+
+
+def accumulate_records(width, height, stat_types, pixels, stream=None):
+    """statmc_accumulate_records (include/statmc.h): `pixels` is an int32 device tensor, one entry per record (y * width + x;
+    anything outside the film marks a skipped record); every stat type (make_stat_type_records) holds one sample per record.
+    Per pixel the records are folded in ascending record index: the bits of statmc_accumulate after the same samples."""
+    tc = _torch()
+    if pixels.dtype != tc.int32 or not pixels.is_contiguous():
+        raise ValueError("accumulate_records: pixels must be a contiguous int32 tensor")
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    check(load().statmc_accumulate_records(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), pixels.numel(),
+                                           stream if stream is not None else current_stream_handle()))
 
 
 def calculate_mean_vars(n, film_m2, film_var, row_n_quirk=True, stream=None):

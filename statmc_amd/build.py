@@ -8,7 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
-SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip"]
+SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
+           "statmc_records.hip"]
 HEADERS = ["statmc_device.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
@@ -91,9 +92,11 @@ DENOISE_BIN = os.path.join(ROOT, "tools", "bin", "statmc_denoise")
 RENDER_SIM_BIN = os.path.join(ROOT, "tools", "bin", "statmc_render_sim")
 CV_ADAPTOR_BIN = os.path.join(ROOT, "tools", "bin", "test_cv_adaptor")   # tests/cpp/test_cv_adaptor.cpp: include/statmc_cv.hpp in use
 DEVICE_ACC_BIN = os.path.join(ROOT, "tools", "bin", "test_device_accumulate")   # tests/cpp/test_device_accumulate.cpp: Estimator::DeviceStatistics
+ACC_RECORDS_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records")   # tests/cpp/test_accumulate_records.cpp: Estimator::AccumulateRecords
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
-         DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp")}
+         DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
+         ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")

@@ -42,6 +42,7 @@ struct DeviceState {
     int force_variant = 0;                                    // statmc_debug_force_filter_variant
     int acc_resident_blocks = 0, acc_umul = 1, acc_dma = 1;   // film-major accumulation
     int acc_grid_mode = -1, acc_dma_first = 0;                // launch shape: -1 automatic (by batch length), 0 capped grid, 1 one pass per workgroup; A/B: ring rows requested before the state
+    int rec_phases = 3;                                       // statmc_accumulate_records: 1 grouping, 2 fold, 3 both (statmc_debug_accumulate_records_phases; timing)
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
 std::unordered_map<int, DeviceState> g_dev;  // guarded by g_mu
@@ -165,6 +166,28 @@ int partial_workspace(size_t bytes, void *stream, float **out) {
         w.bytes = bytes;
     }
     *out = w.ptr;
+    return STATMC_OK;
+}
+
+// statmc_accumulate_records' scratch (sorted keys, order, per-pixel runs, the sort's temporary): the same scheme, a map of its
+// own -- a filter call and a records call on one stream follow each other, but neither may shrink or move the other's block
+std::unordered_map<WsKey, Workspace, WsHash> g_rec_ws;
+int records_workspace(size_t bytes, void *stream, char **out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_mu);
+    Workspace &w = g_rec_ws[WsKey{dev, stream}];
+    if (w.bytes < bytes) {
+        if (w.ptr) {
+            HIP_TRY(hipStreamSynchronize(S(stream)));  // earlier launches on this stream may still read the old block
+            HIP_TRY(statmc::workspace_free(w.ptr));
+        }
+        w.ptr = nullptr;
+        w.bytes = 0;
+        HIP_TRY(statmc::workspace_alloc(reinterpret_cast<void **>(&w.ptr), bytes));   // never backs or probes a placed slot
+        w.bytes = bytes;
+    }
+    *out = reinterpret_cast<char *>(w.ptr);
     return STATMC_OK;
 }
 
@@ -456,17 +479,18 @@ int statmc_stream_destroy(void *stream) {
     std::vector<std::shared_ptr<DenseArena>> arenas;
     {
         std::lock_guard<std::mutex> lk(g_mu);
-        for (auto it = g_ws.begin(); it != g_ws.end();) {
-            if (it->first.stream == stream && stream != nullptr) {
-                if (it->second.ptr) {
-                    (void)hipStreamSynchronize(S(stream));
-                    (void)statmc::workspace_free(it->second.ptr);
+        for (auto *ws : {&g_ws, &g_rec_ws})
+            for (auto it = ws->begin(); it != ws->end();) {
+                if (it->first.stream == stream && stream != nullptr) {
+                    if (it->second.ptr) {
+                        (void)hipStreamSynchronize(S(stream));
+                        (void)statmc::workspace_free(it->second.ptr);
+                    }
+                    it = ws->erase(it);
+                } else {
+                    ++it;
                 }
-                it = g_ws.erase(it);
-            } else {
-                ++it;
             }
-        }
         arenas = detach_dense_arenas(stream);
     }
     free_detached_arenas(arenas, stream);
@@ -1438,6 +1462,40 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
     return STATMC_OK;
 }
 
+// Samples as unordered (pixel, sample) records (include/statmc.h; kernels and the scheme: statmc_records.hip).
+int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
+                              int64_t n_records, void *stream) {
+    // the limits first: an argument error is reported whether or not a device has been set up
+    if (n_types < 0 || n_types > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
+    if (n_records < 0 || n_records > (int64_t)INT32_MAX) return fail(STATMC_ERR_INVALID, "n_records must be in [0, 2^31)");
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0 || n_records == 0) return STATMC_OK;
+    if (!types || !pixels) return fail(STATMC_ERR_INVALID, "null types or pixels");
+    statmc::RecordsArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_types = n_types;
+    k.n_records = n_records;
+    k.n_px = (long long)width * height;
+    bool epilogue = false;
+    for (int i = 0; i < n_types; i++) {
+        statmc::AccumulateType checked;   // the validation of every accumulate entry; n_samples is ignored here
+        if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, checked)) return rc;
+        k.t[i] = types[i];
+        k.t[i].transform = types[i].transform ? 1 : 0;
+        epilogue = epilogue || types[i].mean_corr != nullptr;
+    }
+    if (epilogue)
+        if (int rc = statmc_get_prepass_context(&k.ctx)) return rc;
+    statmc::RecordsWorkspace w;
+    HIP_TRY(statmc::records_workspace_layout(k.n_records, k.n_px, w));
+    char *ws = nullptr;
+    if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
+    HIP_TRY(statmc::launch_accumulate_records(k, pixels, w, ws, dstate.rec_phases, S(stream)));
+    return STATMC_OK;
+}
+
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,
                        const int32_t *tile_bounds, const int64_t *tile_offsets, int n_tiles, int max_tile_pixels,
                        int32_t *n, float *mean, float *m2, float *m3, float *film_mean, float *film_m2, void *stream) {
@@ -1540,6 +1598,12 @@ int statmc_debug_accumulate_umul(int umul) {   // film-major kernel: 2 = the mea
 }
 int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu) {  // experiments (time_accumulate_tiles.py)
     STATMC_DEBUG_SET(d.tiles_umul = umul == 2 ? 2 : 1; d.tiles_order = order < 0 || order > 2 ? 0 : order; d.tiles_wg_per_cu = wg_per_cu < 0 ? 0 : wg_per_cu);
+}
+// timing aid (tools/time_accumulate_records.py): 1 = only the grouping, 2 = only the fold, over the index the last call with
+// the same pixels and record count left in the stream's workspace, 3 = both (default)
+int statmc_debug_accumulate_records_phases(int phases) {
+    if (phases < 1 || phases > 3) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_records_phases(%d): 1, 2 or 3", phases);
+    STATMC_DEBUG_SET(d.rec_phases = phases);
 }
 int statmc_debug_force_filter_parts(int k) { return statmc_set_filter_split(k < 0 ? 0 : k); }   // the older name of the pin
 int statmc_debug_last_filter_parts(void) { return g_last_parts; }

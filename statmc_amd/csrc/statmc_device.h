@@ -119,6 +119,25 @@ struct CombineManyArgs {
 static_assert(sizeof(CombineManyArgs) <= 4096, "CombineManyArgs is passed by value: the kernel-argument limit");
 hipError_t launch_combine_many(const CombineManyArgs &a, hipStream_t s);
 
+// statmc_accumulate_records (statmc_records.hip): every type's `samples` is record-major [n_records][channels]; the types
+// travel as the ABI's own descriptors, which is what statmc::device::PixelStats loads and stores through.
+struct RecordsArgs {
+    statmc_stat_type t[kMaxStatTypes];
+    statmc_prepass_context ctx;      // the pre-pass epilogue's table and flags (types with mean_corr / discriminator)
+    const int32_t *order;            // record indices sorted by pixel, stable          (workspace)
+    const int32_t *seg;              // {start, end} of every pixel's run in order[]    (workspace)
+    long long n_records, n_px;
+    int n_types;
+};
+// the per-(device, stream) scratch of one call: byte offsets into one block
+struct RecordsWorkspace {
+    size_t keys_off, order_off, seg_off, seg_bytes, temp_off, temp_bytes, bytes;
+};
+hipError_t records_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w);   // host only: no launch
+// phases: 1 = grouping, 2 = fold, 3 = both (the ABI's call; 1 and 2 alone: statmc_debug_accumulate_records_phases)
+hipError_t launch_accumulate_records(const RecordsArgs &a, const int32_t *pixels, const RecordsWorkspace &w, char *ws, int phases,
+                                     hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

@@ -1,0 +1,356 @@
+"""statmc_accumulate_records on the GPU: samples handed in as unordered (pixel, sample) records leave, per pixel, the bits
+statmc_accumulate leaves after the same samples in ascending record order -- whatever the order of the records of different
+pixels, however many records a pixel has, and on every run.  Comparisons are bitwise on int32 views of every state image
+unless a test says otherwise."""
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import rel_l2
+
+pytestmark = pytest.mark.gpu
+
+FILMS = [(37, 29), (64, 32)]     # odd width, ragged last group, unaligned planes / the vector path of the yardsticks
+# (name, channels, transform, max_moment, pre-pass epilogue)
+TYPES = [("radiance", 3, 1, 3, True), ("normal", 3, 0, 1, False), ("depth", 1, 0, 1, False), ("extra", 1, 1, 2, False)]
+FIELDS = ("n", "mean", "m2", "m3", "film_mean", "film_m2")
+
+
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def bits(t):
+    a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+    return a.view(np.int32) if a.dtype == np.float32 else a
+
+
+class States:
+    """One set of state images per stat type of TYPES, plus the radiance type's mean_corr / discriminator."""
+
+    def __init__(self, W, H, fill=None):
+        import torch
+        from statmc_amd import film
+        self.W, self.H = W, H
+        self.st = [film.new_state(H, W, c, torch.device("cuda:0"), transform=bool(t)) for _, c, t, _, _ in TYPES]
+        self.mc = torch.zeros(H, W, 3, device="cuda:0")
+        self.dc = torch.zeros(H, W, 3, device="cuda:0")
+        if fill is not None:       # a seeded random bit pattern in every image
+            for img in self.images():
+                raw = fill.integers(-2 ** 31, 2 ** 31, size=tuple(img.shape), dtype=np.int64).astype(np.int32)
+                img.copy_(dev(raw).view(img.dtype))
+
+    def images(self):
+        out = []
+        for st in self.st:
+            out += [st[k] for k in FIELDS if st.get(k) is not None]
+        return out + [self.mc, self.dc]
+
+    def snapshot(self):
+        import torch
+        torch.cuda.synchronize()
+        return [bits(img).copy() for img in self.images()]
+
+    def pre(self, i):
+        return (self.mc, self.dc) if TYPES[i][4] else None
+
+
+def same(a, b):
+    for k, (x, y) in enumerate(zip(a, b)):
+        assert np.array_equal(x, y), "image %d differs in %d elements" % (k, int((x != y).sum()))
+
+
+def make_samples(rng, n):
+    """Per type [n, C] fp32: log-normal, a fifth exact zeros, one x 1000 value (the shape of accumulate_edge_cases.npz)."""
+    out = []
+    for _, c, _, _, _ in TYPES:
+        s = np.exp(rng.normal(0.0, 1.0, (n, c))).astype(np.float32)
+        s[rng.random((n, c)) < 0.2] = 0.0
+        if n:
+            s[int(rng.integers(0, n))] *= np.float32(1000.0)
+        out.append(s)
+    return out
+
+
+def records_of_counts(rng, counts, dead=0.0):
+    """counts [H * W] -> (pixels [n] int32 in shuffled record order, with a share `dead` of skipped records mixed in)."""
+    npx = counts.size
+    px = np.repeat(np.arange(npx, dtype=np.int32), counts)
+    n_dead = int(round(dead * px.size))
+    marks = np.where(np.arange(n_dead) % 2 == 0, -1, npx + 7).astype(np.int32)
+    px = np.concatenate([px, marks])
+    return px[rng.permutation(px.size)]
+
+
+def run_records(api, S, pixels, samples, lo=0, hi=None):
+    """records [lo, hi) into S; the device tensors stay alive until the call has run"""
+    import torch
+    hi = len(pixels) if hi is None else hi
+    d_px = dev(pixels[lo:hi])
+    d_s = [dev(s[lo:hi]) for s in samples]
+    sts = [api.make_stat_type_records(d_s[i], TYPES[i][1], S.st[i], TYPES[i][2], TYPES[i][3], prepass_into=S.pre(i))
+           for i in range(len(TYPES))]
+    api.accumulate_records(S.W, S.H, sts, d_px)
+    torch.cuda.synchronize()
+
+
+def sorted_live(pixels, npx):
+    """the live records' indices sorted by pixel, ascending record index inside a pixel"""
+    live = np.flatnonzero((pixels >= 0) & (pixels < npx))
+    return live[np.argsort(pixels[live], kind="stable")]
+
+
+def run_tiles(api, S, pixels, samples):
+    """The yardstick for ragged counts: statmc_accumulate_tiles with one 1 x 1 tile per pixel, tile_samples = the pixel's
+    count; a tile's block [count][1][1][C] is the pixel's records in ascending record index."""
+    import torch
+    W, H = S.W, S.H
+    npx = W * H
+    order = sorted_live(pixels, npx)
+    counts = np.bincount(pixels[order], minlength=npx).astype(np.int32)
+    p = np.arange(npx, dtype=np.int32)
+    bounds = np.stack([p % W, p // W, p % W + 1, p // W + 1], axis=1).astype(np.int32)
+    offsets = (np.cumsum(counts, dtype=np.int64) - counts).astype(np.int64)
+    arenas = [dev(s[order].reshape(-1)) if order.size else dev(np.zeros(1, np.float32)) for s in samples]
+    sts = [api.make_stat_type_arena(arenas[i], TYPES[i][1], S.st[i], TYPES[i][2], TYPES[i][3], prepass_into=S.pre(i))
+           for i in range(len(TYPES))]
+    api.accumulate_tiles(W, H, sts, dev(bounds), dev(offsets), dev(counts))
+    torch.cuda.synchronize()
+
+
+def run_arena(api, S, pixels, samples, k):
+    """The yardstick for uniform counts: statmc_accumulate on the film-major arena, pixel p's j-th record in plane j."""
+    import torch
+    W, H = S.W, S.H
+    order = sorted_live(pixels, W * H)
+    arenas = [dev(s[order].reshape(H, W, k, -1).transpose(2, 0, 1, 3)) for s in samples]
+    sts = [api.make_stat_type(arenas[i], S.st[i], TYPES[i][2], TYPES[i][3], prepass_into=S.pre(i)) for i in range(len(TYPES))]
+    api.accumulate(W, H, sts)
+    torch.cuda.synchronize()
+
+
+def ragged_counts(rng, npx):
+    """0 .. 9 records per pixel, about a fifth of the pixels at 0, one pixel at 300"""
+    counts = rng.integers(1, 10, npx).astype(np.int64)
+    counts[rng.random(npx) < 0.2] = 0
+    counts[int(rng.integers(0, npx))] = 300
+    return counts
+
+
+@pytest.fixture(scope="module", params=FILMS, ids=lambda f: "%dx%d" % f)
+def ragged(request, gpu):
+    """One ragged record set per film, shared by the tests that need one; about 5 % dead records."""
+    W, H = request.param
+    rng = np.random.default_rng(1000 + W)
+    counts = ragged_counts(rng, W * H)
+    pixels = records_of_counts(rng, counts, dead=0.05)
+    samples = make_samples(rng, pixels.size)
+    return W, H, counts, pixels, samples
+
+
+@pytest.mark.parametrize("film", FILMS, ids=lambda f: "%dx%d" % f)
+def test_uniform_counts_equal_the_arena(gpu, film):
+    W, H = film
+    rng = np.random.default_rng(7 + W)
+    A, B = States(W, H), States(W, H)
+    for batch in range(2):                       # the second batch continues a non-zero state
+        pixels = records_of_counts(rng, np.full(W * H, 5))
+        samples = make_samples(rng, pixels.size)
+        run_records(gpu, A, pixels, samples)
+        run_arena(gpu, B, pixels, samples, 5)
+    assert int(A.st[0]["n"].min()) == int(A.st[0]["n"].max()) == 10
+    same(A.snapshot(), B.snapshot())
+
+
+@pytest.mark.parametrize("film", FILMS, ids=lambda f: "%dx%d" % f)
+def test_tile_path_with_one_pixel_tiles_is_statmc_accumulate(gpu, film):
+    """Guards the yardstick of the ragged tests: at uniform counts the 1 x 1-tile path leaves statmc_accumulate's bits."""
+    W, H = film
+    rng = np.random.default_rng(11 + W)
+    A, B = States(W, H), States(W, H)
+    for batch in range(2):
+        pixels = records_of_counts(rng, np.full(W * H, 5))
+        samples = make_samples(rng, pixels.size)
+        run_tiles(gpu, A, pixels, samples)
+        run_arena(gpu, B, pixels, samples, 5)
+    same(A.snapshot(), B.snapshot())
+
+
+def test_ragged_counts_equal_the_tile_path(gpu, ragged):
+    W, H, counts, pixels, samples = ragged
+    assert (counts == 0).mean() > 0.1 and counts.max() == 300
+    assert (pixels == -1).any() and (pixels == W * H + 7).any()
+    A, B = States(W, H), States(W, H)
+    run_records(gpu, A, pixels, samples)
+    run_tiles(gpu, B, pixels, samples)
+    assert np.array_equal(A.st[0]["n"].cpu().numpy().reshape(-1), counts)
+    same(A.snapshot(), B.snapshot())
+
+
+@pytest.fixture(scope="module")
+def many(gpu):
+    """64 x 32 with 200 000 records, about 100 per pixel: several workgroups in every step and several passes of the sort."""
+    W, H = 64, 32
+    rng = np.random.default_rng(3)
+    pixels = rng.integers(0, W * H, 200000).astype(np.int32)
+    samples = make_samples(rng, pixels.size)
+    S = States(W, H)
+    run_records(gpu, S, pixels, samples)
+    return W, H, pixels, samples, S.snapshot()
+
+
+def test_many_records_equal_the_tile_path(gpu, many):
+    W, H, pixels, samples, got = many
+    B = States(W, H)
+    run_tiles(gpu, B, pixels, samples)
+    same(got, B.snapshot())
+
+
+def test_many_records_are_deterministic(gpu, many):
+    W, H, pixels, samples, first = many
+    for run in range(2):                         # three runs with the fixture's
+        S = States(W, H)
+        run_records(gpu, S, pixels, samples)
+        same(first, S.snapshot())
+
+
+def test_order_properties(gpu, ragged):
+    W, H, counts, pixels, samples = ragged
+    ref = States(W, H)
+    run_records(gpu, ref, pixels, samples)
+    ref = ref.snapshot()
+    # one call equals two calls over a split of the record range
+    S = States(W, H)
+    m = len(pixels) // 3
+    run_records(gpu, S, pixels, samples, 0, m)
+    run_records(gpu, S, pixels, samples, m, None)
+    same(ref, S.snapshot())
+    # a permutation that keeps every pixel's relative order (here: the records sorted by pixel, dead ones first) changes no bit
+    perm = np.argsort(np.where((pixels >= 0) & (pixels < W * H), pixels, -1), kind="stable")
+    assert not np.array_equal(perm, np.arange(len(pixels)))
+    S = States(W, H)
+    run_records(gpu, S, pixels[perm], [s[perm] for s in samples])
+    same(ref, S.snapshot())
+    # swapping two records of one pixel that hold different values does change bits: the order is honoured
+    p = int(np.argmax(counts == 9))
+    i, j = np.flatnonzero(pixels == p)[[0, -1]]
+    swapped = [s.copy() for s in samples]
+    for s in swapped:
+        s[[i, j]] = s[[j, i]]
+    assert not np.array_equal(samples[0][i], samples[0][j])
+    S = States(W, H)
+    run_records(gpu, S, pixels, swapped)
+    got = S.snapshot()
+    assert any(not np.array_equal(x, y) for x, y in zip(ref, got))
+    untouched_elsewhere = np.arange(W * H) != p           # ... and only that pixel's
+    for x, y in zip(ref, got):
+        xs, ys = x.reshape(W * H, -1), y.reshape(W * H, -1)
+        assert np.array_equal(xs[untouched_elsewhere], ys[untouched_elsewhere])
+
+
+def test_untouched_pixels_keep_every_bit(gpu, ragged):
+    W, H, counts, pixels, samples = ragged
+    S = States(W, H, fill=np.random.default_rng(5))
+    for st in S.st:                              # touched pixels start from a count the fold can continue
+        st["n"].remainder_(1000).abs_()
+    before = S.snapshot()
+    run_records(gpu, S, pixels, samples)
+    after = S.snapshot()
+    untouched = counts == 0
+    assert untouched.any()
+    for x, y in zip(before, after):
+        xs, ys = x.reshape(W * H, -1), y.reshape(W * H, -1)
+        assert np.array_equal(xs[untouched], ys[untouched])
+    n0, n1 = before[0].reshape(-1), after[0].reshape(-1)
+    assert np.array_equal(n1 - n0, counts)
+    # only dead records: nothing changes anywhere
+    dead = np.where(np.arange(50) % 2 == 0, -1, W * H + 7).astype(np.int32)
+    run_records(gpu, S, dead, make_samples(np.random.default_rng(6), dead.size))
+    same(after, S.snapshot())
+
+
+def prepass_of(api, st, c):
+    import torch
+    mc, dc = torch.zeros_like(st["mean"]), torch.zeros_like(st["mean"])
+    args, keep = api.make_filter_args(n=[st["n"]], mean=[st["mean"]], m2=[st["m2"]], m3=[st["m3"]], film=[st["mean"]],
+                                      mean_corr=[mc], disc=[dc], film_filtered=[torch.zeros_like(mc)], g_buffers=[])
+    api.prepass(args, c)
+    torch.cuda.synchronize()
+    return mc, dc
+
+
+@pytest.mark.parametrize("spec", ["default", "welch_exclude"])
+def test_epilogue_is_statmc_prepass(gpu, ragged, spec):
+    api = gpu
+    W, H, counts, pixels, samples = ragged
+    try:
+        if spec == "welch_exclude":
+            api.set_filter_spec(dof=api.DOF_WELCH, small_n=1)
+        else:
+            api.set_filter_spec()
+        S = States(W, H)
+        S.mc.fill_(7.0)
+        S.dc.fill_(7.0)
+        run_records(api, S, pixels, samples)
+        mc, dc = prepass_of(api, S.st[0], 3)
+        touched = (counts > 0).reshape(H, W)
+        assert (counts == 1).any()               # n = 1: the small-n branch
+        for got, want in ((S.mc, mc), (S.dc, dc)):
+            g, w = bits(got), bits(want)
+            assert np.array_equal(g[touched], w[touched])
+            assert (g[~touched] == np.float32(7.0).view(np.int32)).all()      # untouched pixels keep what was there
+    finally:
+        api.set_filter_spec()
+
+
+def test_ragged_counts_match_the_oracle(gpu, oracle, ragged):
+    """The oracle's per-sample update folded per pixel on the CPU, held to test_accumulate_matches_oracle's bound: bit-exact
+    counts, raw-sample moments and non-transform moments; <= 1e-5 relative L2 where the GPU's sqrt stands in for pow."""
+    W, H, counts, pixels, samples = ragged
+    S = States(W, H)
+    run_records(gpu, S, pixels, samples)
+    order = sorted_live(pixels, W * H)
+    starts = np.cumsum(counts) - counts
+    for i, (name, c, transform, max_moment, _) in enumerate(TYPES):
+        ref = oracle.new_state(H, W, c)
+        flat = {k: v.reshape(W * H, -1) for k, v in ref.items()}
+        srt = samples[i][order]
+        for p in np.flatnonzero(counts):
+            px = oracle.add_samples_to_pixel(srt[starts[p]:starts[p] + counts[p]], c, transform, max_moment)
+            for k in FIELDS:
+                flat[k][p] = px[k]
+        got = {k: v.cpu().numpy() for k, v in S.st[i].items() if v is not None}
+        assert np.array_equal(got["n"], ref["n"]), name
+        if transform:
+            assert np.array_equal(got["film_mean"], ref["film_mean"]), name
+            assert np.array_equal(got["film_m2"], ref["film_m2"]), name
+            for k in ("mean", "m2", "m3"):
+                assert rel_l2(got[k], ref[k]) <= 1e-5, (name, k)
+        else:
+            for k in ("mean", "m2", "m3"):
+                assert np.array_equal(got[k], ref[k]), (name, k)
+
+
+def test_no_records_or_no_types_is_a_no_op(gpu):
+    import torch
+    api = gpu
+    W, H = 37, 29
+    S = States(W, H, fill=np.random.default_rng(8))
+    before = S.snapshot()
+    run_records(api, S, np.zeros(0, np.int32), make_samples(np.random.default_rng(9), 0))
+    api.accumulate_records(W, H, [], dev(np.arange(10, dtype=np.int32)))
+    torch.cuda.synchronize()
+    same(before, S.snapshot())
+
+
+def test_estimator_accumulate_records_equals_merge_tiles(gpu):
+    """C++ host: an Estimator fed through AccumulateRecords holds the bits of one fed the same samples through Merge*Tile,
+    and denoises to the same film-f (tests/cpp/test_accumulate_records.cpp)."""
+    from statmc_amd import build
+    build.build_tools()
+    for w, h in ((61, 37), (96, 64)):
+        out = subprocess.run([build.ACC_RECORDS_BIN, str(w), str(h)], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stdout + out.stderr
+        assert "accumulate records ok" in out.stdout

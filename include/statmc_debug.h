@@ -30,6 +30,16 @@ int statmc_debug_last_filter_tail(int *parts_hi, int *tail_rows);
 int statmc_debug_accumulate_resident_blocks(int n);
 /* Workgroups of the calling thread's last statmc_accumulate launch (which launch shape the sizes chose: DESIGN.md 4.1). */
 int statmc_debug_last_accumulate_grid(void);
+/* Film-major accumulation, the type-fused walk (one wave folds every stat type of its pixel groups in one pass over the samples;
+ * launches of one RGB type with the transform and three moments plus up to two mean-only RGB and up to two mean-only 1-channel
+ * types, all of the same pixels and batch length, 16-byte aligned): 0 = by shape (default: where the resident grid is taken, and from 128 samples per
+ * launch up on films of 960 x 540 to 1920 x 1080 pixels);
+ * 1 = every eligible launch, at any film size, with min(compute units, 256-group units) workgroups or the number set through
+ * statmc_debug_accumulate_resident_blocks(n); -1 = never.  statmc_debug_accumulate_resident_blocks(-1) and
+ * statmc_debug_accumulate_dma(0) switch it off as well.  Same bits either way.  Any other value: STATMC_ERR_INVALID. */
+int statmc_debug_accumulate_fused(int mode);
+/* 1 if the calling thread's last statmc_accumulate launch ran the type-fused walk, else 0. */
+int statmc_debug_last_accumulate_fused(void);
 /* 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers (same bits).  Any other value:
  * STATMC_ERR_INVALID. */
 int statmc_debug_accumulate_dma(int on);

@@ -194,6 +194,8 @@ def load():
     lib.statmc_debug_last_filter_parts.restype = C.c_int
     lib.statmc_debug_accumulate_resident_blocks.argtypes = [C.c_int]
     lib.statmc_debug_accumulate_dma.argtypes = [C.c_int]
+    lib.statmc_debug_accumulate_fused.argtypes = [C.c_int]
+    lib.statmc_debug_last_accumulate_fused.restype = C.c_int
     _lib = lib
     return lib
 
@@ -252,6 +254,16 @@ def accumulate_resident_blocks(n):
 def accumulate_dma(on):
     """1 (default): the RGB sample planes of the accumulation stream through LDS-DMA; 0: loads into registers (A/B, tests)."""
     check(load().statmc_debug_accumulate_dma(int(on)))
+
+
+def accumulate_fused(mode):
+    """The accumulation's type-fused walk: 0 by shape (default), 1 whenever the launch is eligible, -1 never (A/B, tests)."""
+    check(load().statmc_debug_accumulate_fused(int(mode)))
+
+
+def last_accumulate_fused():
+    """1 if the calling thread's last film-major accumulation ran the type-fused walk, else 0."""
+    return int(load().statmc_debug_last_accumulate_fused())
 
 
 def force_filter_parts(k):

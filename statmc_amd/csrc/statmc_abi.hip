@@ -42,6 +42,7 @@ struct DeviceState {
     int force_variant = 0;                                    // statmc_debug_force_filter_variant
     int acc_resident_blocks = 0, acc_umul = 1, acc_dma = 1;   // film-major accumulation
     int acc_grid_mode = -1, acc_dma_first = 0;                // launch shape: -1 automatic (by batch length), 0 capped grid, 1 one pass per workgroup; A/B: ring rows requested before the state
+    int acc_fused = 0;                                        // the type-fused walk: 0 by shape, 1 whenever eligible, -1 never (statmc_debug_accumulate_fused)
     int rec_phases = 3;                                       // statmc_accumulate_records: 1 grouping, 2 fold, 3 both (statmc_debug_accumulate_records_phases; timing)
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
@@ -1236,6 +1237,7 @@ int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_s
     k.dma = dstate.acc_dma;
     k.grid_mode = dstate.acc_grid_mode;
     k.dma_first = dstate.acc_dma_first;
+    k.fused = dstate.acc_fused;
     k.occ = 0;   // (unused)
     // every type's samples in a STREAM block and its moments in a STATE block of the placed allocator: apart by construction
     k.apart = 1;
@@ -1586,6 +1588,11 @@ int statmc_debug_accumulate_resident_blocks(int n) {  // 0 by shape (default), n
     STATMC_DEBUG_SET(d.acc_resident_blocks = n < 0 ? -1 : n);
 }
 int statmc_debug_last_accumulate_grid(void) { return (int)statmc::last_accumulate_grid(); }
+int statmc_debug_accumulate_fused(int mode) {   // the type-fused walk: 0 by shape (default), 1 whenever the launch is eligible, -1 never
+    if (mode < -1 || mode > 1) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_fused(%d): -1, 0 or 1", mode);
+    STATMC_DEBUG_SET(d.acc_fused = mode);
+}
+int statmc_debug_last_accumulate_fused(void) { return statmc::last_accumulate_fused(); }
 int statmc_debug_accumulate_dma(int on) {   // 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers
     if (on != 0 && on != 1) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_dma(%d): 0 or 1", on);
     STATMC_DEBUG_SET(d.acc_dma = on);

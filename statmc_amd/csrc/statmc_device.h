@@ -58,6 +58,9 @@ struct AccumulateArgs {
     int n_slots;
     int type_slots[kMaxStatTypes];
     unsigned char slot_type[kMaxSlots], slot_rank[kMaxSlots];
+    // the type-fused walk (launch_accumulate): 0 by shape, 1 whenever the launch is eligible, -1 never (statmc_debug_accumulate_fused);
+    // read by the host only, and last so that the fields before it keep their kernel-argument offsets
+    int fused;
 };
 
 // samples of every type arrive tile by tile: AccumulateType::samples is the type's arena, tile k's
@@ -257,6 +260,7 @@ hipError_t launch_prepass(const PrepassArgs &a, hipStream_t s);
 hipError_t launch_mean_vars(const MeanVarsArgs &a, hipStream_t s);
 hipError_t launch_accumulate(const AccumulateArgs &a, hipStream_t s);
 unsigned last_accumulate_grid();
+int last_accumulate_fused();         // 1: the calling thread's last film-major launch ran the type-fused walk
 hipError_t launch_accumulate_tiles(const AccumulateTilesArgs &a, hipStream_t s);
 hipError_t launch_merge_tiles(const MergeTilesArgs &a, int n_tiles, int max_tile_pixels, hipStream_t s);
 hipError_t launch_tile_moments(const TileMomentsArgs &a, hipStream_t s);

@@ -658,8 +658,352 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
     else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
 }
 
+// ------------------------------------------------------------------ accumulate, every stat type of a pixel group in one walk
+// The type-fused walk: a lane owns its 4-pixel group in EVERY stat type of the launch -- the radiance type (RGB, Box-Cox, three
+// moments), K mean-only RGB types and M mean-only 1-channel types -- and folds sample s of all of them before sample s + 1 of
+// any.  Every element still sees its own samples in order through the same add_sample2 stages, so the bits are those of
+// accumulate_lane type after type.  What changes is the mix a wave runs: the radiance arithmetic issues while the wave's own
+// feature rows are in flight (the per-type walk leaves a lone VALU-bound wave per SIMD in its radiance walk and an idle VALU in
+// its feature walks), the count conversion and the refined reciprocal are formed once per sample instead of once per type, and
+// a pixel group pays one chain of state-load, first-row and store latencies instead of one per type.
+// Sample rows: all by LDS-DMA, one wave-private ring slot per sample -- three 1-KiB transfers per RGB type, one per 1-channel type
+// (lane l fetches its own 16 bytes there), so the prefetch of no type lives in registers.  The rows are awaited by COUNT, hence
+// a fixed issue order and a number of transfers per row that does not depend on how many lanes of the wave hold a group.
+#ifndef STATMC_ACC_FUSED_D
+#define STATMC_ACC_FUSED_D 3
+#endif
+constexpr int kAccFusedD = STATMC_ACC_FUSED_D;          // sample rows in flight per wave (2 against 3)
+constexpr int kAccFusedTypes = 5;
+struct AccumulateFusedArgs {
+    AccumulateType t[kAccFusedTypes];   // the radiance type, the K mean-only RGB types, the M mean-only 1-channel types
+    long long n_groups;                 // 4-pixel groups of the film (every type has the same pixels)
+    int n_samples;                      // ... and the same batch length
+};
+constexpr int acc_fused_slot_floats(int k, int m) { return 768 * (1 + k) + 256 * m; }       // one sample row of every type, per wave
+constexpr size_t acc_fused_lds_bytes(int k, int m, int d) { return (size_t)4 * d * acc_fused_slot_floats(k, m) * sizeof(float); }
+
+// A wave whose lanes do not all hold one count per group in every type (adaptively sampled films): today's walk, type after
+// type, in the wave's ring -- the same bits, no second ragged code.
+template <int K, int M, int D>
+__device__ __forceinline__ void accumulate_fused_ragged(const AccumulateFusedArgs &a, long long gw, int n_active, float *ring) {
+    // (the descriptors below are picked by comparisons, never by a run-time index into the kernel argument -- see accumulate_kernel on
+    // what that costs; with at most two types of a kind "the first or the last" names them all)
+    static_assert(K >= 0 && K <= 2 && M >= 0 && M <= 2, "a.t[1] / a.t[K] and a.t[1 + K] / a.t[K + M] name every feature type only up to two of a kind");
+    constexpr int kFit = D * acc_fused_slot_floats(K, M) / 768;       // rows of one RGB type the wave's ring holds
+    constexpr int FD = kFit < kAccDmaD ? kFit : kAccDmaD;
+    const int lane = threadIdx.x & 63;
+    const long long p0 = (gw + lane) << 2;
+    const bool active = lane < n_active;
+    const int S = a.n_samples;
+    {
+        const AccumulateType t = a.t[0];    // (copies, not references into the kernel argument: see accumulate_kernel)
+        accumulate_lane<3, 3, true, 1, FD>(t, p0, t.samples + p0 * 3, t.stride, S, ring, active, n_active, false);
+    }
+    if constexpr (K > 0) {
+#pragma unroll 1
+        for (int i = 0; i < K; i++) {
+            const AccumulateType t = i == 0 ? a.t[1] : a.t[K];
+            accumulate_lane<3, 1, false, 1, FD>(t, p0, t.samples + p0 * 3, t.stride, S, ring, active, n_active, false);
+        }
+    }
+    if constexpr (M > 0) {
+#pragma unroll 1
+        for (int i = 0; i < M; i++) {
+            const AccumulateType t = i == 0 ? a.t[1 + K] : a.t[K + M];
+            accumulate_lane<1, 1, false, 1, FD>(t, p0, t.samples + p0, t.stride, S, ring, active, n_active, false);
+        }
+    }
+}
+
+// The wave's 64 groups from group gw on (the first n_active of them exist; wave-uniform arguments).
+template <int K, int M, int D>
+__device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs &a, long long gw, int n_active, float *ring) {
+    constexpr int NT = 1 + K + M;
+    constexpr int SLOT = acc_fused_slot_floats(K, M);
+    constexpr int T = 3 * (1 + K) + M;                      // transfers per sample row
+    static_assert(T * (D - 1) <= 63, "the counted wait must fit vmcnt");
+    constexpr int KA = K > 0 ? K : 1, MA = M > 0 ? M : 1;
+    const int lane = threadIdx.x & 63;
+    const bool active = lane < n_active;
+    const long long p0 = active ? (gw + lane) << 2 : 0;     // an inactive lane reads group 0 and stores nothing
+    const int S = a.n_samples;
+    // counts first: which walk the wave takes
+    int nb[NT];
+    bool lane_same = true, lane_one = true;
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+        const int4 n4 = *reinterpret_cast<const int4 *>(a.t[i].n + p0);
+        nb[i] = n4.x;
+        lane_same = lane_same && n4.x == n4.y && n4.y == n4.z && n4.z == n4.w;
+        lane_one = lane_one && n4.x == nb[0];
+    }
+    if (__builtin_amdgcn_ballot_w64(active && !lane_same) != 0) {
+        accumulate_fused_ragged<K, M, D>(a, gw, n_active, ring);
+        return;
+    }
+    // (the descriptors' fields, all read before the first store: see accumulate_lane)
+    float *const r_mean = a.t[0].mean, *const r_m2 = a.t[0].m2, *const r_m3 = a.t[0].m3, *const r_fmean = a.t[0].film_mean,
+                 *const r_fm2 = a.t[0].film_m2, *const pre_mc = a.t[0].mean_corr, *const pre_dc = a.t[0].disc;
+    const int pre_table = a.t[0].pre_table, pre_flags = a.t[0].pre_flags;
+    int32_t *n_ptr[NT];
+    float *f_mean[NT];
+    const float *row[NT];       // the wave's next sample row to request, per type
+    long long stride[NT];
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+        n_ptr[i] = a.t[i].n;
+        f_mean[i] = a.t[i].mean;
+        row[i] = a.t[i].samples + (gw << 2) * (i <= K ? 3 : 1);
+        stride[i] = a.t[i].stride;
+    }
+    // Every lane issues every transfer of a row, whatever part of the row exists; a piece beyond the row's end re-reads the
+    // row's first 16 bytes (memory that exists) into a part of the slot nobody reads (as in accumulate_lane).
+    int piece3[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) piece3[k] = 256 * k + 4 * lane < 12 * n_active ? 256 * k + 4 * lane : 0;
+    const int piece1 = active ? 4 * lane : 0;
+    auto issue = [&](int slot) {
+        float *dst = ring + slot * SLOT;
+#pragma unroll
+        for (int i = 0; i < NT; i++) {
+            if (i <= K) {
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    __builtin_amdgcn_global_load_lds(row[i] + piece3[k], (__attribute__((address_space(3))) void *)(dst + 768 * i + 256 * k), 16, 0, 2);
+            } else {
+                __builtin_amdgcn_global_load_lds(row[i] + piece1, (__attribute__((address_space(3))) void *)(dst + 768 * (1 + K) + 256 * (i - 1 - K)), 16, 0, 2);
+            }
+            row[i] += stride[i];
+        }
+    };
+    // state: radiance 5 planes, every feature type its mean
+    const long long e3 = p0 * 3;
+    PairState st[6], fr[KA][6], f1[MA][2];
+    auto load3 = [&](const float *p, v2f (&d)[6]) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float4 v = *reinterpret_cast<const float4 *>(p + e3 + 4 * k);
+            d[2 * k] = v2f{v.x, v.y};
+            d[2 * k + 1] = v2f{v.z, v.w};
+        }
+    };
+    {
+        v2f d[6];
+#define STATMC_FUSED_LOAD(ptr, arr, field) load3(ptr, d); _Pragma("unroll") for (int j = 0; j < 6; j++) arr[j].field = d[j];
+        STATMC_FUSED_LOAD(r_mean, st, mean)
+        STATMC_FUSED_LOAD(r_m2, st, m2)
+        STATMC_FUSED_LOAD(r_m3, st, m3)
+        STATMC_FUSED_LOAD(r_fmean, st, fmean)
+        STATMC_FUSED_LOAD(r_fm2, st, fm2)
+#pragma unroll
+        for (int i = 0; i < K; i++) { STATMC_FUSED_LOAD(f_mean[1 + i], fr[i], mean) }
+#undef STATMC_FUSED_LOAD
+#pragma unroll
+        for (int i = 0; i < M; i++) {
+            const float4 v = *reinterpret_cast<const float4 *>(f_mean[1 + K + i] + p0);
+            f1[i][0].mean = v2f{v.x, v.y};
+            f1[i][1].mean = v2f{v.z, v.w};
+        }
+    }
+    // ONE: every type of the wave starts from the same count (all but films whose radiance has seen samples the features have
+    // not): one count conversion and one refined reciprocal per sample for all of them, else one per type.
+    auto walk = [&](auto one) {
+        // every earlier access of the wave to memory has completed before the counted waits start
+        acc_wait_vmcnt<0>();
+#pragma unroll
+        for (int d = 0; d < D; d++)
+            if (d < S) issue(d);
+        const int S_full = S >= D ? S - D + 1 : 0;          // samples s < S_full have D - 1 later rows in flight behind them
+        int slot = 0;
+#pragma unroll 1
+        for (int s = 0; s < S; s++) {
+            if (s < S_full) acc_wait_vmcnt<T * (D - 1)>(); else acc_wait_vmcnt<0>();
+            const float *mine = ring + slot * SLOT;
+            vfloat4 q[1 + K][3], q1[MA];
+#pragma unroll
+            for (int i = 0; i <= K; i++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) q[i][k] = *reinterpret_cast<const vfloat4 *>(mine + 768 * i + 12 * lane + 4 * k);
+#pragma unroll
+            for (int i = 0; i < M; i++) q1[i] = *reinterpret_cast<const vfloat4 *>(mine + 768 * (1 + K) + 256 * i + 4 * lane);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
+            if (s + D < S) issue(slot);
+            v2f nf[NT], rc[NT];
+            if constexpr (decltype(one)::value) {
+                const float nf0 = (float)(nb[0] + s + 1);
+                const float rc0 = refined_rcp(nf0);
+#pragma unroll
+                for (int i = 0; i < NT; i++) { nf[i] = v2f{nf0, nf0}; rc[i] = v2f{rc0, rc0}; }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NT; i++) {
+                    const float nfi = (float)(nb[i] + s + 1);
+                    const float rci = refined_rcp(nfi);
+                    nf[i] = v2f{nfi, nfi};
+                    rc[i] = v2f{rci, rci};
+                }
+            }
+            // the feature types first (their temporaries are few), then the radiance type
+#pragma unroll
+            for (int i = 0; i < M; i++) {
+                const v2f nf2[2] = {nf[1 + K + i], nf[1 + K + i]}, rc2[2] = {rc[1 + K + i], rc[1 + K + i]};
+                const v2f smp2[2] = {v2f{q1[i][0], q1[i][1]}, v2f{q1[i][2], q1[i][3]}};
+                add_sample2<2, 1, false>(f1[i], nf2, rc2, smp2);
+            }
+            auto fold3 = [&](PairState *state, int i, auto radiance) {
+                const v2f nf3[3] = {nf[i], nf[i], nf[i]}, rc3[3] = {rc[i], rc[i], rc[i]};
+                v2f smp2[6];
+#pragma unroll
+                for (int j = 0; j < 6; j++) smp2[j] = v2f{q[i][j >> 1][2 * (j & 1)], q[i][j >> 1][2 * (j & 1) + 1]};
+#pragma unroll
+                for (int g = 0; g < 6; g += kAccPairGroup) {
+                    if constexpr (decltype(radiance)::value) add_sample2<kAccPairGroup, 3, true>(state + g, nf3, rc3, smp2 + g);
+                    else add_sample2<kAccPairGroup, 1, false>(state + g, nf3, rc3, smp2 + g);
+                }
+            };
+#pragma unroll
+            for (int i = 0; i < K; i++) fold3(fr[i], 1 + i, std::false_type{});
+            fold3(st, 0, std::true_type{});
+            slot = slot + 1 == D ? 0 : slot + 1;
+        }
+    };
+    if (__builtin_amdgcn_ballot_w64(active && !lane_one) == 0) walk(std::true_type{});
+    else walk(std::false_type{});
+    if (!active) return;                                    // nothing of an inactive lane is stored
+    auto store3 = [&](float *p, const v2f (&d)[6]) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const vfloat4 v = {d[2 * k].x, d[2 * k].y, d[2 * k + 1].x, d[2 * k + 1].y};
+            *reinterpret_cast<vfloat4 *>(p + e3 + 4 * k) = v;
+        }
+    };
+    {
+        v2f d[6];
+#define STATMC_FUSED_STORE(ptr, arr, field) _Pragma("unroll") for (int j = 0; j < 6; j++) d[j] = arr[j].field; store3(ptr, d);
+        STATMC_FUSED_STORE(r_mean, st, mean)
+        STATMC_FUSED_STORE(r_m2, st, m2)
+        STATMC_FUSED_STORE(r_m3, st, m3)
+        STATMC_FUSED_STORE(r_fmean, st, fmean)
+        STATMC_FUSED_STORE(r_fm2, st, fm2)
+#pragma unroll
+        for (int i = 0; i < K; i++) { STATMC_FUSED_STORE(f_mean[1 + i], fr[i], mean) }
+#undef STATMC_FUSED_STORE
+#pragma unroll
+        for (int i = 0; i < M; i++) {
+            const vfloat4 v = {f1[i][0].mean.x, f1[i][0].mean.y, f1[i][1].mean.x, f1[i][1].mean.y};
+            *reinterpret_cast<vfloat4 *>(f_mean[1 + K + i] + p0) = v;
+        }
+    }
+    // Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
+    typedef int vint4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int i = 0; i < NT; i++) {
+        const vint4 n_out = {nb[i] + S, nb[i] + S, nb[i] + S, nb[i] + S};
+        *reinterpret_cast<vint4 *>(n_ptr[i] + p0) = n_out;
+    }
+    // the radiance type's optional pre-pass epilogue, as in accumulate_lane (the four pixels hold one count: one quantile)
+    if (pre_mc != nullptr) {
+        const int n_out = nb[0] + S;
+        const float tq = (pre_flags & 1) ? 1.f : t_quantile(pre_table, n_out - 1);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            vfloat4 mc, dc;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int e = 4 * k + j;
+                float m, d;
+                prepass_elem(n_out, tq, st[e >> 1].mean[e & 1], st[e >> 1].m2[e & 1], st[e >> 1].m3[e & 1], m, d, (pre_flags & 2) != 0);
+                mc[j] = m;
+                dc[j] = d;
+            }
+            *reinterpret_cast<vfloat4 *>(pre_mc + e3 + 4 * k) = mc;
+            *reinterpret_cast<vfloat4 *>(pre_dc + e3 + 4 * k) = dc;
+        }
+    }
+}
+
+// A resident grid: every workgroup walks 256-group units with a grid stride, its four waves 64 consecutive groups each, every
+// pass covering every type.  One wave per SIMD (the ring of the 11-channel set at three rows is 132 KiB per workgroup).
+template <int K, int M, int D>
+__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_kernel(AccumulateFusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float acc_lds[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float *ring = acc_lds + wave * (D * acc_fused_slot_floats(K, M));
+    for (long long gw = (long long)blockIdx.x * kBlock + wave * 64; gw < a.n_groups; gw += (long long)gridDim.x * kBlock) {
+        const long long left = a.n_groups - gw;
+        accumulate_fused_wave<K, M, D>(a, gw, left >= 64 ? 64 : (int)left, ring);
+    }
+}
+
+// The launches the fused walk serves: exactly one RGB type with the transform and three moments, K <= 2 mean-only RGB types,
+// M <= 2 mean-only 1-channel types, K + M >= 1, in any order; the same pixels and the same batch length in every type.
+static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &f, int &K, int &M) {
+    K = M = 0;
+    if (a.n_types < 2 || a.n_types > kAccFusedTypes) return false;
+    const long long n_px = a.t[0].n_elems / a.t[0].channels;
+    const int S = a.t[0].n_samples;
+    if (S < 1 || n_px < 4 || n_px % 4 != 0) return false;
+    int rad = -1, rgb[2] = {0, 0}, f1[2] = {0, 0};
+    for (int i = 0; i < a.n_types; i++) {
+        const AccumulateType &t = a.t[i];
+        if (t.n_elems / t.channels != n_px || t.n_samples != S) return false;
+        if (t.channels == 3 && t.transform && t.max_moment >= 3) {
+            if (rad >= 0) return false;
+            rad = i;
+        } else if (!t.transform && t.max_moment == 1 && t.channels == 3) {
+            if (K == 2) return false;
+            rgb[K++] = i;
+        } else if (!t.transform && t.max_moment == 1 && t.channels == 1) {
+            if (M == 2) return false;
+            f1[M++] = i;
+        } else {
+            return false;
+        }
+    }
+    if (rad < 0 || K + M < 1) return false;
+    f = AccumulateFusedArgs{};
+    f.t[0] = a.t[rad];
+    for (int i = 0; i < K; i++) f.t[1 + i] = a.t[rgb[i]];
+    for (int i = 0; i < M; i++) f.t[1 + K + i] = a.t[f1[i]];
+    f.n_groups = n_px / 4;
+    f.n_samples = S;
+    return true;
+}
+
+template <int K, int M>
+static hipError_t launch_accumulate_fused_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
+    constexpr size_t lds = acc_fused_lds_bytes(K, M, kAccFusedD);
+    const void *fn = reinterpret_cast<const void *>(&accumulate_fused_kernel<K, M, kAccFusedD>);
+    // more dynamic LDS than a launch may ask for by default: allowed once per device (and thread)
+    static thread_local unsigned long long allowed = 0;
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !((allowed >> dev) & 1)) {
+        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) allowed |= 1ull << dev;
+    }
+    hipLaunchKernelGGL((accumulate_fused_kernel<K, M, kAccFusedD>), dim3(blocks), dim3(kBlock), lds, s, f);
+    return hipGetLastError();
+}
+
+static hipError_t launch_accumulate_fused(const AccumulateFusedArgs &f, int K, int M, unsigned blocks, hipStream_t s) {
+    switch (3 * K + M) {
+    case 1: return launch_accumulate_fused_km<0, 1>(f, blocks, s);
+    case 2: return launch_accumulate_fused_km<0, 2>(f, blocks, s);
+    case 3: return launch_accumulate_fused_km<1, 0>(f, blocks, s);
+    case 4: return launch_accumulate_fused_km<1, 1>(f, blocks, s);
+    case 5: return launch_accumulate_fused_km<1, 2>(f, blocks, s);
+    case 6: return launch_accumulate_fused_km<2, 0>(f, blocks, s);
+    case 7: return launch_accumulate_fused_km<2, 1>(f, blocks, s);
+    case 8: return launch_accumulate_fused_km<2, 2>(f, blocks, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 static thread_local unsigned g_last_acc_grid = 0;
+static thread_local int g_last_acc_fused = 0;
 unsigned last_accumulate_grid() { return g_last_acc_grid; }   // workgroups of the calling thread's last film-major launch (tests)
+int last_accumulate_fused() { return g_last_acc_fused; }      // ... and whether it ran the type-fused walk
 
 hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
     AccumulateArgs a = a_in;
@@ -718,11 +1062,45 @@ hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
     // Only there: at 128 samples a tie, at 64 slower (1.044 against 1.016 ms); 1280 x 720, 2560 x 1440 (14.06 walks per workgroup: the
     // fifteenth is nearly empty) and 3840 x 2160 slower by 2 - 6 % (profiles/r06_ab_resident_spp.log).  So: the film's groups must fill the
     // workgroups' last walk (>= 97 %), and the film must be of about that size.
+    const int resident_asked = a.resident_blocks;
     if (a.resident_blocks == 0 && a.grid_mode < 0 && a.apart && a.cus > 0 && max_s >= 256 && max_groups >= (1 << 18) && max_groups < 3 * (1 << 18)) {
         const double walks = (double)max_groups / ((double)a.cus * kBlock);
         if (walks / ceil(walks) >= 0.97) a.resident_blocks = a.cus;
     }
     if (a.resident_blocks < 0) a.resident_blocks = 0;
+    // The type-fused walk (accumulate_fused_kernel): a resident grid of its own, every workgroup covering every type of its groups in
+    // one pass.  By shape (a.fused = 0) it stands wherever the resident grid above stands, and, measured against whatever launch the
+    // rules of this function choose otherwise (tools/time_accumulate_fused.py, six alternating pairs per process, the accumulation
+    // in the step, ms fused / per type; profiles/accumulate_fused.jsonl), on uniformly random samples first: 1080p, 256 samples, placed
+    // 3.65 - 3.66 / 3.76 in three processes, the filter behind it 1.55 / 1.59; torch's allocator 3.71 - 3.74 / 3.99; 128 samples 1.89 / 1.99
+    // placed, 1.97 / 2.12 unplaced; the 9-channel set 3.00 / 3.16 and 1.56 / 1.64; 1600 x 900 2.71 / 2.83; 1280 x 720 1.64 - 1.72 / 1.74 -
+    // 1.84 (128 samples 0.85 / 0.89); 960 x 540 0.90 / 1.02 -- every pair of every one a win, the median gain 3.7 - 16 x the larger spread.
+    // Not at 96 samples (1.43 / 1.46, inside the spread), 64 and 16 (level), 2048 x 1152 (4.24 / 4.29, every pair but 2.9 x the spread),
+    // 2560 x 1440 (level) or 4K at 64 and 16 samples (1 - 2 % slower).  Then every one of the shapes taken once more on the sample stream
+    // bench.py times (synthetic.Scene, the tool's default since), one box, one process each (two at the headline): 1080p / 256 placed
+    // 3.51 / 3.61 (uniform samples in the same call: 3.51 / 3.61 -- the stream makes no difference, the box does), unplaced 3.74 / 3.99,
+    // 128 samples 1.83 / 1.91 and 1.96 / 2.11, 9 channels 2.87 / 3.04 and 1.55 / 1.63, 900p 2.56 / 2.73, 720p 1.63 / 1.74, 0.82 / 0.86 at 128,
+    // 1.67 / 1.74 unplaced, 540p 0.88 / 0.97: again every pair, 3.8 - 12 x the spread.  (64 samples and 2048 x 1152 also won there, 5.4 x and
+    // 3.4 x: one box against one, left as they are.)  So: from 128 samples per launch up on films of 960 x 540 to 1920 x 1080, whatever
+    // the allocator.  What these pairs do NOT settle is the size of the gain between processes: bench.py on the parent build against
+    // this one is ahead in every alternating pair (eleven, three sessions) but by 0.3 - 2.1 % of the step, under the 3 x spread margin in each
+    // session.
+    // a.fused = 1 (statmc_debug_accumulate_fused): every eligible launch, min(CUs, units) workgroups or the number asked for; never with
+    // statmc_debug_accumulate_resident_blocks(-1), with the LDS-DMA walk switched off, or on unaligned films.
+    g_last_acc_fused = 0;
+    if (a.fused >= 0 && resident_asked >= 0 && vec && a.dma) {
+        const bool by_shape = a.fused == 0 && resident_asked == 0 && a.grid_mode < 0 && a.cus > 0 &&
+                              (a.resident_blocks > 0 || (max_s >= 128 && max_groups >= 128000 && max_groups < (1 << 19)));
+        AccumulateFusedArgs f;
+        int K = 0, M = 0;
+        if ((by_shape || a.fused == 1) && accumulate_fused_plan(a, f, K, M)) {
+            const long long most = a.cus > 0 && a.cus < units ? a.cus : units;
+            const unsigned blocks = resident_asked > 0 ? (unsigned)resident_asked : a.resident_blocks > 0 ? (unsigned)a.resident_blocks : (unsigned)most;
+            g_last_acc_grid = blocks;
+            g_last_acc_fused = 1;
+            return launch_accumulate_fused(f, K, M, blocks, s);
+        }
+    }
     if (a.grid_mode < 0) {
         const bool big = max_groups >= (1 << 20);
         if (a.apart) a.grid_mode = (max_s <= 16 || big || max_s >= 128) ? 1 : 0;

@@ -422,6 +422,28 @@ int statmc_accumulate_rows(uint16_t width, uint16_t height, const statmc_stat_ty
 int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                                  const int32_t *ranges, int n_ranges, void *stream);
 
+/* ---- sample arenas in the format the renderer holds them in.  sample_formats[t] says what types[t].samples points to:
+ * STATMC_SAMPLES_F32, today's arenas, or STATMC_SAMPLES_F16, IEEE binary16, two bytes per element, in the same
+ * [n_samples][height][width][channels] order, tightly packed.  sample_formats == NULL: every type is fp32.  ranges / n_ranges as
+ * in statmc_accumulate_row_ranges; NULL / 0: the whole film (n_types x max(n_ranges, 1) <= 16).  statmc_stat_type itself does not
+ * change: only the meaning of `samples` follows the type's format.
+ * The call leaves, bit for bit, what statmc_accumulate (_rows, _row_ranges) leaves when given the same samples widened to fp32:
+ * n, every moment, the film chain and the optional mean_corr / discriminator epilogue.  Every finite half widens to fp32 exactly,
+ * subnormals included; the widening happens in registers on the way into the fold, the arena is read once and nothing is
+ * allocated.  +-inf and NaN do what the fp32 path does with their widened values (not promised bit for bit).  With every format
+ * fp32 the call IS the existing one: the same launch.
+ * What the caller gives up is decided before the call: a value above 65504 is already inf in the caller's half, and values below
+ * 6e-8 are 0 there.  Keep radiance in fp32 unless the renderer clamps it; normals, albedo, depth and material ids -- bounded,
+ * low-precision quantities -- are the natural candidates for half (44 -> 28 bytes per sample of the 11-channel set, 22 all half).
+ * Any 2-byte aligned half arena and any film size are accepted; arenas at 8-byte alignment (fp32 ones and the state images at
+ * 16) on films whose pixel count is a multiple of 4 take the vector path, everything else goes element by element -- the same
+ * bits.  STATMC_ERR_INVALID, before any launch: a format other than the two (statmc_last_error() names sample_formats), a 16-bit
+ * arena at an odd address, the limits of statmc_accumulate_row_ranges.  STATMC_ERR_NO_DEVICE before statmc_setup. */
+#define STATMC_SAMPLES_F32 0
+#define STATMC_SAMPLES_F16 1
+int statmc_accumulate_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
+                              int n_types, const int32_t *ranges, int n_ranges, void *stream);
+
 /* The same accumulation fed tile by tile, the way StatPathIntegrator::Render produces samples
  * (src/statistics/statpath.cpp:132-190: 16 x 16 tiles; 355-371: every sample of a pixel is handed to
  * the tile of every stat type; 381-388: Merge*Tiles once per tile and iteration).  Every type's

@@ -40,6 +40,9 @@ int statmc_debug_last_accumulate_grid(void);
 int statmc_debug_accumulate_fused(int mode);
 /* 1 if the calling thread's last statmc_accumulate launch ran the type-fused walk, else 0. */
 int statmc_debug_last_accumulate_fused(void);
+/* How the calling thread's last film-major launch read its 16-bit arenas (statmc_accumulate_formats): 0 = it had none, 1 = the
+ * vector path (8-byte pieces per lane, or the type-fused walk's LDS-DMA rows), 2 = the element-by-element fallback. */
+int statmc_debug_last_accumulate_loader(void);
 /* 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers (same bits).  Any other value:
  * STATMC_ERR_INVALID. */
 int statmc_debug_accumulate_dma(int on);

@@ -1125,6 +1125,34 @@ class Estimator {
         check(statmc_accumulate_records(width, height, types.data(), (int)types.size(), d_pixels, n_records, stream.handle()));
     }
 
+    // ---- whole-film sample arenas, in the format the renderer holds them in (statmc_accumulate_formats, include/statmc.h)
+    // Per listed (type, bounce) an arena [nSamples][height][width][channels of the type] on this Estimator's device: fp32
+    // (format STATMC_SAMPLES_F32) or IEEE half (STATMC_SAMPLES_F16: the bits of the same samples widened to fp32 -- the natural
+    // format for normals, albedo, depth and ids; radiance only where the renderer clamps it below 65504).  Every pixel's samples
+    // are folded in ascending sample index: the bits Merge*Tile(s) leave for the same samples in that order.  Needs
+    // EnableDeviceAccumulation(); samples staged by Merge*Tile(s) so far are flushed first; one launch on DeviceStream(), so the
+    // arenas must stay valid and unchanged until work enqueued there behind this call has run.  withPrepass as in
+    // AccumulateRecords.  At most 16 buffers per call.
+    struct FilmSamples {
+        unsigned char statTypeIndex, bounceIndex;
+        const void *d_samples;
+        int format;
+        bool withPrepass = false;
+    };
+    void AccumulateFilm(int nSamples, const std::vector<FilmSamples> &buffers) {
+        std::vector<statmc_stat_type> types;
+        std::vector<int32_t> formats;
+        for (const FilmSamples &b : buffers) {
+            statmc_stat_type t = DeviceStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
+            t.samples = static_cast<const float *>(b.d_samples);
+            t.n_samples = nSamples;
+            types.push_back(t);
+            formats.push_back(b.format);
+        }
+        check(statmc_set_device(device));
+        check(statmc_accumulate_formats(width, height, types.data(), formats.data(), (int)types.size(), nullptr, 0, stream.handle()));
+    }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     size_t flushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nFlushes; }

@@ -63,6 +63,7 @@ class PlacementInfo(C.Structure):
 
 
 MEM_STATE, MEM_STREAM = 0, 1
+SAMPLES_F32, SAMPLES_F16 = 0, 1     # statmc_accumulate_formats: what a stat type's sample arena holds
 
 
 class StatType(C.Structure):
@@ -102,7 +103,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -176,6 +177,9 @@ def load():
     lib.statmc_accumulate.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p]
     lib.statmc_accumulate_rows.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.statmc_accumulate_row_ranges.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+    lib.statmc_accumulate_formats.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                              C.c_void_p]
+    lib.statmc_debug_last_accumulate_loader.restype = C.c_int
     lib.statmc_accumulate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]
     lib.statmc_accumulate_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
@@ -254,6 +258,12 @@ def accumulate_resident_blocks(n):
 def accumulate_dma(on):
     """1 (default): the RGB sample planes of the accumulation stream through LDS-DMA; 0: loads into registers (A/B, tests)."""
     check(load().statmc_debug_accumulate_dma(int(on)))
+
+
+def last_accumulate_loader():
+    """How the calling thread's last film-major accumulation read its 16-bit arenas: 0 it had none, 1 the vector path, 2 element by
+    element."""
+    return int(load().statmc_debug_last_accumulate_loader())
 
 
 def accumulate_fused(mode):
@@ -434,7 +444,7 @@ def empty_placed(shape, dtype, device, role):
     """torch tensor on `device` in memory placed by HBM rank (include/statmc.h: statmc_malloc_placed): role MEM_STATE for
     the images a launch reads and writes (the running moments), MEM_STREAM for read-once sample arenas.  Uninitialised."""
     import torch
-    typestr = {torch.float32: "<f4", torch.int32: "<i4", torch.uint8: "|u1", torch.int64: "<i8"}[dtype]
+    typestr = {torch.float32: "<f4", torch.float16: "<f2", torch.int32: "<i4", torch.uint8: "|u1", torch.int64: "<i8"}[dtype]
     n = 1
     for d in shape:
         n *= int(d)
@@ -604,12 +614,24 @@ def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_
     return t
 
 
-def accumulate(width, height, stat_types, stream=None, rows=None):
+def accumulate(width, height, stat_types, stream=None, rows=None, sample_formats=None):
     """rows = (y0, y1): only those rows of the film (statmc_accumulate_rows); rows = [(y0, y1), ...]: several disjoint
-    ranges in one launch (statmc_accumulate_row_ranges)."""
+    ranges in one launch (statmc_accumulate_row_ranges).  sample_formats = [SAMPLES_F32 | SAMPLES_F16, ...], one per stat
+    type: what each type's sample arena holds (statmc_accumulate_formats)."""
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
     st = stream if stream is not None else current_stream_handle()
-    if rows is None:
+    if sample_formats is not None:
+        if len(sample_formats) != len(stat_types):
+            raise ValueError("accumulate: one sample format per stat type")
+        fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
+        if rows is None:
+            flat, n_ranges = None, 0
+        else:
+            if len(rows) == 2 and not hasattr(rows[0], "__len__"):
+                rows = [rows]
+            flat, n_ranges = (C.c_int32 * (2 * len(rows)))(*[int(v) for r in rows for v in r]), len(rows)
+        check(load().statmc_accumulate_formats(width, height, arr, fmts, len(stat_types), flat, n_ranges, st))
+    elif rows is None:
         check(load().statmc_accumulate(width, height, arr, len(stat_types), st))
     elif len(rows) == 2 and not hasattr(rows[0], "__len__"):
         check(load().statmc_accumulate_rows(width, height, arr, len(stat_types), int(rows[0]), int(rows[1]), st))

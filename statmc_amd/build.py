@@ -93,10 +93,12 @@ RENDER_SIM_BIN = os.path.join(ROOT, "tools", "bin", "statmc_render_sim")
 CV_ADAPTOR_BIN = os.path.join(ROOT, "tools", "bin", "test_cv_adaptor")   # tests/cpp/test_cv_adaptor.cpp: include/statmc_cv.hpp in use
 DEVICE_ACC_BIN = os.path.join(ROOT, "tools", "bin", "test_device_accumulate")   # tests/cpp/test_device_accumulate.cpp: Estimator::DeviceStatistics
 ACC_RECORDS_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records")   # tests/cpp/test_accumulate_records.cpp: Estimator::AccumulateRecords
+ACC_FILM_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_film")   # tests/cpp/test_accumulate_film.cpp: Estimator::AccumulateFilm
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
-         ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp")}
+         ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp"),
+         ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")

@@ -1197,8 +1197,39 @@ int statmc_accumulate_rows(uint16_t width, uint16_t height, const statmc_stat_ty
 }
 // Several disjoint row ranges in ONE launch (the two border strips of a block: a 20-row launch on its own is bound by the
 // latency of its few waves, two of them together cost what one costs).
+static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
+                                      const int32_t *ranges, int n_ranges, void *stream);
 int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *ranges,
                                  int n_ranges, void *stream) {
+    return accumulate_row_ranges_impl(width, height, types, nullptr, n_types, ranges, n_ranges, stream);
+}
+// Samples in the format the renderer holds them in.  Everything that can be refused is refused before the device is looked at.
+int statmc_accumulate_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                              const int32_t *ranges, int n_ranges, void *stream) {
+    const int32_t whole[2] = {0, height};
+    if (!ranges || n_ranges == 0) {
+        if (n_ranges != 0) return fail(STATMC_ERR_INVALID, "n_ranges = %d without ranges", n_ranges);
+        ranges = whole;
+        n_ranges = 1;
+    }
+    if (!sample_formats) return statmc_accumulate_row_ranges(width, height, types, n_types, ranges, n_ranges, stream);   // the existing call
+    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_types x row ranges must be in [0,%d]", statmc::kMaxStatTypes);
+    bool any_half = false;
+    for (int i = 0; i < n_types; i++) {
+        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
+            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
+        any_half = any_half || sample_formats[i] == STATMC_SAMPLES_F16;
+    }
+    if (!any_half) return statmc_accumulate_row_ranges(width, height, types, n_types, ranges, n_ranges, stream);        // the existing call
+    if (!types) return fail(STATMC_ERR_INVALID, "null types");
+    for (int i = 0; i < n_types; i++)
+        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
+            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
+    return accumulate_row_ranges_impl(width, height, types, sample_formats, n_types, ranges, n_ranges, stream);
+}
+static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
+                                      const int32_t *ranges, int n_ranges, void *stream) {
     NEED_READY();
     if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
     if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
@@ -1218,7 +1249,9 @@ int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_s
             statmc::AccumulateType &d = k.t[k.n_types];
             if (int rc = fill_stat_type(dstate, types[i], i, width, height, true, d)) return rc;
             const long long px0 = (long long)y0 * width, e0 = px0 * d.channels;
-            if (d.samples) d.samples += e0;
+            const bool half = formats && formats[i] == STATMC_SAMPLES_F16;
+            if (d.samples) d.samples = half ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(d.samples) + e0) : d.samples + e0;
+            if (half) k.half_mask |= 1 << k.n_types;
             d.n += px0;
             d.mean += e0;
             if (d.m2) d.m2 += e0;
@@ -1593,6 +1626,7 @@ int statmc_debug_accumulate_fused(int mode) {   // the type-fused walk: 0 by sha
     STATMC_DEBUG_SET(d.acc_fused = mode);
 }
 int statmc_debug_last_accumulate_fused(void) { return statmc::last_accumulate_fused(); }
+int statmc_debug_last_accumulate_loader(void) { return statmc::last_accumulate_loader(); }
 int statmc_debug_accumulate_dma(int on) {   // 1 (default): RGB sample planes stream through LDS-DMA; 0: loads into registers
     if (on != 0 && on != 1) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_dma(%d): 0 or 1", on);
     STATMC_DEBUG_SET(d.acc_dma = on);

@@ -61,6 +61,9 @@ struct AccumulateArgs {
     // the type-fused walk (launch_accumulate): 0 by shape, 1 whenever the launch is eligible, -1 never (statmc_debug_accumulate_fused);
     // read by the host only, and last so that the fields before it keep their kernel-argument offsets
     int fused;
+    // statmc_accumulate_formats: bit i = t[i].samples is an IEEE-half arena (n_elems and stride still count elements).  Read by
+    // accumulate_half_kernel alone; it takes the padding behind `fused`, so the argument keeps its size.
+    int half_mask;
 };
 
 // samples of every type arrive tile by tile: AccumulateType::samples is the type's arena, tile k's
@@ -261,6 +264,7 @@ hipError_t launch_mean_vars(const MeanVarsArgs &a, hipStream_t s);
 hipError_t launch_accumulate(const AccumulateArgs &a, hipStream_t s);
 unsigned last_accumulate_grid();
 int last_accumulate_fused();         // 1: the calling thread's last film-major launch ran the type-fused walk
+int last_accumulate_loader();        // that launch's 16-bit arenas: 0 it had none, 1 the vector path, 2 element by element
 hipError_t launch_accumulate_tiles(const AccumulateTilesArgs &a, hipStream_t s);
 hipError_t launch_merge_tiles(const MergeTilesArgs &a, int n_tiles, int max_tile_pixels, hipStream_t s);
 hipError_t launch_tile_moments(const TileMomentsArgs &a, hipStream_t s);

@@ -306,11 +306,17 @@ __device__ __forceinline__ void add_sample2(PairState *st, const v2f *nf, const 
 // lane fetches belongs to another lane's pixels -- so the whole wave calls in: lane l owns the 4-pixel group at
 // sp_wave + 12 l floats, `active` says whether that group exists, `n_active` (wave-uniform) how many lanes' groups do
 // (they are the first n_active lanes).  Without DMA an inactive lane returns at once.
-template <int C, int MAXM, bool TRANSFORM, int UMUL = 1, int DMA = 0>
-__device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long long p0_in, const float *sp,
+// ST: what the arena holds -- float, or _Float16 (statmc_accumulate_formats): the lane's piece of a half row is 8 C bytes at
+// 8-byte alignment, widened with one v_cvt_f32_f16 per element on its way into the same q[C] (every finite half is an fp32
+// value, subnormals included: the fold sees what it would see had the caller widened the arena).  Register loads only.
+typedef _Float16 vhalf4 __attribute__((ext_vector_type(4)));
+template <int C, int MAXM, bool TRANSFORM, int UMUL = 1, int DMA = 0, typename ST = float>
+__device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long long p0_in, const ST *sp,
                                                 long long stride, int S, float *ring = nullptr, bool active = true, int n_active = 64,
                                                 bool dma_first = false) {
     constexpr bool kDma = DMA > 0 && C == 3;
+    constexpr bool kHalf = !std::is_same<ST, float>::value;
+    static_assert(!(kDma && kHalf), "the LDS-DMA walk of accumulate_lane reads fp32 rows");
     constexpr int kD = DMA > 0 ? DMA : 1;               // ring depth: sample rows in flight
     if constexpr (!kDma) {
         if (!active) return;
@@ -331,7 +337,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     };
     if constexpr (kDma) {
         const int lane = threadIdx.x & 63;
-        dma_row0 = sp - 12 * lane;                          // the wave's row of sample 0 (lane l sits 12 l floats in; the same value in every lane)
+        dma_row0 = reinterpret_cast<const float *>(sp) - 12 * lane;                          // the wave's row of sample 0 (lane l sits 12 l floats in; the same value in every lane)
         const int row_floats = 12 * n_active;               // the part of the wave's row that exists
         // Every lane issues all three transfers of a row, whatever part of the row exists: the waits of the walk COUNT
         // transfers (vmcnt), so their number per row must not depend on n_active.  A piece beyond the row's end re-reads the
@@ -379,11 +385,21 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     // re-fetch the shared lines: 4.8 vs 6.4 TB/s, tools/microbench/hbm_read.hip).  C = 1
     // streams with non-temporal loads.
     constexpr int U = UMUL * (C == 3 ? (TRANSFORM ? kAccURgbT : kAccURgb) : kAccUF);
-    auto load_sample = [&](vfloat4 (&dst)[C], const float *src) {
+    auto load_sample = [&](vfloat4 (&dst)[C], const ST *src) {
+        if constexpr (kHalf) {
+            vhalf4 h[C];
 #pragma unroll
-        for (int k = 0; k < C; k++)
-            dst[k] = C == 1 ? __builtin_nontemporal_load(reinterpret_cast<const vfloat4 *>(src + 4 * k))
-                            : *reinterpret_cast<const vfloat4 *>(src + 4 * k);
+            for (int k = 0; k < C; k++)
+                h[k] = C == 1 ? __builtin_nontemporal_load(reinterpret_cast<const vhalf4 *>(src + 4 * k))
+                              : *reinterpret_cast<const vhalf4 *>(src + 4 * k);
+#pragma unroll
+            for (int k = 0; k < C; k++) dst[k] = __builtin_convertvector(h[k], vfloat4);
+        } else {
+#pragma unroll
+            for (int k = 0; k < C; k++)
+                dst[k] = C == 1 ? __builtin_nontemporal_load(reinterpret_cast<const vfloat4 *>(src + 4 * k))
+                                : *reinterpret_cast<const vfloat4 *>(src + 4 * k);
+        }
     };
     // SAME: the lane's 4 pixels hold the same count (every film whose pixels have seen the
     // same number of samples, i.e. all but adaptively sampled ones) -> one count conversion and
@@ -429,7 +445,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
             for (int u = 0; u < U; u++) load_sample(cur[u], sp + (long long)u * stride);
         }
         for (int s = 0; s < S_main; s += U) {
-            const float *np = sp + (long long)(s + U) * stride;
+            const ST *np = sp + (long long)(s + U) * stride;
             if (s + U < S_main) {
 #pragma unroll
                 for (int u = 0; u < U; u++) load_sample(nxt[u], np + (long long)u * stride);
@@ -537,8 +553,8 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
 
 // One pixel, scalar accesses: unaligned images, ragged ends, tiles whose rows do not split into
 // 4-pixel groups.  Sample s of channel c is at sp[s * stride + c].
-template <int C, int MAXM, bool TRANSFORM>
-__device__ __forceinline__ void accumulate_pixel(const AccumulateType &t, long long p, const float *sp,
+template <int C, int MAXM, bool TRANSFORM, typename ST = float>
+__device__ __forceinline__ void accumulate_pixel(const AccumulateType &t, long long p, const ST *sp,
                                                  long long stride, int S) {
     const int n0 = t.n[p];
     float *const pre_mc = MAXM >= 3 ? t.mean_corr : nullptr;      // (read before the first store: see accumulate_lane)
@@ -550,7 +566,7 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateType &t, long l
                         TRANSFORM ? t.film_mean[e] : 0.f, TRANSFORM ? t.film_m2[e] : 0.f};
         for (int s = 0; s < S; s++) {
             const float nf = (float)(n0 + s + 1);
-            add_sample<MAXM, TRANSFORM>(st, nf, refined_rcp(nf), sp[(long long)s * stride + c]);
+            add_sample<MAXM, TRANSFORM>(st, nf, refined_rcp(nf), (float)sp[(long long)s * stride + c]);
         }
         t.mean[e] = st.mean;
         if (MAXM >= 2) t.m2[e] = st.m2;
@@ -572,8 +588,9 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateType &t, long l
 
 // Film-major batch: one lane owns 4 consecutive PIXELS of one stat type and walks the batch's
 // samples in order (sample s of pixel p, channel c is at samples[s*n_elems + p*C + c]).
-template <int C, int MAXM, bool TRANSFORM, bool VEC, int UMUL, int DMA>
+template <int C, int MAXM, bool TRANSFORM, bool VEC, int UMUL, int DMA, typename ST = float>
 __device__ __forceinline__ void accumulate_type(const AccumulateType &t, long long blk, long long nblk, float *ring, bool dma_first) {
+    const ST *const samples = reinterpret_cast<const ST *>(t.samples);   // (t.stride and t.n_elems count elements, whatever their width)
     const long long n_px = t.n_elems / C;
     const long long n_groups = (n_px + 3) >> 2;
     const long long n_full = VEC ? (n_px >> 2) : 0;          // complete 4-pixel groups: the vector path's share
@@ -586,25 +603,25 @@ __device__ __forceinline__ void accumulate_type(const AccumulateType &t, long lo
         const long long left = n_full - gw;
         const int n_active = left >= 64 ? 64 : left > 0 ? (int)left : 0;
         if (n_active > 0)
-            accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA>(t, p0, t.samples + p0 * C, t.stride, t.n_samples,
-                                                                                            ring, active, n_active, dma_first);
+            accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA, ST>(t, p0, samples + p0 * C, t.stride, t.n_samples,
+                                                                                                ring, active, n_active, dma_first);
         if (!active && g < n_groups) {   // unaligned images, the ragged last group
             for (long long p = p0; p < n_px && p < p0 + 4; p++)
-                accumulate_pixel<C, MAXM, TRANSFORM>(t, p, t.samples + p * C, t.stride, t.n_samples);
+                accumulate_pixel<C, MAXM, TRANSFORM, ST>(t, p, samples + p * C, t.stride, t.n_samples);
         }
     }
 }
 
-template <int C, bool VEC, int UMUL, int DMA>
+template <int C, bool VEC, int UMUL, int DMA, typename ST = float>
 __device__ __forceinline__ void accumulate_dispatch(const AccumulateType &t, long long blk, long long nblk, float *ring, bool dma_first) {
     if (t.transform) {
-        if (t.max_moment >= 3) accumulate_type<C, 3, true, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
-        else if (t.max_moment == 2) accumulate_type<C, 2, true, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
-        else accumulate_type<C, 1, true, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
+        if (t.max_moment >= 3) accumulate_type<C, 3, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
+        else if (t.max_moment == 2) accumulate_type<C, 2, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
+        else accumulate_type<C, 1, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
     } else {
-        if (t.max_moment >= 3) accumulate_type<C, 3, false, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
-        else if (t.max_moment == 2) accumulate_type<C, 2, false, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
-        else accumulate_type<C, 1, false, VEC, UMUL, DMA>(t, blk, nblk, ring, dma_first);
+        if (t.max_moment >= 3) accumulate_type<C, 3, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
+        else if (t.max_moment == 2) accumulate_type<C, 2, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
+        else accumulate_type<C, 1, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
     }
 }
 
@@ -658,6 +675,29 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
     else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
 }
 
+// Launches in which at least one type's arena is IEEE half (statmc_accumulate_formats; a.half_mask: bit i = type i) and which the
+// type-fused walk below does not take: a kernel of its own, so that accumulate_kernel stays the code object it was.  Register
+// loads for every type, the two launch shapes that need no slot table: a resident grid walking every type, or one pass per
+// workgroup with the types round-robin.  VEC = false: every pixel through accumulate_pixel (unaligned arenas, pixel counts
+// that are no multiple of 4).
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void accumulate_half_kernel(AccumulateArgs a) {
+    const bool resident = a.resident_blocks > 0;
+    const int n_walks = resident ? a.n_types : 1;
+    for (int i = 0; i < n_walks; i++) {
+        const int ti = ((int)blockIdx.x + i) % a.n_types;
+        const AccumulateType t = a.t[ti];                                      // (a copy: see accumulate_kernel)
+        const long long blk = resident ? blockIdx.x : blockIdx.x / a.n_types, nblk = resident ? gridDim.x : gridDim.x / a.n_types;
+        if ((a.half_mask >> ti) & 1) {
+            if (t.channels == 3) accumulate_dispatch<3, VEC, 1, 0, _Float16>(t, blk, nblk, nullptr, false);
+            else accumulate_dispatch<1, VEC, 1, 0, _Float16>(t, blk, nblk, nullptr, false);
+        } else {
+            if (t.channels == 3) accumulate_dispatch<3, VEC, 1, 0>(t, blk, nblk, nullptr, false);
+            else accumulate_dispatch<1, VEC, 1, 0>(t, blk, nblk, nullptr, false);
+        }
+    }
+}
+
 // ------------------------------------------------------------------ accumulate, every stat type of a pixel group in one walk
 // The type-fused walk: a lane owns its 4-pixel group in EVERY stat type of the launch -- the radiance type (RGB, Box-Cox, three
 // moments), K mean-only RGB types and M mean-only 1-channel types -- and folds sample s of all of them before sample s + 1 of
@@ -681,46 +721,74 @@ struct AccumulateFusedArgs {
 };
 constexpr int acc_fused_slot_floats(int k, int m) { return 768 * (1 + k) + 256 * m; }       // one sample row of every type, per wave
 constexpr size_t acc_fused_lds_bytes(int k, int m, int d) { return (size_t)4 * d * acc_fused_slot_floats(k, m) * sizeof(float); }
+// 16-bit arenas (statmc_accumulate_formats), FMT: 0 every type fp32 (the kernels above all), 1 the feature types half and the radiance
+// type fp32, 2 every type half.  A wave's half row is half as long -- 1 536 B of an RGB type, 512 B of a 1-channel type -- and
+// arrives in 16-byte pieces like the fp32 rows: the first 1 KiB of an RGB row is one transfer of the wave; what is left of it and a
+// 1-channel row are 512-B UNITS, 32 lanes' worth, and two units share one transfer (lanes 0 .. 31 fetch one, lanes 32 .. 63 the
+// other: the source address of an LDS-DMA transfer is per lane, its destination is not).  An odd last unit is fetched twice, its
+// second copy into 512 B nobody reads.  No lane sits a transfer out: a branch around an LDS-DMA builtin is not safe (the compiler
+// threads such branches as if the transfer were a per-lane load), and the counted waits want every transfer issued anyway.
+// Slot, in dwords: [radiance fp32: 768 (FMT 1)] [first KiB of every half RGB row: 256 each] [units: 128 each, a pair per transfer].
+// This asks more of the arena than the register loads do: 16-byte aligned rows, i.e. a 16-byte aligned arena and a pixel count that
+// is a multiple of 8 (launch_accumulate_half), and a wave that holds all its 64 groups -- the film's last, partial wave takes
+// the register loads of accumulate_fused_ragged.  Rows and strides are counted in dwords, so the rows stay `const float *`.
+constexpr bool acc_fused_is_half(int fmt, int i) { return fmt == 2 || (fmt == 1 && i >= 1); }
+constexpr int acc_fused_head_offset(int fmt, int i) { return fmt == 2 ? 256 * i : 768 + 256 * (i - 1); }      // half RGB type i: its first KiB
+constexpr int acc_fused_unit0(int fmt, int k) { return fmt == 2 ? 256 * (1 + k) : 768 + 256 * k; }
+constexpr int acc_fused_unit_of(int fmt, int i) { return i - (fmt == 1 ? 1 : 0); }                            // half type i: its unit (RGB: the row's tail)
+constexpr int acc_fused_units(int fmt, int k, int m) { return 1 + k + m - (fmt == 1 ? 1 : 0); }
+constexpr int acc_fused_slot_dwords(int fmt, int k, int m) {
+    return fmt == 0 ? acc_fused_slot_floats(k, m) : acc_fused_unit0(fmt, k) + 256 * ((acc_fused_units(fmt, k, m) + 1) / 2);
+}
+constexpr int acc_fused_transfers(int fmt, int k, int m) {
+    return fmt == 0 ? 3 * (1 + k) + m : (fmt == 1 ? 3 : 1) + k + (acc_fused_units(fmt, k, m) + 1) / 2;
+}
+// ring depth: the half rows' shorter slots are spent on rows in flight, about the bytes per CU the fp32 ring holds (132 KiB for the
+// 11-channel set): six all-half slots (6 KiB each per wave) are 144 KiB, five mixed ones (7 KiB) 140 KiB; T (D - 1) stays below 64
+constexpr int acc_fused_half_depth(int fmt) { return fmt == 2 ? 6 : 5; }
+static_assert(acc_fused_slot_dwords(0, 2, 2) == acc_fused_slot_floats(2, 2) && acc_fused_transfers(0, 2, 2) == 11, "FMT 0 is the fp32 layout");
 
 // A wave whose lanes do not all hold one count per group in every type (adaptively sampled films): today's walk, type after
 // type, in the wave's ring -- the same bits, no second ragged code.
-template <int K, int M, int D>
+template <int K, int M, int D, int FMT = 0>
 __device__ __forceinline__ void accumulate_fused_ragged(const AccumulateFusedArgs &a, long long gw, int n_active, float *ring) {
     // (the descriptors below are picked by comparisons, never by a run-time index into the kernel argument -- see accumulate_kernel on
     // what that costs; with at most two types of a kind "the first or the last" names them all)
     static_assert(K >= 0 && K <= 2 && M >= 0 && M <= 2, "a.t[1] / a.t[K] and a.t[1 + K] / a.t[K + M] name every feature type only up to two of a kind");
     constexpr int kFit = D * acc_fused_slot_floats(K, M) / 768;       // rows of one RGB type the wave's ring holds
-    constexpr int FD = kFit < kAccDmaD ? kFit : kAccDmaD;
+    constexpr int FD = FMT != 0 ? 0 : kFit < kAccDmaD ? kFit : kAccDmaD;   // (launches with 16-bit arenas: register loads, whatever the type's format)
+    typedef typename std::conditional<FMT == 2, _Float16, float>::type ST0;
+    typedef typename std::conditional<FMT != 0, _Float16, float>::type STF;
     const int lane = threadIdx.x & 63;
     const long long p0 = (gw + lane) << 2;
     const bool active = lane < n_active;
     const int S = a.n_samples;
     {
         const AccumulateType t = a.t[0];    // (copies, not references into the kernel argument: see accumulate_kernel)
-        accumulate_lane<3, 3, true, 1, FD>(t, p0, t.samples + p0 * 3, t.stride, S, ring, active, n_active, false);
+        accumulate_lane<3, 3, true, 1, FD, ST0>(t, p0, reinterpret_cast<const ST0 *>(t.samples) + p0 * 3, t.stride, S, ring, active, n_active, false);
     }
     if constexpr (K > 0) {
 #pragma unroll 1
         for (int i = 0; i < K; i++) {
             const AccumulateType t = i == 0 ? a.t[1] : a.t[K];
-            accumulate_lane<3, 1, false, 1, FD>(t, p0, t.samples + p0 * 3, t.stride, S, ring, active, n_active, false);
+            accumulate_lane<3, 1, false, 1, FD, STF>(t, p0, reinterpret_cast<const STF *>(t.samples) + p0 * 3, t.stride, S, ring, active, n_active, false);
         }
     }
     if constexpr (M > 0) {
 #pragma unroll 1
         for (int i = 0; i < M; i++) {
             const AccumulateType t = i == 0 ? a.t[1 + K] : a.t[K + M];
-            accumulate_lane<1, 1, false, 1, FD>(t, p0, t.samples + p0, t.stride, S, ring, active, n_active, false);
+            accumulate_lane<1, 1, false, 1, FD, STF>(t, p0, reinterpret_cast<const STF *>(t.samples) + p0, t.stride, S, ring, active, n_active, false);
         }
     }
 }
 
 // The wave's 64 groups from group gw on (the first n_active of them exist; wave-uniform arguments).
-template <int K, int M, int D>
+template <int K, int M, int D, int FMT = 0>
 __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs &a, long long gw, int n_active, float *ring) {
     constexpr int NT = 1 + K + M;
-    constexpr int SLOT = acc_fused_slot_floats(K, M);
-    constexpr int T = 3 * (1 + K) + M;                      // transfers per sample row
+    constexpr int SLOT = acc_fused_slot_dwords(FMT, K, M);
+    constexpr int T = acc_fused_transfers(FMT, K, M);       // transfers per sample row
     static_assert(T * (D - 1) <= 63, "the counted wait must fit vmcnt");
     constexpr int KA = K > 0 ? K : 1, MA = M > 0 ? M : 1;
     const int lane = threadIdx.x & 63;
@@ -737,8 +805,8 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
         lane_same = lane_same && n4.x == n4.y && n4.y == n4.z && n4.z == n4.w;
         lane_one = lane_one && n4.x == nb[0];
     }
-    if (__builtin_amdgcn_ballot_w64(active && !lane_same) != 0) {
-        accumulate_fused_ragged<K, M, D>(a, gw, n_active, ring);
+    if (__builtin_amdgcn_ballot_w64(active && !lane_same) != 0 || (FMT != 0 && n_active < 64)) {
+        accumulate_fused_ragged<K, M, D, FMT>(a, gw, n_active, ring);
         return;
     }
     // (the descriptors' fields, all read before the first store: see accumulate_lane)
@@ -753,8 +821,9 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
     for (int i = 0; i < NT; i++) {
         n_ptr[i] = a.t[i].n;
         f_mean[i] = a.t[i].mean;
-        row[i] = a.t[i].samples + (gw << 2) * (i <= K ? 3 : 1);
-        stride[i] = a.t[i].stride;
+        // (a half row and its stride in dwords: half the elements -- the pixel count is a multiple of 4)
+        row[i] = a.t[i].samples + (((gw << 2) * (i <= K ? 3 : 1)) >> (acc_fused_is_half(FMT, i) ? 1 : 0));
+        stride[i] = a.t[i].stride >> (acc_fused_is_half(FMT, i) ? 1 : 0);
     }
     // Every lane issues every transfer of a row, whatever part of the row exists; a piece beyond the row's end re-reads the
     // row's first 16 bytes (memory that exists) into a part of the slot nobody reads (as in accumulate_lane).
@@ -764,6 +833,31 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
     const int piece1 = active ? 4 * lane : 0;
     auto issue = [&](int slot) {
         float *dst = ring + slot * SLOT;
+        if constexpr (FMT != 0) {
+            // (full waves only; FMT 0 keeps the statements below, with their offsets written as they always were)
+            constexpr int NU = acc_fused_units(FMT, K, M), U0 = acc_fused_unit0(FMT, K);
+            const float *unit[NU + 1];
+#pragma unroll
+            for (int i = 0; i < NT; i++) {
+                if (!acc_fused_is_half(FMT, i)) {       // the fp32 radiance row of a mixed launch
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        __builtin_amdgcn_global_load_lds(row[i] + 256 * k + 4 * lane, (__attribute__((address_space(3))) void *)(dst + 256 * k), 16, 0, 2);
+                } else if (i <= K) {
+                    __builtin_amdgcn_global_load_lds(row[i] + 4 * lane, (__attribute__((address_space(3))) void *)(dst + acc_fused_head_offset(FMT, i)), 16, 0, 2);
+                    unit[acc_fused_unit_of(FMT, i)] = row[i] + 256;
+                } else {
+                    unit[acc_fused_unit_of(FMT, i)] = row[i];
+                }
+                row[i] += stride[i];
+            }
+            unit[NU] = unit[NU - 1];
+#pragma unroll
+            for (int u = 0; u < NU; u += 2)
+                __builtin_amdgcn_global_load_lds((lane < 32 ? unit[u] : unit[u + 1] - 128) + 4 * lane,
+                                                 (__attribute__((address_space(3))) void *)(dst + U0 + 128 * u), 16, 0, 2);
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NT; i++) {
             if (i <= K) {
@@ -820,6 +914,34 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
             if (s < S_full) acc_wait_vmcnt<T * (D - 1)>(); else acc_wait_vmcnt<0>();
             const float *mine = ring + slot * SLOT;
             vfloat4 q[1 + K][3], q1[MA];
+            if constexpr (FMT != 0) {
+                // a half piece is read as it lies (8-byte LDS reads: lane l's 6 dwords of an RGB row start 6 l dwords into it, before
+                // or behind the row's first KiB) and widened once the slot is free again
+                constexpr int U0 = acc_fused_unit0(FMT, K);
+                vhalf4 h[1 + K][3], h1[MA];
+#pragma unroll
+                for (int i = 0; i <= K; i++)
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        if (acc_fused_is_half(FMT, i)) {
+                            const int o = 6 * lane + 2 * k;
+                            const int at = o < 256 ? acc_fused_head_offset(FMT, i) + o : U0 + 128 * acc_fused_unit_of(FMT, i) + o - 256;
+                            h[i][k] = *reinterpret_cast<const vhalf4 *>(mine + at);
+                        } else {
+                            q[i][k] = *reinterpret_cast<const vfloat4 *>(mine + 12 * lane + 4 * k);
+                        }
+                    }
+#pragma unroll
+                for (int i = 0; i < M; i++) h1[i] = *reinterpret_cast<const vhalf4 *>(mine + U0 + 128 * acc_fused_unit_of(FMT, 1 + K + i) + 2 * lane);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
+#pragma unroll
+                for (int i = 0; i <= K; i++)
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        if (acc_fused_is_half(FMT, i)) q[i][k] = __builtin_convertvector(h[i][k], vfloat4);
+#pragma unroll
+                for (int i = 0; i < M; i++) q1[i] = __builtin_convertvector(h1[i], vfloat4);
+            } else {
 #pragma unroll
             for (int i = 0; i <= K; i++)
 #pragma unroll
@@ -827,6 +949,7 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
 #pragma unroll
             for (int i = 0; i < M; i++) q1[i] = *reinterpret_cast<const vfloat4 *>(mine + 768 * (1 + K) + 256 * i + 4 * lane);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
+            }
             if (s + D < S) issue(slot);
             v2f nf[NT], rc[NT];
             if constexpr (decltype(one)::value) {
@@ -935,9 +1058,22 @@ __global__ __launch_bounds__(kBlock, 1) void accumulate_fused_kernel(AccumulateF
     }
 }
 
+// The same grid for launches with 16-bit arenas: a kernel of its own, so that the fp32 one above stays the code object it was.
+template <int K, int M, int FMT>
+__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_half_kernel(AccumulateFusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float acc_lds[];
+    constexpr int D = acc_fused_half_depth(FMT);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float *ring = acc_lds + wave * (D * acc_fused_slot_dwords(FMT, K, M));
+    for (long long gw = (long long)blockIdx.x * kBlock + wave * 64; gw < a.n_groups; gw += (long long)gridDim.x * kBlock) {
+        const long long left = a.n_groups - gw;
+        accumulate_fused_wave<K, M, D, FMT>(a, gw, left >= 64 ? 64 : (int)left, ring);
+    }
+}
+
 // The launches the fused walk serves: exactly one RGB type with the transform and three moments, K <= 2 mean-only RGB types,
 // M <= 2 mean-only 1-channel types, K + M >= 1, in any order; the same pixels and the same batch length in every type.
-static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &f, int &K, int &M) {
+static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &f, int &K, int &M, int *order = nullptr) {
     K = M = 0;
     if (a.n_types < 2 || a.n_types > kAccFusedTypes) return false;
     const long long n_px = a.t[0].n_elems / a.t[0].channels;
@@ -967,6 +1103,11 @@ static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &
     for (int i = 0; i < M; i++) f.t[1 + K + i] = a.t[f1[i]];
     f.n_groups = n_px / 4;
     f.n_samples = S;
+    if (order) {                    // f.t[j] is a.t[order[j]]
+        order[0] = rad;
+        for (int i = 0; i < K; i++) order[1 + i] = rgb[i];
+        for (int i = 0; i < M; i++) order[1 + K + i] = f1[i];
+    }
     return true;
 }
 
@@ -1001,11 +1142,98 @@ static hipError_t launch_accumulate_fused(const AccumulateFusedArgs &f, int K, i
 }
 
 static thread_local unsigned g_last_acc_grid = 0;
-static thread_local int g_last_acc_fused = 0;
+static thread_local int g_last_acc_fused = 0, g_last_acc_loader = 0;
 unsigned last_accumulate_grid() { return g_last_acc_grid; }   // workgroups of the calling thread's last film-major launch (tests)
 int last_accumulate_fused() { return g_last_acc_fused; }      // ... and whether it ran the type-fused walk
+int last_accumulate_loader() { return g_last_acc_loader; }    // ... and how its 16-bit arenas were read: 0 none, 1 vector path, 2 element by element
+
+template <int K, int M, int FMT>
+static hipError_t launch_accumulate_fused_half_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
+    constexpr size_t lds = (size_t)4 * acc_fused_half_depth(FMT) * acc_fused_slot_dwords(FMT, K, M) * sizeof(float);
+    static_assert(lds <= 160 * 1024, "the ring of a workgroup must fit the CU's LDS");
+    const void *fn = reinterpret_cast<const void *>(&accumulate_fused_half_kernel<K, M, FMT>);
+    static thread_local unsigned long long allowed = 0;       // (as in launch_accumulate_fused_km)
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    if (dev < 0 || dev >= 64 || !((allowed >> dev) & 1)) {
+        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) allowed |= 1ull << dev;
+    }
+    hipLaunchKernelGGL((accumulate_fused_half_kernel<K, M, FMT>), dim3(blocks), dim3(kBlock), lds, s, f);
+    return hipGetLastError();
+}
+template <int FMT>
+static hipError_t launch_accumulate_fused_half(const AccumulateFusedArgs &f, int K, int M, unsigned blocks, hipStream_t s) {
+    switch (3 * K + M) {
+    case 1: return launch_accumulate_fused_half_km<0, 1, FMT>(f, blocks, s);
+    case 2: return launch_accumulate_fused_half_km<0, 2, FMT>(f, blocks, s);
+    case 3: return launch_accumulate_fused_half_km<1, 0, FMT>(f, blocks, s);
+    case 4: return launch_accumulate_fused_half_km<1, 1, FMT>(f, blocks, s);
+    case 5: return launch_accumulate_fused_half_km<1, 2, FMT>(f, blocks, s);
+    case 6: return launch_accumulate_fused_half_km<2, 0, FMT>(f, blocks, s);
+    case 7: return launch_accumulate_fused_half_km<2, 1, FMT>(f, blocks, s);
+    case 8: return launch_accumulate_fused_half_km<2, 2, FMT>(f, blocks, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+// A launch with at least one 16-bit arena (a.half_mask != 0).  The vector path wants what the fp32 one wants of the state planes
+// and the fp32 arenas (16-byte alignment), 8-byte alignment of the half arenas, and a pixel count that is a multiple of 4 (then
+// every plane of every arena starts at that alignment); everything else goes element by element.
+// Dispatch: the type-fused walk (accumulate_fused_half_kernel) wherever the launch has its shape -- the radiance type and up to
+// two mean-only types of each kind, the same pixels and batch length --, its formats are "features half" with the radiance
+// type in either format, and its half rows are 16-byte aligned (16-byte aligned arenas, a multiple of 8 pixels); min(CUs, units) workgroups or the number asked for.  Measured against the per-type kernel and against
+// the fp32 launch: DESIGN.md 4.1d.  statmc_debug_accumulate_fused(-1), statmc_debug_accumulate_dma(0),
+// statmc_debug_accumulate_resident_blocks(-1) and every other mix of formats take accumulate_half_kernel.
+static hipError_t launch_accumulate_half(const AccumulateArgs &a_in, hipStream_t s) {
+    AccumulateArgs a = a_in;
+    bool vec = true;
+    long long max_groups = 1;
+    for (int i = 0; i < a.n_types; i++) {
+        const AccumulateType &t = a.t[i];
+        const bool half = (a.half_mask >> i) & 1;
+        vec = vec && (half ? (reinterpret_cast<uintptr_t>(t.samples) & 7) == 0 : aligned16(t.samples)) && aligned16(t.n) && aligned16(t.mean) &&
+              (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&
+              (!t.transform || (aligned16(t.film_mean) && aligned16(t.film_m2))) &&
+              (!t.mean_corr || (aligned16(t.mean_corr) && aligned16(t.disc))) &&
+              (t.n_elems % (4 * t.channels) == 0) && (t.stride % (4 * t.channels) == 0);
+        const long long groups = (t.n_elems / t.channels + 3) / 4;
+        if (groups > max_groups) max_groups = groups;
+    }
+    const long long units = (max_groups + kBlock - 1) / kBlock;
+    const int resident_asked = a.resident_blocks;
+    g_last_acc_fused = 0;
+    g_last_acc_loader = vec ? 1 : 2;
+    bool rows16 = vec;              // what the fused walk's LDS-DMA rows want beyond `vec`: 16-byte aligned half rows
+    for (int i = 0; i < a.n_types && rows16; i++)
+        rows16 = !((a.half_mask >> i) & 1) || (aligned16(a.t[i].samples) && a.t[i].n_elems % (8 * a.t[i].channels) == 0 && a.t[i].stride % (8 * a.t[i].channels) == 0);
+    if (rows16 && a.fused >= 0 && resident_asked >= 0 && a.dma) {
+        AccumulateFusedArgs f;
+        int K = 0, M = 0, order[kAccFusedTypes];
+        if (accumulate_fused_plan(a, f, K, M, order)) {
+            bool features_half = true;
+            for (int j = 1; j < 1 + K + M; j++) features_half = features_half && ((a.half_mask >> order[j]) & 1);
+            if (features_half) {
+                const long long most = a.cus > 0 && a.cus < units ? a.cus : units;
+                const unsigned blocks = resident_asked > 0 ? (unsigned)resident_asked : (unsigned)most;
+                g_last_acc_grid = blocks;
+                g_last_acc_fused = 1;
+                if ((a.half_mask >> order[0]) & 1) return launch_accumulate_fused_half<2>(f, K, M, blocks, s);
+                return launch_accumulate_fused_half<1>(f, K, M, blocks, s);
+            }
+        }
+    }
+    a.resident_blocks = resident_asked > 0 ? resident_asked : 0;
+    const dim3 grid(a.resident_blocks > 0 ? (unsigned)a.resident_blocks : (unsigned)(units * a.n_types));
+    g_last_acc_grid = grid.x;
+    if (vec) hipLaunchKernelGGL((accumulate_half_kernel<true>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((accumulate_half_kernel<false>), grid, dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
+    if (a_in.half_mask != 0) return launch_accumulate_half(a_in, s);
+    g_last_acc_loader = 0;
     AccumulateArgs a = a_in;
     // slots per type ~ relative cost: 4 B x channels per sample, x1.3 for transform types
     a.n_slots = 0;

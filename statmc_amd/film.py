@@ -68,12 +68,21 @@ class FilmStats:
                     v.zero_()
 
     def accumulate(self, samples, rows=None):
-        """samples: {type: [S, H, W, C]}; one kernel launch covers every stat type.  rows = (y0, y1): only those rows."""
+        """samples: {type: [S, H, W, C]}; one kernel launch covers every stat type.  rows = (y0, y1): only those rows.
+        A type's arena is read in the format of its tensor: torch.float32, or torch.float16 (statmc_accumulate_formats: the bits
+        of the same samples widened to fp32)."""
         fuse = self.fused_prepass and rows is None and "radiance" in samples
         sts = [api.make_stat_type(samples[t], self.state[t], STAT_TYPES[t]["transform"], STAT_TYPES[t]["max_moment"],
                                   prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None)
                for t in self.types if t in samples]
-        api.accumulate(self.width, self.height, sts, rows=rows)
+        fmts = []
+        for t in self.types:
+            if t in samples:
+                if samples[t].dtype not in (torch.float32, torch.float16):
+                    raise TypeError("FilmStats.accumulate: samples of %r are %s; torch.float32 or torch.float16" % (t, samples[t].dtype))
+                fmts.append(api.SAMPLES_F16 if samples[t].dtype == torch.float16 else api.SAMPLES_F32)
+        # (an all-fp32 batch makes the call it always made)
+        api.accumulate(self.width, self.height, sts, rows=rows, sample_formats=fmts if api.SAMPLES_F16 in fmts else None)
         self._prepass_current = self._prepass_key() if fuse else None
 
     def combine_(self, other):

@@ -94,11 +94,13 @@ CV_ADAPTOR_BIN = os.path.join(ROOT, "tools", "bin", "test_cv_adaptor")   # tests
 DEVICE_ACC_BIN = os.path.join(ROOT, "tools", "bin", "test_device_accumulate")   # tests/cpp/test_device_accumulate.cpp: Estimator::DeviceStatistics
 ACC_RECORDS_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records")   # tests/cpp/test_accumulate_records.cpp: Estimator::AccumulateRecords
 ACC_FILM_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_film")   # tests/cpp/test_accumulate_film.cpp: Estimator::AccumulateFilm
+ACC_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_plan")   # tests/cpp/test_accumulate_plan.cpp: statmc::plan_accumulate, no device
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
          ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp"),
-         ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp")}
+         ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp"),
+         ACC_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_plan.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")
@@ -116,6 +118,7 @@ def tools_hash():
     inc = os.path.join(ROOT, "include")
     files = [os.path.join(ROOT, "tools", src) for src in list(TOOLS.values()) + [DEVICE_EXAMPLE_SRC]]
     files += [os.path.join(inc, f) for f in sorted(os.listdir(inc))]
+    files.append(os.path.join(CSRC, "statmc_device.h"))    # test_accumulate_plan.cpp reads the library's own argument blocks
     for path in files:
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
@@ -141,6 +144,7 @@ def build_tools(force=False):
         build()
     os.makedirs(os.path.dirname(DENOISE_BIN), exist_ok=True)
     rocm_lib = os.path.join(os.path.dirname(os.path.dirname(_hipcc())), "lib")
+    rocm_inc = os.path.join(os.path.dirname(rocm_lib), "include")
     tmp = DEVICE_EXAMPLE_SO + ".tmp%d" % os.getpid()
     subprocess.check_call([_hipcc()] + DEVICE_EXAMPLE_FLAGS + ["-I", os.path.join(ROOT, "include"),
                                                              os.path.join(ROOT, "tools", DEVICE_EXAMPLE_SRC), "-o", tmp])
@@ -148,6 +152,8 @@ def build_tools(force=False):
     for binary, src in TOOLS.items():
         tmp = binary + ".tmp%d" % os.getpid()
         extra = ["-L", os.path.dirname(DEVICE_EXAMPLE_SO), "-lstatmc_device_example", "-Wl,-rpath,$ORIGIN"] if binary == DEVICE_ACC_BIN else []
+        if binary == ACC_PLAN_BIN:      # statmc_device.h includes the HIP runtime's header
+            extra = ["-D__HIP_PLATFORM_AMD__", "-I", rocm_inc]
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread",
                                "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", src), "-o", tmp,
                                "-L", HERE, "-lstatmc_hip"] + extra + ["-L", rocm_lib, "-Wl,-rpath,$ORIGIN/../../statmc_amd",

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/statmc.h"
@@ -46,7 +47,7 @@ constexpr int kMaxSlots = 64;
 struct AccumulateArgs {
     AccumulateType t[kMaxStatTypes];
     int n_types;
-    int resident_blocks;  // 0: by shape (launch_accumulate); > 0: that many workgroups walk all types; -1: never (A/B)
+    int resident_blocks;  // 0: by shape (plan_accumulate); > 0: that many workgroups walk all types; -1: never (A/B)
     int cus;              // compute units of the device (the resident grid's size where the shape calls for one)
     int umul;             // 2: the mean-only feature types prefetch twice as deep (statmc_debug_accumulate_umul; A/B)
     int dma;              // RGB sample planes arrive by LDS-DMA (default 1; 0: loads into registers, A/B)
@@ -58,13 +59,15 @@ struct AccumulateArgs {
     int n_slots;
     int type_slots[kMaxStatTypes];
     unsigned char slot_type[kMaxSlots], slot_rank[kMaxSlots];
-    // the type-fused walk (launch_accumulate): 0 by shape, 1 whenever the launch is eligible, -1 never (statmc_debug_accumulate_fused);
+    // the type-fused walk (plan_accumulate): 0 by shape, 1 whenever the launch is eligible, -1 never (statmc_debug_accumulate_fused);
     // read by the host only, and last so that the fields before it keep their kernel-argument offsets
     int fused;
     // statmc_accumulate_formats: bit i = t[i].samples is an IEEE-half arena (n_elems and stride still count elements).  Read by
     // accumulate_half_kernel alone; it takes the padding behind `fused`, so the argument keeps its size.
     int half_mask;
 };
+// the kernels take the block by value: nothing in it moves (occ, fused and half_mask are where they are for that reason)
+static_assert(sizeof(AccumulateArgs) == 2032 && offsetof(AccumulateArgs, n_slots) == 1828, "AccumulateArgs: kernel-argument offsets");
 
 // samples of every type arrive tile by tile: AccumulateType::samples is the type's arena, tile k's
 // block starts at float offset tile_offsets[k] * channels and holds tile_samples[k] planes of
@@ -261,6 +264,21 @@ const float *t_table_device_ptr(int table);  // current device's copy of quantil
 const float *t_table_sq_device_ptr(int table);  // ... of its squares (fl(t * t), what the Welch pair test multiplies with)
 hipError_t launch_prepass(const PrepassArgs &a, hipStream_t s);
 hipError_t launch_mean_vars(const MeanVarsArgs &a, hipStream_t s);
+// What one film-major accumulation runs.  plan_accumulate decides it from the argument alone -- no HIP call, no global or
+// thread-local state, so tests/cpp/test_accumulate_plan.cpp pins every rule without a GPU -- and launch_accumulate launches it.
+enum { kAccPerType = 0, kAccPerTypeHalf, kAccFused, kAccFusedHalf };
+struct AccumulateFusedArgs;     // the type-fused walk's argument (statmc_pointwise.hip)
+struct AccumulatePlan {
+    int kernel;             // kAccPerType: accumulate_kernel, kAccPerTypeHalf: accumulate_half_kernel, kAccFused / kAccFusedHalf: accumulate_fused[_half]_kernel
+    int vec;                // whole 4-pixel groups move as 16-byte (half arenas: 8-byte) pieces; 0: element by element
+    int dma, umul;          // accumulate_kernel's template arguments: the LDS-DMA ring's depth (0: register loads), the prefetch depth
+    int K, M, fmt;          // the fused kernels': mean-only RGB types, mean-only 1-channel types, formats (0 / 1 / 2 as acc_fused_is_half has it)
+    unsigned grid;          // workgroups
+    size_t lds;             // dynamic LDS per workgroup, bytes
+    int resident_blocks, grid_mode;     // what the per-type kernels read from their argument
+    int loader;             // what last_accumulate_loader() reports
+};
+AccumulatePlan plan_accumulate(const AccumulateArgs &a, AccumulateFusedArgs *fused_out);   // fused_out (may be NULL): filled when a fused kernel is planned
 hipError_t launch_accumulate(const AccumulateArgs &a, hipStream_t s);
 unsigned last_accumulate_grid();
 int last_accumulate_fused();         // 1: the calling thread's last film-major launch ran the type-fused walk

@@ -786,7 +786,7 @@ hipError_t workspace_free(void *p) {
 
 // -1: not a block of the placed allocator's (or the allocator is not telling classes apart on that device); else the role it was
 // dealt for.  What statmc_accumulate asks about its buffers: samples in STREAM blocks and moments in STATE blocks are known to
-// lie in different interference classes, and the film-major launch shape is chosen with that in mind (launch_accumulate).
+// lie in different interference classes, and the film-major launch shape is chosen with that in mind (plan_accumulate).
 int placement_role_of(const void *ptr) {
     std::lock_guard<std::mutex> lk(g_place_mu);
     for (auto &kv : g_place) {

@@ -100,6 +100,8 @@ __device__ __forceinline__ float t_quantile(int table, int dof) {
     if (dof > STATMC_TQ_N_DOF) dof = STATMC_TQ_N_DOF;
     return g_tq[table][dof - 1];
 }
+// the quantile the pre-pass epilogues hand prepass_elem for a pixel of n samples (flags: AccumulateType::pre_flags)
+__device__ __forceinline__ float prepass_quantile(int table, int flags, int n) { return (flags & 1) ? 1.f : t_quantile(table, n - 1); }
 
 constexpr int kBlock = 256;
 typedef float vfloat4 __attribute__((ext_vector_type(4)));
@@ -532,7 +534,7 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
         if (pre_mc != nullptr) {
             float tq[4];
 #pragma unroll
-            for (int p = 0; p < 4; p++) tq[p] = (pre_flags & 1) ? 1.f : t_quantile(pre_table, n_out[p] - 1);
+            for (int p = 0; p < 4; p++) tq[p] = prepass_quantile(pre_table, pre_flags, n_out[p]);
 #pragma unroll
             for (int k = 0; k < C; k++) {
                 vfloat4 mc, dc;
@@ -578,7 +580,7 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateType &t, long l
         if (MAXM >= 3 && pre_mc != nullptr) {   // (the optional pre-pass epilogue, as in accumulate_lane)
             const int ni = n0 + S;
             float m, d;
-            prepass_elem(ni, (pre_flags & 1) ? 1.f : t_quantile(pre_table, ni - 1), st.mean, st.m2, st.m3, m, d, (pre_flags & 2) != 0);
+            prepass_elem(ni, prepass_quantile(pre_table, pre_flags, ni), st.mean, st.m2, st.m3, m, d, (pre_flags & 2) != 0);
             pre_mc[e] = m;
             pre_dc[e] = d;
         }
@@ -730,7 +732,7 @@ constexpr size_t acc_fused_lds_bytes(int k, int m, int d) { return (size_t)4 * d
 // threads such branches as if the transfer were a per-lane load), and the counted waits want every transfer issued anyway.
 // Slot, in dwords: [radiance fp32: 768 (FMT 1)] [first KiB of every half RGB row: 256 each] [units: 128 each, a pair per transfer].
 // This asks more of the arena than the register loads do: 16-byte aligned rows, i.e. a 16-byte aligned arena and a pixel count that
-// is a multiple of 8 (launch_accumulate_half), and a wave that holds all its 64 groups -- the film's last, partial wave takes
+// is a multiple of 8 (plan_accumulate), and a wave that holds all its 64 groups -- the film's last, partial wave takes
 // the register loads of accumulate_fused_ragged.  Rows and strides are counted in dwords, so the rows stay `const float *`.
 constexpr bool acc_fused_is_half(int fmt, int i) { return fmt == 2 || (fmt == 1 && i >= 1); }
 constexpr int acc_fused_head_offset(int fmt, int i) { return fmt == 2 ? 256 * i : 768 + 256 * (i - 1); }      // half RGB type i: its first KiB
@@ -1027,7 +1029,7 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
     // the radiance type's optional pre-pass epilogue, as in accumulate_lane (the four pixels hold one count: one quantile)
     if (pre_mc != nullptr) {
         const int n_out = nb[0] + S;
-        const float tq = (pre_flags & 1) ? 1.f : t_quantile(pre_table, n_out - 1);
+        const float tq = prepass_quantile(pre_table, pre_flags, n_out);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             vfloat4 mc, dc;
@@ -1073,7 +1075,7 @@ __global__ __launch_bounds__(kBlock, 1) void accumulate_fused_half_kernel(Accumu
 
 // The launches the fused walk serves: exactly one RGB type with the transform and three moments, K <= 2 mean-only RGB types,
 // M <= 2 mean-only 1-channel types, K + M >= 1, in any order; the same pixels and the same batch length in every type.
-static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &f, int &K, int &M, int *order = nullptr) {
+static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &f, int &K, int &M, int *order) {
     K = M = 0;
     if (a.n_types < 2 || a.n_types > kAccFusedTypes) return false;
     const long long n_px = a.t[0].n_elems / a.t[0].channels;
@@ -1103,40 +1105,59 @@ static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &
     for (int i = 0; i < M; i++) f.t[1 + K + i] = a.t[f1[i]];
     f.n_groups = n_px / 4;
     f.n_samples = S;
-    if (order) {                    // f.t[j] is a.t[order[j]]
-        order[0] = rad;
-        for (int i = 0; i < K; i++) order[1 + i] = rgb[i];
-        for (int i = 0; i < M; i++) order[1 + K + i] = f1[i];
-    }
+    order[0] = rad;                 // f.t[j] is a.t[order[j]]
+    for (int i = 0; i < K; i++) order[1 + i] = rgb[i];
+    for (int i = 0; i < M; i++) order[1 + K + i] = f1[i];
     return true;
 }
 
-template <int K, int M>
-static hipError_t launch_accumulate_fused_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
-    constexpr size_t lds = acc_fused_lds_bytes(K, M, kAccFusedD);
-    const void *fn = reinterpret_cast<const void *>(&accumulate_fused_kernel<K, M, kAccFusedD>);
-    // more dynamic LDS than a launch may ask for by default: allowed once per device (and thread)
+// The vector path of one stat type: every plane it has is 16-byte aligned, the pre-pass epilogue's images too, and, in a film-major
+// launch, the element count and the sample stride keep every sample plane so.  A half arena wants 8 bytes and whole 4-pixel groups
+// (n_elems % (4 channels)); an fp32 one is asked for n_elems % 4, which says the same of every count the C ABI can hand over
+// (pixels x channels, channels 1 or 3), also of an fp32 type beside half ones.  A tile-fed launch checks its rows tile by tile.
+static bool acc_type_vectorizable(const AccumulateType &t, bool half_arena, bool film_major) {
+    const long long whole = half_arena ? 4 * t.channels : 4;
+    return (half_arena ? (reinterpret_cast<uintptr_t>(t.samples) & 7) == 0 : aligned16(t.samples)) && aligned16(t.n) && aligned16(t.mean) &&
+           (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&
+           (!t.transform || (aligned16(t.film_mean) && aligned16(t.film_m2))) &&
+           (!t.mean_corr || (aligned16(t.mean_corr) && aligned16(t.disc))) &&
+           (!film_major || (t.n_elems % whole == 0 && t.stride % whole == 0));
+}
+
+// The fused kernels ask for more dynamic LDS than a launch may have by default: allowed once per kernel, device and thread.
+template <void (*KERNEL)(AccumulateFusedArgs)>
+static hipError_t launch_big_lds(size_t lds, const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
     static thread_local unsigned long long allowed = 0;
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !((allowed >> dev) & 1)) {
-        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+        if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) allowed |= 1ull << dev;
     }
-    hipLaunchKernelGGL((accumulate_fused_kernel<K, M, kAccFusedD>), dim3(blocks), dim3(kBlock), lds, s, f);
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(kBlock), lds, s, f);
     return hipGetLastError();
 }
-
+constexpr size_t acc_fused_ring_bytes(int fmt, int k, int m) {      // per workgroup: four waves
+    return (size_t)4 * (fmt == 0 ? kAccFusedD : acc_fused_half_depth(fmt)) * acc_fused_slot_dwords(fmt, k, m) * sizeof(float);
+}
+static_assert(acc_fused_ring_bytes(0, 2, 2) == acc_fused_lds_bytes(2, 2, kAccFusedD), "FMT 0 is the fp32 ring");
+static_assert(acc_fused_ring_bytes(1, 2, 2) <= 160 * 1024 && acc_fused_ring_bytes(2, 2, 2) <= 160 * 1024, "the ring of a workgroup must fit the CU's LDS");
+template <int FMT, int K, int M>
+static hipError_t launch_accumulate_fused_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
+    if constexpr (FMT == 0) return launch_big_lds<&accumulate_fused_kernel<K, M, kAccFusedD>>(acc_fused_ring_bytes(FMT, K, M), f, blocks, s);
+    else return launch_big_lds<&accumulate_fused_half_kernel<K, M, FMT>>(acc_fused_ring_bytes(FMT, K, M), f, blocks, s);
+}
+template <int FMT>
 static hipError_t launch_accumulate_fused(const AccumulateFusedArgs &f, int K, int M, unsigned blocks, hipStream_t s) {
     switch (3 * K + M) {
-    case 1: return launch_accumulate_fused_km<0, 1>(f, blocks, s);
-    case 2: return launch_accumulate_fused_km<0, 2>(f, blocks, s);
-    case 3: return launch_accumulate_fused_km<1, 0>(f, blocks, s);
-    case 4: return launch_accumulate_fused_km<1, 1>(f, blocks, s);
-    case 5: return launch_accumulate_fused_km<1, 2>(f, blocks, s);
-    case 6: return launch_accumulate_fused_km<2, 0>(f, blocks, s);
-    case 7: return launch_accumulate_fused_km<2, 1>(f, blocks, s);
-    case 8: return launch_accumulate_fused_km<2, 2>(f, blocks, s);
+    case 1: return launch_accumulate_fused_km<FMT, 0, 1>(f, blocks, s);
+    case 2: return launch_accumulate_fused_km<FMT, 0, 2>(f, blocks, s);
+    case 3: return launch_accumulate_fused_km<FMT, 1, 0>(f, blocks, s);
+    case 4: return launch_accumulate_fused_km<FMT, 1, 1>(f, blocks, s);
+    case 5: return launch_accumulate_fused_km<FMT, 1, 2>(f, blocks, s);
+    case 6: return launch_accumulate_fused_km<FMT, 2, 0>(f, blocks, s);
+    case 7: return launch_accumulate_fused_km<FMT, 2, 1>(f, blocks, s);
+    case 8: return launch_accumulate_fused_km<FMT, 2, 2>(f, blocks, s);
     }
     return hipErrorInvalidValue;
 }
@@ -1147,206 +1168,146 @@ unsigned last_accumulate_grid() { return g_last_acc_grid; }   // workgroups of t
 int last_accumulate_fused() { return g_last_acc_fused; }      // ... and whether it ran the type-fused walk
 int last_accumulate_loader() { return g_last_acc_loader; }    // ... and how its 16-bit arenas were read: 0 none, 1 vector path, 2 element by element
 
-template <int K, int M, int FMT>
-static hipError_t launch_accumulate_fused_half_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
-    constexpr size_t lds = (size_t)4 * acc_fused_half_depth(FMT) * acc_fused_slot_dwords(FMT, K, M) * sizeof(float);
-    static_assert(lds <= 160 * 1024, "the ring of a workgroup must fit the CU's LDS");
-    const void *fn = reinterpret_cast<const void *>(&accumulate_fused_half_kernel<K, M, FMT>);
-    static thread_local unsigned long long allowed = 0;       // (as in launch_accumulate_fused_km)
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !((allowed >> dev) & 1)) {
-        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) allowed |= 1ull << dev;
-    }
-    hipLaunchKernelGGL((accumulate_fused_half_kernel<K, M, FMT>), dim3(blocks), dim3(kBlock), lds, s, f);
-    return hipGetLastError();
+// Slots of the capped grid per type ~ relative cost: 4 B x channels per sample, x 1.3 for transform types: 4 / 3 / 1 slots
+// (rgb transform / rgb / float).
+static int acc_type_slots(const AccumulateType &t) {
+    const int w = (t.channels * (t.transform ? 4 : 3) + 2) / 3;
+    return w < 1 ? 1 : w;
 }
-template <int FMT>
-static hipError_t launch_accumulate_fused_half(const AccumulateFusedArgs &f, int K, int M, unsigned blocks, hipStream_t s) {
-    switch (3 * K + M) {
-    case 1: return launch_accumulate_fused_half_km<0, 1, FMT>(f, blocks, s);
-    case 2: return launch_accumulate_fused_half_km<0, 2, FMT>(f, blocks, s);
-    case 3: return launch_accumulate_fused_half_km<1, 0, FMT>(f, blocks, s);
-    case 4: return launch_accumulate_fused_half_km<1, 1, FMT>(f, blocks, s);
-    case 5: return launch_accumulate_fused_half_km<1, 2, FMT>(f, blocks, s);
-    case 6: return launch_accumulate_fused_half_km<2, 0, FMT>(f, blocks, s);
-    case 7: return launch_accumulate_fused_half_km<2, 1, FMT>(f, blocks, s);
-    case 8: return launch_accumulate_fused_half_km<2, 2, FMT>(f, blocks, s);
+// The capped grid's slot table: the slots of different types interleaved (round-robin over types) so that neighbours differ.
+static void acc_fill_slots(AccumulateArgs &a) {
+    a.n_slots = 0;
+    for (int i = 0; i < a.n_types; i++) a.type_slots[i] = acc_type_slots(a.t[i]);
+    for (int r = 0, left = 1; left && a.n_slots < kMaxSlots; r++) {
+        left = 0;
+        for (int i = 0; i < a.n_types && a.n_slots < kMaxSlots; i++)
+            if (r < a.type_slots[i]) {
+                a.slot_type[a.n_slots] = (unsigned char)i;
+                a.slot_rank[a.n_slots] = (unsigned char)r;
+                a.n_slots++;
+                left = 1;
+            }
     }
-    return hipErrorInvalidValue;
 }
 
-// A launch with at least one 16-bit arena (a.half_mask != 0).  The vector path wants what the fp32 one wants of the state planes
-// and the fp32 arenas (16-byte alignment), 8-byte alignment of the half arenas, and a pixel count that is a multiple of 4 (then
-// every plane of every arena starts at that alignment); everything else goes element by element.
-// Dispatch: the type-fused walk (accumulate_fused_half_kernel) wherever the launch has its shape -- the radiance type and up to
-// two mean-only types of each kind, the same pixels and batch length --, its formats are "features half" with the radiance
-// type in either format, and its half rows are 16-byte aligned (16-byte aligned arenas, a multiple of 8 pixels); min(CUs, units) workgroups or the number asked for.  Measured against the per-type kernel and against
-// the fp32 launch: DESIGN.md 4.1d.  statmc_debug_accumulate_fused(-1), statmc_debug_accumulate_dma(0),
-// statmc_debug_accumulate_resident_blocks(-1) and every other mix of formats take accumulate_half_kernel.
-static hipError_t launch_accumulate_half(const AccumulateArgs &a_in, hipStream_t s) {
-    AccumulateArgs a = a_in;
-    bool vec = true;
+// Every rule of the film-major launch, from the argument alone (no HIP call, no global state: tests/cpp/test_accumulate_plan.cpp
+// runs it without a GPU and tests/golden/accumulate_plan.json pins what it answers).  The measurements behind each rule:
+// DESIGN.md 4.1 and, under the names given here, HISTORY.md 4.1f.
+AccumulatePlan plan_accumulate(const AccumulateArgs &a, AccumulateFusedArgs *fused_out) {
+    AccumulatePlan p{};
+    const bool any_half = a.half_mask != 0;
+    // The vector path: every type passes acc_type_vectorizable.  rows16: what the fused half walk's LDS-DMA rows want beyond
+    // that -- 16-byte aligned half rows, i.e. a 16-byte aligned arena and a multiple of 8 pixels.
+    bool vec = true, rows16 = true;
     long long max_groups = 1;
+    int max_s = 0, n_slots = 0;
     for (int i = 0; i < a.n_types; i++) {
         const AccumulateType &t = a.t[i];
         const bool half = (a.half_mask >> i) & 1;
-        vec = vec && (half ? (reinterpret_cast<uintptr_t>(t.samples) & 7) == 0 : aligned16(t.samples)) && aligned16(t.n) && aligned16(t.mean) &&
-              (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&
-              (!t.transform || (aligned16(t.film_mean) && aligned16(t.film_m2))) &&
-              (!t.mean_corr || (aligned16(t.mean_corr) && aligned16(t.disc))) &&
-              (t.n_elems % (4 * t.channels) == 0) && (t.stride % (4 * t.channels) == 0);
+        vec = vec && acc_type_vectorizable(t, half, true);
+        rows16 = rows16 && (!half || (aligned16(t.samples) && t.n_elems % (8 * t.channels) == 0 && t.stride % (8 * t.channels) == 0));
         const long long groups = (t.n_elems / t.channels + 3) / 4;
         if (groups > max_groups) max_groups = groups;
+        if (t.n_samples > max_s) max_s = t.n_samples;
+        n_slots += acc_type_slots(t);
     }
-    const long long units = (max_groups + kBlock - 1) / kBlock;
-    const int resident_asked = a.resident_blocks;
-    g_last_acc_fused = 0;
-    g_last_acc_loader = vec ? 1 : 2;
-    bool rows16 = vec;              // what the fused walk's LDS-DMA rows want beyond `vec`: 16-byte aligned half rows
-    for (int i = 0; i < a.n_types && rows16; i++)
-        rows16 = !((a.half_mask >> i) & 1) || (aligned16(a.t[i].samples) && a.t[i].n_elems % (8 * a.t[i].channels) == 0 && a.t[i].stride % (8 * a.t[i].channels) == 0);
-    if (rows16 && a.fused >= 0 && resident_asked >= 0 && a.dma) {
+    if (n_slots > kMaxSlots) n_slots = kMaxSlots;
+    const long long units = (max_groups + kBlock - 1) / kBlock;     // workgroups that cover the largest type once
+    p.vec = vec ? 1 : 0;
+    p.loader = any_half ? (vec ? 1 : 2) : 0;
+    p.umul = 1;
+    // A resident grid of the per-type kernel: the number asked for (statmc_debug_accumulate_resident_blocks), or, fp32 arenas
+    // only, one workgroup per CU on 1080p-sized films ([2^18, 3 x 2^18) groups) from 256 samples per launch up with placed
+    // buffers, where the film's groups fill the workgroups' last walk to 97 % at least (HISTORY.md 4.1f, "one workgroup per CU").
+    p.resident_blocks = a.resident_blocks > 0 ? a.resident_blocks : 0;
+    if (!any_half && a.resident_blocks == 0 && a.grid_mode < 0 && a.apart && a.cus > 0 && max_s >= 256 && max_groups >= (1 << 18) && max_groups < 3 * (1 << 18)) {
+        const double walks = (double)max_groups / ((double)a.cus * kBlock);
+        if (walks / ceil(walks) >= 0.97) p.resident_blocks = a.cus;
+    }
+    // The type-fused walk: never with statmc_debug_accumulate_fused(-1), statmc_debug_accumulate_resident_blocks(-1), the LDS-DMA
+    // walk switched off or off the vector path; min(CUs, units) workgroups, or the resident grid's number.
+    // fp32 arenas, by shape (a.fused = 0): wherever the resident grid above stands, and from 128 samples per launch up on films of
+    // 960 x 540 to 1920 x 1080 ([128 000, 2^19) groups), whatever the allocator; a.fused = 1: every eligible launch (DESIGN.md 4.1,
+    // HISTORY.md 4.1e and 4.1f, "the type-fused walk").
+    // 16-bit arenas: whenever the rows are 16-byte aligned and the feature types are half, the radiance type in either format
+    // (DESIGN.md 4.1d); every other mix of formats takes the per-type half kernel.
+    if (a.fused >= 0 && a.resident_blocks >= 0 && vec && a.dma && (!any_half || rows16)) {
+        const bool by_shape = a.fused == 0 && a.resident_blocks == 0 && a.grid_mode < 0 && a.cus > 0 &&
+                              (p.resident_blocks > 0 || (max_s >= 128 && max_groups >= 128000 && max_groups < (1 << 19)));
         AccumulateFusedArgs f;
         int K = 0, M = 0, order[kAccFusedTypes];
-        if (accumulate_fused_plan(a, f, K, M, order)) {
+        if ((any_half || by_shape || a.fused == 1) && accumulate_fused_plan(a, f, K, M, order)) {
             bool features_half = true;
             for (int j = 1; j < 1 + K + M; j++) features_half = features_half && ((a.half_mask >> order[j]) & 1);
-            if (features_half) {
-                const long long most = a.cus > 0 && a.cus < units ? a.cus : units;
-                const unsigned blocks = resident_asked > 0 ? (unsigned)resident_asked : (unsigned)most;
-                g_last_acc_grid = blocks;
-                g_last_acc_fused = 1;
-                if ((a.half_mask >> order[0]) & 1) return launch_accumulate_fused_half<2>(f, K, M, blocks, s);
-                return launch_accumulate_fused_half<1>(f, K, M, blocks, s);
+            if (!any_half || features_half) {
+                p.kernel = any_half ? kAccFusedHalf : kAccFused;
+                p.K = K;
+                p.M = M;
+                p.fmt = !any_half ? 0 : ((a.half_mask >> order[0]) & 1) ? 2 : 1;
+                p.grid = p.resident_blocks > 0 ? (unsigned)p.resident_blocks : (unsigned)(a.cus > 0 && a.cus < units ? a.cus : units);
+                p.lds = acc_fused_ring_bytes(p.fmt, K, M);
+                if (fused_out) *fused_out = f;
+                return p;
             }
         }
     }
-    a.resident_blocks = resident_asked > 0 ? resident_asked : 0;
-    const dim3 grid(a.resident_blocks > 0 ? (unsigned)a.resident_blocks : (unsigned)(units * a.n_types));
-    g_last_acc_grid = grid.x;
-    if (vec) hipLaunchKernelGGL((accumulate_half_kernel<true>), grid, dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL((accumulate_half_kernel<false>), grid, dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    // The per-type half kernel (register loads, no slot table): the resident grid asked for, or one pass per workgroup.
+    if (any_half) {
+        p.kernel = kAccPerTypeHalf;
+        p.grid_mode = 1;
+        p.grid = p.resident_blocks > 0 ? (unsigned)p.resident_blocks : (unsigned)(units * a.n_types);
+        return p;
+    }
+    // The per-type fp32 kernel's shape where no resident grid stands.  0, the capped grid: every type holds slots in proportion
+    // to its cost, grid-stride walk.  1: every workgroup makes ONE pass, types round-robin -- short batches, which are bound by
+    // the chain of latencies a workgroup pays per pass (up to 8 samples, up to 16 on films below 2^20 groups: HISTORY.md 4.1f,
+    // "launch shape"); with placed buffers also films from 2^20 groups up and batches from 128 samples up, so that only 17 - 127
+    // samples on smaller films keep the capped grid ("launch shape, placed buffers").
+    p.kernel = kAccPerType;
+    p.grid_mode = a.grid_mode;
+    if (a.grid_mode < 0) {
+        const bool big = max_groups >= (1 << 20);
+        if (a.apart) p.grid_mode = (max_s <= 16 || big || max_s >= 128) ? 1 : 0;
+        else p.grid_mode = (max_s <= 8 || (max_s <= 16 && !big)) ? 1 : 0;
+    }
+    const int rounds = (grid_for(max_groups, 256 * 8) * a.n_types + n_slots - 1) / n_slots;
+    p.grid = p.resident_blocks > 0 ? (unsigned)p.resident_blocks : p.grid_mode == 1 ? (unsigned)(units * a.n_types) : (unsigned)(rounds * n_slots);
+    // the LDS-DMA ring (a.dma, default) and the deeper prefetch of the mean-only types (a.umul = 2, A/B) exist on the vector path only
+    if (vec && a.dma) {
+        p.dma = kAccDmaD;
+        p.lds = acc_lds_bytes(kAccDmaD);
+    } else if (vec && a.umul == 2) {
+        p.umul = 2;
+    }
+    return p;
 }
 
 hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
-    if (a_in.half_mask != 0) return launch_accumulate_half(a_in, s);
-    g_last_acc_loader = 0;
+    AccumulateFusedArgs f;
+    const AccumulatePlan p = plan_accumulate(a_in, &f);
     AccumulateArgs a = a_in;
-    // slots per type ~ relative cost: 4 B x channels per sample, x1.3 for transform types
-    a.n_slots = 0;
-    for (int i = 0; i < a.n_types; i++) {
-        int w = a.t[i].channels * (a.t[i].transform ? 4 : 3);  // 12 / 9 / 3 (rgb transform / rgb / float)
-        w = (w + 2) / 3;                                       // 4 / 3 / 1 slots
-        if (w < 1) w = 1;
-        a.type_slots[i] = w;
-        for (int r = 0; r < w && a.n_slots < kMaxSlots; r++) {
-            a.slot_type[a.n_slots] = (unsigned char)i;
-            a.slot_rank[a.n_slots] = (unsigned char)r;
-            a.n_slots++;
-        }
+    a.resident_blocks = p.resident_blocks;
+    a.grid_mode = p.grid_mode;
+    if (p.kernel == kAccPerType && p.resident_blocks == 0 && p.grid_mode != 1) acc_fill_slots(a);
+    g_last_acc_grid = p.grid;
+    g_last_acc_fused = p.kernel == kAccFused || p.kernel == kAccFusedHalf;
+    g_last_acc_loader = p.loader;
+    const dim3 grid(p.grid), block(kBlock);
+    switch (p.kernel) {
+    case kAccPerType:
+        if (p.dma) hipLaunchKernelGGL((accumulate_kernel<true, 1, kAccDmaD>), grid, block, p.lds, s, a);
+        else if (p.umul == 2) hipLaunchKernelGGL((accumulate_kernel<true, 2, 0>), grid, block, 0, s, a);
+        else if (p.vec) hipLaunchKernelGGL((accumulate_kernel<true, 1, 0>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((accumulate_kernel<false, 1, 0>), grid, block, 0, s, a);
+        break;
+    case kAccPerTypeHalf:
+        if (p.vec) hipLaunchKernelGGL((accumulate_half_kernel<true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((accumulate_half_kernel<false>), grid, block, 0, s, a);
+        break;
+    case kAccFused: return launch_accumulate_fused<0>(f, p.K, p.M, p.grid, s);
+    case kAccFusedHalf: return p.fmt == 2 ? launch_accumulate_fused<2>(f, p.K, p.M, p.grid, s) : launch_accumulate_fused<1>(f, p.K, p.M, p.grid, s);
+    default: return hipErrorInvalidValue;
     }
-    // interleave the slots of different types (round-robin over types) so neighbours differ
-    {
-        unsigned char st[kMaxSlots], sr[kMaxSlots];
-        int n = 0;
-        for (int r = 0; n < a.n_slots; r++)
-            for (int i = 0; i < a.n_types; i++)
-                if (r < a.type_slots[i]) { st[n] = (unsigned char)i; sr[n] = (unsigned char)r; n++; }
-        for (int k = 0; k < a.n_slots; k++) { a.slot_type[k] = st[k]; a.slot_rank[k] = sr[k]; }
-    }
-    bool vec = true;
-    long long max_groups = 1;
-    for (int i = 0; i < a.n_types; i++) {
-        const AccumulateType &t = a.t[i];
-        vec = vec && aligned16(t.samples) && aligned16(t.n) && aligned16(t.mean) &&
-              (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&
-              (!t.transform || (aligned16(t.film_mean) && aligned16(t.film_m2))) &&
-              (!t.mean_corr || (aligned16(t.mean_corr) && aligned16(t.disc))) &&      // the pre-pass epilogue's images
-              (t.n_elems % 4 == 0) && (t.stride % 4 == 0);  // sample planes stay 16-B aligned
-        const long long groups = (t.n_elems / t.channels + 3) / 4;
-        if (groups > max_groups) max_groups = groups;
-    }
-    const int rounds = (grid_for(max_groups, 256 * 8) * a.n_types + a.n_slots - 1) / a.n_slots;
-    const long long units = (max_groups + kBlock - 1) / kBlock;     // workgroups that cover the largest type once
-    // Launch shape.  Long batches: a capped grid, every type holding slots in proportion to its cost, grid-stride walk
-    // (the resident mix favours the ALU-heavy radiance type: + 1 - 2 % at 64 and 256 samples per pixel).  Short batches --
-    // the 4-, 4-, 8-, 16-sample iterations the reference's progressive schedule starts with (statpath.cpp:272-279) -- are
-    // bound by the chain of latencies a workgroup pays per pass, and the capped grid gives the cheap 1-channel types up to
-    // three passes per workgroup: there every workgroup makes ONE pass, types round-robin (1080p: 4 spp 5.1 -> 6.6 TB/s,
-    // 8 spp 6.1 -> 7.0, 16 spp 6.2 -> 6.6; 4K: 4 spp 4.9 -> 5.7, 16 spp 5.74 -> 5.63; profiles/r04_acc_launch.log).
-    int max_s = 0;
-    for (int i = 0; i < a.n_types; i++) max_s = a.t[i].n_samples > max_s ? a.t[i].n_samples : max_s;
-    // Round 5: with the samples and the moments in different interference classes (a.apart: statmc_malloc_placed blocks) the one-pass
-    // shape also wins on 4K films at every batch length (+ 1 - 5 %) and on long batches at 1080p (256 spp: 3.61 against 3.67 - 3.70
-    // ms); 32 - 64 samples on films up to 1080p keep the capped grid (+ 1.5 - 2.5 %).  Three processes, profiles/r05_acc_launch_placed.log.
-    // Round 6, last session: ONE workgroup per CU walking every type (four waves per CU, half the occupancy) on 1080p-sized films from
-    // 256 samples per launch up, placed buffers: the accumulation 3.72 - 3.73 against 3.77 - 3.78 ms in the step, three rounds on each of
-    // two boxes with the same placement (profiles/r06_ab_resident.log, r06_ab_resident2.log; round 5 had seen 3.57 / 3.62 and 3.74 / 3.76
-    // back to back and left it an experiment hook: it loses at 720p -- 900 units on 256 workgroups -- and at 4K).  Fewer CUs than all
-    // starve the stream (192 workgroups: 4.17 ms) though the filter behind it then holds 2.15 instead of 1.98 GHz (1.49 against 1.61 ms).
-    // Only there: at 128 samples a tie, at 64 slower (1.044 against 1.016 ms); 1280 x 720, 2560 x 1440 (14.06 walks per workgroup: the
-    // fifteenth is nearly empty) and 3840 x 2160 slower by 2 - 6 % (profiles/r06_ab_resident_spp.log).  So: the film's groups must fill the
-    // workgroups' last walk (>= 97 %), and the film must be of about that size.
-    const int resident_asked = a.resident_blocks;
-    if (a.resident_blocks == 0 && a.grid_mode < 0 && a.apart && a.cus > 0 && max_s >= 256 && max_groups >= (1 << 18) && max_groups < 3 * (1 << 18)) {
-        const double walks = (double)max_groups / ((double)a.cus * kBlock);
-        if (walks / ceil(walks) >= 0.97) a.resident_blocks = a.cus;
-    }
-    if (a.resident_blocks < 0) a.resident_blocks = 0;
-    // The type-fused walk (accumulate_fused_kernel): a resident grid of its own, every workgroup covering every type of its groups in
-    // one pass.  By shape (a.fused = 0) it stands wherever the resident grid above stands, and, measured against whatever launch the
-    // rules of this function choose otherwise (tools/time_accumulate_fused.py, six alternating pairs per process, the accumulation
-    // in the step, ms fused / per type; profiles/accumulate_fused.jsonl), on uniformly random samples first: 1080p, 256 samples, placed
-    // 3.65 - 3.66 / 3.76 in three processes, the filter behind it 1.55 / 1.59; torch's allocator 3.71 - 3.74 / 3.99; 128 samples 1.89 / 1.99
-    // placed, 1.97 / 2.12 unplaced; the 9-channel set 3.00 / 3.16 and 1.56 / 1.64; 1600 x 900 2.71 / 2.83; 1280 x 720 1.64 - 1.72 / 1.74 -
-    // 1.84 (128 samples 0.85 / 0.89); 960 x 540 0.90 / 1.02 -- every pair of every one a win, the median gain 3.7 - 16 x the larger spread.
-    // Not at 96 samples (1.43 / 1.46, inside the spread), 64 and 16 (level), 2048 x 1152 (4.24 / 4.29, every pair but 2.9 x the spread),
-    // 2560 x 1440 (level) or 4K at 64 and 16 samples (1 - 2 % slower).  Then every one of the shapes taken once more on the sample stream
-    // bench.py times (synthetic.Scene, the tool's default since), one box, one process each (two at the headline): 1080p / 256 placed
-    // 3.51 / 3.61 (uniform samples in the same call: 3.51 / 3.61 -- the stream makes no difference, the box does), unplaced 3.74 / 3.99,
-    // 128 samples 1.83 / 1.91 and 1.96 / 2.11, 9 channels 2.87 / 3.04 and 1.55 / 1.63, 900p 2.56 / 2.73, 720p 1.63 / 1.74, 0.82 / 0.86 at 128,
-    // 1.67 / 1.74 unplaced, 540p 0.88 / 0.97: again every pair, 3.8 - 12 x the spread.  (64 samples and 2048 x 1152 also won there, 5.4 x and
-    // 3.4 x: one box against one, left as they are.)  So: from 128 samples per launch up on films of 960 x 540 to 1920 x 1080, whatever
-    // the allocator.  What these pairs do NOT settle is the size of the gain between processes: bench.py on the parent build against
-    // this one is ahead in every alternating pair (eleven, three sessions) but by 0.3 - 2.1 % of the step, under the 3 x spread margin in each
-    // session.
-    // a.fused = 1 (statmc_debug_accumulate_fused): every eligible launch, min(CUs, units) workgroups or the number asked for; never with
-    // statmc_debug_accumulate_resident_blocks(-1), with the LDS-DMA walk switched off, or on unaligned films.
-    g_last_acc_fused = 0;
-    if (a.fused >= 0 && resident_asked >= 0 && vec && a.dma) {
-        const bool by_shape = a.fused == 0 && resident_asked == 0 && a.grid_mode < 0 && a.cus > 0 &&
-                              (a.resident_blocks > 0 || (max_s >= 128 && max_groups >= 128000 && max_groups < (1 << 19)));
-        AccumulateFusedArgs f;
-        int K = 0, M = 0;
-        if ((by_shape || a.fused == 1) && accumulate_fused_plan(a, f, K, M)) {
-            const long long most = a.cus > 0 && a.cus < units ? a.cus : units;
-            const unsigned blocks = resident_asked > 0 ? (unsigned)resident_asked : a.resident_blocks > 0 ? (unsigned)a.resident_blocks : (unsigned)most;
-            g_last_acc_grid = blocks;
-            g_last_acc_fused = 1;
-            return launch_accumulate_fused(f, K, M, blocks, s);
-        }
-    }
-    if (a.grid_mode < 0) {
-        const bool big = max_groups >= (1 << 20);
-        if (a.apart) a.grid_mode = (max_s <= 16 || big || max_s >= 128) ? 1 : 0;
-        else a.grid_mode = (max_s <= 8 || (max_s <= 16 && !big)) ? 1 : 0;
-    }
-    const dim3 grid(a.resident_blocks > 0 ? a.resident_blocks : a.grid_mode == 1 ? (unsigned)(units * a.n_types) : rounds * a.n_slots);
-    g_last_acc_grid = grid.x;
-    // a.dma: 1 = the LDS-DMA ring (default), 0 = loads into registers (A/B)
-    if (vec && a.dma) {
-        hipLaunchKernelGGL((accumulate_kernel<true, 1, kAccDmaD>), grid, dim3(kBlock), acc_lds_bytes(kAccDmaD), s, a);
-        return hipGetLastError();
-    }
-    if (vec && a.umul == 2)
-        hipLaunchKernelGGL((accumulate_kernel<true, 2, 0>), grid, dim3(kBlock), 0, s, a);
-    else if (vec)
-        hipLaunchKernelGGL((accumulate_kernel<true, 1, 0>), grid, dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((accumulate_kernel<false, 1, 0>), grid, dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1441,18 +1402,12 @@ __global__ __launch_bounds__(kBlock) void accumulate_tiles_kernel(AccumulateTile
 hipError_t launch_accumulate_tiles(const AccumulateTilesArgs &a_in, hipStream_t s) {
     AccumulateTilesArgs a = a_in;
     bool vec = true;
-    for (int i = 0; i < a.n_types; i++) {
-        const AccumulateType &t = a.t[i];
-        vec = vec && aligned16(t.samples) && aligned16(t.n) && aligned16(t.mean) &&
-              (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&
-              (!t.transform || (aligned16(t.film_mean) && aligned16(t.film_m2))) &&
-              (!t.mean_corr || (aligned16(t.mean_corr) && aligned16(t.disc)));
-    }
+    for (int i = 0; i < a.n_types; i++) vec = vec && acc_type_vectorizable(a.t[i], false, false);
     a.vec = vec ? 1 : 0;
     const long long items = a.order == 2 ? (((long long)a.n_tiles + 3) >> 2) * 4 * a.n_types : (long long)a.n_tiles * a.n_types;
     // one wave per item; films up to ~ 4 Mpixels: at most 8 workgroups per CU, walking the items with a grid stride; larger ones
     // (4K: 32 400 tiles): every wave ONE item, the dispatcher hands the workgroups out -- + 1 - 4 % at 4 .. 64 samples per tile there,
-    // - 1 - 2 % at 1080p (profiles/r05_tiles_first.log; the film-major launch has the same rule, launch_accumulate)
+    // - 1 - 2 % at 1080p (profiles/r05_tiles_first.log; the film-major launch has the same rule, plan_accumulate)
     const bool big = a.n_tiles >= 16384;
     const int grid = grid_for(items * 64, a.wg_per_cu > 0 ? 256 * a.wg_per_cu : big ? (1 << 30) : 256 * 8);
     // (the DMA walk needs the vector path: a.vec; the scalar path of unaligned images never touches the ring)
@@ -1691,7 +1646,7 @@ __device__ __forceinline__ void combine_entry(const CombineEntry &e, long long p
 #pragma unroll
             for (int j = 0; j < 4 * C; j++) {
                 const int p = j / C, ni = nA[p] + nB[p];
-                prepass_elem(ni, (e.pre_flags & 1) ? 1.f : t_quantile(e.pre_table, ni - 1), mA[j], m2A[j], m3A[j], mc[j], dc[j],
+                prepass_elem(ni, prepass_quantile(e.pre_table, e.pre_flags, ni), mA[j], m2A[j], m3A[j], mc[j], dc[j],
                              (e.pre_flags & 2) != 0);
             }
             comb_store<C, VEC>(e.mean_corr, px0, npx, mc);
@@ -1863,7 +1818,7 @@ __device__ __forceinline__ void combine_many_entry(const CombineManyEntry &e, co
 #pragma unroll
         for (int j = 0; j < 4 * C; j++) {
             const int ni = nA[j / C];
-            prepass_elem(ni, (flags & 1) ? 1.f : t_quantile(table, ni - 1), A[0][j], A[M >= 2 ? 1 : 0][j], A[M >= 3 ? 2 : 0][j], mc[j],
+            prepass_elem(ni, prepass_quantile(table, flags, ni), A[0][j], A[M >= 2 ? 1 : 0][j], A[M >= 3 ? 2 : 0][j], mc[j],
                          dc[j], (flags & 2) != 0);
         }
         comb_store<C, VEC>(e.mean_corr, px0, npx, mc);

@@ -1,7 +1,8 @@
 // statmc::plan_accumulate over a fixed list of launches: films on either side of every group-count threshold, every batch-length
 // threshold, the type sets the fused walk takes and refuses, every mix of sample formats, misaligned arenas, row ranges and each
-// debug knob on its own.  Nothing is launched and no device is looked at: the pointers are made up (and aligned as a caller's
-// would be).  One line per case, which tests/test_accumulate_plan_cpu.py compares with tests/golden/accumulate_plan.json:
+// debug knob on its own, and last every (K, M) x format instantiation of the fused walk.  Nothing is launched and no device is
+// looked at: the pointers are made up (and aligned as a caller's would be).  One line per case, which
+// tests/test_accumulate_plan_cpu.py compares with tests/golden/accumulate_plan.json:
 //   name : grid fused loader kernel vec dma umul grid_mode resident_blocks K M fmt lds
 #include <cstdint>
 #include <cstdio>
@@ -27,6 +28,12 @@ const TypeSet kSets[] = {
     {"rad+rgb3", {RAD, RGB, RGB, RGB}},     // K > 2: not fusable
 };
 const TypeSet &kFive = kSets[1];
+// every (K, M) the fused walk is instantiated for: K mean-only RGB types, M mean-only 1-channel types beside the radiance type
+// (a list of its own: the loops over kSets keep their cases)
+const TypeSet kFusedSets[] = {
+    {"k0m1", {RAD, F1}},          {"k0m2", {RAD, F1, F1}},      {"k1m0", {RAD, RGB}},          {"k1m1", {RAD, RGB, F1}},
+    {"k1m2", {RAD, RGB, F1, F1}}, {"k2m0", {RAD, RGB, RGB}},    {"k2m1", {RAD, RGB, RGB, F1}}, {"k2m2", {RAD, RGB, RGB, F1, F1}},
+};
 enum { F32 = 0, FEAT16, ALL16, RAD16 };
 const char *kFmtName[] = {"f32", "feat16", "all16", "rad16"};
 
@@ -165,5 +172,11 @@ int main() {
         for (int s : {256, 16})
             for (int fmt : {F32, FEAT16})
                 show(nameOf(hd, s, kFive, fmt, 1, 256) + " " + kn.name, makeArgs(hd, 0, hd.h, s, kFive, fmt, 1, 256, kn.k));
+    // every instantiation of the fused walk, asked for on one workgroup's film (tests/test_accumulate_fused_sets_gpu.py runs them)
+    Knobs fused1;
+    fused1.fused = 1;
+    for (const TypeSet &set : kFusedSets)
+        for (int fmt : {F32, FEAT16, ALL16})
+            show(nameOf(Film{256, 4}, 4, set, fmt, 1, 256) + " fused1", makeArgs(Film{256, 4}, 0, 4, 4, set, fmt, 1, 256, fused1));
     return 0;
 }

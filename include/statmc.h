@@ -491,6 +491,41 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
 int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                               const int32_t *pixels, int64_t n_records, void *stream);
 
+/* ---- the same queue as the renderer holds it: one interleaved (array-of-structures) record per finished sample, e.g.
+ * struct { int32_t pixel; float radiance[3]; float albedo[3]; float normal[3]; float depth; float id; } -- 48 bytes, or 28 with
+ * the four G-buffer fields in IEEE half.  Record i starts at (char *)records + i * stride; `layout` says where in a record the
+ * pixel index and every type's `channels` values lie and what they are:
+ *   stride            bytes from one record to the next: a multiple of 4, at least 4
+ *   pixel_offset      byte offset of the record's int32 pixel index: a multiple of 4 in [0, stride - 4]; the index means what
+ *                     pixels[i] means for statmc_accumulate_records (outside [0, width * height): a skipped record)
+ *   sample_offset[t]  byte offset of types[t]'s values: a multiple of the element size, the field ends at or before `stride`
+ *   sample_format[t]  STATMC_SAMPLES_F32 (4-byte elements) or STATMC_SAMPLES_F16 (IEEE binary16, 2-byte elements)
+ * Fields may lie in any order, leave padding between them and overlap: the same radiance field may feed a type with the
+ * transform and a plain one.  types[t].samples and n_samples are ignored; `records` must be 4-byte aligned.
+ * DEFINITION: the call leaves, bit for bit, what statmc_accumulate_records leaves when given pixels[i] = record i's pixel and,
+ * for every type, the record-major array of that type's field with half fields widened to fp32 (every finite half widens
+ * exactly, subnormals included).  Everything that entry promises carries over: the per-pixel fold in ascending i, skipped
+ * records that never become an address, untouched pixels that keep every bit, a call over [0, n) equal to calls over [0, m)
+ * and [m, n), the same bits on every run, the optional pre-pass epilogue, asynchronous on `stream`, nothing read back, the
+ * same per-(device, stream) workspace.  The records are read in place: nothing is de-interleaved or copied first.
+ * STATMC_ERR_INVALID before any launch (statmc_last_error() names the argument): the n_records and n_types limits of
+ * statmc_accumulate_records; layout == NULL with n_types > 0 or n_records > 0; a stride, records address, pixel_offset,
+ * sample_offset or sample_format outside the rules above.  Zero records or zero types is a no-op; STATMC_ERR_NO_DEVICE before
+ * statmc_setup.
+ * Why a second entry: a shuffled record of the per-array entry costs one memory line per stat type, an interleaved one costs
+ * one or two in all. */
+typedef struct statmc_record_layout {
+    int32_t stride;             /* bytes from one record to the next */
+    int32_t pixel_offset;       /* byte offset of the record's int32 pixel index */
+    int32_t sample_offset[16];  /* per types[t]: byte offset of its `channels` values */
+    int32_t sample_format[16];  /* per types[t]: STATMC_SAMPLES_F32 or STATMC_SAMPLES_F16 */
+} statmc_record_layout;
+
+int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height,
+        const statmc_stat_type *types, int n_types,
+        const void *records, const statmc_record_layout *layout,
+        int64_t n_records, void *stream);
+
 /* ---- combining independently accumulated statistics (no counterpart in the reference, whose renders can only be split by
  * --baseseed and then not put back together: src/main/pbrt.cpp:71,165-168).  Per pixel and channel, part A in `dst`, part B
  * in `src`, n = nA + nB, delta = meanB - meanA (Chan et al. 1979, Pebay 2008):

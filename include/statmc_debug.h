@@ -59,6 +59,15 @@ int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu);
  * fold only, over the index that the last full or grouping-only call with the same pixels and record count left in the
  * stream's workspace, 3 = both (default).  Any other value: STATMC_ERR_INVALID. */
 int statmc_debug_accumulate_records_phases(int phases);
+/* statmc_accumulate_records_interleaved (to which the phases above apply too), the kernel of its fold: 0 = chosen by the type set
+ * (default); 1 = the general kernel, one lane per pixel and stat type; 2 = the fused kernel, one lane per pixel holding every
+ * type's state, where the call is eligible for it (one RGB type with the transform and three moments plus up to two mean-only
+ * RGB and up to two mean-only 1-channel types, every field fp32, or the feature fields half with the radiance field in either
+ * format), the general kernel elsewhere.  Same bits either way.  Any other value: STATMC_ERR_INVALID. */
+int statmc_debug_accumulate_records_interleaved_path(int path);
+/* The kernel the calling thread's last statmc_accumulate_records_interleaved call planned for its fold: 1 general, 2 fused; 0 if
+ * it has not planned one (no call yet, a no-op, a refused call). */
+int statmc_debug_last_accumulate_records_interleaved_path(void);
 
 /* The placed allocator's probe (statmc_amd/csrc/statmc_placement.hip) on memory of the caller's: streams [stream_ptr, + stream_bytes)
  * while every fourth step read-modify-writes 16 bytes inside [rmw_ptr, + rmw_bytes) -- the words there change.  Best of five, ms.

@@ -1125,6 +1125,38 @@ class Estimator {
         check(statmc_accumulate_records(width, height, types.data(), (int)types.size(), d_pixels, n_records, stream.handle()));
     }
 
+    // ---- the same queue as the renderer holds it: one interleaved record per finished sample (statmc_accumulate_records_interleaved)
+    // d_records: n_records records of layout.stride bytes on this Estimator's device, 4-byte aligned; each holds its int32 pixel
+    // index at layout.pixelOffset and, per listed (type, bounce), the type's channels at `offset` as fp32 (STATMC_SAMPLES_F32) or
+    // IEEE half (STATMC_SAMPLES_F16).  Fields may lie in any order, leave padding and overlap.  The bits of AccumulateRecords on
+    // the de-interleaved arrays (half fields widened to fp32); flushing, device, stream and withPrepass as there, and the records
+    // must stay valid and unchanged until work enqueued on DeviceStream() behind this call has run.  At most 16 fields per call.
+    struct RecordLayout {
+        int stride;          // bytes from one record to the next: a multiple of 4
+        int pixelOffset;     // byte offset of the int32 pixel index: a multiple of 4
+    };
+    struct RecordField {
+        unsigned char statTypeIndex, bounceIndex;
+        int offset;                          // byte offset of the type's values: a multiple of the element size
+        int format = STATMC_SAMPLES_F32;
+        bool withPrepass = false;
+    };
+    void AccumulateRecordsInterleaved(const void *d_records, int64_t n_records, const RecordLayout &layout, const std::vector<RecordField> &fields) {
+        if (fields.size() > 16) throw Error(STATMC_ERR_INVALID, "AccumulateRecordsInterleaved: at most 16 fields per call");
+        std::vector<statmc_stat_type> types;
+        statmc_record_layout l{};
+        l.stride = layout.stride;
+        l.pixel_offset = layout.pixelOffset;
+        for (const RecordField &f : fields) {
+            statmc_stat_type t = DeviceStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
+            l.sample_offset[types.size()] = f.offset;
+            l.sample_format[types.size()] = f.format;
+            types.push_back(t);
+        }
+        check(statmc_set_device(device));
+        check(statmc_accumulate_records_interleaved(width, height, types.data(), (int)types.size(), d_records, &l, n_records, stream.handle()));
+    }
+
     // ---- whole-film sample arenas, in the format the renderer holds them in (statmc_accumulate_formats, include/statmc.h)
     // Per listed (type, bounce) an arena [nSamples][height][width][channels of the type] on this Estimator's device: fp32
     // (format STATMC_SAMPLES_F32) or IEEE half (STATMC_SAMPLES_F16: the bits of the same samples widened to fp32 -- the natural

@@ -76,6 +76,12 @@ class StatType(C.Structure):
     ]
 
 
+class RecordLayout(C.Structure):
+    """statmc_record_layout: where in an interleaved record the pixel index and every stat type's values lie, and in which
+    format (statmc_accumulate_records_interleaved)."""
+    _fields_ = [("stride", C.c_int32), ("pixel_offset", C.c_int32), ("sample_offset", C.c_int32 * 16), ("sample_format", C.c_int32 * 16)]
+
+
 class PrepassContext(C.Structure):
     """statmc_prepass_context: what a renderer's own kernel needs for the pre-pass store of statmc::device::PixelStats
     (include/statmc_device_api.hpp): the current device's t table (device pointer) and the epilogue's flags (1 Welch, 2 small n
@@ -103,7 +109,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -184,6 +190,10 @@ def load():
                                             C.c_void_p, C.c_int, C.c_void_p]
     lib.statmc_accumulate_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.statmc_debug_accumulate_records_phases.argtypes = [C.c_int]
+    lib.statmc_accumulate_records_interleaved.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
+                                                          C.c_int64, C.c_void_p]
+    lib.statmc_debug_accumulate_records_interleaved_path.argtypes = [C.c_int]
+    lib.statmc_debug_last_accumulate_records_interleaved_path.restype = C.c_int
     lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
@@ -668,6 +678,99 @@ def accumulate_records(width, height, stat_types, pixels, stream=None):
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
     check(load().statmc_accumulate_records(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), pixels.numel(),
                                            stream if stream is not None else current_stream_handle()))
+
+
+RECORDS_PATH_AUTO, RECORDS_PATH_GENERAL, RECORDS_PATH_FUSED = 0, 1, 2
+
+
+def make_stat_type_record_field(channels, state, transform, max_moment, prepass_into=None):
+    """Stat type of accumulate_records_interleaved: the state images only -- where its values lie in a record is the layout's to say."""
+    t = StatType()
+    t.channels, t.transform, t.max_moment = int(channels), int(bool(transform)), int(max_moment)
+    t.n = state["n"].data_ptr()
+    t.mean = state["mean"].data_ptr()
+    t.m2 = state["m2"].data_ptr() if state.get("m2") is not None else None
+    t.m3 = state["m3"].data_ptr() if state.get("m3") is not None else None
+    t.film_mean = state["film_mean"].data_ptr() if state.get("film_mean") is not None else None
+    t.film_m2 = state["film_m2"].data_ptr() if state.get("film_m2") is not None else None
+    if prepass_into is not None:
+        t.mean_corr, t.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
+    return t
+
+
+def make_record_layout(stride, pixel_offset, sample_offsets, sample_formats=None):
+    """statmc_record_layout from plain numbers: one offset (and format, default fp32) per stat type, in the order of the types."""
+    lay = RecordLayout()
+    lay.stride, lay.pixel_offset = int(stride), int(pixel_offset)
+    if len(sample_offsets) > 16:
+        raise ValueError("make_record_layout: at most 16 stat types")
+    formats = [SAMPLES_F32] * len(sample_offsets) if sample_formats is None else list(sample_formats)
+    if len(formats) != len(sample_offsets):
+        raise ValueError("make_record_layout: one format per offset")
+    for i, (o, f) in enumerate(zip(sample_offsets, formats)):
+        lay.sample_offset[i], lay.sample_format[i] = int(o), int(f)
+    return lay
+
+
+def pack_records(pixels, fields, formats=None, stride=None, pixel_offset=0, offsets=None, fill=0):
+    """Interleaves numpy arrays into one record buffer (host side; the tests and tools/time_accumulate_records.py use it).
+    pixels: int32 [n]; fields: per stat type a float array [n, C] (or [n]); formats: SAMPLES_F32 | SAMPLES_F16 per field (a half
+    field is rounded to IEEE half here).  offsets: the byte offset of every field; default: the fields behind the pixel index
+    in the order given, each at the next multiple of its element size.  stride: default the end of the last field rounded up to 4.
+    Bytes no field covers hold `fill`.  Returns (records uint8 [n * stride], RecordLayout)."""
+    import numpy as np
+    pixels = np.ascontiguousarray(pixels, dtype=np.int32)
+    n = pixels.size
+    formats = [SAMPLES_F32] * len(fields) if formats is None else list(formats)
+    cols = []
+    for f, fmt in zip(fields, formats):
+        a = np.ascontiguousarray(f, dtype=np.float16 if fmt == SAMPLES_F16 else np.float32)
+        a = a.reshape(n, a.shape[1] if a.ndim == 2 else 1)      # (n = 0 cannot infer the channels)
+        cols.append(a.view(np.uint8).reshape(n, a.shape[1] * a.itemsize))
+    if offsets is None:
+        offsets, at = [], pixel_offset + 4
+        for c, fmt in zip(cols, formats):
+            elem = 2 if fmt == SAMPLES_F16 else 4
+            at = (at + elem - 1) // elem * elem
+            offsets.append(at)
+            at += c.shape[1]
+    end = max([pixel_offset + 4] + [o + c.shape[1] for o, c in zip(offsets, cols)])
+    if stride is None:
+        stride = (end + 3) // 4 * 4
+    if end > stride:
+        raise ValueError("pack_records: a field ends at byte %d, behind the stride %d" % (end, stride))
+    rec = np.full((n, stride), fill, dtype=np.uint8)
+    for o, c in zip(offsets, cols):       # later fields win where fields overlap: hand an overlapping pair the same values
+        rec[:, o:o + c.shape[1]] = c
+    rec[:, pixel_offset:pixel_offset + 4] = pixels.view(np.uint8).reshape(n, 4)
+    return rec.reshape(-1), make_record_layout(stride, pixel_offset, offsets, formats)
+
+
+def accumulate_records_interleaved(width, height, stat_types, records, layout, n_records=None, stream=None):
+    """statmc_accumulate_records_interleaved (include/statmc.h): `records` is a contiguous uint8 or int32 device tensor of
+    n_records records of layout.stride bytes each (default: as many as the tensor holds); stat_types from
+    make_stat_type_record_field, in the order of the layout's fields.  The bits of accumulate_records on the de-interleaved arrays."""
+    tc = _torch()
+    if records.dtype not in (tc.uint8, tc.int32) or not records.is_contiguous():
+        raise ValueError("accumulate_records_interleaved: records must be a contiguous uint8 or int32 tensor")
+    nbytes = records.numel() * records.element_size()
+    if n_records is None:
+        n_records = nbytes // layout.stride if layout.stride > 0 else 0
+    elif int(n_records) * layout.stride > nbytes:
+        raise ValueError("accumulate_records_interleaved: %d records of %d bytes do not fit the tensor (%d bytes)" % (n_records, layout.stride, nbytes))
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    check(load().statmc_accumulate_records_interleaved(int(width), int(height), arr, len(stat_types), records.data_ptr(), C.byref(layout),
+                                                       int(n_records), stream if stream is not None else current_stream_handle()))
+
+
+def accumulate_records_interleaved_path(path):
+    """statmc_debug_accumulate_records_interleaved_path: RECORDS_PATH_AUTO | _GENERAL | _FUSED (where eligible)."""
+    check(load().statmc_debug_accumulate_records_interleaved_path(int(path)))
+
+
+def last_accumulate_records_interleaved_path():
+    """The fold the calling thread's last accumulate_records_interleaved planned: RECORDS_PATH_GENERAL | _FUSED (0: none)."""
+    return int(load().statmc_debug_last_accumulate_records_interleaved_path())
 
 
 def calculate_mean_vars(n, film_m2, film_var, row_n_quirk=True, stream=None):

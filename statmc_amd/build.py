@@ -10,7 +10,7 @@ SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
            "statmc_records.hip"]
-HEADERS = ["statmc_device.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+HEADERS = ["statmc_device.h", "statmc_records_plan.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -95,12 +95,16 @@ DEVICE_ACC_BIN = os.path.join(ROOT, "tools", "bin", "test_device_accumulate")   
 ACC_RECORDS_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records")   # tests/cpp/test_accumulate_records.cpp: Estimator::AccumulateRecords
 ACC_FILM_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_film")   # tests/cpp/test_accumulate_film.cpp: Estimator::AccumulateFilm
 ACC_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_plan")   # tests/cpp/test_accumulate_plan.cpp: statmc::plan_accumulate, no device
+REC_ILV_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_interleaved_plan")   # tests/cpp/test_records_interleaved_plan.cpp: statmc_records_plan.h, no device, no library
+REC_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_interleaved")   # tests/cpp/test_accumulate_records_interleaved.cpp: Estimator::AccumulateRecordsInterleaved
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
          ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp"),
          ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp"),
-         ACC_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_plan.cpp")}
+         ACC_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_plan.cpp"),
+         REC_ILV_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_interleaved_plan.cpp"),
+         REC_ILV_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_interleaved.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")
@@ -119,6 +123,7 @@ def tools_hash():
     files = [os.path.join(ROOT, "tools", src) for src in list(TOOLS.values()) + [DEVICE_EXAMPLE_SRC]]
     files += [os.path.join(inc, f) for f in sorted(os.listdir(inc))]
     files.append(os.path.join(CSRC, "statmc_device.h"))    # test_accumulate_plan.cpp reads the library's own argument blocks
+    files.append(os.path.join(CSRC, "statmc_records_plan.h"))    # ... and test_records_interleaved_plan.cpp the records entries' host decisions
     for path in files:
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "statmc_device.h"
+#include "statmc_records_plan.h"
 
 #include <atomic>
 
@@ -26,6 +27,7 @@ thread_local char g_variant[96] = "none";
 thread_local int g_last_parts = 0, g_last_parts_hi = 0, g_last_tail_rows = 0;
 thread_local const int *g_last_redo = nullptr;   // the item flags of the calling thread's last Welch launch (device memory)
 thread_local int g_last_redo_n = 0;
+thread_local int g_last_rec_ilv_path = 0;   // the fold the calling thread's last statmc_accumulate_records_interleaved call planned (0: none)
 std::mutex g_mu;
 
 // Everything the library remembers is kept per device (one Estimator per device in a process that drives
@@ -44,6 +46,7 @@ struct DeviceState {
     int acc_grid_mode = -1, acc_dma_first = 0;                // launch shape: -1 automatic (by batch length), 0 capped grid, 1 one pass per workgroup; A/B: ring rows requested before the state
     int acc_fused = 0;                                        // the type-fused walk: 0 by shape, 1 whenever eligible, -1 never (statmc_debug_accumulate_fused)
     int rec_phases = 3;                                       // statmc_accumulate_records: 1 grouping, 2 fold, 3 both (statmc_debug_accumulate_records_phases; timing)
+    int rec_ilv_path = 0;                                     // statmc_accumulate_records_interleaved's fold: 0 by the type set, 1 general, 2 fused where eligible (statmc_debug_accumulate_records_interleaved_path)
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
 std::unordered_map<int, DeviceState> g_dev;  // guarded by g_mu
@@ -1531,6 +1534,50 @@ int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat
     return STATMC_OK;
 }
 
+// The same queue as interleaved records (include/statmc.h; what is valid and which fold runs: statmc_records_plan.h).
+int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
+                                          const statmc_record_layout *layout, int64_t n_records, void *stream) {
+    // the limits and the layout first: an argument error is reported whether or not a device has been set up
+    g_last_rec_ilv_path = 0;
+    char why[256];
+    if (!statmc::check_records_interleaved(types, n_types, records, layout, n_records, why, sizeof(why))) return fail(STATMC_ERR_INVALID, "%s", why);
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0 || n_records == 0) return STATMC_OK;
+    if (!records) return fail(STATMC_ERR_INVALID, "null records");
+    statmc::RecordsInterleavedArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_types = n_types;
+    k.n_records = n_records;
+    k.n_px = (long long)width * height;
+    k.records = static_cast<const char *>(records);
+    k.stride = layout->stride;
+    k.pixel_off = layout->pixel_offset;
+    bool epilogue = false;
+    for (int i = 0; i < n_types; i++) {
+        statmc::AccumulateType checked;   // the validation of every accumulate entry; samples and n_samples are ignored here
+        statmc_stat_type t = types[i];
+        t.samples = static_cast<const float *>(records);
+        if (int rc = fill_stat_type(dstate, t, i, width, height, false, checked)) return rc;
+        k.t[i] = t;
+        k.t[i].samples = nullptr;
+        k.t[i].transform = t.transform ? 1 : 0;
+        k.off[i] = layout->sample_offset[i];
+        if (layout->sample_format[i] == STATMC_SAMPLES_F16) k.half_mask |= 1u << i;
+        epilogue = epilogue || t.mean_corr != nullptr;
+    }
+    if (epilogue)
+        if (int rc = statmc_get_prepass_context(&k.ctx)) return rc;
+    const statmc::RecordsInterleavedPlan plan = statmc::plan_records_interleaved(k.t, n_types, *layout, dstate.rec_ilv_path);
+    statmc::RecordsWorkspace w;
+    HIP_TRY(statmc::records_interleaved_workspace_layout(k.n_records, k.n_px, w));
+    char *ws = nullptr;
+    if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
+    HIP_TRY(statmc::launch_accumulate_records_interleaved(k, plan, w, ws, dstate.rec_phases, S(stream)));
+    g_last_rec_ilv_path = plan.path;
+    return STATMC_OK;
+}
+
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,
                        const int32_t *tile_bounds, const int64_t *tile_offsets, int n_tiles, int max_tile_pixels,
                        int32_t *n, float *mean, float *m2, float *m3, float *film_mean, float *film_m2, void *stream) {
@@ -1646,6 +1693,11 @@ int statmc_debug_accumulate_records_phases(int phases) {
     if (phases < 1 || phases > 3) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_records_phases(%d): 1, 2 or 3", phases);
     STATMC_DEBUG_SET(d.rec_phases = phases);
 }
+int statmc_debug_accumulate_records_interleaved_path(int path) {   // the interleaved records' fold: 0 by the type set, 1 general, 2 fused where eligible
+    if (path < 0 || path > 2) return fail(STATMC_ERR_INVALID, "statmc_debug_accumulate_records_interleaved_path(%d): 0, 1 or 2", path);
+    STATMC_DEBUG_SET(d.rec_ilv_path = path);
+}
+int statmc_debug_last_accumulate_records_interleaved_path(void) { return g_last_rec_ilv_path; }
 int statmc_debug_force_filter_parts(int k) { return statmc_set_filter_split(k < 0 ? 0 : k); }   // the older name of the pin
 int statmc_debug_last_filter_parts(void) { return g_last_parts; }
 // the tail split of the calling thread's last pair-symmetric launch: parts of the last `*tail_rows` tile rows (0: uniform)

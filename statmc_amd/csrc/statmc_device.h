@@ -147,6 +147,26 @@ hipError_t records_workspace_layout(long long n_records, long long n_px, Records
 hipError_t launch_accumulate_records(const RecordsArgs &a, const int32_t *pixels, const RecordsWorkspace &w, char *ws, int phases,
                                      hipStream_t s);
 
+// statmc_accumulate_records_interleaved (statmc_records.hip; the host's decisions: statmc_records_plan.h): record i starts at
+// records + i * stride and holds its pixel index at pixel_off and type t's values at off[t], half where bit t of half_mask is set.
+// The grouping, order[], seg[] and the workspace are statmc_accumulate_records'.
+struct RecordsInterleavedArgs {
+    statmc_stat_type t[kMaxStatTypes];
+    statmc_prepass_context ctx;
+    const int32_t *order;
+    const int32_t *seg;
+    const char *records;
+    long long n_records, n_px;
+    int n_types;
+    int stride, pixel_off;
+    int off[kMaxStatTypes];
+    unsigned half_mask;
+};
+struct RecordsInterleavedPlan;      // statmc_records_plan.h
+hipError_t records_interleaved_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w);   // host only: no launch
+hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w, char *ws,
+                                                 int phases, hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

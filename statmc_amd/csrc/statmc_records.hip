@@ -30,6 +30,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "statmc_device.h"
+#include "statmc_records_plan.h"
 
 #include "../../include/statmc_device_api.hpp"
 
@@ -197,6 +198,318 @@ hipError_t sort_records(void *temp, size_t &temp_bytes, const int32_t *pixels, u
                                      (unsigned)n, 0u, key_bits(n_px), s);
 }
 
+// ------------------------------------------------------------------ interleaved (array-of-structures) records
+// statmc_accumulate_records_interleaved: record i is `stride` bytes at records + i * stride and holds its pixel index and every
+// type's values (include/statmc.h).  The grouping is the one above -- the sort's key iterator reads record i's pixel through the
+// stride, nothing is copied out first -- and leaves the same order[] and seg[].  Two folds (which one: plan_records_interleaved):
+//
+//   general   records_fold_kernel's shape: workgroup b serves stat type b % n_types and 256 pixels, one lane per pixel and type.
+//             The lane reads its own field of the record at order[j]: a 4-byte aligned load of C floats, or a 2-byte aligned one of
+//             C halves.  Every valid call.
+//   fused     one lane per pixel holds the state of every type of the set (the type-fused film-major walk's sets: the radiance
+//             type, K <= 2 mean-only RGB types, M <= 2 mean-only 1-channel types) and reads every field of the record once, as
+//             dwords at 4-byte alignment -- a half field as the one or two dwords that hold it, taken apart in registers: a
+//             record's memory line is requested by one lane instead of by one lane per type, in five workgroups.
+//
+// Both walk a run the way fold_pixel does (walk_run below is that walk with the gather and the fold handed in): four indices
+// per load, the gathers of the next batches requested before this batch's dependent adds, clamped past the last whole batch.
+// What is in flight stays RAW (the loaded dwords): a half is widened when its sample is folded, not when it is requested -- a
+// conversion behind the load would wait for it there and nothing would run ahead.
+
+// record i's key: its pixel, read in place (`pixel0` = records + pixel_offset), or n_px for a dead one
+struct StridedRecordKey {
+    const char *pixel0;
+    long long stride;
+    unsigned n_px;
+    __host__ __device__ unsigned operator()(int32_t i) const {
+        const int32_t p = *reinterpret_cast<const int32_t *>(pixel0 + (long long)i * stride);
+        return (p >= 0 && (unsigned)p < n_px) ? (unsigned)p : n_px;
+    }
+};
+using StridedKeyIterator = rocprim::transform_iterator<rocprim::counting_iterator<int32_t>, StridedRecordKey, unsigned>;
+
+hipError_t sort_records_strided(void *temp, size_t &temp_bytes, const char *pixel0, long long stride, unsigned *keys, int32_t *order, long long n,
+                                unsigned n_px, hipStream_t s) {
+    return rocprim::radix_sort_pairs(temp, temp_bytes, StridedKeyIterator(rocprim::counting_iterator<int32_t>(0), StridedRecordKey{pixel0, stride, n_px}),
+                                     keys, rocprim::counting_iterator<int32_t>(0), order, (unsigned)n, 0u, key_bits(n_px), s);
+}
+
+typedef unsigned rec_uint3 __attribute__((ext_vector_type(3), aligned(4)));
+typedef unsigned rec_uint2 __attribute__((ext_vector_type(2), aligned(4)));
+
+// the loaded dwords of one record: what a batch holds between request and fold
+template <int N>
+struct RecRaw {
+    unsigned r[N];
+    __device__ __forceinline__ void pin() {      // fold_pixel's empty asm (trap 1 of DESIGN 4.1c)
+#pragma unroll
+        for (int i = 0; i < N; i++) asm("" : "+v"(r[i]));
+    }
+};
+
+// every finite half is an fp32 value, subnormals included: one v_cvt_f32_f16
+__device__ __forceinline__ float rec_half_to_float(unsigned bits16) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16); }
+
+// One field of a record -- C elements -- as it is requested and as it is folded.
+//   kFieldF32         C floats at a 4-byte aligned address: one dword, or one dwordx3
+//   kFieldHalfElems   C halves at a 2-byte aligned address, element by element (the general fold)
+//   kFieldHalfDwords  C halves as the dwords that hold them (the fused fold): load() is given the field's address rounded DOWN
+//                     to 4 bytes, decode() the bit position of the first element in the first dword (0 or 16).  The record
+//                     starts 4-byte aligned and the stride is a multiple of 4, so the dwords lie inside the record: three
+//                     halves at offset o occupy [o, o + 6) and are read as [o & ~3, (o & ~3) + 8), one half as one dword.
+enum { kFieldF32 = 0, kFieldHalfElems, kFieldHalfDwords };
+template <int C, int F>
+struct RecField {
+    static constexpr int kRegs = F == kFieldHalfDwords ? (C == 3 ? 2 : 1) : C;
+    static __device__ __forceinline__ void load(const char *__restrict__ at, unsigned *r) {
+        if constexpr (F == kFieldHalfElems) {
+            const unsigned short *h = reinterpret_cast<const unsigned short *>(at);
+#pragma unroll
+            for (int c = 0; c < C; c++) r[c] = h[c];
+        } else if constexpr (kRegs == 3) {
+            const rec_uint3 x = *reinterpret_cast<const rec_uint3 *>(at);
+            r[0] = x.x;
+            r[1] = x.y;
+            r[2] = x.z;
+        } else if constexpr (kRegs == 2) {
+            const rec_uint2 x = *reinterpret_cast<const rec_uint2 *>(at);
+            r[0] = x.x;
+            r[1] = x.y;
+        } else {
+            r[0] = *reinterpret_cast<const unsigned *>(at);
+        }
+    }
+    static __device__ __forceinline__ void decode(const unsigned *r, int shift, float *v) {
+        if constexpr (F == kFieldF32) {
+#pragma unroll
+            for (int c = 0; c < C; c++) v[c] = __uint_as_float(r[c]);
+        } else if constexpr (F == kFieldHalfElems) {
+#pragma unroll
+            for (int c = 0; c < C; c++) v[c] = rec_half_to_float(r[c]);
+        } else if constexpr (C == 3) {
+            const unsigned long long w = (((unsigned long long)r[1] << 32) | r[0]) >> shift;
+            v[0] = rec_half_to_float((unsigned)w & 0xffffu);
+            v[1] = rec_half_to_float((unsigned)(w >> 16) & 0xffffu);
+            v[2] = rec_half_to_float((unsigned)(w >> 32) & 0xffffu);
+        } else {
+            v[0] = rec_half_to_float((r[0] >> shift) & 0xffffu);
+        }
+    }
+};
+
+// fold_pixel's walk over run[0 .. cnt) with the request and the fold handed in: gather(rec, s) requests record rec into s (loads
+// only), fold(s) folds it.  The comments there apply word for word.
+template <class S, class G, class F>
+__device__ __forceinline__ void walk_run(const int32_t *__restrict__ run, int cnt, G gather, F fold) {
+    int j = 0;
+    if (cnt >= kRecBatch) {
+        const int last = cnt - kRecBatch;
+        rec_int4 idx_a = *reinterpret_cast<const rec_int4 *>(run);
+        rec_int4 idx_b = *reinterpret_cast<const rec_int4 *>(run + min(kRecBatch, last));
+        S A[kRecBatch], B[kRecBatch];
+#pragma unroll
+        for (int u = 0; u < kRecBatch; u++) gather(idx_a[u], A[u]);
+#pragma unroll
+        for (int u = 0; u < kRecBatch; u++) {
+            asm("" : "+v"(idx_b[u]));
+            A[u].pin();
+        }
+        // invariant: A = the records of batch j / 4 (requested), idx_b = the indices of the batch after it
+        for (; j + 2 * kRecBatch <= cnt; j += 2 * kRecBatch) {
+            idx_a = *reinterpret_cast<const rec_int4 *>(run + min(j + 2 * kRecBatch, last));
+            rec_issue_fence();
+#pragma unroll
+            for (int u = 0; u < kRecBatch; u++) gather(idx_b[u], B[u]);
+#pragma unroll
+            for (int u = 0; u < kRecBatch; u++) fold(A[u]);
+            idx_b = *reinterpret_cast<const rec_int4 *>(run + min(j + 3 * kRecBatch, last));
+            rec_issue_fence();
+#pragma unroll
+            for (int u = 0; u < kRecBatch; u++) gather(idx_a[u], A[u]);
+#pragma unroll
+            for (int u = 0; u < kRecBatch; u++) fold(B[u]);
+        }
+        if (j + kRecBatch <= cnt) {   // an odd number of whole batches: the last one is in A
+#pragma unroll
+            for (int u = 0; u < kRecBatch; u++) fold(A[u]);
+            j += kRecBatch;
+        }
+    }
+    for (; j < cnt; j++) {   // the last cnt % 4 records, and runs shorter than a batch
+        S s;
+        gather(run[j], s);
+        fold(s);
+    }
+}
+
+template <int C, int MAXM, bool TRANSFORM, bool HALF>
+__device__ __forceinline__ void fold_pixel_interleaved(const statmc_stat_type &t, const statmc_prepass_context &ctx, const int32_t *__restrict__ order,
+                                                       const char *__restrict__ field0, long long stride, long long p, int start, int cnt) {
+    using Field = RecField<C, HALF ? kFieldHalfElems : kFieldF32>;
+    using S = RecRaw<Field::kRegs>;
+    device::PixelStats<C, MAXM, TRANSFORM> ps;
+    ps.load(t, p);
+    walk_run<S>(
+        order + start, cnt, [&](int rec, S &s) __attribute__((always_inline)) { Field::load(field0 + (long long)rec * stride, s.r); },
+        [&](const S &s) __attribute__((always_inline)) {
+            float v[C];
+            Field::decode(s.r, 0, v);
+            ps.add(v);
+        });
+    if constexpr (MAXM >= 3) {
+        if (t.mean_corr != nullptr) {
+            ps.store(t, p, ctx);
+            return;
+        }
+    }
+    ps.store(t, p);
+}
+
+template <int C, bool HALF>
+__device__ __forceinline__ void fold_type_interleaved(const statmc_stat_type &t, const statmc_prepass_context &ctx, const int32_t *__restrict__ order,
+                                                      const char *__restrict__ field0, long long stride, long long p, int start, int cnt) {
+    if (t.transform) {
+        if (t.max_moment >= 3) fold_pixel_interleaved<C, 3, true, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+        else if (t.max_moment == 2) fold_pixel_interleaved<C, 2, true, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+        else fold_pixel_interleaved<C, 1, true, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+    } else {
+        if (t.max_moment >= 3) fold_pixel_interleaved<C, 3, false, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+        else if (t.max_moment == 2) fold_pixel_interleaved<C, 2, false, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+        else fold_pixel_interleaved<C, 1, false, HALF>(t, ctx, order, field0, stride, p, start, cnt);
+    }
+}
+
+// The general fold.  Workgroup b serves stat type b % n_types and pixels [256 (b / n_types), + 256), as in records_fold_kernel.
+__global__ __launch_bounds__(kRecBlock) void records_interleaved_fold_kernel(RecordsInterleavedArgs a) {
+    const int ti = (int)(blockIdx.x % (unsigned)a.n_types);
+    const long long p = (long long)(blockIdx.x / (unsigned)a.n_types) * kRecBlock + threadIdx.x;
+    if (p >= a.n_px) return;
+    const int start = a.seg[2 * p], cnt = a.seg[2 * p + 1] - start;
+    if (cnt <= 0) return;
+    // COPIED out of the by-value argument
+    const statmc_stat_type t = a.t[ti];
+    const statmc_prepass_context ctx = a.ctx;
+    const int32_t *order = a.order;
+    const char *field0 = a.records + a.off[ti];     // the type's field of record 0
+    const long long stride = a.stride;
+    const bool half = (a.half_mask >> ti) & 1u;
+    if (t.channels == 3) {
+        if (half) fold_type_interleaved<3, true>(t, ctx, order, field0, stride, p, start, cnt);
+        else fold_type_interleaved<3, false>(t, ctx, order, field0, stride, p, start, cnt);
+    } else {
+        if (half) fold_type_interleaved<1, true>(t, ctx, order, field0, stride, p, start, cnt);
+        else fold_type_interleaved<1, false>(t, ctx, order, field0, stride, p, start, cnt);
+    }
+}
+
+// The fused fold's argument: slot 0 the radiance type, then the K mean-only RGB types, then the M mean-only 1-channel types.
+struct RecordsFusedArgs {
+    statmc_stat_type t[kRecFusedTypes];
+    statmc_prepass_context ctx;
+    const int32_t *order;
+    const int32_t *seg;
+    const char *records;
+    long long n_px;
+    int stride;
+    int off[kRecFusedTypes];
+};
+
+// FMT as plan_records_interleaved has it: 0 every field fp32, 1 the feature fields half, 2 the radiance field too.
+template <int K, int M, int FMT>
+__global__ __launch_bounds__(kRecBlock) void records_interleaved_fused_kernel(RecordsFusedArgs a) {
+    using FRad = RecField<3, FMT == 2 ? kFieldHalfDwords : kFieldF32>;
+    using FRgb = RecField<3, FMT >= 1 ? kFieldHalfDwords : kFieldF32>;
+    using FOne = RecField<1, FMT >= 1 ? kFieldHalfDwords : kFieldF32>;
+    constexpr int kRgb0 = FRad::kRegs, kOne0 = kRgb0 + K * FRgb::kRegs;
+    using S = RecRaw<kOne0 + M * FOne::kRegs>;
+    constexpr int kAlign = FMT >= 1 ? ~3 : ~0;      // where a field's load starts: half fields at the dword that holds their first element
+
+    const long long p = (long long)blockIdx.x * kRecBlock + threadIdx.x;
+    if (p >= a.n_px) return;
+    const int start = a.seg[2 * p], cnt = a.seg[2 * p + 1] - start;
+    if (cnt <= 0) return;
+    // COPIED out of the by-value argument; every index below is a constant after unrolling
+    const statmc_stat_type t_rad = a.t[0];
+    statmc_stat_type t_rgb[K > 0 ? K : 1], t_one[M > 0 ? M : 1];
+    const char *rgb0[K > 0 ? K : 1], *one0[M > 0 ? M : 1];       // the field of record 0
+    int rgb_shift[K > 0 ? K : 1], one_shift[M > 0 ? M : 1];
+    const char *rad0 = a.records + (a.off[0] & (FMT == 2 ? ~3 : ~0));
+    const int rad_shift = (a.off[0] & 2) * 8;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        t_rgb[i] = a.t[1 + i];
+        rgb0[i] = a.records + (a.off[1 + i] & kAlign);
+        rgb_shift[i] = (a.off[1 + i] & 2) * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        t_one[i] = a.t[1 + K + i];
+        one0[i] = a.records + (a.off[1 + K + i] & kAlign);
+        one_shift[i] = (a.off[1 + K + i] & 2) * 8;
+    }
+    const statmc_prepass_context ctx = a.ctx;
+    const long long stride = a.stride;
+
+    device::PixelStats<3, 3, true> rad;
+    device::PixelStats<3, 1, false> rgb[K > 0 ? K : 1];
+    device::PixelStats<1, 1, false> one[M > 0 ? M : 1];
+    rad.load(t_rad, p);
+#pragma unroll
+    for (int i = 0; i < K; i++) rgb[i].load(t_rgb[i], p);
+#pragma unroll
+    for (int i = 0; i < M; i++) one[i].load(t_one[i], p);
+
+    walk_run<S>(
+        a.order + start, cnt,
+        [&](int rec, S &s) __attribute__((always_inline)) {
+            const long long at = (long long)rec * stride;
+            FRad::load(rad0 + at, s.r);
+#pragma unroll
+            for (int i = 0; i < K; i++) FRgb::load(rgb0[i] + at, s.r + kRgb0 + i * FRgb::kRegs);
+#pragma unroll
+            for (int i = 0; i < M; i++) FOne::load(one0[i] + at, s.r + kOne0 + i * FOne::kRegs);
+        },
+        [&](const S &s) __attribute__((always_inline)) {
+            float v[3];
+            FRad::decode(s.r, rad_shift, v);
+            rad.add(v);
+#pragma unroll
+            for (int i = 0; i < K; i++) {
+                FRgb::decode(s.r + kRgb0 + i * FRgb::kRegs, rgb_shift[i], v);
+                rgb[i].add(v);
+            }
+#pragma unroll
+            for (int i = 0; i < M; i++) {
+                FOne::decode(s.r + kOne0 + i * FOne::kRegs, one_shift[i], v);
+                one[i].add(v);
+            }
+        });
+
+    if (t_rad.mean_corr != nullptr) rad.store(t_rad, p, ctx);
+    else rad.store(t_rad, p);
+#pragma unroll
+    for (int i = 0; i < K; i++) rgb[i].store(t_rgb[i], p);
+#pragma unroll
+    for (int i = 0; i < M; i++) one[i].store(t_one[i], p);
+}
+
+template <int FMT>
+hipError_t launch_records_fused(const RecordsFusedArgs &f, int K, int M, unsigned blocks, hipStream_t s) {
+    const dim3 grid(blocks), block(kRecBlock);
+    switch (3 * K + M) {
+    case 1: hipLaunchKernelGGL((records_interleaved_fused_kernel<0, 1, FMT>), grid, block, 0, s, f); break;
+    case 2: hipLaunchKernelGGL((records_interleaved_fused_kernel<0, 2, FMT>), grid, block, 0, s, f); break;
+    case 3: hipLaunchKernelGGL((records_interleaved_fused_kernel<1, 0, FMT>), grid, block, 0, s, f); break;
+    case 4: hipLaunchKernelGGL((records_interleaved_fused_kernel<1, 1, FMT>), grid, block, 0, s, f); break;
+    case 5: hipLaunchKernelGGL((records_interleaved_fused_kernel<1, 2, FMT>), grid, block, 0, s, f); break;
+    case 6: hipLaunchKernelGGL((records_interleaved_fused_kernel<2, 0, FMT>), grid, block, 0, s, f); break;
+    case 7: hipLaunchKernelGGL((records_interleaved_fused_kernel<2, 1, FMT>), grid, block, 0, s, f); break;
+    case 8: hipLaunchKernelGGL((records_interleaved_fused_kernel<2, 2, FMT>), grid, block, 0, s, f); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t records_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w) {
@@ -231,6 +544,64 @@ hipError_t launch_accumulate_records(const RecordsArgs &a_in, const int32_t *pix
         a.seg = seg;
         const long long blocks = (a.n_px + kRecBlock - 1) / kRecBlock * a.n_types;
         hipLaunchKernelGGL(records_fold_kernel, dim3((unsigned)blocks), dim3(kRecBlock), 0, s, a);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// statmc_accumulate_records' blocks at their offsets; the sort's temporary -- the last block -- is what the sort over the strided
+// key iterator asks for, where that is more
+hipError_t records_interleaved_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w) {
+    if (hipError_t e = records_workspace_layout(n_records, n_px, w); e != hipSuccess) return e;
+    size_t need = 0;
+    if (hipError_t e = sort_records_strided(nullptr, need, nullptr, 4, nullptr, nullptr, n_records, (unsigned)n_px, nullptr); e != hipSuccess) return e;
+    if (need > w.temp_bytes) {
+        w.temp_bytes = need;
+        w.bytes = w.temp_off + align256(w.temp_bytes);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a_in, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w,
+                                                 char *ws, int phases, hipStream_t s) {
+    RecordsInterleavedArgs a = a_in;
+    unsigned *keys = reinterpret_cast<unsigned *>(ws + w.keys_off);
+    int32_t *order = reinterpret_cast<int32_t *>(ws + w.order_off);
+    int32_t *seg = reinterpret_cast<int32_t *>(ws + w.seg_off);
+    if (phases & 1) {
+        if (hipError_t e = hipMemsetAsync(seg, 0, w.seg_bytes, s); e != hipSuccess) return e;
+        size_t temp_bytes = w.temp_bytes;
+        if (hipError_t e = sort_records_strided(ws + w.temp_off, temp_bytes, a.records + a.pixel_off, a.stride, keys, order, a.n_records, (unsigned)a.n_px, s);
+            e != hipSuccess)
+            return e;
+        const long long blocks = (a.n_records + kRecBlock - 1) / kRecBlock;
+        hipLaunchKernelGGL(records_segments_kernel, dim3((unsigned)blocks), dim3(kRecBlock), 0, s, keys, a.n_records, (unsigned)a.n_px, seg);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    if (phases & 2) {
+        const long long px_blocks = (a.n_px + kRecBlock - 1) / kRecBlock;
+        if (plan.path == kRecIlvFused) {
+            RecordsFusedArgs f{};
+            for (int j = 0; j < 1 + plan.K + plan.M; j++) {
+                f.t[j] = a.t[plan.order[j]];
+                f.off[j] = a.off[plan.order[j]];
+            }
+            f.ctx = a.ctx;
+            f.order = order;
+            f.seg = seg;
+            f.records = a.records;
+            f.n_px = a.n_px;
+            f.stride = a.stride;
+            switch (plan.fmt) {
+            case 0: return launch_records_fused<0>(f, plan.K, plan.M, (unsigned)px_blocks, s);
+            case 1: return launch_records_fused<1>(f, plan.K, plan.M, (unsigned)px_blocks, s);
+            case 2: return launch_records_fused<2>(f, plan.K, plan.M, (unsigned)px_blocks, s);
+            }
+            return hipErrorInvalidValue;
+        }
+        a.order = order;
+        a.seg = seg;
+        hipLaunchKernelGGL(records_interleaved_fold_kernel, dim3((unsigned)(px_blocks * a.n_types)), dim3(kRecBlock), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;

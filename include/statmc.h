@@ -485,9 +485,8 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
  * slot.
  * Cost: the grouping is linear in the records whatever their distribution.  The fold gives a pixel to one lane, and the fold of
  * one pixel is a sequential chain BY DEFINITION: the launch ends when its longest run ends, so a few pixels with tens of
- * thousands of records end it on a few lanes.  Remedy: deal such a pixel's records to several states (several calls into
- * several sets of images) and put them together with statmc_combine_many -- not the same bits as one fold, but the same
- * statistics. */
+ * thousands of records end it on a few lanes.  Remedy: statmc_accumulate_records_split below, which folds a long run with the
+ * 64 lanes of a wave -- not the same bits as one fold, but the same statistics. */
 int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                               const int32_t *pixels, int64_t n_records, void *stream);
 
@@ -525,6 +524,47 @@ int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height,
         const statmc_stat_type *types, int n_types,
         const void *records, const statmc_record_layout *layout,
         int64_t n_records, void *stream);
+
+/* ---- the same two queues with heavy-tailed counts: a pixel's LONG run is split over the 64 lanes of a wave.  The argument lists
+ * are statmc_accumulate_records' and statmc_accumulate_records_interleaved's plus split_above in front of `stream`.
+ * DEFINITION, per pixel.  Pixel p's run is its live records of this call in ascending record index, exactly as for
+ * statmc_accumulate_records; c is its length.
+ *   c <= split_above  the pixel is folded as statmc_accumulate_records folds it: the same bits.  c == 0: untouched, every bit of
+ *                     every image stays, mean_corr / discriminator included.
+ *   c >  split_above  the run is cut into STATMC_RECORDS_SPLIT_LANES = 64 contiguous chunks of L = ceil(c / 64) records: slot j
+ *                     owns the run's positions [min(j L, c), min((j + 1) L, c)); trailing slots may be empty.  Slot 0 starts
+ *                     from the pixel's stored state, every slot j > 0 from the state of no samples (n = 0, all moments 0), and
+ *                     each folds its chunk in order.  The 64 states are merged in the tree of statmc::device::merge_lanes<64>
+ *                     (include/statmc_device_api.hpp):
+ *                         for stride = 1, 2, 4, 8, 16, 32: for every j with j % (2 stride) == 0: slot[j].merge(slot[j + stride])
+ *                     and slot 0's result is stored -- with mean_corr / discriminator given, the pre-pass of the merged moments
+ *                     too.
+ * Through the other entries, a split pixel holds bit for bit what these calls leave: statmc_accumulate_records of chunk 0 into
+ * the stored state; statmc_accumulate_records of chunk j into zeroed images, j = 1 .. 63; 63 two-part
+ * statmc_combine_statistics calls in the tree's order (dst = set j, src = set j + stride); statmc_prepass of the result where
+ * the epilogue is asked for.  The chunks and the tree are functions of c alone: which lanes, waves or compute units did the work
+ * reaches no bit.  The interleaved entry leaves, bit for bit, what the per-array split entry leaves on the de-interleaved arrays
+ * with half fields widened -- the relation of the two entries above.
+ * Carried over from those entries: dead records (any pixel value outside [0, width * height)) are never folded and never become
+ * an address; the result does not depend on how records of DIFFERENT pixels interleave; the same inputs and the same
+ * split_above give the same bits on every run; asynchronous on `stream`, nothing read back, the same per-(device, stream)
+ * workspace, which may grow; zero records or zero types is a no-op; the n_records / n_types / layout limits and their
+ * STATMC_ERR_INVALID messages; STATMC_ERR_NO_DEVICE before statmc_setup, after the argument limits.
+ * NOT carried over: for a split pixel a call over [0, n) is NOT a call over [0, m) followed by one over [m, n) (the chunks are
+ * those of the call's run), and the bits differ from statmc_accumulate_records' in the last places: the statistics are the
+ * same, the fold order is not.
+ * split_above < 1 is STATMC_ERR_INVALID before any launch (statmc_last_error() names split_above).  With split_above at least
+ * the longest run (INT32_MAX: never split) every bit is statmc_accumulate_records'.  STATMC_RECORDS_SPLIT_DEFAULT is the
+ * measured choice.
+ * A single pixel beyond what 64 lanes handle well (millions of records) stays the caller's business: deal its records to
+ * several states (several calls into several sets of images) and put them together with statmc_combine_many. */
+#define STATMC_RECORDS_SPLIT_LANES 64
+#define STATMC_RECORDS_SPLIT_DEFAULT 256
+int statmc_accumulate_records_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                                    const int32_t *pixels, int64_t n_records, int32_t split_above, void *stream);
+int statmc_accumulate_records_interleaved_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                                    const void *records, const statmc_record_layout *layout, int64_t n_records,
+                                    int32_t split_above, void *stream);
 
 /* ---- combining independently accumulated statistics (no counterpart in the reference, whose renders can only be split by
  * --baseseed and then not put back together: src/main/pbrt.cpp:71,165-168).  Per pixel and channel, part A in `dst`, part B

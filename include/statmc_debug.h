@@ -57,7 +57,8 @@ int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu);
 
 /* statmc_accumulate_records, for timing its two steps apart (tools/time_accumulate_records.py): 1 = the grouping only, 2 = the
  * fold only, over the index that the last full or grouping-only call with the same pixels and record count left in the
- * stream's workspace, 3 = both (default).  Any other value: STATMC_ERR_INVALID. */
+ * stream's workspace, 3 = both (default).  Any other value: STATMC_ERR_INVALID.  Applies to statmc_accumulate_records_split and
+ * statmc_accumulate_records_interleaved_split as well (tools/time_accumulate_records_split.py). */
 int statmc_debug_accumulate_records_phases(int phases);
 /* statmc_accumulate_records_interleaved (to which the phases above apply too), the kernel of its fold: 0 = chosen by the type set
  * (default); 1 = the general kernel, one lane per pixel and stat type; 2 = the fused kernel, one lane per pixel holding every

@@ -1124,6 +1124,20 @@ class Estimator {
         check(statmc_set_device(device));
         check(statmc_accumulate_records(width, height, types.data(), (int)types.size(), d_pixels, n_records, stream.handle()));
     }
+    // ... for queues with heavy-tailed counts (statmc_accumulate_records_split): a pixel with more than splitAbove records in this
+    // call is folded by the 64 lanes of a wave -- 64 chunks of its run, merged in a fixed tree: the same statistics as above, other
+    // last bits, and for such a pixel one call is not two calls over halves of the queue.  Pixels up to splitAbove keep the bits
+    // above.  splitAbove >= 1; STATMC_RECORDS_SPLIT_DEFAULT is the measured choice.
+    void AccumulateRecords(const int32_t *d_pixels, int64_t n_records, const std::vector<RecordSamples> &buffers, int splitAbove) {
+        std::vector<statmc_stat_type> types;
+        for (const RecordSamples &r : buffers) {
+            statmc_stat_type t = DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);
+            t.samples = r.d_samples;
+            types.push_back(t);
+        }
+        check(statmc_set_device(device));
+        check(statmc_accumulate_records_split(width, height, types.data(), (int)types.size(), d_pixels, n_records, splitAbove, stream.handle()));
+    }
 
     // ---- the same queue as the renderer holds it: one interleaved record per finished sample (statmc_accumulate_records_interleaved)
     // d_records: n_records records of layout.stride bytes on this Estimator's device, 4-byte aligned; each holds its int32 pixel
@@ -1142,6 +1156,16 @@ class Estimator {
         bool withPrepass = false;
     };
     void AccumulateRecordsInterleaved(const void *d_records, int64_t n_records, const RecordLayout &layout, const std::vector<RecordField> &fields) {
+        accumulateRecordsInterleaved(d_records, n_records, layout, fields, false, 0);
+    }
+    // ... with long runs split (statmc_accumulate_records_interleaved_split): the bits of AccumulateRecords(..., splitAbove) on the
+    // de-interleaved arrays.  splitAbove >= 1.
+    void AccumulateRecordsInterleaved(const void *d_records, int64_t n_records, const RecordLayout &layout, const std::vector<RecordField> &fields,
+                                      int splitAbove) {
+        accumulateRecordsInterleaved(d_records, n_records, layout, fields, true, splitAbove);
+    }
+    void accumulateRecordsInterleaved(const void *d_records, int64_t n_records, const RecordLayout &layout, const std::vector<RecordField> &fields,
+                                      bool split, int splitAbove) {
         if (fields.size() > 16) throw Error(STATMC_ERR_INVALID, "AccumulateRecordsInterleaved: at most 16 fields per call");
         std::vector<statmc_stat_type> types;
         statmc_record_layout l{};
@@ -1154,7 +1178,8 @@ class Estimator {
             types.push_back(t);
         }
         check(statmc_set_device(device));
-        check(statmc_accumulate_records_interleaved(width, height, types.data(), (int)types.size(), d_records, &l, n_records, stream.handle()));
+        if (!split) check(statmc_accumulate_records_interleaved(width, height, types.data(), (int)types.size(), d_records, &l, n_records, stream.handle()));
+        else check(statmc_accumulate_records_interleaved_split(width, height, types.data(), (int)types.size(), d_records, &l, n_records, splitAbove, stream.handle()));
     }
 
     // ---- whole-film sample arenas, in the format the renderer holds them in (statmc_accumulate_formats, include/statmc.h)

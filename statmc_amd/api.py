@@ -109,7 +109,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -192,6 +192,9 @@ def load():
     lib.statmc_debug_accumulate_records_phases.argtypes = [C.c_int]
     lib.statmc_accumulate_records_interleaved.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
                                                           C.c_int64, C.c_void_p]
+    lib.statmc_accumulate_records_split.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.statmc_accumulate_records_interleaved_split.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
+                                                                C.c_int64, C.c_int32, C.c_void_p]
     lib.statmc_debug_accumulate_records_interleaved_path.argtypes = [C.c_int]
     lib.statmc_debug_last_accumulate_records_interleaved_path.restype = C.c_int
     lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
@@ -668,16 +671,26 @@ def make_stat_type_records(samples, channels, state, transform, max_moment, prep
     return make_stat_type_arena(samples.view(-1), channels, state, transform, max_moment, prepass_into=prepass_into)
 
 
-def accumulate_records(width, height, stat_types, pixels, stream=None):
+RECORDS_SPLIT_LANES = 64          # STATMC_RECORDS_SPLIT_LANES
+RECORDS_SPLIT_DEFAULT = 256       # STATMC_RECORDS_SPLIT_DEFAULT (include/statmc.h; measured: DESIGN.md 4.1f)
+
+
+def accumulate_records(width, height, stat_types, pixels, stream=None, split_above=None):
     """statmc_accumulate_records (include/statmc.h): `pixels` is an int32 device tensor, one entry per record (y * width + x;
     anything outside the film marks a skipped record); every stat type (make_stat_type_records) holds one sample per record.
-    Per pixel the records are folded in ascending record index: the bits of statmc_accumulate after the same samples."""
+    Per pixel the records are folded in ascending record index: the bits of statmc_accumulate after the same samples.
+    split_above = k: statmc_accumulate_records_split -- a pixel with more than k records is folded by the 64 lanes of a wave
+    (64 chunks, merged in a fixed tree: the same statistics, other last bits); None: the sequential entry."""
     tc = _torch()
     if pixels.dtype != tc.int32 or not pixels.is_contiguous():
         raise ValueError("accumulate_records: pixels must be a contiguous int32 tensor")
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
-    check(load().statmc_accumulate_records(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), pixels.numel(),
-                                           stream if stream is not None else current_stream_handle()))
+    stream = stream if stream is not None else current_stream_handle()
+    if split_above is None:
+        check(load().statmc_accumulate_records(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), pixels.numel(), stream))
+    else:
+        check(load().statmc_accumulate_records_split(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), pixels.numel(),
+                                                     int(split_above), stream))
 
 
 RECORDS_PATH_AUTO, RECORDS_PATH_GENERAL, RECORDS_PATH_FUSED = 0, 1, 2
@@ -746,10 +759,11 @@ def pack_records(pixels, fields, formats=None, stride=None, pixel_offset=0, offs
     return rec.reshape(-1), make_record_layout(stride, pixel_offset, offsets, formats)
 
 
-def accumulate_records_interleaved(width, height, stat_types, records, layout, n_records=None, stream=None):
+def accumulate_records_interleaved(width, height, stat_types, records, layout, n_records=None, stream=None, split_above=None):
     """statmc_accumulate_records_interleaved (include/statmc.h): `records` is a contiguous uint8 or int32 device tensor of
     n_records records of layout.stride bytes each (default: as many as the tensor holds); stat_types from
-    make_stat_type_record_field, in the order of the layout's fields.  The bits of accumulate_records on the de-interleaved arrays."""
+    make_stat_type_record_field, in the order of the layout's fields.  The bits of accumulate_records on the de-interleaved arrays.
+    split_above = k: statmc_accumulate_records_interleaved_split (the bits of accumulate_records(..., split_above=k) on those arrays)."""
     tc = _torch()
     if records.dtype not in (tc.uint8, tc.int32) or not records.is_contiguous():
         raise ValueError("accumulate_records_interleaved: records must be a contiguous uint8 or int32 tensor")
@@ -759,8 +773,13 @@ def accumulate_records_interleaved(width, height, stat_types, records, layout, n
     elif int(n_records) * layout.stride > nbytes:
         raise ValueError("accumulate_records_interleaved: %d records of %d bytes do not fit the tensor (%d bytes)" % (n_records, layout.stride, nbytes))
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
-    check(load().statmc_accumulate_records_interleaved(int(width), int(height), arr, len(stat_types), records.data_ptr(), C.byref(layout),
-                                                       int(n_records), stream if stream is not None else current_stream_handle()))
+    stream = stream if stream is not None else current_stream_handle()
+    if split_above is None:
+        check(load().statmc_accumulate_records_interleaved(int(width), int(height), arr, len(stat_types), records.data_ptr(), C.byref(layout),
+                                                           int(n_records), stream))
+    else:
+        check(load().statmc_accumulate_records_interleaved_split(int(width), int(height), arr, len(stat_types), records.data_ptr(), C.byref(layout),
+                                                                 int(n_records), int(split_above), stream))
 
 
 def accumulate_records_interleaved_path(path):

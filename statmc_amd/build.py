@@ -97,6 +97,8 @@ ACC_FILM_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_film")   # te
 ACC_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_plan")   # tests/cpp/test_accumulate_plan.cpp: statmc::plan_accumulate, no device
 REC_ILV_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_interleaved_plan")   # tests/cpp/test_records_interleaved_plan.cpp: statmc_records_plan.h, no device, no library
 REC_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_interleaved")   # tests/cpp/test_accumulate_records_interleaved.cpp: Estimator::AccumulateRecordsInterleaved
+REC_SPLIT_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_split_plan")   # tests/cpp/test_records_split_plan.cpp: the split entries' chunk rule, no device, no library
+REC_SPLIT_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_split")   # tests/cpp/test_accumulate_records_split.cpp: Estimator::AccumulateRecords(..., splitAbove)
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
@@ -104,7 +106,9 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp"),
          ACC_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_plan.cpp"),
          REC_ILV_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_interleaved_plan.cpp"),
-         REC_ILV_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_interleaved.cpp")}
+         REC_ILV_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_interleaved.cpp"),
+         REC_SPLIT_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_split_plan.cpp"),
+         REC_SPLIT_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_split.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")

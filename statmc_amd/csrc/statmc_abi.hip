@@ -1501,12 +1501,15 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
 }
 
 // Samples as unordered (pixel, sample) records (include/statmc.h; kernels and the scheme: statmc_records.hip).
-int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
-                              int64_t n_records, void *stream) {
+// split_above: 0 = statmc_accumulate_records; otherwise statmc_accumulate_records_split's argument, checked here
+static int accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels, int64_t n_records,
+                              bool split, int32_t split_above, void *stream) {
     // the limits first: an argument error is reported whether or not a device has been set up
     if (n_types < 0 || n_types > statmc::kMaxStatTypes)
         return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
     if (n_records < 0 || n_records > (int64_t)INT32_MAX) return fail(STATMC_ERR_INVALID, "n_records must be in [0, 2^31)");
+    char why_split[96];
+    if (split && !statmc::check_records_split_above(split_above, why_split, sizeof(why_split))) return fail(STATMC_ERR_INVALID, "%s", why_split);
     NEED_READY();
     if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
     if (n_types == 0 || n_records == 0) return STATMC_OK;
@@ -1530,17 +1533,27 @@ int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat
     HIP_TRY(statmc::records_workspace_layout(k.n_records, k.n_px, w));
     char *ws = nullptr;
     if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
-    HIP_TRY(statmc::launch_accumulate_records(k, pixels, w, ws, dstate.rec_phases, S(stream)));
+    HIP_TRY(statmc::launch_accumulate_records(k, pixels, w, ws, dstate.rec_phases, split ? split_above : 0, S(stream)));
     return STATMC_OK;
+}
+int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
+                              int64_t n_records, void *stream) {
+    return accumulate_records(width, height, types, n_types, pixels, n_records, false, 0, stream);
+}
+// ... with a pixel's run of more than split_above records folded by the 64 lanes of a wave (include/statmc.h)
+int statmc_accumulate_records_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
+                                    int64_t n_records, int32_t split_above, void *stream) {
+    return accumulate_records(width, height, types, n_types, pixels, n_records, true, split_above, stream);
 }
 
 // The same queue as interleaved records (include/statmc.h; what is valid and which fold runs: statmc_records_plan.h).
-int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
-                                          const statmc_record_layout *layout, int64_t n_records, void *stream) {
+static int accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
+                                          const statmc_record_layout *layout, int64_t n_records, bool split, int32_t split_above, void *stream) {
     // the limits and the layout first: an argument error is reported whether or not a device has been set up
     g_last_rec_ilv_path = 0;
     char why[256];
     if (!statmc::check_records_interleaved(types, n_types, records, layout, n_records, why, sizeof(why))) return fail(STATMC_ERR_INVALID, "%s", why);
+    if (split && !statmc::check_records_split_above(split_above, why, sizeof(why))) return fail(STATMC_ERR_INVALID, "%s", why);
     NEED_READY();
     if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
     if (n_types == 0 || n_records == 0) return STATMC_OK;
@@ -1573,9 +1586,17 @@ int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const
     HIP_TRY(statmc::records_interleaved_workspace_layout(k.n_records, k.n_px, w));
     char *ws = nullptr;
     if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
-    HIP_TRY(statmc::launch_accumulate_records_interleaved(k, plan, w, ws, dstate.rec_phases, S(stream)));
+    HIP_TRY(statmc::launch_accumulate_records_interleaved(k, plan, w, ws, dstate.rec_phases, split ? split_above : 0, S(stream)));
     g_last_rec_ilv_path = plan.path;
     return STATMC_OK;
+}
+int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
+                                          const statmc_record_layout *layout, int64_t n_records, void *stream) {
+    return accumulate_records_interleaved(width, height, types, n_types, records, layout, n_records, false, 0, stream);
+}
+int statmc_accumulate_records_interleaved_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
+                                                const statmc_record_layout *layout, int64_t n_records, int32_t split_above, void *stream) {
+    return accumulate_records_interleaved(width, height, types, n_types, records, layout, n_records, true, split_above, stream);
 }
 
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,

@@ -144,8 +144,9 @@ struct RecordsWorkspace {
 };
 hipError_t records_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w);   // host only: no launch
 // phases: 1 = grouping, 2 = fold, 3 = both (the ABI's call; 1 and 2 alone: statmc_debug_accumulate_records_phases)
+// split_above: 0 = statmc_accumulate_records (records_fold_kernel); >= 1 = statmc_accumulate_records_split (records_split_fold_kernel)
 hipError_t launch_accumulate_records(const RecordsArgs &a, const int32_t *pixels, const RecordsWorkspace &w, char *ws, int phases,
-                                     hipStream_t s);
+                                     int split_above, hipStream_t s);
 
 // statmc_accumulate_records_interleaved (statmc_records.hip; the host's decisions: statmc_records_plan.h): record i starts at
 // records + i * stride and holds its pixel index at pixel_off and type t's values at off[t], half where bit t of half_mask is set.
@@ -164,8 +165,9 @@ struct RecordsInterleavedArgs {
 };
 struct RecordsInterleavedPlan;      // statmc_records_plan.h
 hipError_t records_interleaved_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w);   // host only: no launch
+// split_above: 0 = statmc_accumulate_records_interleaved; >= 1 = statmc_accumulate_records_interleaved_split
 hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w, char *ws,
-                                                 int phases, hipStream_t s);
+                                                 int phases, int split_above, hipStream_t s);
 
 struct MergeTilesArgs {
     const void *tile_pixels;

@@ -22,14 +22,15 @@
 //              the type asks for it.  The arithmetic is include/statmc_device_api.hpp's: nothing is restated here.
 //
 // The fold of one pixel is a sequential chain by definition: a launch ends when its longest run ends, and a few pixels with
-// tens of thousands of records end it on a few lanes.  The remedy is the caller's: deal such records to several states and
-// put them together with statmc_combine_many (include/statmc.h says so too).
+// tens of thousands of records end it on a few lanes.  statmc_accumulate_records_split (the end of this file) is the entry for
+// such queues: another definition -- a long run is cut into 64 chunks, one per lane of a wave -- and a kernel of its own.
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "statmc_device.h"
+#define STATMC_PLAN_HOST_DEVICE __host__ __device__      // records_split_chunk runs in records_split_fold_kernel
 #include "statmc_records_plan.h"
 
 #include "../../include/statmc_device_api.hpp"
@@ -412,6 +413,7 @@ struct RecordsFusedArgs {
     long long n_px;
     int stride;
     int off[kRecFusedTypes];
+    int skip_above;       // a run of more records is left alone (the split entry folds it elsewhere); INT32_MAX: never
 };
 
 // FMT as plan_records_interleaved has it: 0 every field fp32, 1 the feature fields half, 2 the radiance field too.
@@ -427,7 +429,7 @@ __global__ __launch_bounds__(kRecBlock) void records_interleaved_fused_kernel(Re
     const long long p = (long long)blockIdx.x * kRecBlock + threadIdx.x;
     if (p >= a.n_px) return;
     const int start = a.seg[2 * p], cnt = a.seg[2 * p + 1] - start;
-    if (cnt <= 0) return;
+    if (cnt <= 0 || cnt > a.skip_above) return;
     // COPIED out of the by-value argument; every index below is a constant after unrolling
     const statmc_stat_type t_rad = a.t[0];
     statmc_stat_type t_rgb[K > 0 ? K : 1], t_one[M > 0 ? M : 1];
@@ -510,6 +512,139 @@ hipError_t launch_records_fused(const RecordsFusedArgs &f, int K, int M, unsigne
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ long runs over the lanes of a wave
+// statmc_accumulate_records_split / statmc_accumulate_records_interleaved_split (include/statmc.h): a pixel whose run is longer
+// than split_above is folded by the 64 lanes of a wave, lane j over chunk j of the run (records_split_chunk,
+// statmc_records_plan.h: THE chunk rule), lane 0 from the stored state and the others from clear(); the 64 states are put
+// together by statmc::device::merge_lanes<64> -- a fixed tree of PixelStats::merge -- and lane 0 stores.  Which lanes do the
+// work decides no bit: the chunks and the tree are functions of the run's length alone.
+//
+// One kernel template serves both entries (RecSplitSrc below: where a type's field of record i lies; the per-array entry's phase 1
+// is fold_pixel, records_fold_kernel's own body, and its stride a constant).  records_fold_kernel's grid: workgroup b
+// serves stat type b % n_types and 256 consecutive pixels.  No lane returns early -- the wave's lanes meet again in phase 2:
+//   phase 1   a lane with 0 < cnt <= split_above folds its own pixel with walk_run and stores: statmc_accumulate_records' bits.
+//   phase 2   m = ballot(cnt > split_above).  For every set bit in ascending lane order -- a wave-uniform loop -- all 64 lanes
+//             take that lane's (start, cnt) by __shfl (its pixel is the wave's first pixel + the lane's number), walk their
+//             chunk with the same walk_run (an empty chunk issues no load; the walk's clamped requests stay inside the chunk,
+//             hence inside order[]), merge, and lane 0 stores -- with the pre-pass epilogue where the type asks for it.
+// No list of long pixels, no atomics, no LDS, and one launch -- except where plan_records_interleaved sends the interleaved
+// entry's short pixels to the fused kernel: that kernel then leaves the runs above split_above alone (skip_above) and this one
+// follows it with short_too == 0, which skips phase 1 and serves the long pixels alone.
+
+// Where type ti's field of record i lies: field0 + i * stride, fp32 or half.
+struct RecSplitSrc {
+    const char *field0;
+    long long stride;
+    bool half;
+};
+__device__ __forceinline__ RecSplitSrc rec_split_src(const RecordsArgs &, const statmc_stat_type &t, int) {
+    return {reinterpret_cast<const char *>(t.samples), 4ll * t.channels, false};      // record-major [n_records][channels] fp32
+}
+__device__ __forceinline__ RecSplitSrc rec_split_src(const RecordsInterleavedArgs &a, const statmc_stat_type &, int ti) {
+    return {a.records + a.off[ti], (long long)a.stride, ((a.half_mask >> ti) & 1u) != 0};
+}
+template <class Args>
+constexpr bool kRecSplitArrays = false;
+template <>
+constexpr bool kRecSplitArrays<RecordsArgs> = true;
+
+// ARRAYS: the per-array entry -- record-major fp32 arrays, the stride 4 C a constant, and phase 1 is fold_pixel itself.
+template <int C, int MAXM, bool TRANSFORM, bool HALF, bool ARRAYS>
+__device__ __forceinline__ void fold_pixel_split(const statmc_stat_type &t, const statmc_prepass_context &ctx, const int32_t *__restrict__ order,
+                                                 const char *__restrict__ field0, long long stride_in, long long p, int start, int cnt, int split_above,
+                                                 int short_too) {
+    static_assert(!(ARRAYS && HALF), "the per-array entry's samples are fp32");
+    using Field = RecField<C, HALF ? kFieldHalfElems : kFieldF32>;
+    using S = RecRaw<Field::kRegs>;
+    using PS = device::PixelStats<C, MAXM, TRANSFORM>;
+    const long long stride = ARRAYS ? 4ll * C : stride_in;
+    auto walk = [&](PS &ps, const int32_t *__restrict__ run, int len) __attribute__((always_inline)) {
+        walk_run<S>(
+            run, len, [&](int rec, S &s) __attribute__((always_inline)) { Field::load(field0 + (long long)rec * stride, s.r); },
+            [&](const S &s) __attribute__((always_inline)) {
+                float v[C];
+                Field::decode(s.r, 0, v);
+                ps.add(v);
+            });
+    };
+    auto store = [&](const PS &ps, long long px) __attribute__((always_inline)) {
+        if constexpr (MAXM >= 3) {
+            if (t.mean_corr != nullptr) {
+                ps.store(t, px, ctx);
+                return;
+            }
+        }
+        ps.store(t, px);
+    };
+    if (short_too && cnt > 0 && cnt <= split_above) {
+        if constexpr (ARRAYS) {
+            fold_pixel<C, MAXM, TRANSFORM>(t, ctx, order, p, start, cnt);       // records_fold_kernel's own body
+        } else {
+            PS ps;
+            ps.load(t, p);
+            walk(ps, order + start, cnt);
+            store(ps, p);
+        }
+    }
+    const int lane = (int)(threadIdx.x & 63u);
+    const long long p0 = p - lane;                                     // the wave's first pixel: 256 consecutive pixels per workgroup
+    for (unsigned long long m = __ballot(cnt > split_above); m != 0; m &= m - 1) {
+        const int src = __ffsll((long long)m) - 1;
+        const int s0 = __shfl(start, src, 64), c0 = __shfl(cnt, src, 64);
+        int begin, len;
+        records_split_chunk(c0, lane, &begin, &len);
+        PS ps;
+        if (lane == 0) ps.load(t, p0 + src);
+        else ps.clear();
+        walk(ps, order + s0 + begin, len);
+        device::merge_lanes<kRecSplitLanes>(ps);
+        if (lane == 0) store(ps, p0 + src);
+    }
+}
+
+template <int C, bool HALF, bool ARRAYS>
+__device__ __forceinline__ void fold_type_split(const statmc_stat_type &t, const statmc_prepass_context &ctx, const int32_t *__restrict__ order,
+                                                const char *__restrict__ field0, long long stride, long long p, int start, int cnt, int split_above,
+                                                int short_too) {
+    if (t.transform) {
+        if (t.max_moment >= 3) fold_pixel_split<C, 3, true, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+        else if (t.max_moment == 2) fold_pixel_split<C, 2, true, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+        else fold_pixel_split<C, 1, true, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+    } else {
+        if (t.max_moment >= 3) fold_pixel_split<C, 3, false, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+        else if (t.max_moment == 2) fold_pixel_split<C, 2, false, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+        else fold_pixel_split<C, 1, false, HALF, ARRAYS>(t, ctx, order, field0, stride, p, start, cnt, split_above, short_too);
+    }
+}
+
+// Args: RecordsArgs (the per-array entry) or RecordsInterleavedArgs.  The type dispatch is block-uniform.
+template <class Args>
+__global__ __launch_bounds__(kRecBlock) void records_split_fold_kernel(Args a, int split_above, int short_too) {
+    static_assert(kRecSplitLanes == 64, "a split pixel's slots are the lanes of one wave");
+    const int ti = (int)(blockIdx.x % (unsigned)a.n_types);
+    const long long p = (long long)(blockIdx.x / (unsigned)a.n_types) * kRecBlock + threadIdx.x;
+    int start = 0, cnt = 0;          // a lane past the film or with an empty run carries cnt = 0 and stays
+    if (p < a.n_px) {
+        start = a.seg[2 * p];
+        cnt = a.seg[2 * p + 1] - start;
+    }
+    // COPIED out of the by-value argument
+    const statmc_stat_type t = a.t[ti];
+    const statmc_prepass_context ctx = a.ctx;
+    const int32_t *order = a.order;
+    const RecSplitSrc src = rec_split_src(a, t, ti);
+    if constexpr (kRecSplitArrays<Args>) {
+        if (t.channels == 3) fold_type_split<3, false, true>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+        else fold_type_split<1, false, true>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+    } else if (t.channels == 3) {
+        if (src.half) fold_type_split<3, true, false>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+        else fold_type_split<3, false, false>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+    } else {
+        if (src.half) fold_type_split<1, true, false>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+        else fold_type_split<1, false, false>(t, ctx, order, src.field0, src.stride, p, start, cnt, split_above, short_too);
+    }
+}
+
 }  // namespace
 
 hipError_t records_workspace_layout(long long n_records, long long n_px, RecordsWorkspace &w) {
@@ -526,7 +661,7 @@ hipError_t records_workspace_layout(long long n_records, long long n_px, Records
 }
 
 hipError_t launch_accumulate_records(const RecordsArgs &a_in, const int32_t *pixels, const RecordsWorkspace &w, char *ws, int phases,
-                                     hipStream_t s) {
+                                     int split_above, hipStream_t s) {
     RecordsArgs a = a_in;
     unsigned *keys = reinterpret_cast<unsigned *>(ws + w.keys_off);
     int32_t *order = reinterpret_cast<int32_t *>(ws + w.order_off);
@@ -543,7 +678,8 @@ hipError_t launch_accumulate_records(const RecordsArgs &a_in, const int32_t *pix
         a.order = order;
         a.seg = seg;
         const long long blocks = (a.n_px + kRecBlock - 1) / kRecBlock * a.n_types;
-        hipLaunchKernelGGL(records_fold_kernel, dim3((unsigned)blocks), dim3(kRecBlock), 0, s, a);
+        if (split_above >= 1) hipLaunchKernelGGL(records_split_fold_kernel<RecordsArgs>, dim3((unsigned)blocks), dim3(kRecBlock), 0, s, a, split_above, 1);
+        else hipLaunchKernelGGL(records_fold_kernel, dim3((unsigned)blocks), dim3(kRecBlock), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -563,7 +699,7 @@ hipError_t records_interleaved_workspace_layout(long long n_records, long long n
 }
 
 hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a_in, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w,
-                                                 char *ws, int phases, hipStream_t s) {
+                                                 char *ws, int phases, int split_above, hipStream_t s) {
     RecordsInterleavedArgs a = a_in;
     unsigned *keys = reinterpret_cast<unsigned *>(ws + w.keys_off);
     int32_t *order = reinterpret_cast<int32_t *>(ws + w.order_off);
@@ -592,16 +728,27 @@ hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a
             f.records = a.records;
             f.n_px = a.n_px;
             f.stride = a.stride;
+            f.skip_above = split_above >= 1 ? split_above : INT32_MAX;
+            hipError_t e = hipErrorInvalidValue;
             switch (plan.fmt) {
-            case 0: return launch_records_fused<0>(f, plan.K, plan.M, (unsigned)px_blocks, s);
-            case 1: return launch_records_fused<1>(f, plan.K, plan.M, (unsigned)px_blocks, s);
-            case 2: return launch_records_fused<2>(f, plan.K, plan.M, (unsigned)px_blocks, s);
+            case 0: e = launch_records_fused<0>(f, plan.K, plan.M, (unsigned)px_blocks, s); break;
+            case 1: e = launch_records_fused<1>(f, plan.K, plan.M, (unsigned)px_blocks, s); break;
+            case 2: e = launch_records_fused<2>(f, plan.K, plan.M, (unsigned)px_blocks, s); break;
             }
-            return hipErrorInvalidValue;
+            if (e != hipSuccess || split_above < 1) return e;
+            // the split entry: the fused fold has left the runs above split_above alone; one lane group per pixel and type folds them
+            a.order = order;
+            a.seg = seg;
+            hipLaunchKernelGGL(records_split_fold_kernel<RecordsInterleavedArgs>, dim3((unsigned)(px_blocks * a.n_types)), dim3(kRecBlock), 0, s, a,
+                               split_above, 0);
+            return hipGetLastError();
         }
         a.order = order;
         a.seg = seg;
-        hipLaunchKernelGGL(records_interleaved_fold_kernel, dim3((unsigned)(px_blocks * a.n_types)), dim3(kRecBlock), 0, s, a);
+        if (split_above >= 1)
+            hipLaunchKernelGGL(records_split_fold_kernel<RecordsInterleavedArgs>, dim3((unsigned)(px_blocks * a.n_types)), dim3(kRecBlock), 0, s, a,
+                               split_above, 1);
+        else hipLaunchKernelGGL(records_interleaved_fold_kernel, dim3((unsigned)(px_blocks * a.n_types)), dim3(kRecBlock), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -1,6 +1,8 @@
 // statmc_records_plan.h -- what statmc_accumulate_records_interleaved decides on the host: whether a record layout is valid and
 // which kernel folds it.  Pure functions of their arguments: no HIP call, no device, no global or thread-local state, nothing but
 // the C ABI's own structs -- tests/cpp/test_records_interleaved_plan.cpp compiles this header alone, with and without sanitizers.
+// Also here, for the same reason: the chunk rule of the split entries (statmc_accumulate_records_split), the one definition the
+// fold kernel and tests/cpp/test_records_split_plan.cpp share.
 #pragma once
 
 #include <stddef.h>
@@ -8,6 +10,13 @@
 #include <stdio.h>
 
 #include "../../include/statmc.h"
+
+// What a function the device calls too is declared with.  A translation unit that calls records_split_chunk in a kernel defines
+// this to the compiler's host-and-device attributes before the include (statmc_records.hip); everywhere else, and alone under
+// g++, it is empty.
+#ifndef STATMC_PLAN_HOST_DEVICE
+#define STATMC_PLAN_HOST_DEVICE
+#endif
 
 namespace statmc {
 
@@ -121,6 +130,30 @@ inline RecordsInterleavedPlan plan_records_interleaved(const statmc_stat_type *t
     for (int i = 0; i < K; i++) p.order[1 + i] = rgb[i];
     for (int i = 0; i < M; i++) p.order[1 + K + i] = f1[i];
     return p;
+}
+
+// ------------------------------------------------------------------ the split entries (statmc_accumulate_records_split, include/statmc.h)
+constexpr int kRecSplitLanes = STATMC_RECORDS_SPLIT_LANES;   // the slots of a split pixel: the lanes of one wave
+
+// split_above: a run of more than split_above records is split; anything below 1 is refused.  true: valid; false: `msg` names it.
+inline bool check_records_split_above(int32_t split_above, char *msg, size_t msg_len) {
+    if (split_above >= 1) return true;
+    snprintf(msg, msg_len, "split_above %d: at least 1 (INT32_MAX: never split)", (int)split_above);
+    return false;
+}
+
+// THE chunk rule.  A split pixel's run of cnt records -- positions [0, cnt) in ascending record index -- is cut into
+// kRecSplitLanes contiguous chunks of L = ceil(cnt / kRecSplitLanes) records: slot j owns positions
+// [min(j L, cnt), min((j + 1) L, cnt)) = [*begin, *begin + *len).  The chunks tile [0, cnt) in slot order; trailing slots may be
+// empty (*len == 0, *begin == cnt).  cnt in [0, 2^31), slot in [0, kRecSplitLanes); 64-bit intermediates: (slot + 1) L passes
+// 2^31 for the largest counts.
+STATMC_PLAN_HOST_DEVICE inline void records_split_chunk(int cnt, int slot, int *begin, int *len) {
+    const int64_t c = cnt;
+    const int64_t L = (c + kRecSplitLanes - 1) / kRecSplitLanes;
+    const int64_t lo = (int64_t)slot * L, hi = lo + L;
+    const int64_t b = lo < c ? lo : c, e = hi < c ? hi : c;
+    *begin = (int)b;
+    *len = (int)(e - b);
 }
 
 }  // namespace statmc

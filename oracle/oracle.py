@@ -67,6 +67,10 @@ def lib():
         _lib.oracle_filter_spec_run.argtypes = ([C.c_int] * 3 + [C.c_float, C.c_int, C.c_int, C.POINTER(FilterSpec), i32p] +
                                                 [f32p] * 3 + [C.c_int, C.POINTER(f32p), C.POINTER(C.c_int), f32p, f32p] +
                                                 [C.c_int] * 5)
+        f64p = C.POINTER(C.c_double)
+        _lib.oracle_filter_spec_run_f64.argtypes = ([C.c_int] * 3 + [C.c_float, C.c_int, C.c_int, C.POINTER(FilterSpec), i32p] +
+                                                    [f32p] * 3 + [C.c_int, C.POINTER(f32p), C.POINTER(C.c_int), f32p] +
+                                                    [f64p] * 3 + [C.c_int] * 5)
         _lib.oracle_film_update.argtypes = [C.c_void_p, C.c_size_t, C.c_float, C.c_float, f32p]
         _lib.oracle_num_threads.restype = C.c_int
         _lib.oracle_tile_moments.argtypes = [C.c_int] * 3 + [f32p, C.c_int, f32p]
@@ -249,3 +253,28 @@ def filter_image(mean_corr, disc, colour, g_buffers, g_dr, ds, radius, roi=None,
                                  _i(n) if n is not None else None, _f(mean_corr), _f(disc), _f(colour),
                                  ng, gptrs, gch, _f(gdr), _f(out), x0, y0, x1, y1, threads)
     return out
+
+
+def filter_image_f64(mean_corr, disc, colour, g_buffers, g_dr, ds, radius, roi=None, threads=0, spec=None, n=None,
+                     alpha_index=None):
+    """filter_image with the same tap decisions (the float tests, bit for bit) and the weights and sums in double.
+    Returns (out, scale, sum_w) as float64: sum w c / sum w and sum w |c| / sum w per pixel and channel (the pixel's own
+    colour / |colour| where sum w = 0), and sum w per pixel.  Outside the ROI all three are 0."""
+    h, w = mean_corr.shape[:2]
+    c = mean_corr.shape[2] if mean_corr.ndim == 3 else 1
+    gs = [np.ascontiguousarray(g, dtype=np.float32) for g in g_buffers]
+    ng = len(gs)
+    gptrs = (C.POINTER(C.c_float) * max(ng, 1))(*[_f(g) for g in gs])
+    gch = (C.c_int * max(ng, 1))(*[(g.shape[2] if g.ndim == 3 else 1) for g in gs])
+    gdr = np.asarray(list(g_dr) + ([] if ng else [0.0]), dtype=np.float32)
+    out, scale = np.zeros(colour.shape, np.float64), np.zeros(colour.shape, np.float64)
+    sum_w = np.zeros((h, w), np.float64)
+    x0, y0, x1, y1 = roi if roi is not None else (0, 0, w, h)
+    spec = spec if spec is not None else default_spec()
+    alpha_index = default_significance() if alpha_index is None else alpha_index
+    assert spec.dof == DOF_PIXEL or n is not None, "Welch mode reads the sample counts"
+    d = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    lib().oracle_filter_spec_run_f64(w, h, c, float(ds), int(radius), int(alpha_index), C.byref(spec),
+                                     _i(n) if n is not None else None, _f(mean_corr), _f(disc), _f(colour),
+                                     ng, gptrs, gch, _f(gdr), d(out), d(scale), d(sum_w), x0, y0, x1, y1, threads)
+    return out, scale, sum_w

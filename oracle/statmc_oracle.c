@@ -541,6 +541,71 @@ void oracle_filter_spec_run(int width, int height, int channels, float ds, int r
     }
 }
 
+/* The same windows -- pixel_valid and pair_member above, so every tap decision is the float one, bit for bit -- with
+ * the weights and the sums in double: w = exp(ds r^2 + sum_g dr_g |dG|^2) from the float inputs, no rounding to float
+ * anywhere.  What the float filter's own rounding error is measured against (tests/test_filter_probes_cpu.py).
+ * out [h][w][channels]: sum w c / sum w, or the pixel's colour where sum w = 0;  scale [h][w][channels]: sum w |c| / sum w
+ * (|colour| where sum w = 0), the magnitude an error of the quotient is relative to;  sum_w [h][w].  Pixels outside the
+ * ROI are left alone. */
+void oracle_filter_spec_run_f64(int width, int height, int channels, float ds, int radius, int alpha_index,
+                                const oracle_filter_spec *spec, const int32_t *n,
+                                const float *mean_corr, const float *disc, const float *colour,
+                                int n_g, const float *const *g_buffers, const int *g_channels, const float *g_dr,
+                                double *out, double *scale, double *sum_w_out, int rx0, int ry0, int rx1, int ry1, int threads) {
+    const int table = alpha_index + ORACLE_TQ_N_ALPHAS * (spec->sides ? 1 : 0);
+    const int clamp = spec->border == ORACLE_BORDER_CLAMP;
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+#endif
+    for (int y = ry0; y < ry1; y++) {
+        for (int x = rx0; x < rx1; x++) {
+            const size_t p = (size_t)y * width + x;
+            double sum_w = 0., acc[3] = {0., 0., 0.}, mag[3] = {0., 0., 0.};
+            const int p_valid = pixel_valid(channels, mean_corr, disc, colour, n_g, g_buffers, g_channels, p);
+            for (int dy = -radius; p_valid && dy <= radius; dy++) {
+                int qy = y + dy;
+                if (qy < 0 || qy >= height) {
+                    if (!clamp) continue;
+                    qy = qy < 0 ? 0 : height - 1;
+                }
+                for (int dx = -radius; dx <= radius; dx++) {
+                    int qx = x + dx;
+                    if (qx < 0 || qx >= width) {
+                        if (!clamp) continue;
+                        qx = qx < 0 ? 0 : width - 1;
+                    }
+                    const size_t q = (size_t)qy * width + qx;
+                    if (!pixel_valid(channels, mean_corr, disc, colour, n_g, g_buffers, g_channels, q)) continue;
+                    if (!pair_member(spec, channels, table, mean_corr, disc, n, p, q)) continue;
+                    double e = (double)ds * (double)(dx * dx + dy * dy);
+                    for (int g = 0; g < n_g; g++) {
+                        const int gc = g_channels[g];
+                        const float *G = g_buffers[g];
+                        double dist2 = 0.;
+                        for (int c = 0; c < gc; c++) {
+                            const double dc = (double)G[p * gc + c] - (double)G[q * gc + c];
+                            dist2 += dc * dc;
+                        }
+                        e += (double)g_dr[g] * dist2;
+                    }
+                    const double w = exp(e);
+                    sum_w += w;
+                    for (int c = 0; c < channels; c++) {
+                        acc[c] += w * (double)colour[q * channels + c];
+                        mag[c] += w * fabs((double)colour[q * channels + c]);
+                    }
+                }
+            }
+            for (int c = 0; c < channels; c++) {
+                out[p * channels + c] = sum_w > 0. ? acc[c] / sum_w : (double)colour[p * channels + c];
+                scale[p * channels + c] = sum_w > 0. ? mag[c] / sum_w : fabs((double)colour[p * channels + c]);
+            }
+            sum_w_out[p] = sum_w;
+        }
+    }
+}
+
 void oracle_filter(int width, int height, int channels, float ds, int radius,
                    const float *mean_corr, const float *disc, const float *colour,
                    int n_g, const float *const *g_buffers, const int *g_channels, const float *g_dr,

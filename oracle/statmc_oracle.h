@@ -163,6 +163,14 @@ void oracle_filter_spec_run(int width, int height, int channels, float ds, int r
                             int n_g, const float *const *g_buffers, const int *g_channels, const float *g_dr,
                             float *out, int rx0, int ry0, int rx1, int ry1, int threads);
 
+/* The same tap decisions (the float tests above, bit for bit) with the weights and the sums in double: the measure of the
+ * float filter's rounding error.  out, scale: [h][w][channels] (sum w c / sum w and sum w |c| / sum w); sum_w: [h][w]. */
+void oracle_filter_spec_run_f64(int width, int height, int channels, float ds, int radius, int alpha_index,
+                                const oracle_filter_spec *spec, const int32_t *n,
+                                const float *mean_corr, const float *disc, const float *colour,
+                                int n_g, const float *const *g_buffers, const int *g_channels, const float *g_dr,
+                                double *out, double *scale, double *sum_w, int rx0, int ry0, int rx1, int ry1, int threads);
+
 /* Tile-local pooled moments {count, mean, M2} per tile_size x tile_size tile and channel (out: [tiles_y][tiles_x]
  * [channels][3]); the lane order and merge tree of the product's wave-level kernel, restated (statmc_oracle.c). */
 void oracle_tile_moments(int width, int height, int channels, const float *values, int tile_size, float *out);

@@ -10,7 +10,12 @@ namespace statmc {
 
 constexpr float kLog2e = 1.44269504088896340736f;
 // A G-buffer's factor in the staged features, sqrt(-DR * log2 e): the range weight is then one exp2 of a sum of squares.
-inline float gbuffer_scale(float dr) { return sqrtf(-dr * kLog2e); }
+// A G-buffer of the argument list whose DR factor is exactly 0 moves no weight, but its pixels with a non-finite value still take
+// no part (spec v2.1; the oracle and the general kernel read every buffer of the list).  Factor 0 means "absent, never read" in
+// the LDS kernels, so such a buffer is staged with 2^-100 instead: it is read and its values are checked, and their squared
+// differences -- below 2^-24 for values up to 2^88 -- round away in every exponent.
+constexpr float kZeroFactorScale = 0x1p-100f;
+inline float gbuffer_scale(float dr) { return dr == 0.f ? kZeroFactorScale : sqrtf(-dr * kLog2e); }
 
 // LDS row layout of the LDS kernels: 15 channel planes of `pitch` floats.
 enum { C_G0 = 0, C_G1 = 3, C_MC = 6, C_ND = 9, C_COL = 12 };
@@ -31,7 +36,7 @@ struct StagedPixel {
 };
 
 // The six feature values of pixel q (before the k0 / k1 scaling of the two-RGB-buffer layout; already
-// scaled, with k0 = k1 = 1, in the generic slot layout).  A slot or buffer with factor 0 is never read.
+// scaled, with k0 = k1 = 1, in the generic slot layout).  A slot or buffer with factor 0 (an absent one: gbuffer_scale) is never read.
 __device__ __forceinline__ void load_features(const FilterArgs &a, long long q, f3 &g0, f3 &g1) {
     if (a.feat_generic) {
         float v[6];

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import FILTER_SD, RADIUS, SD_ALBEDO, SD_NORMAL, make_case, rel_l2
+from test_filter_probes_cpu import PROBE_DS, PROBE_SD, integer_colour, same_bits, scaled_error
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -641,6 +642,37 @@ def stats_case(oracle, W, H, spp, seed):
     return mc, disc, rad["film_mean"], [st["normal"]["mean"], st["albedo"]["mean"]]
 
 
+def assert_per_pixel(oracle, out, ref, mc, disc, colour, gbs, g_dr, ds, radius, what, roi=None, spec=None, n=None, alpha_index=None, probe=None):
+    """Beside the whole-image L2: every pixel within 4 e_or S(p) of the oracle.  The membership probe
+    (tests/test_filter_per_pixel_gpu.py) shows the kernels to take the oracle's taps; what is left is the weights' and sums'
+    rounding, bounded there (weight probe) by four times the float oracle's own.  e_or = max_p |oracle - ref64| / S(p) and
+    S(p) = sum w |c| / sum w come from the double-sum oracle on the same tap decisions (oracle.filter_image_f64), for this case.
+    probe(colour, g_dr, sd) -> out runs the same kernel on other colours and factors: on a failure it tells, by the membership
+    probe on this case's own statistics, a tap or gate error from a weight or sum error."""
+    ref64, S, _ = oracle.filter_image_f64(mc, disc, colour, gbs, g_dr, ds, radius, roi=roi, spec=spec, n=n, alpha_index=alpha_index)
+    h, w = ref.shape[:2]
+    x0, y0, x1, y1 = roi if roi is not None else (0, 0, w, h)
+    inside = np.zeros(ref.shape, bool)
+    inside[y0:y1, x0:x1] = np.isfinite(ref[y0:y1, x0:x1])                # (a pixel that keeps its own non-finite colour: compared by the caller)
+    e_or = scaled_error(ref, ref64, S)[inside].max()
+    assert e_or < (2 * radius + 1) ** 2 * 2.0 ** -24, e_or                # the worst case of the oracle's sequential float sum
+    ok = np.abs(out.astype(np.float64) - ref) <= 4 * e_or * S
+    bad = np.argwhere(inside & ~ok)
+    if not len(bad):
+        return
+    y, x, c = bad[0]
+    cause = ""
+    if probe is not None:
+        ints = integer_colour(colour.shape, seed=1)
+        taps = same_bits(probe(ints, [0.0] * len(gbs), PROBE_SD), oracle.filter_image(mc, disc, ints, gbs, [0.0] * len(gbs), PROBE_DS, radius, roi=roi, spec=spec,
+                                                                                      n=n, alpha_index=alpha_index))
+        cause = ": a weight or sum error (the membership probe on these statistics passes)" if taps[inside].all() else \
+            ": a tap or gate error (the membership probe on these statistics fails at %d pixels, first (y, x, c) %s)" % ((inside & ~taps).any(2).sum(), np.argwhere(inside & ~taps)[0].tolist())
+    raise AssertionError("%s: %d values beyond 4 e_or S (e_or = %.3g); first pixel (x %d, y %d) channel %d: out %r oracle %r, off by %.3g S = %.1f e_or%s" % (
+        what, len(bad), e_or, x, y, c, float(out[y, x, c]), float(ref[y, x, c]), abs(float(out[y, x, c]) - float(ref[y, x, c])) / S[y, x, c],
+        abs(float(out[y, x, c]) - float(ref[y, x, c])) / S[y, x, c] / e_or, cause))
+
+
 @pytest.mark.parametrize("W,H,radius,sd,force,variant", [
     (300, 41, 20, 10.0, 0, "sym_r20"),     # shipped default; 2 tile columns, ragged right edge, 11 tile rows
     (300, 41, 20, 10.0, 3, "lds_r20"),     # the one-sided r = 20 kernel
@@ -664,6 +696,8 @@ def test_filter_matches_oracle(gpu, oracle, W, H, radius, sd, force, variant):
     assert v == variant
     for c in range(3):
         assert rel_l2(out[..., c], ref[..., c]) <= TOL, c
+    assert_per_pixel(oracle, out, ref, mc, disc, colour, gbs, G_DR, -0.5 / sd ** 2, radius, v,
+                     probe=lambda col, dr, s: run_filter(gpu, mc, disc, col, gbs, dr, s, radius, force=force)[0])
 
 
 @pytest.mark.parametrize("parts", [1, 2, 3, 7, 41, 64])
@@ -680,6 +714,14 @@ def test_filter_window_sweep_parts(gpu, oracle, parts):
     assert v == "sym_r20"
     assert max(rel_l2(out[..., c], ref[..., c]) for c in range(3)) <= TOL
 
+    def probe(col, dr, s):
+        gpu.force_filter_parts(parts)
+        try:
+            return run_filter(gpu, mc, disc, col, gbs, dr, s, RADIUS)[0]
+        finally:
+            gpu.force_filter_parts(0)
+    assert_per_pixel(oracle, out, ref, mc, disc, colour, gbs, G_DR, -0.5 / FILTER_SD ** 2, RADIUS, "%s, %d parts" % (v, parts), probe=probe)
+
 
 def test_filter_low_spp_high_rejection(gpu, oracle):
     """4 spp: wide confidence intervals at some pixels, heavy rejection at edges."""
@@ -688,6 +730,8 @@ def test_filter_low_spp_high_rejection(gpu, oracle):
     out, v = run_filter(gpu, mc, disc, colour, gbs, G_DR, FILTER_SD, RADIUS)
     assert v == "sym_r20"
     assert max(rel_l2(out[..., c], ref[..., c]) for c in range(3)) <= TOL
+    assert_per_pixel(oracle, out, ref, mc, disc, colour, gbs, G_DR, -0.5 / FILTER_SD ** 2, RADIUS, v,
+                     probe=lambda col, dr, s: run_filter(gpu, mc, disc, col, gbs, dr, s, RADIUS)[0])
 
 
 def test_filter_special_pixels(gpu, oracle):
@@ -790,6 +834,8 @@ def test_filter_roi(gpu, oracle):
         out, v = run_filter(gpu, mc, disc, colour, gbs, G_DR, FILTER_SD, RADIUS, roi=roi, force=force)
         assert not out[:20].any() and not out[40:].any() and not out[:, :20].any() and not out[:, 310:].any()
         assert max(rel_l2(out[..., c], ref[..., c]) for c in range(3)) <= TOL, v
+        assert_per_pixel(oracle, out, ref, mc, disc, colour, gbs, G_DR, -0.5 / FILTER_SD ** 2, RADIUS, v, roi=roi,
+                         probe=lambda col, dr, s: run_filter(gpu, mc, disc, col, gbs, dr, s, RADIUS, roi=roi, force=force)[0])
 
 
 @pytest.mark.parametrize("channels", [1, 3])
@@ -1527,6 +1573,21 @@ def test_filter_spec_variants_match_oracle(gpu, oracle, spec_kw):
     assert variant == expected_lds_variant(spec_kw, 3, 7), variant
     for c in range(3):
         assert rel_l2(out[..., c], oout[..., c]) <= TOL, c
+    rad, gbs, ospec = st["radiance"], [st["normal"]["mean"], st["albedo"]["mean"]], oracle.FilterSpec(**spec_kw)
+
+    def probe_with(force):
+        def probe(col, dr, s):
+            gpu.set_filter_spec(**spec_kw)
+            gpu.check(gpu.load().statmc_set_significance(2))
+            try:
+                return run_filter(gpu, omc, odc, col, gbs, dr, s, 7, force=force, n=rad["n"])[0]
+            finally:
+                gpu.set_filter_spec()
+                gpu.load().statmc_set_significance(0)
+        return probe
+    per_pixel = lambda o, v, force: assert_per_pixel(oracle, o, oout, omc, odc, rad["film_mean"], gbs, G_DR, -0.5 / 4.0 ** 2, 7, v, spec=ospec, n=rad["n"],
+                                                      alpha_index=2, probe=probe_with(force))
+    per_pixel(out, variant, 0)
     if variant != "generic":       # the general kernel under the same spec: the two HIP paths agree as well
         _, _, out_g, variant_g, _ = run_spec(gpu, oracle, st, spec_kw, radius=7, sd=4.0, alpha_index=2, force=1)
         assert variant_g == "generic"
@@ -1538,6 +1599,8 @@ def test_filter_spec_variants_match_oracle(gpu, oracle, spec_kw):
         assert variant_l == ("generic" if spec_kw.get("dof", 0) else "lds_rt" + ("", "_asym", "_centre")[gate] + ("_joint" if joint else "")), variant_l
         for c in range(3):
             assert rel_l2(out_l[..., c], oout[..., c]) <= TOL, c
+        per_pixel(out_g, variant_g, 1)
+        per_pixel(out_l, variant_l, 2)
 
 
 @pytest.mark.parametrize("spec_kw", [dict(), dict(gate=1), dict(dof=1), dict(border=1, channel_rule=1), dict(sides=1, small_n=1),

@@ -15,6 +15,9 @@ FILMS = [(37, 29), (64, 32)]     # odd width, ragged last group, unaligned plane
 # (name, channels, transform, max_moment, pre-pass epilogue)
 TYPES = [("radiance", 3, 1, 3, True), ("normal", 3, 0, 1, False), ("depth", 1, 0, 1, False), ("extra", 1, 1, 2, False)]
 FIELDS = ("n", "mean", "m2", "m3", "film_mean", "film_m2")
+# every (channels, transform, max_moment) a stat type can have: the twelve bodies of the fold's type dispatch; the pre-pass epilogue
+# where TYPES has it
+KINDS = [("c%dt%dm%d" % (c, t, m), c, t, m, (c, t, m) == (3, 1, 3)) for c in (3, 1) for t in (1, 0) for m in (3, 2, 1)]
 
 
 def dev(a):
@@ -28,13 +31,13 @@ def bits(t):
 
 
 class States:
-    """One set of state images per stat type of TYPES, plus the radiance type's mean_corr / discriminator."""
+    """One set of state images per stat type of `types`, plus the radiance type's mean_corr / discriminator."""
 
-    def __init__(self, W, H, fill=None):
+    def __init__(self, W, H, fill=None, types=TYPES):
         import torch
         from statmc_amd import film
-        self.W, self.H = W, H
-        self.st = [film.new_state(H, W, c, torch.device("cuda:0"), transform=bool(t)) for _, c, t, _, _ in TYPES]
+        self.W, self.H, self.types = W, H, types
+        self.st = [film.new_state(H, W, c, torch.device("cuda:0"), transform=bool(t)) for _, c, t, _, _ in types]
         self.mc = torch.zeros(H, W, 3, device="cuda:0")
         self.dc = torch.zeros(H, W, 3, device="cuda:0")
         if fill is not None:       # a seeded random bit pattern in every image
@@ -54,7 +57,7 @@ class States:
         return [bits(img).copy() for img in self.images()]
 
     def pre(self, i):
-        return (self.mc, self.dc) if TYPES[i][4] else None
+        return (self.mc, self.dc) if self.types[i][4] else None
 
 
 def same(a, b):
@@ -62,10 +65,10 @@ def same(a, b):
         assert np.array_equal(x, y), "image %d differs in %d elements" % (k, int((x != y).sum()))
 
 
-def make_samples(rng, n):
+def make_samples(rng, n, types=TYPES):
     """Per type [n, C] fp32: log-normal, a fifth exact zeros, one x 1000 value (the shape of accumulate_edge_cases.npz)."""
     out = []
-    for _, c, _, _, _ in TYPES:
+    for _, c, _, _, _ in types:
         s = np.exp(rng.normal(0.0, 1.0, (n, c))).astype(np.float32)
         s[rng.random((n, c)) < 0.2] = 0.0
         if n:
@@ -90,8 +93,7 @@ def run_records(api, S, pixels, samples, lo=0, hi=None):
     hi = len(pixels) if hi is None else hi
     d_px = dev(pixels[lo:hi])
     d_s = [dev(s[lo:hi]) for s in samples]
-    sts = [api.make_stat_type_records(d_s[i], TYPES[i][1], S.st[i], TYPES[i][2], TYPES[i][3], prepass_into=S.pre(i))
-           for i in range(len(TYPES))]
+    sts = [api.make_stat_type_records(d_s[i], k[1], S.st[i], k[2], k[3], prepass_into=S.pre(i)) for i, k in enumerate(S.types)]
     api.accumulate_records(S.W, S.H, sts, d_px)
     torch.cuda.synchronize()
 
@@ -305,15 +307,13 @@ def test_epilogue_is_statmc_prepass(gpu, ragged, spec):
         api.set_filter_spec()
 
 
-def test_ragged_counts_match_the_oracle(gpu, oracle, ragged):
+def assert_matches_the_oracle(oracle, S, counts, pixels, samples):
     """The oracle's per-sample update folded per pixel on the CPU, held to test_accumulate_matches_oracle's bound: bit-exact
     counts, raw-sample moments and non-transform moments; <= 1e-5 relative L2 where the GPU's sqrt stands in for pow."""
-    W, H, counts, pixels, samples = ragged
-    S = States(W, H)
-    run_records(gpu, S, pixels, samples)
+    W, H = S.W, S.H
     order = sorted_live(pixels, W * H)
     starts = np.cumsum(counts) - counts
-    for i, (name, c, transform, max_moment, _) in enumerate(TYPES):
+    for i, (name, c, transform, max_moment, _) in enumerate(S.types):
         ref = oracle.new_state(H, W, c)
         flat = {k: v.reshape(W * H, -1) for k, v in ref.items()}
         srt = samples[i][order]
@@ -331,6 +331,27 @@ def test_ragged_counts_match_the_oracle(gpu, oracle, ragged):
         else:
             for k in ("mean", "m2", "m3"):
                 assert np.array_equal(got[k], ref[k]), (name, k)
+
+
+def test_ragged_counts_match_the_oracle(gpu, oracle, ragged):
+    W, H, counts, pixels, samples = ragged
+    S = States(W, H)
+    run_records(gpu, S, pixels, samples)
+    assert_matches_the_oracle(oracle, S, counts, pixels, samples)
+
+
+def test_every_kind_at_the_walks_edges_matches_the_oracle(gpu, oracle):
+    """All twelve bodies of the type dispatch in one call, on runs at every edge of the walk: empty, shorter than a batch of
+    four, whole batches in odd and even number, each with and without a tail.  test_ragged_counts_match_the_oracle's bounds."""
+    W, H = 16, 8
+    rng = np.random.default_rng(41)
+    counts = np.resize(np.array([0, 1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13, 16, 17]), W * H)
+    pixels = records_of_counts(rng, counts, dead=0.05)
+    assert (pixels == -1).any() and (pixels == W * H + 7).any()
+    samples = make_samples(rng, pixels.size, KINDS)
+    S = States(W, H, types=KINDS)
+    run_records(gpu, S, pixels, samples)
+    assert_matches_the_oracle(oracle, S, counts, pixels, samples)
 
 
 def test_no_records_or_no_types_is_a_no_op(gpu):

@@ -239,6 +239,25 @@ def test_records_at_a_4_byte_aligned_address(gpu, ragged):
         check_case(gpu, W, H, kinds, pixels, fields, fusable=kinds is FIVE, shift=shift)
 
 
+def test_every_kind_at_the_walks_edges_in_the_general_fold(gpu):
+    """All 24 bodies of the general fold's type dispatch -- twelve (channels, transform, max_moment) kinds, every field fp32 and
+    every field half -- on runs at every edge of the walk (tests/test_records_gpu.py's lengths): bit-equal to
+    statmc_accumulate_records on the de-interleaved arrays that hold the widened values."""
+    W, H = 16, 8
+    from test_records_gpu import KINDS as kinds
+    rng = np.random.default_rng(43)
+    counts = np.resize(np.array([0, 1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13, 16, 17]), W * H)
+    pixels = records_of_counts(rng, counts, dead=0.05)
+    fields = [np.minimum(f, np.float32(60000.0)) for f in make_fields(rng, kinds, pixels.size)]      # finite in half
+    for formats in (None, [F16] * len(kinds)):
+        ref = States(W, H, kinds)
+        run_arrays(gpu, ref, pixels, widened(fields, formats))
+        rec, layout = gpu.pack_records(pixels, fields, formats=formats, fill=0xEE)
+        S = States(W, H, kinds)
+        assert run_interleaved(gpu, S, rec, layout, GENERAL) == GENERAL
+        same(ref.snapshot(), S.snapshot(), "fp32" if formats is None else "half")
+
+
 @pytest.mark.parametrize("set_name", list(SETS))
 def test_run_lengths_at_the_batch_edges(gpu, set_name):
     """Runs of 1, 2, 3, 4, 5, 7, 8, 9, 11, 12, 13 records on consecutive pixels: shorter than a batch of four, whole batches, an odd

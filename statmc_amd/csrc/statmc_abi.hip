@@ -212,6 +212,8 @@ void apply_spec(const DeviceState &d, statmc::FilterArgs &k, const statmc_filter
     (void)a;
 }
 int prepass_table(const DeviceState &d) { return d.alpha_index + STATMC_TQ_N_ALPHAS * (d.spec.sides ? 1 : 0); }
+// what the pre-pass epilogues call pre_flags (AccumulateType::pre_flags): 1 Welch degrees of freedom, 2 n < 2 excludes the pixel
+int prepass_flags(const DeviceState &d) { return (d.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (d.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0); }
 
 int check_image(const statmc_image &im, int w, int h, int channels, const char *what, int idx) {
     if (!im.data) return fail(STATMC_ERR_INVALID, "%s[%d]: null device pointer", what, idx);
@@ -550,8 +552,8 @@ static int prepass_impl(const statmc_filter_args *a, int channels) {
         k.n_elems = (long long)W * H * channels;
         k.channels = channels;
         k.table = prepass_table(dstate);
-        k.welch = dstate.spec.dof == STATMC_DOF_WELCH;
-        k.small_n_exclude = dstate.spec.small_n == STATMC_SMALL_N_EXCLUDE;
+        k.welch = prepass_flags(dstate) & 1;
+        k.small_n_exclude = (prepass_flags(dstate) >> 1) & 1;
         HIP_TRY(statmc::launch_prepass(k, S(a->stream)));
     }
     return STATMC_OK;
@@ -1170,7 +1172,7 @@ static int fill_stat_type(const DeviceState &ds, const statmc_stat_type &t, int 
         d.mean_corr = t.mean_corr;
         d.disc = t.discriminator;
         d.pre_table = prepass_table(ds);
-        d.pre_flags = (ds.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (ds.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0);
+        d.pre_flags = prepass_flags(ds);
     }
     return STATMC_OK;
 }
@@ -1183,7 +1185,7 @@ int statmc_get_prepass_context(statmc_prepass_context *out) {
     const float *table = statmc::t_table_device_ptr(prepass_table(dstate));
     if (!table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
     out->t_table = table;
-    out->flags = (dstate.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (dstate.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0);
+    out->flags = prepass_flags(dstate);
     out->reserved = 0;
     return STATMC_OK;
 }
@@ -1285,8 +1287,7 @@ static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const sta
 
 // statmc_combine_statistics: validation (include/statmc.h) and the entry order of the launch -- entries that borrow counts
 // first, so that they read their owner's counts before the owner's lane writes n = nA + nB
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // NULL: an absent plane
-
+using statmc::aligned16;   // (statmc_device.h; NULL, an absent plane, passes)
 static int fill_combine_entry(const DeviceState &ds, const statmc_combine_entry *entries, int n_entries, int i,
                               statmc::CombineEntry &k) {
     const statmc_combine_entry &e = entries[i];
@@ -1349,7 +1350,7 @@ static int fill_combine_entry(const DeviceState &ds, const statmc_combine_entry 
         k.mean_corr = d.mean_corr;
         k.disc = d.discriminator;
         k.pre_table = prepass_table(ds);   // as statmc_prepass (prepass_impl) and the accumulation's epilogue (fill_stat_type)
-        k.pre_flags = (ds.spec.dof == STATMC_DOF_WELCH ? 1 : 0) | (ds.spec.small_n == STATMC_SMALL_N_EXCLUDE ? 2 : 0);
+        k.pre_flags = prepass_flags(ds);
     }
     return STATMC_OK;
 }

@@ -10,6 +10,9 @@
 
 namespace statmc {
 
+// a plane that whole 4-pixel groups can move to and from as dwordx4 (NULL, an absent plane, passes)
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 // ---------------------------------------------------------------- pointwise kernels
 struct PrepassArgs {
     const int32_t *n;

@@ -147,8 +147,6 @@ __global__ __launch_bounds__(kBlock) void prepass_kernel(PrepassArgs a) {
     }
 }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 hipError_t launch_prepass(const PrepassArgs &a, hipStream_t s) {
     const bool vec = aligned16(a.mean) && aligned16(a.m2) && aligned16(a.m3) && aligned16(a.mean_corr) &&
                      aligned16(a.disc);
@@ -299,6 +297,96 @@ __device__ __forceinline__ void add_sample2(PairState *st, const v2f *nf, const 
 }
 #undef STATMC_PAIRS
 
+// One state plane of a lane's 4 consecutive pixels -- C float4 from p on -- into the field of the lane's element pairs (2 i, 2 i + 1)
+// and back.  ON = false: a plane the stat type does not hold; it reads as zeros and is not stored.
+template <int C, bool ON = true>
+__device__ __forceinline__ void load_plane(PairState *st, v2f PairState::*field, const float *p) {
+#pragma unroll
+    for (int k = 0; k < C; k++) {
+        float4 v = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (ON) v = *reinterpret_cast<const float4 *>(p + 4 * k);
+        st[2 * k].*field = v2f{v.x, v.y};
+        st[2 * k + 1].*field = v2f{v.z, v.w};
+    }
+}
+template <int C, bool ON = true>
+__device__ __forceinline__ void store_plane(float *p, const PairState *st, v2f PairState::*field) {
+    if constexpr (ON) {
+#pragma unroll
+        for (int k = 0; k < C; k++) {
+            const vfloat4 v = {(st[2 * k].*field).x, (st[2 * k].*field).y, (st[2 * k + 1].*field).x, (st[2 * k + 1].*field).y};
+            *reinterpret_cast<vfloat4 *>(p + 4 * k) = v;
+        }
+    }
+}
+// The counts of the lane's 4 pixels after the batch: one per pixel, or (NC = 1) the one count a group is known to hold.
+// Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
+template <int NC>
+__device__ __forceinline__ void store_counts(int32_t *n, const int (&n_out)[NC]) {
+    typedef int vint4 __attribute__((ext_vector_type(4)));
+    const vint4 v = {n_out[0], n_out[NC > 1 ? 1 : 0], n_out[NC > 1 ? 2 : 0], n_out[NC > 1 ? 3 : 0]};
+    *reinterpret_cast<vint4 *>(n) = v;
+}
+// Optional epilogue (round 6): the pre-pass of the moments just written, from the registers that hold them -- the same
+// prepass_elem as prepass_kernel, hence the same bits -- instead of a launch that reads 40 B per pixel back.  NC as above: one
+// count, one quantile.  (The caller reads pre_mc, pre_dc, table and flags out of its descriptor BEFORE its first store: see
+// accumulate_lane.)
+template <int C, int NC>
+__device__ __forceinline__ void store_prepass(float *pre_mc, float *pre_dc, const PairState *st, const int (&n_out)[NC], int table, int flags) {
+    float tq[NC];
+#pragma unroll
+    for (int p = 0; p < NC; p++) tq[p] = prepass_quantile(table, flags, n_out[p]);
+#pragma unroll
+    for (int k = 0; k < C; k++) {
+        vfloat4 mc, dc;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int e = 4 * k + j, px = NC > 1 ? e / C : 0;
+            float m, d;
+            prepass_elem(n_out[px], tq[px], st[e >> 1].mean[e & 1], st[e >> 1].m2[e & 1], st[e >> 1].m3[e & 1], m, d, (flags & 2) != 0);
+            mc[j] = m;
+            dc[j] = d;
+        }
+        *reinterpret_cast<vfloat4 *>(pre_mc + 4 * k) = mc;
+        *reinterpret_cast<vfloat4 *>(pre_dc + 4 * k) = dc;
+    }
+}
+
+// The LDS-DMA ring of a wave, its protocol written once: D sample rows in flight, every row T transfers that `issue(s, slot)`
+// requests; row s has landed when at most T (D - 1) transfers issued after it are outstanding (VMEM operations of a wave complete
+// in order; nothing else touches memory inside the walk).  `take_and_fold(s, slot, refill)` reads the lane's piece of the slot,
+// waits for those LDS reads (a slot is refilled once every lane has read its piece), calls refill() and folds sample s.
+// primed: the caller has requested the first D rows already (acc_ring_prime, ahead of its state loads).
+template <int D, typename Issue>
+__device__ __forceinline__ void acc_ring_prime(int S, Issue issue) {
+#pragma unroll
+    for (int d = 0; d < D; d++)
+        if (d < S) issue(d, d);
+}
+template <int D, int T, typename Issue, typename TakeFold>
+__device__ __forceinline__ void acc_ring_walk(int S, bool primed, Issue issue, TakeFold take_and_fold) {
+    static_assert(T * (D - 1) <= 63, "the counted wait must fit vmcnt");
+    // every earlier access of the wave to memory (the state loads; a primed ring's first D rows, requested ahead of them) has
+    // completed before the counted waits start
+    acc_wait_vmcnt<0>();
+    if (!primed) acc_ring_prime<D>(S, issue);
+    const int S_full = S >= D ? S - D + 1 : 0;          // samples s < S_full have D - 1 later rows in flight behind them
+    // One row per trip, the slot a run-time index (round 5): unrolled by D with compile-time slots the compiler hoisted the
+    // LDS reads of all D rows to the top of the body -- D x 12 registers, which is what capped the ring at three rows
+    // (240 VGPRs; 5 rows: 256 + AGPR copies, one wave per SIMD).  The body is ~200 instructions; the loop costs nothing.
+    int slot = 0;
+#pragma unroll 1
+    for (int s = 0; s < S; s++) {
+        if (s < S_full) acc_wait_vmcnt<T * (D - 1)>(); else acc_wait_vmcnt<0>();   // the last D - 1 rows: nothing is issued behind them
+        take_and_fold(s, slot, [&] { if (s + D < S) issue(s + D, slot); });
+        slot = slot + 1 == D ? 0 : slot + 1;
+    }
+}
+// Every lane issues all three transfers of an RGB row, whatever part of the row exists: the waits of the walk COUNT transfers
+// (vmcnt), so their number per row must not depend on n_active.  A piece beyond the row's end re-reads the row's first 16 bytes
+// (memory that exists) into a part of the slot nobody reads.  Piece k of lane `lane`, in floats from the row's start:
+__device__ __forceinline__ int acc_row_piece(int k, int lane, int n_active) { return 256 * k + 4 * lane < 12 * n_active ? 256 * k + 4 * lane : 0; }
+
 // The lane's 4 consecutive pixels starting at film pixel p0 (16-B aligned planes): load the
 // state, fold S samples in order, store.  Sample s of the lane's elements is at sp + s * stride
 // (4*C consecutive floats): stride = n_elems for sample-major film planes, = tile pixels * C for
@@ -340,17 +428,9 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     if constexpr (kDma) {
         const int lane = threadIdx.x & 63;
         dma_row0 = reinterpret_cast<const float *>(sp) - 12 * lane;                          // the wave's row of sample 0 (lane l sits 12 l floats in; the same value in every lane)
-        const int row_floats = 12 * n_active;               // the part of the wave's row that exists
-        // Every lane issues all three transfers of a row, whatever part of the row exists: the waits of the walk COUNT
-        // transfers (vmcnt), so their number per row must not depend on n_active.  A piece beyond the row's end re-reads the
-        // row's first 16 bytes (memory that exists) into a part of the slot nobody reads.
 #pragma unroll
-        for (int k = 0; k < 3; k++) dma_piece[k] = 256 * k + 4 * lane < row_floats ? 256 * k + 4 * lane : 0;
-        if (dma_first) {
-#pragma unroll
-            for (int d = 0; d < kD; d++)
-                if (d < S) dma_issue(d, d);
-        }
+        for (int k = 0; k < 3; k++) dma_piece[k] = acc_row_piece(k, lane, n_active);
+        if (dma_first) acc_ring_prime<kD>(S, dma_issue);
     }
     constexpr int NE = 4 * C;  // elements per lane
     const long long e0 = p0 * C;
@@ -360,25 +440,13 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     float *const pre_dc = MAXM >= 3 ? t.disc : nullptr;
     const int pre_table = t.pre_table, pre_flags = t.pre_flags;
     PairState st[NE / 2];   // element pairs (2 i, 2 i + 1) of the lane's 4 C consecutive elements
-    float tmp[NE];
     const int4 n4 = *reinterpret_cast<const int4 *>(t.n + p0);
     const int n0[4] = {n4.x, n4.y, n4.z, n4.w};
-#define STATMC_LOAD_PLANE(ptr, field, enabled)                                   \
-    if (enabled) {                                                               \
-        _Pragma("unroll") for (int k = 0; k < C; k++) {                          \
-            const float4 v = *reinterpret_cast<const float4 *>((ptr) + e0 + 4 * k); \
-            tmp[4 * k] = v.x; tmp[4 * k + 1] = v.y; tmp[4 * k + 2] = v.z; tmp[4 * k + 3] = v.w; \
-        }                                                                        \
-    } else {                                                                     \
-        _Pragma("unroll") for (int j = 0; j < NE; j++) tmp[j] = 0.f;             \
-    }                                                                            \
-    _Pragma("unroll") for (int j = 0; j < NE / 2; j++) st[j].field = v2f{tmp[2 * j], tmp[2 * j + 1]};
-    STATMC_LOAD_PLANE(t.mean, mean, true)
-    STATMC_LOAD_PLANE(t.m2, m2, MAXM >= 2)
-    STATMC_LOAD_PLANE(t.m3, m3, MAXM >= 3)
-    STATMC_LOAD_PLANE(t.film_mean, fmean, TRANSFORM)
-    STATMC_LOAD_PLANE(t.film_m2, fm2, TRANSFORM)
-#undef STATMC_LOAD_PLANE
+    load_plane<C>(st, &PairState::mean, t.mean + e0);
+    load_plane<C, MAXM >= 2>(st, &PairState::m2, t.m2 + e0);
+    load_plane<C, MAXM >= 3>(st, &PairState::m3, t.m3 + e0);
+    load_plane<C, TRANSFORM>(st, &PairState::fmean, t.film_mean + e0);
+    load_plane<C, TRANSFORM>(st, &PairState::fm2, t.film_m2 + e0);
     // Software-pipelined sample walk: the loads of the next U samples are issued before
     // the current U are folded into the moments, so 2U sample rows per lane are in flight
     // (the compiler would otherwise drain each unrolled body before loading again).
@@ -465,41 +533,19 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
             fold_sample(q, s, same);
         }
     };
-    // The same walk with the sample rows arriving by LDS-DMA (C == 3): D rows in flight in the wave's ring; row s has
-    // landed when at most 3 (D - 1) transfers issued after it are outstanding (VMEM operations of a wave complete in
-    // order; nothing else touches memory inside the walk).  A slot is refilled once every lane has read its 48 B.
+    // The same walk with the sample rows arriving by LDS-DMA (C == 3): kD rows in flight in the wave's ring, three transfers each
+    // (acc_ring_walk); every lane reads its own 48 B back.
     auto walk_samples_dma = [&](auto same) {
-        constexpr int D = kD;
         const int lane = threadIdx.x & 63;
-        auto issue = dma_issue;
-        auto take = [&](vfloat4 (&q)[C], int slot) {
+        acc_ring_walk<kD, 3>(S, dma_first, dma_issue, [&](int s, int slot, auto refill) {
+            vfloat4 q[C];
             const float *mine = ring + slot * 768 + 12 * lane;
 #pragma unroll
             for (int k = 0; k < C; k++) q[k] = *reinterpret_cast<const vfloat4 *>(mine + 4 * k);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
-        };
-        // every earlier access of the wave to memory (the state loads above; with dma_first also the first D rows, requested
-        // ahead of them) has completed before the counted waits start
-        acc_wait_vmcnt<0>();
-        if (!dma_first) {
-#pragma unroll
-            for (int d = 0; d < D; d++)
-                if (d < S) issue(d, d);
-        }
-        const int S_full = S >= D ? S - D + 1 : 0;          // samples s < S_full have D - 1 later rows in flight behind them
-        // One row per trip, the slot a run-time index (round 5): unrolled by D with compile-time slots the compiler hoisted the
-        // LDS reads of all D rows to the top of the body -- D x 12 registers, which is what capped the ring at three rows
-        // (240 VGPRs; 5 rows: 256 + AGPR copies, one wave per SIMD).  The body is ~200 instructions; the loop costs nothing.
-        int slot = 0;
-#pragma unroll 1
-        for (int s = 0; s < S; s++) {
-            vfloat4 q[C];
-            if (s < S_full) acc_wait_vmcnt<3 * (D - 1)>(); else acc_wait_vmcnt<0>();   // the last D - 1 rows: nothing is issued behind them
-            take(q, slot);
-            if (s + D < S) issue(s + D, slot);
+            refill();
             fold_sample(q, s, same);
-            slot = slot + 1 == D ? 0 : slot + 1;
-        }
+        });
     };
     // wave-uniform choice: the fast walk only when every active lane qualifies
     const bool lane_same = !active || (n0[0] == n0[1] && n0[1] == n0[2] && n0[2] == n0[3]);
@@ -511,45 +557,15 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
         if (__builtin_amdgcn_ballot_w64(!lane_same) == 0) walk_samples(std::true_type{});
         else walk_samples(std::false_type{});
     }
-#define STATMC_STORE_PLANE(ptr, field, enabled)                                  \
-    if (enabled) {                                                               \
-        _Pragma("unroll") for (int k = 0; k < C; k++) {                          \
-            const vfloat4 v = {st[2 * k].field.x, st[2 * k].field.y, st[2 * k + 1].field.x, st[2 * k + 1].field.y}; \
-            *reinterpret_cast<vfloat4 *>((ptr) + e0 + 4 * k) = v;                \
-        }                                                                        \
-    }
-    STATMC_STORE_PLANE(t.mean, mean, true)
-    STATMC_STORE_PLANE(t.m2, m2, MAXM >= 2)
-    STATMC_STORE_PLANE(t.m3, m3, MAXM >= 3)
-    STATMC_STORE_PLANE(t.film_mean, fmean, TRANSFORM)
-    STATMC_STORE_PLANE(t.film_m2, fm2, TRANSFORM)
-#undef STATMC_STORE_PLANE
-    // Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
-    typedef int vint4 __attribute__((ext_vector_type(4)));
-    const vint4 n_out = {n0[0] + S, n0[1] + S, n0[2] + S, n0[3] + S};
-    *reinterpret_cast<vint4 *>(t.n + p0) = n_out;
-    // Optional epilogue (round 6): the pre-pass of the moments just written, from the registers that hold them -- the same
-    // prepass_elem as prepass_kernel, hence the same bits -- instead of a launch that reads 40 B per pixel back.
+    store_plane<C>(t.mean + e0, st, &PairState::mean);
+    store_plane<C, MAXM >= 2>(t.m2 + e0, st, &PairState::m2);
+    store_plane<C, MAXM >= 3>(t.m3 + e0, st, &PairState::m3);
+    store_plane<C, TRANSFORM>(t.film_mean + e0, st, &PairState::fmean);
+    store_plane<C, TRANSFORM>(t.film_m2 + e0, st, &PairState::fm2);
+    const int n_out[4] = {n0[0] + S, n0[1] + S, n0[2] + S, n0[3] + S};
+    store_counts(t.n + p0, n_out);
     if constexpr (MAXM >= 3) {
-        if (pre_mc != nullptr) {
-            float tq[4];
-#pragma unroll
-            for (int p = 0; p < 4; p++) tq[p] = prepass_quantile(pre_table, pre_flags, n_out[p]);
-#pragma unroll
-            for (int k = 0; k < C; k++) {
-                vfloat4 mc, dc;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int e = 4 * k + j, px = e / C;
-                    float m, d;
-                    prepass_elem(n_out[px], tq[px], st[e >> 1].mean[e & 1], st[e >> 1].m2[e & 1], st[e >> 1].m3[e & 1], m, d, (pre_flags & 2) != 0);
-                    mc[j] = m;
-                    dc[j] = d;
-                }
-                *reinterpret_cast<vfloat4 *>(pre_mc + e0 + 4 * k) = mc;
-                *reinterpret_cast<vfloat4 *>(pre_dc + e0 + 4 * k) = dc;
-            }
-        }
+        if (pre_mc != nullptr) store_prepass<C>(pre_mc + e0, pre_dc + e0, st, n_out, pre_table, pre_flags);
     }
 }
 
@@ -604,9 +620,11 @@ __device__ __forceinline__ void accumulate_type(const AccumulateType &t, long lo
         const bool active = g < n_full;
         const long long left = n_full - gw;
         const int n_active = left >= 64 ? 64 : left > 0 ? (int)left : 0;
-        if (n_active > 0)
-            accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA, ST>(t, p0, samples + p0 * C, t.stride, t.n_samples,
-                                                                                                ring, active, n_active, dma_first);
+        if constexpr (VEC) {    // (VEC = false: no complete group, by construction and not by what the compiler can prove of n_full)
+            if (n_active > 0)
+                accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA, ST>(t, p0, samples + p0 * C, t.stride, t.n_samples,
+                                                                                                    ring, active, n_active, dma_first);
+        }
         if (!active && g < n_groups) {   // unaligned images, the ragged last group
             for (long long p = p0; p < n_px && p < p0 + 4; p++)
                 accumulate_pixel<C, MAXM, TRANSFORM, ST>(t, p, samples + p * C, t.stride, t.n_samples);
@@ -614,17 +632,30 @@ __device__ __forceinline__ void accumulate_type(const AccumulateType &t, long lo
     }
 }
 
-template <int C, bool VEC, int UMUL, int DMA, typename ST = float>
+// From a run-time descriptor to the compile-time shape of its walk: f(C, MAXM, TRANSFORM), each an integral constant.  The
+// film-major, the 16-bit and the tile-fed kernels all come through here.
+template <typename F>
+__device__ __forceinline__ void acc_dispatch_type(const AccumulateType &t, F f) {
+    auto moments = [&](auto c) {
+        if (t.transform) {
+            if (t.max_moment >= 3) f(c, std::integral_constant<int, 3>{}, std::true_type{});
+            else if (t.max_moment == 2) f(c, std::integral_constant<int, 2>{}, std::true_type{});
+            else f(c, std::integral_constant<int, 1>{}, std::true_type{});
+        } else {
+            if (t.max_moment >= 3) f(c, std::integral_constant<int, 3>{}, std::false_type{});
+            else if (t.max_moment == 2) f(c, std::integral_constant<int, 2>{}, std::false_type{});
+            else f(c, std::integral_constant<int, 1>{}, std::false_type{});
+        }
+    };
+    if (t.channels == 3) moments(std::integral_constant<int, 3>{});
+    else moments(std::integral_constant<int, 1>{});
+}
+// (the film-major kernels' use of it)
+template <bool VEC, int UMUL, int DMA, typename ST = float>
 __device__ __forceinline__ void accumulate_dispatch(const AccumulateType &t, long long blk, long long nblk, float *ring, bool dma_first) {
-    if (t.transform) {
-        if (t.max_moment >= 3) accumulate_type<C, 3, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-        else if (t.max_moment == 2) accumulate_type<C, 2, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-        else accumulate_type<C, 1, true, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-    } else {
-        if (t.max_moment >= 3) accumulate_type<C, 3, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-        else if (t.max_moment == 2) accumulate_type<C, 2, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-        else accumulate_type<C, 1, false, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
-    }
+    acc_dispatch_type(t, [&](auto c, auto maxm, auto transform) {
+        accumulate_type<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, VEC, UMUL, DMA, ST>(t, blk, nblk, ring, dma_first);
+    });
 }
 
 // Default grid: stat types are interleaved over a large 1-D grid (block b works on type
@@ -635,6 +666,11 @@ __device__ __forceinline__ void accumulate_dispatch(const AccumulateType &t, lon
 // running this bandwidth-bound kernel beside the VALU-bound window filter of the previous
 // iteration on a second stream gains <= 15 % (the two contend for VALU issue), so bench.py
 // keeps the kernels back to back.
+// (The three shapes stay written out, each with its own call of the walk, and accumulate_half_kernel keeps its own copy of the first
+// two: one function handing a workgroup its (type, blk, nblk), called from ONE loop in both kernels, makes accumulate_kernel a third
+// of the code -- 51 412 -> 17 262 instructions with the ring, 66 492 -> 22 322 without -- and the register walk slower: 1080p, 64
+// samples per launch, per-type kernel, loads into registers 1.113 / 1.112 ms before against 1.155 - 1.157 with it, prefetch x 2
+// 1.119 / 1.118 against 1.153 - 1.158; the LDS-DMA walk level, 1.031 - 1.045 against 1.030 - 1.036.  profiles/accumulate_onebody.jsonl)
 template <bool VEC, int UMUL, int DMA, int OCC = kAccWaves>
 __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs a) {
     extern __shared__ __attribute__((aligned(16))) float acc_lds[];
@@ -646,8 +682,7 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
             // starting with the same type: 3.92 against 3.75 ms; the eight workgroups of a dispatch round -- one per XCD -- with the same
             // type: no difference; profiles/r06_ab_resident_start.log)
             const AccumulateType t = a.t[((int)blockIdx.x + i) % a.n_types];   // (by value: see below)
-            if (t.channels == 3) accumulate_dispatch<3, VEC, UMUL, DMA>(t, blockIdx.x, gridDim.x, ring, a.dma_first != 0);
-            else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blockIdx.x, gridDim.x, ring, a.dma_first != 0);
+            accumulate_dispatch<VEC, UMUL, DMA>(t, blockIdx.x, gridDim.x, ring, a.dma_first != 0);
         }
         return;
     }
@@ -661,8 +696,7 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
         // accumulation 3.67 -> 4.60 ms; round 6)
         const AccumulateType t = a.t[ti];
         const long long blk = blockIdx.x / a.n_types, nblk = gridDim.x / a.n_types;
-        if (t.channels == 3) accumulate_dispatch<3, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
-        else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
+        accumulate_dispatch<VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
         return;
     }
     // Workgroups are dealt to the stat types in rounds of n_slots, each type holding a number of
@@ -673,8 +707,7 @@ __global__ __launch_bounds__(kBlock, OCC) void accumulate_kernel(AccumulateArgs 
     const AccumulateType t = a.t[ti];
     const long long blk = (long long)round * a.type_slots[ti] + a.slot_rank[slot];
     const long long nblk = (long long)n_rounds * a.type_slots[ti];
-    if (t.channels == 3) accumulate_dispatch<3, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
-    else accumulate_dispatch<1, VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
+    accumulate_dispatch<VEC, UMUL, DMA>(t, blk, nblk, ring, a.dma_first != 0);
 }
 
 // Launches in which at least one type's arena is IEEE half (statmc_accumulate_formats; a.half_mask: bit i = type i) and which the
@@ -690,13 +723,8 @@ __global__ __launch_bounds__(kBlock) void accumulate_half_kernel(AccumulateArgs 
         const int ti = ((int)blockIdx.x + i) % a.n_types;
         const AccumulateType t = a.t[ti];                                      // (a copy: see accumulate_kernel)
         const long long blk = resident ? blockIdx.x : blockIdx.x / a.n_types, nblk = resident ? gridDim.x : gridDim.x / a.n_types;
-        if ((a.half_mask >> ti) & 1) {
-            if (t.channels == 3) accumulate_dispatch<3, VEC, 1, 0, _Float16>(t, blk, nblk, nullptr, false);
-            else accumulate_dispatch<1, VEC, 1, 0, _Float16>(t, blk, nblk, nullptr, false);
-        } else {
-            if (t.channels == 3) accumulate_dispatch<3, VEC, 1, 0>(t, blk, nblk, nullptr, false);
-            else accumulate_dispatch<1, VEC, 1, 0>(t, blk, nblk, nullptr, false);
-        }
+        if ((a.half_mask >> ti) & 1) accumulate_dispatch<VEC, 1, 0, _Float16>(t, blk, nblk, nullptr, false);
+        else accumulate_dispatch<VEC, 1, 0>(t, blk, nblk, nullptr, false);
     }
 }
 
@@ -721,10 +749,10 @@ struct AccumulateFusedArgs {
     long long n_groups;                 // 4-pixel groups of the film (every type has the same pixels)
     int n_samples;                      // ... and the same batch length
 };
-constexpr int acc_fused_slot_floats(int k, int m) { return 768 * (1 + k) + 256 * m; }       // one sample row of every type, per wave
-constexpr size_t acc_fused_lds_bytes(int k, int m, int d) { return (size_t)4 * d * acc_fused_slot_floats(k, m) * sizeof(float); }
-// 16-bit arenas (statmc_accumulate_formats), FMT: 0 every type fp32 (the kernels above all), 1 the feature types half and the radiance
-// type fp32, 2 every type half.  A wave's half row is half as long -- 1 536 B of an RGB type, 512 B of a 1-channel type -- and
+// The wave's ring slot holds one sample row of every type.  FMT 0, every type fp32 (the kernels above all): 768 dwords per RGB type,
+// the radiance type first, then 256 per 1-channel type.
+// 16-bit arenas (statmc_accumulate_formats), FMT: 1 the feature types half and the radiance type fp32, 2 every type half.  A wave's
+// half row is half as long -- 1 536 B of an RGB type, 512 B of a 1-channel type -- and
 // arrives in 16-byte pieces like the fp32 rows: the first 1 KiB of an RGB row is one transfer of the wave; what is left of it and a
 // 1-channel row are 512-B UNITS, 32 lanes' worth, and two units share one transfer (lanes 0 .. 31 fetch one, lanes 32 .. 63 the
 // other: the source address of an LDS-DMA transfer is per lane, its destination is not).  An odd last unit is fetched twice, its
@@ -740,15 +768,18 @@ constexpr int acc_fused_unit0(int fmt, int k) { return fmt == 2 ? 256 * (1 + k) 
 constexpr int acc_fused_unit_of(int fmt, int i) { return i - (fmt == 1 ? 1 : 0); }                            // half type i: its unit (RGB: the row's tail)
 constexpr int acc_fused_units(int fmt, int k, int m) { return 1 + k + m - (fmt == 1 ? 1 : 0); }
 constexpr int acc_fused_slot_dwords(int fmt, int k, int m) {
-    return fmt == 0 ? acc_fused_slot_floats(k, m) : acc_fused_unit0(fmt, k) + 256 * ((acc_fused_units(fmt, k, m) + 1) / 2);
+    return fmt == 0 ? 768 * (1 + k) + 256 * m : acc_fused_unit0(fmt, k) + 256 * ((acc_fused_units(fmt, k, m) + 1) / 2);
 }
 constexpr int acc_fused_transfers(int fmt, int k, int m) {
     return fmt == 0 ? 3 * (1 + k) + m : (fmt == 1 ? 3 : 1) + k + (acc_fused_units(fmt, k, m) + 1) / 2;
 }
 // ring depth: the half rows' shorter slots are spent on rows in flight, about the bytes per CU the fp32 ring holds (132 KiB for the
 // 11-channel set): six all-half slots (6 KiB each per wave) are 144 KiB, five mixed ones (7 KiB) 140 KiB; T (D - 1) stays below 64
-constexpr int acc_fused_half_depth(int fmt) { return fmt == 2 ? 6 : 5; }
-static_assert(acc_fused_slot_dwords(0, 2, 2) == acc_fused_slot_floats(2, 2) && acc_fused_transfers(0, 2, 2) == 11, "FMT 0 is the fp32 layout");
+constexpr int acc_fused_depth(int fmt) { return fmt == 0 ? kAccFusedD : fmt == 2 ? 6 : 5; }
+constexpr size_t acc_fused_ring_bytes(int fmt, int k, int m) {      // per workgroup: four waves
+    return (size_t)4 * acc_fused_depth(fmt) * acc_fused_slot_dwords(fmt, k, m) * sizeof(float);
+}
+static_assert(acc_fused_ring_bytes(1, 2, 2) <= 160 * 1024 && acc_fused_ring_bytes(2, 2, 2) <= 160 * 1024, "the ring of a workgroup must fit the CU's LDS");
 
 // A wave whose lanes do not all hold one count per group in every type (adaptively sampled films): today's walk, type after
 // type, in the wave's ring -- the same bits, no second ragged code.
@@ -757,7 +788,7 @@ __device__ __forceinline__ void accumulate_fused_ragged(const AccumulateFusedArg
     // (the descriptors below are picked by comparisons, never by a run-time index into the kernel argument -- see accumulate_kernel on
     // what that costs; with at most two types of a kind "the first or the last" names them all)
     static_assert(K >= 0 && K <= 2 && M >= 0 && M <= 2, "a.t[1] / a.t[K] and a.t[1 + K] / a.t[K + M] name every feature type only up to two of a kind");
-    constexpr int kFit = D * acc_fused_slot_floats(K, M) / 768;       // rows of one RGB type the wave's ring holds
+    constexpr int kFit = D * acc_fused_slot_dwords(FMT, K, M) / 768;       // rows of one RGB type the wave's ring holds
     constexpr int FD = FMT != 0 ? 0 : kFit < kAccDmaD ? kFit : kAccDmaD;   // (launches with 16-bit arenas: register loads, whatever the type's format)
     typedef typename std::conditional<FMT == 2, _Float16, float>::type ST0;
     typedef typename std::conditional<FMT != 0, _Float16, float>::type STF;
@@ -791,7 +822,6 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
     constexpr int NT = 1 + K + M;
     constexpr int SLOT = acc_fused_slot_dwords(FMT, K, M);
     constexpr int T = acc_fused_transfers(FMT, K, M);       // transfers per sample row
-    static_assert(T * (D - 1) <= 63, "the counted wait must fit vmcnt");
     constexpr int KA = K > 0 ? K : 1, MA = M > 0 ? M : 1;
     const int lane = threadIdx.x & 63;
     const bool active = lane < n_active;
@@ -827,13 +857,12 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
         row[i] = a.t[i].samples + (((gw << 2) * (i <= K ? 3 : 1)) >> (acc_fused_is_half(FMT, i) ? 1 : 0));
         stride[i] = a.t[i].stride >> (acc_fused_is_half(FMT, i) ? 1 : 0);
     }
-    // Every lane issues every transfer of a row, whatever part of the row exists; a piece beyond the row's end re-reads the
-    // row's first 16 bytes (memory that exists) into a part of the slot nobody reads (as in accumulate_lane).
+    // (every lane issues every transfer of a row, whatever part of the row exists: acc_row_piece; a 1-channel row likewise)
     int piece3[3];
 #pragma unroll
-    for (int k = 0; k < 3; k++) piece3[k] = 256 * k + 4 * lane < 12 * n_active ? 256 * k + 4 * lane : 0;
+    for (int k = 0; k < 3; k++) piece3[k] = acc_row_piece(k, lane, n_active);
     const int piece1 = active ? 4 * lane : 0;
-    auto issue = [&](int slot) {
+    auto issue = [&](int, int slot) {      // (the rows are requested in order: row[] moves on by itself)
         float *dst = ring + slot * SLOT;
         if constexpr (FMT != 0) {
             // (full waves only; FMT 0 keeps the statements below, with their offsets written as they always were)
@@ -875,45 +904,19 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
     // state: radiance 5 planes, every feature type its mean
     const long long e3 = p0 * 3;
     PairState st[6], fr[KA][6], f1[MA][2];
-    auto load3 = [&](const float *p, v2f (&d)[6]) {
+    load_plane<3>(st, &PairState::mean, r_mean + e3);
+    load_plane<3>(st, &PairState::m2, r_m2 + e3);
+    load_plane<3>(st, &PairState::m3, r_m3 + e3);
+    load_plane<3>(st, &PairState::fmean, r_fmean + e3);
+    load_plane<3>(st, &PairState::fm2, r_fm2 + e3);
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float4 v = *reinterpret_cast<const float4 *>(p + e3 + 4 * k);
-            d[2 * k] = v2f{v.x, v.y};
-            d[2 * k + 1] = v2f{v.z, v.w};
-        }
-    };
-    {
-        v2f d[6];
-#define STATMC_FUSED_LOAD(ptr, arr, field) load3(ptr, d); _Pragma("unroll") for (int j = 0; j < 6; j++) arr[j].field = d[j];
-        STATMC_FUSED_LOAD(r_mean, st, mean)
-        STATMC_FUSED_LOAD(r_m2, st, m2)
-        STATMC_FUSED_LOAD(r_m3, st, m3)
-        STATMC_FUSED_LOAD(r_fmean, st, fmean)
-        STATMC_FUSED_LOAD(r_fm2, st, fm2)
+    for (int i = 0; i < K; i++) load_plane<3>(fr[i], &PairState::mean, f_mean[1 + i] + e3);
 #pragma unroll
-        for (int i = 0; i < K; i++) { STATMC_FUSED_LOAD(f_mean[1 + i], fr[i], mean) }
-#undef STATMC_FUSED_LOAD
-#pragma unroll
-        for (int i = 0; i < M; i++) {
-            const float4 v = *reinterpret_cast<const float4 *>(f_mean[1 + K + i] + p0);
-            f1[i][0].mean = v2f{v.x, v.y};
-            f1[i][1].mean = v2f{v.z, v.w};
-        }
-    }
+    for (int i = 0; i < M; i++) load_plane<1>(f1[i], &PairState::mean, f_mean[1 + K + i] + p0);
     // ONE: every type of the wave starts from the same count (all but films whose radiance has seen samples the features have
     // not): one count conversion and one refined reciprocal per sample for all of them, else one per type.
     auto walk = [&](auto one) {
-        // every earlier access of the wave to memory has completed before the counted waits start
-        acc_wait_vmcnt<0>();
-#pragma unroll
-        for (int d = 0; d < D; d++)
-            if (d < S) issue(d);
-        const int S_full = S >= D ? S - D + 1 : 0;          // samples s < S_full have D - 1 later rows in flight behind them
-        int slot = 0;
-#pragma unroll 1
-        for (int s = 0; s < S; s++) {
-            if (s < S_full) acc_wait_vmcnt<T * (D - 1)>(); else acc_wait_vmcnt<0>();
+        acc_ring_walk<D, T>(S, false, issue, [&](int s, int slot, auto refill) {
             const float *mine = ring + slot * SLOT;
             vfloat4 q[1 + K][3], q1[MA];
             if constexpr (FMT != 0) {
@@ -952,7 +955,7 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
             for (int i = 0; i < M; i++) q1[i] = *reinterpret_cast<const vfloat4 *>(mine + 768 * (1 + K) + 256 * i + 4 * lane);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
             }
-            if (s + D < S) issue(slot);
+            refill();
             v2f nf[NT], rc[NT];
             if constexpr (decltype(one)::value) {
                 const float nf0 = (float)(nb[0] + s + 1);
@@ -989,88 +992,53 @@ __device__ __forceinline__ void accumulate_fused_wave(const AccumulateFusedArgs 
 #pragma unroll
             for (int i = 0; i < K; i++) fold3(fr[i], 1 + i, std::false_type{});
             fold3(st, 0, std::true_type{});
-            slot = slot + 1 == D ? 0 : slot + 1;
-        }
+        });
     };
     if (__builtin_amdgcn_ballot_w64(active && !lane_one) == 0) walk(std::true_type{});
     else walk(std::false_type{});
     if (!active) return;                                    // nothing of an inactive lane is stored
-    auto store3 = [&](float *p, const v2f (&d)[6]) {
+    store_plane<3>(r_mean + e3, st, &PairState::mean);
+    store_plane<3>(r_m2 + e3, st, &PairState::m2);
+    store_plane<3>(r_m3 + e3, st, &PairState::m3);
+    store_plane<3>(r_fmean + e3, st, &PairState::fmean);
+    store_plane<3>(r_fm2 + e3, st, &PairState::fm2);
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const vfloat4 v = {d[2 * k].x, d[2 * k].y, d[2 * k + 1].x, d[2 * k + 1].y};
-            *reinterpret_cast<vfloat4 *>(p + e3 + 4 * k) = v;
-        }
-    };
-    {
-        v2f d[6];
-#define STATMC_FUSED_STORE(ptr, arr, field) _Pragma("unroll") for (int j = 0; j < 6; j++) d[j] = arr[j].field; store3(ptr, d);
-        STATMC_FUSED_STORE(r_mean, st, mean)
-        STATMC_FUSED_STORE(r_m2, st, m2)
-        STATMC_FUSED_STORE(r_m3, st, m3)
-        STATMC_FUSED_STORE(r_fmean, st, fmean)
-        STATMC_FUSED_STORE(r_fm2, st, fm2)
+    for (int i = 0; i < K; i++) store_plane<3>(f_mean[1 + i] + e3, fr[i], &PairState::mean);
 #pragma unroll
-        for (int i = 0; i < K; i++) { STATMC_FUSED_STORE(f_mean[1 + i], fr[i], mean) }
-#undef STATMC_FUSED_STORE
-#pragma unroll
-        for (int i = 0; i < M; i++) {
-            const vfloat4 v = {f1[i][0].mean.x, f1[i][0].mean.y, f1[i][1].mean.x, f1[i][1].mean.y};
-            *reinterpret_cast<vfloat4 *>(f_mean[1 + K + i] + p0) = v;
-        }
-    }
-    // Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
-    typedef int vint4 __attribute__((ext_vector_type(4)));
+    for (int i = 0; i < M; i++) store_plane<1>(f_mean[1 + K + i] + p0, f1[i], &PairState::mean);
+    // every group of this walk holds one count per type: one count to store, and one quantile for the radiance type's optional
+    // pre-pass epilogue
 #pragma unroll
     for (int i = 0; i < NT; i++) {
-        const vint4 n_out = {nb[i] + S, nb[i] + S, nb[i] + S, nb[i] + S};
-        *reinterpret_cast<vint4 *>(n_ptr[i] + p0) = n_out;
+        const int n_out[1] = {nb[i] + S};
+        store_counts(n_ptr[i] + p0, n_out);
     }
-    // the radiance type's optional pre-pass epilogue, as in accumulate_lane (the four pixels hold one count: one quantile)
     if (pre_mc != nullptr) {
-        const int n_out = nb[0] + S;
-        const float tq = prepass_quantile(pre_table, pre_flags, n_out);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            vfloat4 mc, dc;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int e = 4 * k + j;
-                float m, d;
-                prepass_elem(n_out, tq, st[e >> 1].mean[e & 1], st[e >> 1].m2[e & 1], st[e >> 1].m3[e & 1], m, d, (pre_flags & 2) != 0);
-                mc[j] = m;
-                dc[j] = d;
-            }
-            *reinterpret_cast<vfloat4 *>(pre_mc + e3 + 4 * k) = mc;
-            *reinterpret_cast<vfloat4 *>(pre_dc + e3 + 4 * k) = dc;
-        }
+        const int n_out[1] = {nb[0] + S};
+        store_prepass<3>(pre_mc + e3, pre_dc + e3, st, n_out, pre_table, pre_flags);
     }
 }
 
 // A resident grid: every workgroup walks 256-group units with a grid stride, its four waves 64 consecutive groups each, every
 // pass covering every type.  One wave per SIMD (the ring of the 11-channel set at three rows is 132 KiB per workgroup).
-template <int K, int M, int D>
-__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_kernel(AccumulateFusedArgs a) {
+template <int K, int M, int D, int FMT>
+__device__ __forceinline__ void accumulate_fused_grid(const AccumulateFusedArgs &a) {
     extern __shared__ __attribute__((aligned(16))) float acc_lds[];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *ring = acc_lds + wave * (D * acc_fused_slot_floats(K, M));
-    for (long long gw = (long long)blockIdx.x * kBlock + wave * 64; gw < a.n_groups; gw += (long long)gridDim.x * kBlock) {
-        const long long left = a.n_groups - gw;
-        accumulate_fused_wave<K, M, D>(a, gw, left >= 64 ? 64 : (int)left, ring);
-    }
-}
-
-// The same grid for launches with 16-bit arenas: a kernel of its own, so that the fp32 one above stays the code object it was.
-template <int K, int M, int FMT>
-__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_half_kernel(AccumulateFusedArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float acc_lds[];
-    constexpr int D = acc_fused_half_depth(FMT);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float *ring = acc_lds + wave * (D * acc_fused_slot_dwords(FMT, K, M));
     for (long long gw = (long long)blockIdx.x * kBlock + wave * 64; gw < a.n_groups; gw += (long long)gridDim.x * kBlock) {
         const long long left = a.n_groups - gw;
         accumulate_fused_wave<K, M, D, FMT>(a, gw, left >= 64 ? 64 : (int)left, ring);
     }
+}
+template <int K, int M, int D>
+__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_kernel(AccumulateFusedArgs a) {
+    accumulate_fused_grid<K, M, D, 0>(a);
+}
+// The same grid for launches with 16-bit arenas: a kernel of its own, so that the fp32 one above stays the code object it was.
+template <int K, int M, int FMT>
+__global__ __launch_bounds__(kBlock, 1) void accumulate_fused_half_kernel(AccumulateFusedArgs a) {
+    accumulate_fused_grid<K, M, acc_fused_depth(FMT), FMT>(a);
 }
 
 // The launches the fused walk serves: exactly one RGB type with the transform and three moments, K <= 2 mean-only RGB types,
@@ -1137,11 +1105,6 @@ static hipError_t launch_big_lds(size_t lds, const AccumulateFusedArgs &f, unsig
     hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(kBlock), lds, s, f);
     return hipGetLastError();
 }
-constexpr size_t acc_fused_ring_bytes(int fmt, int k, int m) {      // per workgroup: four waves
-    return (size_t)4 * (fmt == 0 ? kAccFusedD : acc_fused_half_depth(fmt)) * acc_fused_slot_dwords(fmt, k, m) * sizeof(float);
-}
-static_assert(acc_fused_ring_bytes(0, 2, 2) == acc_fused_lds_bytes(2, 2, kAccFusedD), "FMT 0 is the fp32 ring");
-static_assert(acc_fused_ring_bytes(1, 2, 2) <= 160 * 1024 && acc_fused_ring_bytes(2, 2, 2) <= 160 * 1024, "the ring of a workgroup must fit the CU's LDS");
 template <int FMT, int K, int M>
 static hipError_t launch_accumulate_fused_km(const AccumulateFusedArgs &f, unsigned blocks, hipStream_t s) {
     if constexpr (FMT == 0) return launch_big_lds<&accumulate_fused_kernel<K, M, kAccFusedD>>(acc_fused_ring_bytes(FMT, K, M), f, blocks, s);
@@ -1347,20 +1310,6 @@ __device__ __forceinline__ void accumulate_tile(const AccumulateType &t, const A
     }
 }
 
-template <int C, int UMUL, int DMA>
-__device__ __forceinline__ void accumulate_tile_dispatch(const AccumulateType &t, const AccumulateTilesArgs &a, int x0,
-                                                         int y0, int tw, int th, long long off, int S, float *ring) {
-    if (t.transform) {
-        if (t.max_moment >= 3) accumulate_tile<C, 3, true, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-        else if (t.max_moment == 2) accumulate_tile<C, 2, true, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-        else accumulate_tile<C, 1, true, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-    } else {
-        if (t.max_moment >= 3) accumulate_tile<C, 3, false, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-        else if (t.max_moment == 2) accumulate_tile<C, 2, false, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-        else accumulate_tile<C, 1, false, UMUL, DMA>(t, a, x0, y0, tw, th, off, S, ring);
-    }
-}
-
 template <int UMUL, int DMA>
 __global__ __launch_bounds__(kBlock) void accumulate_tiles_kernel(AccumulateTilesArgs a) {
     extern __shared__ __attribute__((aligned(16))) float acc_lds[];
@@ -1394,8 +1343,9 @@ __global__ __launch_bounds__(kBlock) void accumulate_tiles_kernel(AccumulateTile
         const int S = a.tile_samples[tile];
         if (S <= 0 || x1 <= x0 || y1 <= y0) continue;
         const AccumulateType &t = a.t[ti];
-        if (t.channels == 3) accumulate_tile_dispatch<3, UMUL, DMA>(t, a, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
-        else accumulate_tile_dispatch<1, UMUL, DMA>(t, a, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
+        acc_dispatch_type(t, [&](auto c, auto maxm, auto transform) {
+            accumulate_tile<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, UMUL, DMA>(t, a, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
+        });
     }
 }
 

@@ -15,7 +15,7 @@ DEV = torch.device("cuda:0")
 SET9 = ("radiance", "normal", "albedo")
 SET11 = ("radiance", "normal", "albedo", "depth", "materialid")
 ORDERS = {SET9: ("normal", "radiance", "albedo"), SET11: ("depth", "normal", "materialid", "radiance", "albedo")}
-RINGS = (5, 6)    # rows in flight per wave of the fused 16-bit walk: features half (acc_fused_half_depth(1)), all half (2)
+RINGS = (5, 6)    # rows in flight per wave of the fused 16-bit walk: features half (acc_fused_depth(1)), all half (2)
 BATCHES = sorted({s for d in RINGS for s in (1, d - 1, d, d + 1, d + 2, 3 * d)})
 # which types are handed over as half
 MIXES = {"all_half": lambda t: True, "features_half": lambda t: t != "radiance", "radiance_half": lambda t: t == "radiance"}

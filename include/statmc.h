@@ -389,6 +389,14 @@ typedef struct statmc_stat_type {
     float *mean_corr, *discriminator;
 } statmc_stat_type;
 
+/* The arithmetic is the reference's, operation by operation in fp32, with two stated differences:
+ *   - Box-Cox takes v_sqrt_f32 (within 1 ulp of the root; the root of an exact square is exact) for pow(x, .5);
+ *   - the division by the count (include/statmc_device_api.hpp, div_by_count) returns the bits of the reference's division
+ *     wherever the quotient is a normal number or zero, and lies within one step of 2^-149 of it where the quotient is subnormal.
+ * Samples that are not finite numbers: a negative or NaN sample leaves NaN in the Box-Cox moments like the reference; an INFINITE
+ * sample leaves NaN in mean and film_mean (and in every higher moment) where the reference's division leaves inf after that
+ * sample -- the quotient's residual is fma(-inf, n, inf).  Either way the element is non-finite, its pre-pass images are NaN and
+ * the pixel stays out of every window. */
 int statmc_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                       void *stream);
 

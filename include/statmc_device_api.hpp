@@ -35,9 +35,16 @@ namespace device {
 
 // d / n for an integer-valued divisor n in [1, 2^24): `r` is 1/n refined from v_rcp_f32 by one
 // Newton step (shared by every division by the same count: all channels, both Welford chains),
-// then one residual correction of the quotient (Markstein).  Bit-identical to the IEEE
-// quotient for the operand ranges of this path (tests/test_gpu_parity.py::test_exact_division
-// sweeps n = 1..4096 against `/`); 3 + 3 instructions instead of ~10 per division.
+// then one residual correction of the quotient (Markstein); 3 + 3 instructions instead of ~10 per
+// division.  What it returns, for finite d:
+//   - the IEEE quotient wherever that quotient is a normal number or zero (tests/test_gpu_parity.py:
+//     test_exact_division_by_count and _any_count sweep every count against `/`);
+//   - within one step of 2^-149 of it where it is subnormal: the residual is then rounded at the
+//     subnormal spacing, and 4 of 80 000 directed operands with a subnormal quotient come out one
+//     step off (the first: 1.5504638832552652e-38 / 448), on the hardware as in an exact emulation
+//     of the sequence (test_exact_division_directed_operands).
+// d = +-inf gives NaN, not inf: the residual is fma(-inf, n, inf).  An infinite sample therefore
+// leaves NaN in mean and film_mean where the reference's division leaves inf (include/statmc.h).
 __device__ __forceinline__ float refined_rcp(float nf) {
 #pragma clang fp contract(off)
     const float y0 = __builtin_amdgcn_rcpf(nf);

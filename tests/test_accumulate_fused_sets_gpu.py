@@ -5,7 +5,9 @@ against three yardsticks:
   A  bits    the same samples from the same state through the per-type kernel (fp32: the switch at -1; half: the widened samples
              through statmc_accumulate), every plane of every type as int32, and each side asked which kernel it ran;
   B  oracle  oracle.accumulate per type from the same HOST-made starting state: counts, raw-sample moments and every mean-only
-             type bit for bit, the Box-Cox moments within TOL, the non-finite elements at the oracle's positions;
+             type bit for bit, the Box-Cox moments within TOL, the non-finite elements at the oracle's positions -- and, element
+             by element, the bits of the oracle's untransformed chain on the device's own Box-Cox values
+             (tests/test_accumulate_boxcox_gpu.py);
   C  epilogue  mean_corr / disc against statmc_prepass of the stored moments and against oracle.prepass, bit for bit.
 The starting state is made with numpy and copied in, so it passes through no kernel under test.  Shapes: the smallest at which
 each mechanism of the walk can break."""
@@ -16,6 +18,8 @@ import pytest
 import torch
 
 from conftest import rel_l2
+from test_accumulate_boxcox_cpu import same_bits_or_nan
+from test_accumulate_boxcox_gpu import device_box_cox
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -60,6 +64,7 @@ def planted(W, H):
 
 
 _SAMPLES, _START, _REF = {}, {}, {}      # this module's samples, starting states and oracle results; emptied by the fixture below
+_V, _CHAIN = {}, {}                      # the device's Box-Cox values of the radiance samples, and the oracle's plain chain on them
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -67,7 +72,7 @@ def shared_inputs():
     """The samples (host and device), starting states and oracle results are computed once and shared by the tests of this module,
     read only; they are released when its last test has run."""
     yield
-    for cache in (_SAMPLES, _START, _REF):
+    for cache in (_SAMPLES, _START, _REF, _V, _CHAIN):
         cache.clear()
 
 
@@ -103,6 +108,9 @@ def samples(W, H, S, half):
             for t in ALL:
                 assert torch.equal(narrow[t].float(), wide[t])
         _SAMPLES[key] = (host, wide, narrow)
+        # the device's own Box-Cox value of every radiance sample, read once per sample set (half: through the 16-bit loader)
+        from statmc_amd import api
+        _V[key] = device_box_cox(api, host["radiance"], "half" if half else "aligned")
     return _SAMPLES[key]
 
 
@@ -153,6 +161,23 @@ def reference(oracle, W, H, S, half, t, count, ragged, rows):
             assert np.isfinite(ref["film_mean"]).all() and np.isfinite(ref["film_m2"]).all()
         _REF[key] = ref
     return _REF[key]
+
+
+def chain(oracle, W, H, S, half, count, ragged, rows):
+    """The radiance type's mean / m2 / m3 as the oracle's UNtransformed chain leaves them on the device's own Box-Cox values, from
+    the same starting state over the rows of the launch (read only, computed once): the per-element yardstick."""
+    key = (W, H, S, half, count, ragged, row_ranges(rows, H))
+    if key not in _CHAIN:
+        samples(W, H, S, half)
+        v = _V[(W, H, S, half)]
+        ref = {k: a.copy() for k, a in start_state(W, H, "radiance", count, ragged).items()}
+        for y0, y1 in row_ranges(rows, H):
+            part = {k: np.ascontiguousarray(a[y0:y1]) for k, a in ref.items()}
+            oracle.accumulate(part, np.ascontiguousarray(v[:, y0:y1]), False, 3)
+            for k, a in part.items():
+                ref[k][y0:y1] = a
+        _CHAIN[key] = ref
+    return _CHAIN[key]
 
 
 def new_film(W, H, order, counts, ragged_type, epilogue):
@@ -235,6 +260,9 @@ def assert_matches_oracle(oracle, fs, W, H, S, half, counts, ragged_type, rows, 
             assert np.array_equal(np.isfinite(got[k]), ok), (what, t, k, "non-finite elements elsewhere than the oracle's")
             err = rel_l2(got[k][ok], ref[k][ok])
             assert err <= TOL, (what, t, k, err)
+        per_element = chain(oracle, W, H, S, half, counts[t], t == ragged_type, rows)
+        for k in ("mean", "m2", "m3"):
+            same_bits_or_nan(got[k], per_element[k], "%s: radiance.%s against the chain on the device's Box-Cox values" % (what, k))
 
 
 def assert_epilogue(gpu, oracle, fs, what, spec=None):

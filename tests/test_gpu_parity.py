@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from conftest import FILTER_SD, RADIUS, SD_ALBEDO, SD_NORMAL, make_case, rel_l2
+from test_accumulate_boxcox_cpu import allowed_quotients_f32, chain_reference, division_operands, f32_bits, ieee_quotients_f32, same_bits_or_nan
+from test_accumulate_boxcox_gpu import device_box_cox
 from test_filter_probes_cpu import PROBE_DS, PROBE_SD, integer_colour, same_bits, scaled_error
 
 pytestmark = pytest.mark.gpu
@@ -38,10 +40,14 @@ def test_accumulate_matches_oracle(gpu, oracle, channels, transform, max_moment)
     smp[3, 5, 7] *= 1000.0                                   # a firefly
     ref = oracle.new_state(H, W, channels)
     st = dev_state(oracle.new_state(H, W, channels))
+    v = device_box_cox(gpu, smp) if transform else None      # the device's own Box-Cox values: the per-element yardstick's input
+    per_element = oracle.new_state(H, W, channels)
     s0 = 0
     for b in batches:
         part = np.ascontiguousarray(smp[s0:s0 + b])
         oracle.accumulate(ref, part, transform, max_moment)
+        if transform:
+            oracle.accumulate(per_element, np.ascontiguousarray(v[s0:s0 + b]), False, max_moment)
         gpu.accumulate(W, H, [gpu.make_stat_type(to_dev(part), st, transform, max_moment)])
         s0 += b
     torch.cuda.synchronize()
@@ -52,6 +58,8 @@ def test_accumulate_matches_oracle(gpu, oracle, channels, transform, max_moment)
         assert np.array_equal(got["film_m2"], ref["film_m2"])
         for k in ("mean", "m2", "m3"):
             assert rel_l2(got[k], ref[k]) <= TOL, k
+        for k in ("mean", "m2", "m3"):                                   # ... and per element: the oracle's plain chain on the device's v
+            same_bits_or_nan(got[k], per_element[k], "transform, %d channels, max moment %d: %s" % (channels, max_moment, k))
     else:
         for k in ("mean", "m2", "m3"):
             assert np.array_equal(got[k], ref[k]), k
@@ -68,7 +76,7 @@ def test_accumulate_randomised_configurations(gpu, oracle):
     for case in range(30):
         W, H = int(rng.integers(1, 300)), int(rng.integers(1, 24))
         n_types = int(rng.integers(1, 7))
-        refs, devs, stypes, cfgs, keep = [], [], [], [], []
+        refs, devs, stypes, cfgs, keep, chains = [], [], [], [], [], []
         for t in range(n_types):
             ch = int(rng.choice([1, 3]))
             transform, mm = bool(rng.integers(0, 2)), int(rng.integers(1, 4))
@@ -85,6 +93,8 @@ def test_accumulate_randomised_configurations(gpu, oracle):
                     ref["film_mean"][...] = ref["mean"]
                     ref["film_m2"][...] = ref["m2"]
             st = dev_state(ref)
+            # transformed types, per element: the oracle's plain chain on the device's own Box-Cox values, from the same start
+            chains.append(chain_reference(oracle, ref, device_box_cox(gpu, smp), mm) if transform else None)
             oracle.accumulate(ref, smp, transform, mm)
             d_smp = to_dev(smp)
             keep.append(d_smp)                              # the descriptors hold raw pointers
@@ -92,7 +102,7 @@ def test_accumulate_randomised_configurations(gpu, oracle):
             refs.append(ref); devs.append(st); cfgs.append((ch, transform, mm, S))
         gpu.accumulate(W, H, stypes)
         torch.cuda.synchronize()
-        for ref, st, cfg in zip(refs, devs, cfgs):
+        for ref, st, cfg, per_element in zip(refs, devs, cfgs, chains):
             ch, transform, mm, S = cfg
             got = {k: v.cpu().numpy() for k, v in st.items()}
             assert np.array_equal(got["n"], ref["n"]), (case, cfg)
@@ -102,6 +112,8 @@ def test_accumulate_randomised_configurations(gpu, oracle):
                 assert np.array_equal(got["film_m2"], ref["film_m2"]), (case, cfg)
                 for k in keys:
                     assert rel_l2(got[k], ref[k]) <= TOL, (case, cfg, k)
+                for k in ("mean", "m2", "m3"):              # the planes above max_moment too: they keep the start's bits
+                    same_bits_or_nan(got[k], per_element[k], "case %d %s: %s" % (case, cfg, k))
             else:
                 for k in keys:
                     assert np.array_equal(got[k], ref[k]), (case, cfg, k)
@@ -109,7 +121,9 @@ def test_accumulate_randomised_configurations(gpu, oracle):
 
 def test_exact_division_by_count(gpu, oracle):
     """The kernel divides by the sample count with a refined reciprocal + residual correction
-    instead of the IEEE sequence; for this path's operands the quotient must be bit-identical:
+    instead of the IEEE sequence: the IEEE quotient where the quotient is normal, within one step of
+    2^-149 where it is subnormal (test_exact_division_directed_operands).  This path's operands keep
+    every quotient normal or zero, so it must be bit-identical here:
     counts 1..4200 (beyond the t-table), heavy-tailed samples, plain M1 and M3 chains."""
     rng = np.random.default_rng(99)
     H, W = 8, 8
@@ -166,6 +180,51 @@ def test_exact_division_any_count(gpu, oracle):
             assert np.array_equal(st[k].cpu().numpy(), ref[k]), (shared, k)
         for k in ("mean", "m2", "m3"):                              # Box-Cox side: sqrt vs pow
             assert rel_l2(st[k].cpu().numpy(), ref[k]) <= TOL, (shared, k)
+
+
+def test_exact_division_directed_operands(gpu, oracle):
+    """Operands the sample recipes above never reach: 2 x 40 000 dividends d = k 2^(-149 + j) over counts up to 4096 and up to
+    2^24 - 1 with a SUBNORMAL quotient, FLT_MAX over 1, 2 and 3, and +-inf.  An untransformed one-channel type from a host-made
+    state with mean = 0 and n = n0: one sample s leaves mean = div_by_count(s, n0 + 1, r).  The yardstick is not the code under
+    test: the exact emulation of the three-instruction sequence (tests/test_accumulate_boxcox_cpu.py) for each of the three
+    v_rcp_f32 results within 1 ulp -- the device must return one of those values, and the IEEE quotient wherever all of them are
+    it.  What the header states follows: the IEEE quotient where it is normal, within one step of 2^-149 where it is subnormal.
+    An infinite dividend leaves NaN (fma(-inf, n, inf)) where the oracle's division leaves inf: include/statmc.h says so.
+    Ragged counts take add_sample's div_by_count; every operand pair repeated over a 4-pixel group takes the packed stages of
+    add_sample2 with the group's shared reciprocal."""
+    ds, ns = division_operands()
+    allowed, quot = allowed_quotients_f32(ds, ns), ieee_quotients_f32(ds, ns)
+    inf_d = np.isinf(ds)
+    assert inf_d.sum() == 4 and np.isnan(allowed[:, inf_d]).all() and np.isinf(quot[inf_d]).all()
+    all_ieee = (f32_bits(allowed) == f32_bits(quot)).all(0)
+    assert (all_ieee | inf_d | (np.abs(quot) < 2.0 ** -126)).all()       # the emulation leaves the IEEE quotient only where it is subnormal (or d infinite)
+    for rep, walk in ((1, "element by element"), (4, "packed")):
+        d, n0 = np.repeat(ds, rep), np.repeat(ns - 1, rep)
+        W = 256
+        H = -(-d.size // W)
+        smp, start = np.ones(W * H, np.float32), oracle.new_state(H, W, 1)
+        smp[:d.size] = d
+        start["n"].reshape(-1)[:d.size] = n0
+        ref = {k: a.copy() for k, a in start.items()}
+        oracle.accumulate(ref, smp.reshape(1, H, W, 1), False, 1)
+        st, d_smp = dev_state(start), to_dev(smp.reshape(1, H, W, 1))
+        gpu.accumulate(W, H, [gpu.make_stat_type(d_smp, st, False, 1)])
+        torch.cuda.synchronize()
+        assert np.array_equal(st["n"].cpu().numpy().reshape(-1)[:d.size], n0 + 1)
+        got = st["mean"].cpu().numpy().reshape(-1)[:d.size][::rep]
+        for j in range(1, rep):                                          # the four pixels of a group: the same bits
+            assert np.array_equal(f32_bits(st["mean"].cpu().numpy().reshape(-1)[:d.size][j::rep]), f32_bits(got)), walk
+        want = ref["mean"].reshape(-1)[:d.size][::rep]
+        assert np.array_equal(f32_bits(want), f32_bits(quot))            # the oracle divides: inf / n = inf
+        assert np.isnan(got[inf_d]).all() and np.isinf(want[inf_d]).all(), walk
+        hit = ((f32_bits(got) == f32_bits(allowed)) | (np.isnan(got) & np.isnan(allowed))).any(0)
+        off = f32_bits(got) != f32_bits(quot)
+        print("\n%s walk: %d of %d results are not the IEEE quotient (%d of them subnormal quotients one step of 2^-149 away; the emulation allows %d)"
+              % (walk, int((off & ~inf_d).sum()), d.size // rep, int((off & ~inf_d & (np.abs(got.astype(np.float64) - quot) <= 2.0 ** -149)).sum()),
+                 int((~all_ieee & ~inf_d).sum())))
+        assert hit.all(), "%s: %d results are none of the values the sequence can give; the first: %r / %d -> %r, allowed %r, IEEE %r" % (
+            walk, int((~hit).sum()), float(ds[~hit][0]), int(ns[~hit][0]), float(got[~hit][0]), allowed[:, ~hit][:, 0].tolist(), float(quot[~hit][0]))
+        assert np.array_equal(f32_bits(got[all_ieee]), f32_bits(quot[all_ieee])), walk
 
 
 @pytest.mark.parametrize("W,H", [(64, 40), (50, 37), (16, 16)], ids=["vector-tiles", "scalar-tiles", "one-tile"])

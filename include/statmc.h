@@ -464,6 +464,26 @@ int statmc_accumulate_formats(uint16_t width, uint16_t height, const statmc_stat
 int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                             const int32_t *tile_bounds, const int64_t *tile_offsets,
                             const int32_t *tile_samples, int n_tiles, void *stream);
+/* ... with the tile arenas in the format the renderer -- or the staging of statmc::Estimator -- holds them in.  sample_formats[t]
+ * is STATMC_SAMPLES_F32 or STATMC_SAMPLES_F16 and says what types[t].samples points to; NULL: every type is fp32.  Tile k's block of
+ * type t starts at element offset tile_offsets[k] * channels in elements of THAT type's format -- one tile_offsets table serves
+ * every type of the call, whatever their formats -- and is [tile_samples[k]][y1-y0][x1-x0][channels], tightly packed.  Everything
+ * else as in statmc_accumulate_tiles.
+ * The call leaves, bit for bit, what statmc_accumulate_tiles leaves for the same tables when every half arena is widened to
+ * fp32: n, every moment, the film chain and the optional mean_corr / discriminator epilogue; a tile with tile_samples[k] == 0
+ * keeps every bit.  Every finite half widens exactly, subnormals included; +-inf and NaN do what the fp32 path does with their
+ * widened values (not promised bit for bit).  With every format fp32 the call IS statmc_accumulate_tiles: the same launch.
+ * What the caller gives up is decided before the call, as for statmc_accumulate_formats; what it gains is exact: 28 instead of 44
+ * bytes per pixel-sample of the 11-channel set in the arena and on the way to the device (features half), 22 all half.
+ * A half type takes the vector path when its arena is 8-byte aligned, the state images 16-byte aligned and the tile's width,
+ * origin, offset and the film's width multiples of 4; everything else goes element by element -- the same bits.  Half RGB rows
+ * arrive by LDS-DMA, which wants more: blocks that start at 16-byte aligned addresses and hold a multiple of 8 pixels (a
+ * 16-byte aligned arena, 16 x 16 tiles and their 8-wide or 8-high parts, offsets that are multiples of 8).
+ * STATMC_ERR_INVALID, before any launch: a format other than the two (statmc_last_error() names sample_formats), a 16-bit arena at
+ * an odd address, the limits of statmc_accumulate_tiles.  STATMC_ERR_NO_DEVICE before statmc_setup. */
+int statmc_accumulate_tiles_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
+                                    int n_types, const int32_t *tile_bounds, const int64_t *tile_offsets,
+                                    const int32_t *tile_samples, int n_tiles, void *stream);
 
 /* ---- samples that finish anywhere: unordered (pixel, sample) records (no counterpart in the reference, whose tiles own their
  * pixels).  statmc_accumulate wants the same count for every pixel of the film, statmc_accumulate_tiles for every pixel of a

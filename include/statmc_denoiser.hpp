@@ -587,6 +587,28 @@ class StatTile {
     std::vector<std::vector<T>> planes;
 };
 
+// fp32 -> IEEE binary16, the bits: round to nearest, ties to even; what rounds above 65504 becomes inf, NaN stays NaN (quiet),
+// subnormal halves are exact, below 2^-25 is +-0.  Plain integer arithmetic -- no _Float16, no F16C: this header is compiled by
+// the renderer's compiler.  (What Estimator::SetSampleFormat(.., STATMC_SAMPLES_F16) stages.)
+inline uint16_t floatToHalfBits(float f) {
+    uint32_t x;
+    std::memcpy(&x, &f, sizeof(x));
+    const uint32_t sign = (x >> 16) & 0x8000u;
+    x &= 0x7fffffffu;
+    if (x > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((x >> 13) & 0x3ffu));
+    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                  // 65520 (the tie above 65504 goes to the even inf) and up
+    if (x >= 0x38800000u) {                                                    // a normal half: 13 mantissa bits go, a carry moves the exponent
+        const uint32_t v = x - 0x38000000u;
+        return (uint16_t)(sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13));
+    }
+    if (x < 0x33000000u) return (uint16_t)sign;                                // below 2^-25, half the smallest subnormal
+    const uint32_t mant = (x & 0x7fffffu) | 0x800000u, shift = 126u - (x >> 23);   // in units of 2^-24: mant >> shift, shift in [14, 24]
+    uint32_t q = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    if (rem > half || (rem == half && (q & 1u))) q++;                          // (q = 0x400 is the smallest normal half)
+    return (uint16_t)(sign | q);
+}
+
 // ------------------------------------------------------------------------------------------
 // src/statistics/estimator.h:241-380.  Public members keep the reference's names because
 // StatPathIntegrator indexes them directly (statpath.cpp:308-311, 504-511).
@@ -1002,19 +1024,22 @@ class Estimator {
     // are updated by statmc_accumulate_tiles; Upload() then moves only what the host still produces
     // (the "film" image).  maxHostBytes bounds the page-locked staging the merges fill between flushes.
     // dryRun (tests of the staging logic on machines without a GPU): plain host memory, and a flush
-    // only counts what it would have handed to the device (stagedMerges()).
+    // only counts what it would have handed to the device (stagedMerges(), stagedBytes()).
     void EnableDeviceAccumulation(size_t maxHostBytes = (size_t)2 << 30, bool dryRun = false) {
         if (!allocateDevice && !dryRun) throw Error(STATMC_ERR_INVALID, "device accumulation needs device images");
         std::lock_guard<std::mutex> lk(acc.mu);
         acc.enabled = true;
         acc.dry = dryRun;
         acc.arenas.clear();
+        acc.flushedBytes = 0;
+        acc.formats.assign(statTypeConfigs.nEnabled, STATMC_SAMPLES_F32);
+        for (size_t i = 0; i < acc.formats.size() && i < sampleFormats.size(); i++) acc.formats[i] = sampleFormats[i];
         // every (type, bounce) arena holds the same number of pixel-samples: the page-locked
-        // staging is split in proportion to the channel counts
-        size_t floatsPerPixelSample = 0;
+        // staging is split in proportion to the bytes a pixel-sample takes in each
+        size_t bytesPerPixelSample = 0;
         for (unsigned char i = 0; i < statTypeConfigs.nEnabled; i++)
-            floatsPerPixelSample += (size_t)statTypeConfigs.configs[i].nChannels * statTypeConfigs.configs[i].nBounces;
-        acc.capacity = (int64_t)(maxHostBytes / (sizeof(float) * std::max<size_t>(floatsPerPixelSample, 1))) / 4 * 4;
+            bytesPerPixelSample += sampleBytes(i) * statTypeConfigs.configs[i].nChannels * statTypeConfigs.configs[i].nBounces;
+        acc.capacity = (int64_t)(maxHostBytes / std::max<size_t>(bytesPerPixelSample, 1)) / 4 * 4;
         for (unsigned char i = 0; i < statTypeConfigs.nEnabled; i++) {
             acc.arenas.emplace_back(statTypeConfigs.configs[i].nBounces);
             for (unsigned char j = 0; j < statTypeConfigs.configs[i].nBounces; j++) {
@@ -1025,6 +1050,21 @@ class Estimator {
                 }
             }
         }
+    }
+    // What the staging of stat type `statTypeIndex` (all its bounces) holds: STATMC_SAMPLES_F32, the default, or
+    // STATMC_SAMPLES_F16 -- Merge*Tile rounds every sample of the type to IEEE half (floatToHalfBits) while it copies, the flush
+    // uploads two bytes per channel and statmc_accumulate_tiles_formats widens them on the device.  The statistics are, bit for
+    // bit, those of fp32 staging fed the rounded samples; types left in fp32 are untouched.  What is given up: values above
+    // 65504 become inf, values below 6e-8 become 0, and eleven bits of mantissa remain -- fine for normals, albedo, depth and
+    // ids; keep radiance in fp32 unless the renderer clamps it.  Call before EnableDeviceAccumulation().
+    void SetSampleFormat(const unsigned char statTypeIndex, const int format) {
+        if (format != STATMC_SAMPLES_F32 && format != STATMC_SAMPLES_F16)
+            throw Error(STATMC_ERR_INVALID, "SetSampleFormat: STATMC_SAMPLES_F32 or STATMC_SAMPLES_F16");
+        if (statTypeIndex >= statTypeConfigs.nEnabled) throw Error(STATMC_ERR_INVALID, "SetSampleFormat: no such stat type");
+        std::lock_guard<std::mutex> lk(acc.mu);
+        if (acc.enabled) throw Error(STATMC_ERR_INVALID, "SetSampleFormat: call it before EnableDeviceAccumulation() (the staging is sized by it)");
+        if (sampleFormats.size() <= statTypeIndex) sampleFormats.resize((size_t)statTypeIndex + 1, STATMC_SAMPLES_F32);
+        sampleFormats[statTypeIndex] = format;
     }
     // Statistics of one stat type back to zero (the reference re-creates the it-radiance tiles
     // every iteration, statpath.cpp:194-207).
@@ -1212,6 +1252,10 @@ class Estimator {
 
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
+    // bytes of samples the flushes have handed to the device (dryRun: would have) since EnableDeviceAccumulation(): per merged
+    // tile and buffer samples x pixels x channels x 4, or x 2 for a type staged in half (the upload rounds every tile's block
+    // up to a multiple of 4 pixel-samples on top)
+    size_t stagedBytes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedBytes; }
     size_t flushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nFlushes; }
     // Statistics images device -> host mats (dumps, OutputBufferSelection::Write); asynchronous.
     void DownloadStatistics() {
@@ -1510,8 +1554,9 @@ class Estimator {
         std::condition_variable idle;    // signalled when the last unlocked copy has finished
         int writers = 0;                 // merges copying into the arenas right now (outside the lock)
         bool enabled = false, uploadInFlight = false, dry = false;
-        size_t flushedMerges = 0, nFlushes = 0;
+        size_t flushedMerges = 0, nFlushes = 0, flushedBytes = 0;
         int64_t capacity = 0;            // pixel-samples per arena
+        std::vector<int> formats;        // [statTypeIndex]: what the type's arenas hold (sampleFormats when the staging was sized)
         std::vector<std::vector<Arena>> arenas;  // [statTypeIndex][bounceIndex]
         std::vector<Slot> slots;
         std::map<std::array<int32_t, 4>, uint32_t> slotOf;
@@ -1520,6 +1565,12 @@ class Estimator {
         std::unordered_set<const Buffer *> deviceProduced;
     };
     mutable Accumulation acc;
+    // tests of the staging (tests/cpp/test_tile_half.cpp defines it): the capacity of the arenas, and the host staging itself,
+    // which is no part of the interface -- worker threads write it outside the lock
+    friend struct EstimatorTestAccess;
+    std::vector<int> sampleFormats;      // SetSampleFormat, by statTypeIndex (shorter than the catalogue: the rest fp32)
+    // bytes per staged element of stat type i (under acc.mu, after EnableDeviceAccumulation)
+    size_t sampleBytes(const unsigned char i) const { return acc.formats[i] == STATMC_SAMPLES_F16 ? sizeof(uint16_t) : sizeof(float); }
 
     // host staging may be rewritten only after the copies of the previous flush have finished
     void beginEpochLocked() const {
@@ -1562,6 +1613,7 @@ class Estimator {
         const size_t npx = (size_t)(rx1 - rx0) * (ry1 - ry0);
         const int64_t need = (int64_t)((S * npx + 3) / 4 * 4);
         float *dst = nullptr;
+        bool half = false;
         {   // ---- under the lock: find or make the tile's slot, claim it for this buffer
             std::unique_lock<std::mutex> lk(acc.mu);
             if (!acc.enabled)
@@ -1591,17 +1643,27 @@ class Estimator {
             if (A.merged.size() <= slot) A.merged.resize((size_t)slot + 1, 0);
             if (A.merged[slot]) throw Error(STATMC_ERR_INVALID, "Merge*Tile: tile merged twice");
             A.merged[slot] = 1;
-            A.host.allocate((size_t)acc.capacity * C, !acc.dry);
+            half = acc.formats[ti] == STATMC_SAMPLES_F16;
+            // (a half arena: capacity x C 16-bit words in the same page-locked block type, counted in floats)
+            A.host.allocate(half ? ((size_t)acc.capacity * C + 1) / 2 : (size_t)acc.capacity * C, !acc.dry);
             A.slots.push_back(slot);
-            dst = A.host.ptr + (size_t)acc.slots[slot].offset * C;
+            dst = half ? A.host.ptr + (size_t)acc.slots[slot].offset * C / 2   // (offset is a multiple of 4: a whole float)
+                       : A.host.ptr + (size_t)acc.slots[slot].offset * C;
             acc.writers++;
         }
         // ---- outside the lock: the copy (the arena does not move; a flush waits for writers == 0)
         const int rw = rx1 - rx0;
         for (uint32_t s = 0; s < S; s++)
-            for (int y = ry0; y < ry1; y++)
-                std::memcpy(dst + ((size_t)s * npx + (size_t)(y - ry0) * rw) * C, &tile.planes[s][(size_t)y * tw + rx0],
-                            (size_t)rw * C * sizeof(float));
+            for (int y = ry0; y < ry1; y++) {
+                const size_t at = ((size_t)s * npx + (size_t)(y - ry0) * rw) * C;
+                const float *src = reinterpret_cast<const float *>(&tile.planes[s][(size_t)y * tw + rx0]);
+                if (half) {
+                    uint16_t *h = reinterpret_cast<uint16_t *>(dst) + at;
+                    for (size_t e = 0; e < (size_t)rw * C; e++) h[e] = floatToHalfBits(src[e]);
+                } else {
+                    std::memcpy(dst + at, src, (size_t)rw * C * sizeof(float));
+                }
+            }
         std::fill(tile.counts.begin(), tile.counts.end(), 0u);
         {
             std::lock_guard<std::mutex> lk(acc.mu);
@@ -1632,8 +1694,14 @@ class Estimator {
         acc.idle.wait(lk, [&] { return acc.writers == 0; });  // merges still copying into the arenas
         if (acc.slots.empty()) return;
         acc.nFlushes++;
-        for (const auto &per_type : acc.arenas)
-            for (const Arena &a : per_type) acc.flushedMerges += a.slots.size();
+        for (unsigned char i = 0; i < acc.arenas.size(); i++)
+            for (const Arena &a : acc.arenas[i]) {
+                acc.flushedMerges += a.slots.size();
+                for (uint32_t k : a.slots) {
+                    const Slot &s = acc.slots[k];
+                    acc.flushedBytes += (size_t)s.samples * (size_t)(s.x1 - s.x0) * (size_t)(s.y1 - s.y0) * statTypeConfigs.configs[i].nChannels * sampleBytes(i);
+                }
+            }
         if (acc.dry) {
             resetEpochLocked();
             return;
@@ -1659,16 +1727,19 @@ class Estimator {
         check(statmc_upload(tab + n * 24, samples.data(), n * 4, stream.handle()));
         check(statmc_synchronize(stream.handle()));
         std::vector<statmc_stat_type> full;
+        std::vector<int32_t> fullFormats;
         for (unsigned char i = 0; i < acc.arenas.size(); i++)
             for (unsigned char j = 0; j < acc.arenas[i].size(); j++) {
                 Arena &A = acc.arenas[i][j];
                 if (A.slots.empty()) continue;
-                const size_t bytes = used * statTypeConfigs.configs[i].nChannels * sizeof(float);
+                const size_t bytes = used * statTypeConfigs.configs[i].nChannels * sampleBytes(i);
+                const int32_t format = acc.formats[i];
                 A.dev.reserve(bytes);
                 check(statmc_upload(A.dev.ptr, A.host.ptr, bytes, stream.handle()));
                 const statmc_stat_type t = statTypeFor(i, j, static_cast<const float *>(A.dev.ptr));
                 if (A.slots.size() == n) {
                     full.push_back(t);
+                    fullFormats.push_back(format);
                 } else {  // this buffer saw only some of the tiles: its own, filtered table
                     std::vector<int64_t> o;
                     std::vector<int32_t> b, sm;
@@ -1684,17 +1755,17 @@ class Estimator {
                     check(statmc_upload(p, o.data(), m * 8, stream.handle()));
                     check(statmc_upload(p + m * 8, b.data(), m * 16, stream.handle()));
                     check(statmc_upload(p + m * 24, sm.data(), m * 4, stream.handle()));
-                    check(statmc_accumulate_tiles(width, height, &t, 1, reinterpret_cast<const int32_t *>(p + m * 8),
-                                                  reinterpret_cast<const int64_t *>(p), reinterpret_cast<const int32_t *>(p + m * 24),
-                                                  (int)m, stream.handle()));
+                    check(statmc_accumulate_tiles_formats(width, height, &t, &format, 1, reinterpret_cast<const int32_t *>(p + m * 8),
+                                                          reinterpret_cast<const int64_t *>(p), reinterpret_cast<const int32_t *>(p + m * 24),
+                                                          (int)m, stream.handle()));
                     check(statmc_synchronize(stream.handle()));  // `own` is freed on scope exit
                 }
             }
         for (size_t first = 0; first < full.size(); first += 8) {  // kMaxStatTypes per launch
             const int cnt = (int)std::min<size_t>(8, full.size() - first);
-            check(statmc_accumulate_tiles(width, height, full.data() + first, cnt, reinterpret_cast<const int32_t *>(tab + n * 8),
-                                          reinterpret_cast<const int64_t *>(tab), reinterpret_cast<const int32_t *>(tab + n * 24),
-                                          (int)n, stream.handle()));
+            check(statmc_accumulate_tiles_formats(width, height, full.data() + first, fullFormats.data() + first, cnt,
+                                                  reinterpret_cast<const int32_t *>(tab + n * 8), reinterpret_cast<const int64_t *>(tab),
+                                                  reinterpret_cast<const int32_t *>(tab + n * 24), (int)n, stream.handle()));
         }
         resetEpochLocked();
     }

@@ -109,7 +109,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -188,6 +188,8 @@ def load():
     lib.statmc_debug_last_accumulate_loader.restype = C.c_int
     lib.statmc_accumulate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_int, C.c_void_p]
+    lib.statmc_accumulate_tiles_formats.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_void_p]
     lib.statmc_accumulate_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.statmc_debug_accumulate_records_phases.argtypes = [C.c_int]
     lib.statmc_accumulate_records_interleaved.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
@@ -621,7 +623,11 @@ def combine_many(width, height, entries, n_sources=None, stream=None):
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):
-    """Stat type whose samples arrive tile by tile (accumulate_tiles): `arena` is a flat fp32 device tensor."""
+    """Stat type whose samples arrive tile by tile (accumulate_tiles): `arena` is a flat device tensor, torch.float32 or -- with
+    SAMPLES_F16 as the type's entry of accumulate_tiles' sample_formats -- torch.float16."""
+    torch = _torch()
+    if arena.dtype not in (torch.float32, torch.float16):
+        raise ValueError("make_stat_type_arena: the arena is torch.float32 or torch.float16, not %s" % arena.dtype)
     t = make_stat_type(arena.view(1, 1, -1, 1), state, transform, max_moment, prepass_into=prepass_into)
     t.channels, t.n_samples = int(channels), 0
     return t
@@ -653,14 +659,22 @@ def accumulate(width, height, stat_types, stream=None, rows=None, sample_formats
         check(load().statmc_accumulate_row_ranges(width, height, arr, len(stat_types), flat, len(rows), st))
 
 
-def accumulate_tiles(width, height, stat_types, tile_bounds, tile_offsets, tile_samples, stream=None):
-    """stat_types: make_stat_type(arena, state, ...) per type, `arena` a flat device tensor holding the
+def accumulate_tiles(width, height, stat_types, tile_bounds, tile_offsets, tile_samples, stream=None, sample_formats=None):
+    """stat_types: make_stat_type_arena(arena, ...) per type, `arena` a flat device tensor holding the
     tiles' sample blocks; tile_bounds int32 [n,4], tile_offsets int64 [n] (pixel-samples),
-    tile_samples int32 [n]: device tensors."""
+    tile_samples int32 [n]: device tensors.  sample_formats = [SAMPLES_F32 | SAMPLES_F16, ...], one per stat type: what each
+    type's arena holds (statmc_accumulate_tiles_formats); None: fp32 arenas, the existing entry."""
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
-    check(load().statmc_accumulate_tiles(width, height, arr, len(stat_types), tile_bounds.data_ptr(),
-                                         tile_offsets.data_ptr(), tile_samples.data_ptr(), tile_bounds.shape[0],
-                                         stream if stream is not None else current_stream_handle()))
+    st = stream if stream is not None else current_stream_handle()
+    if sample_formats is None:
+        check(load().statmc_accumulate_tiles(width, height, arr, len(stat_types), tile_bounds.data_ptr(),
+                                             tile_offsets.data_ptr(), tile_samples.data_ptr(), tile_bounds.shape[0], st))
+        return
+    if len(sample_formats) != len(stat_types):
+        raise ValueError("accumulate_tiles: one sample format per stat type")
+    fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
+    check(load().statmc_accumulate_tiles_formats(width, height, arr, fmts, len(stat_types), tile_bounds.data_ptr(),
+                                                 tile_offsets.data_ptr(), tile_samples.data_ptr(), tile_bounds.shape[0], st))
 
 
 def make_stat_type_records(samples, channels, state, transform, max_moment, prepass_into=None):

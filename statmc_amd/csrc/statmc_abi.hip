@@ -1471,9 +1471,36 @@ int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_ma
     return STATMC_OK;
 }
 
+static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
+                                 const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream);
 int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
                             const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples,
                             int n_tiles, void *stream) {
+    return accumulate_tiles_impl(width, height, types, nullptr, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
+}
+// The tile arenas in the format the renderer holds them in.  As statmc_accumulate_formats: what can be refused is refused before
+// the device is looked at, and a call without a half arena is the existing call.
+int statmc_accumulate_tiles_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                                    const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples,
+                                    int n_tiles, void *stream) {
+    if (!sample_formats) return statmc_accumulate_tiles(width, height, types, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);   // the existing call
+    if (n_types < 0 || n_types > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
+    bool any_half = false;
+    for (int i = 0; i < n_types; i++) {
+        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
+            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
+        any_half = any_half || sample_formats[i] == STATMC_SAMPLES_F16;
+    }
+    if (!any_half) return statmc_accumulate_tiles(width, height, types, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);        // the existing call
+    if (!types) return fail(STATMC_ERR_INVALID, "null types");
+    for (int i = 0; i < n_types; i++)
+        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
+            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
+    return accumulate_tiles_impl(width, height, types, sample_formats, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
+}
+static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
+                                 const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream) {
     NEED_READY();
     if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
     if (n_types < 0 || n_types > statmc::kMaxStatTypes)
@@ -1486,6 +1513,8 @@ int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_t
     k.n_types = n_types;
     for (int i = 0; i < n_types; i++)
         if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, k.t[i])) return rc;
+    for (int i = 0; formats && i < n_types; i++)
+        if (formats[i] == STATMC_SAMPLES_F16) k.half_mask |= 1 << i;
     k.tile_bounds = tile_bounds;
     k.tile_offsets = reinterpret_cast<const long long *>(tile_offsets);
     k.tile_samples = tile_samples;

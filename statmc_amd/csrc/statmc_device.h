@@ -85,7 +85,13 @@ struct AccumulateTilesArgs {
     int dma;                         // RGB sample planes arrive by LDS-DMA (default 1)
     int umul, order, wg_per_cu;      // experiment knobs (statmc_debug_accumulate_tiles_variant): prefetch depth x2, item order, grid size
     int dma_first;                   // A/B (statmc_debug_accumulate_launch): the first rows of the LDS-DMA ring requested before the state loads
+    // statmc_accumulate_tiles_formats: bit i = t[i].samples is an IEEE-half arena (tile_offsets still count pixel-samples).  Non-zero:
+    // the launch is accumulate_tiles_half_kernel's, and `vec` holds one bit per type (the vector path is a type's own there).  It
+    // takes the padding behind dma_first, so the fields before it keep their kernel-argument offsets and the argument its size.
+    int half_mask;
 };
+static_assert(sizeof(AccumulateTilesArgs) == sizeof(AccumulateType) * kMaxStatTypes + 72 && offsetof(AccumulateTilesArgs, half_mask) + 4 == sizeof(AccumulateTilesArgs),
+              "AccumulateTilesArgs: kernel-argument offsets");
 
 // statmc_combine_statistics: one entry per pair of states.  The counts are read from cnt_dst / cnt_src: the entry's own
 // count images, or those of the entry it borrows them from.  The ABI puts borrowing entries first, so that they read the

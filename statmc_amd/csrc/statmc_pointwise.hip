@@ -398,7 +398,8 @@ __device__ __forceinline__ int acc_row_piece(int k, int lane, int n_active) { re
 // (they are the first n_active lanes).  Without DMA an inactive lane returns at once.
 // ST: what the arena holds -- float, or _Float16 (statmc_accumulate_formats): the lane's piece of a half row is 8 C bytes at
 // 8-byte alignment, widened with one v_cvt_f32_f16 per element on its way into the same q[C] (every finite half is an fp32
-// value, subnormals included: the fold sees what it would see had the caller widened the arena).  Register loads only.
+// value, subnormals included: the fold sees what it would see had the caller widened the arena).  Register loads, or (DMA, C == 3: the
+// tile walk) the ring below.
 typedef _Float16 vhalf4 __attribute__((ext_vector_type(4)));
 template <int C, int MAXM, bool TRANSFORM, int UMUL = 1, int DMA = 0, typename ST = float>
 __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long long p0_in, const ST *sp,
@@ -406,7 +407,6 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
                                                 bool dma_first = false) {
     constexpr bool kDma = DMA > 0 && C == 3;
     constexpr bool kHalf = !std::is_same<ST, float>::value;
-    static_assert(!(kDma && kHalf), "the LDS-DMA walk of accumulate_lane reads fp32 rows");
     constexpr int kD = DMA > 0 ? DMA : 1;               // ring depth: sample rows in flight
     if constexpr (!kDma) {
         if (!active) return;
@@ -416,21 +416,46 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     // that the two latencies a wave pays before its first fold overlap instead of adding up -- measured in round 4 at 4 .. 256
     // samples per pixel, 720p / 1080p / 4K: within +- 0.5 % of requesting them behind the state, profiles/r04_acc_launch.log;
     // kept as a switch of the A/B hook, off.)
-    [[maybe_unused]] int dma_piece[3] = {0, 0, 0};
+    // Half RGB rows (the tile walk): a row is 24 bytes per lane, 1536 for a full wave, so a 3-KiB slot holds the rows of TWO
+    // consecutive samples s = 2 p and s + 1 and the ring's unit is the pair p: [0, 1024) the head of row s, [1024, 2048) the head of
+    // row s + 1, [2048, 2560) the 512-byte tail of row s fetched by lanes 0 - 31 and [2560, 3072) the tail of row s + 1 fetched by
+    // lanes 32 - 63 of ONE transfer (the source address is per lane, the destination base + 16 bytes per lane).  Three transfers
+    // per pair, issued by every lane; the protocol is acc_ring_walk's, over pairs.  An odd last sample has no partner: the
+    // partner's addresses name row s again.  The caller guarantees 16-byte aligned rows and an even n_active, so a row is a
+    // whole number of 16-byte pieces and a piece beyond its end is clamped to the row's first one (acc_row_piece's rule).
+    [[maybe_unused]] int dma_piece[3] = {0, 0, 0};                 // fp32: floats; half: bytes -- [0] the head piece, [1] the tail piece
     [[maybe_unused]] const float *dma_row0 = nullptr;
+    [[maybe_unused]] const char *dma_row0_half = nullptr;
+    [[maybe_unused]] const int dma_units = kHalf ? (S + 1) >> 1 : S;     // what the ring walks: sample pairs, or samples
     auto dma_issue = [&](int s, int slot) {
-        const float *src = dma_row0 + (long long)s * stride;
         float *dst = ring + slot * 768;
+        if constexpr (kHalf) {
+            const char *r0 = dma_row0_half + (long long)(2 * s) * stride * 2;
+            const char *r1 = 2 * s + 1 < S ? r0 + stride * 2 : r0;
+            const char *tail = (threadIdx.x & 32) ? r1 : r0;
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(r0 + dma_piece[0]), (__attribute__((address_space(3))) void *)(dst), 16, 0, 2);
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(r1 + dma_piece[0]), (__attribute__((address_space(3))) void *)(dst + 256), 16, 0, 2);
+            __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(tail + dma_piece[1]), (__attribute__((address_space(3))) void *)(dst + 512), 16, 0, 2);
+        } else {
+            const float *src = dma_row0 + (long long)s * stride;
 #pragma unroll
-        for (int k = 0; k < 3; k++)
-            __builtin_amdgcn_global_load_lds(src + dma_piece[k], (__attribute__((address_space(3))) void *)(dst + 256 * k), 16, 0, 2);
+            for (int k = 0; k < 3; k++)
+                __builtin_amdgcn_global_load_lds(src + dma_piece[k], (__attribute__((address_space(3))) void *)(dst + 256 * k), 16, 0, 2);
+        }
     };
     if constexpr (kDma) {
         const int lane = threadIdx.x & 63;
-        dma_row0 = reinterpret_cast<const float *>(sp) - 12 * lane;                          // the wave's row of sample 0 (lane l sits 12 l floats in; the same value in every lane)
+        if constexpr (kHalf) {
+            dma_row0_half = reinterpret_cast<const char *>(sp) - 24 * lane;                  // the wave's row of sample 0, as below
+            const int row_bytes = 24 * n_active, head = 16 * lane, tail = 1024 + 16 * (lane & 31);
+            dma_piece[0] = head < row_bytes ? head : 0;
+            dma_piece[1] = tail < row_bytes ? tail : 0;
+        } else {
+            dma_row0 = reinterpret_cast<const float *>(sp) - 12 * lane;                      // the wave's row of sample 0 (lane l sits 12 l floats in; the same value in every lane)
 #pragma unroll
-        for (int k = 0; k < 3; k++) dma_piece[k] = acc_row_piece(k, lane, n_active);
-        if (dma_first) acc_ring_prime<kD>(S, dma_issue);
+            for (int k = 0; k < 3; k++) dma_piece[k] = acc_row_piece(k, lane, n_active);
+        }
+        if (dma_first) acc_ring_prime<kD>(dma_units, dma_issue);
     }
     constexpr int NE = 4 * C;  // elements per lane
     const long long e0 = p0 * C;
@@ -537,15 +562,46 @@ __device__ __forceinline__ void accumulate_lane(const AccumulateType &t, long lo
     // (acc_ring_walk); every lane reads its own 48 B back.
     auto walk_samples_dma = [&](auto same) {
         const int lane = threadIdx.x & 63;
-        acc_ring_walk<kD, 3>(S, dma_first, dma_issue, [&](int s, int slot, auto refill) {
-            vfloat4 q[C];
-            const float *mine = ring + slot * 768 + 12 * lane;
+        if constexpr (kHalf) {
+            // the lane's 24 bytes of a row as three 8-byte pieces, each wholly in a head or a tail (1024 is a multiple of 8):
+            // row r of the pair has its head at 1024 r and its tail at 2048 + 512 r
+            int at[C], step[C];
 #pragma unroll
-            for (int k = 0; k < C; k++) q[k] = *reinterpret_cast<const vfloat4 *>(mine + 4 * k);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
-            refill();
-            fold_sample(q, s, same);
-        });
+            for (int k = 0; k < C; k++) {
+                const int b = 24 * lane + 8 * k;
+                at[k] = b < 1024 ? b : 1024 + b;
+                step[k] = b < 1024 ? 1024 : 512;
+            }
+            acc_ring_walk<kD, 3>(dma_units, dma_first, dma_issue, [&](int p, int slot, auto refill) {
+                const char *mine = reinterpret_cast<const char *>(ring + slot * 768);
+                vhalf4 h[2][C];
+#pragma unroll
+                for (int r = 0; r < 2; r++)
+#pragma unroll
+                    for (int k = 0; k < C; k++) h[r][k] = *reinterpret_cast<const vhalf4 *>(mine + at[k] + r * step[k]);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
+                refill();
+                vfloat4 q[C];
+#pragma unroll
+                for (int k = 0; k < C; k++) q[k] = __builtin_convertvector(h[0][k], vfloat4);
+                fold_sample(q, 2 * p, same);
+                if (2 * p + 1 < S) {
+#pragma unroll
+                    for (int k = 0; k < C; k++) q[k] = __builtin_convertvector(h[1][k], vfloat4);
+                    fold_sample(q, 2 * p + 1, same);
+                }
+            });
+        } else {
+            acc_ring_walk<kD, 3>(S, dma_first, dma_issue, [&](int s, int slot, auto refill) {
+                vfloat4 q[C];
+                const float *mine = ring + slot * 768 + 12 * lane;
+#pragma unroll
+                for (int k = 0; k < C; k++) q[k] = *reinterpret_cast<const vfloat4 *>(mine + 4 * k);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read before the slot is refilled
+                refill();
+                fold_sample(q, s, same);
+            });
+        }
     };
     // wave-uniform choice: the fast walk only when every active lane qualifies
     const bool lane_same = !active || (n0[0] == n0[1] && n0[1] == n0[2] && n0[2] == n0[3]);
@@ -1280,16 +1336,23 @@ hipError_t launch_accumulate(const AccumulateArgs &a_in, hipStream_t s) {
 // block [S_tile][tile_h][tile_w][C] of a per-type arena, S_tile the same for every pixel of the
 // tile but free to differ between tiles.  One wave per (tile, type): a 16 x 16 tile is exactly
 // 64 lanes x 4 pixels, a sample plane of the block is one contiguous 1 / 3 KiB read of the wave.
-template <int C, int MAXM, bool TRANSFORM, int UMUL, int DMA>
-__device__ __forceinline__ void accumulate_tile(const AccumulateType &t, const AccumulateTilesArgs &a, int x0, int y0,
+// ST: what the type's arena holds (statmc_accumulate_tiles_formats) -- float, or _Float16 through the half loaders of
+// accumulate_lane / accumulate_pixel (register loads); off, stride and the walk count elements of either width.  vec: the
+// type's images (and arena) are aligned for the vector path.
+template <int C, int MAXM, bool TRANSFORM, int UMUL, int DMA, typename ST = float>
+__device__ __forceinline__ void accumulate_tile(const AccumulateType &t, const AccumulateTilesArgs &a, bool vec, int x0, int y0,
                                                 int tw, int th, long long off, int S, float *ring) {
     const int lane = threadIdx.x & 63;
     const int npx = tw * th;
-    const float *base = t.samples + off * C;
+    const ST *base = reinterpret_cast<const ST *>(t.samples) + off * C;
     const long long stride = (long long)npx * C;
     // rows split into 16-B aligned 4-pixel groups: tile width, tile origin, image width and the
-    // block's offset are all multiples of 4 (and the images themselves 16-B aligned: a.vec)
-    const bool fast = a.vec && ((tw | x0 | a.width) & 3) == 0 && (off & 3) == 0;
+    // block's offset are all multiples of 4 (and the images themselves 16-B aligned: vec)
+    bool fast = vec && ((tw | x0 | a.width) & 3) == 0 && (off & 3) == 0;
+    // half RGB rows by LDS-DMA: 16-byte pieces of 16-byte aligned rows -- a 16-byte aligned block and a multiple of 8 pixels
+    // (every 16 x 16 tile and its 8-wide or 8-high parts).  Other blocks go element by element in that kernel: the register walk
+    // beside the ring would cost it the second wave per SIMD.
+    if constexpr (DMA > 0 && C == 3 && !std::is_same<ST, float>::value) fast = fast && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (npx & 7) == 0;
     if (fast) {
         const int n_g = npx >> 2;
         for (int gw = 0; gw < n_g; gw += 64) {   // wave-uniform: the LDS-DMA walk of the RGB types is cooperative
@@ -1298,14 +1361,14 @@ __device__ __forceinline__ void accumulate_tile(const AccumulateType &t, const A
             const int i = g << 2, row = i / tw, col = i - row * tw;
             const long long p0 = (long long)(y0 + row) * a.width + x0 + col;
             // deeper prefetch only where the state is one plane (mean-only feature types): the registers are there
-            accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA>(t, p0, base + (long long)i * C, stride, S, ring, active,
-                                                                                            n_g - gw >= 64 ? 64 : n_g - gw, a.dma_first != 0);
+            accumulate_lane<C, MAXM, TRANSFORM, (!TRANSFORM && MAXM == 1) ? UMUL : 1, DMA, ST>(t, p0, base + (long long)i * C, stride, S, ring, active,
+                                                                                                n_g - gw >= 64 ? 64 : n_g - gw, a.dma_first != 0);
         }
     } else {
         for (int i = lane; i < npx; i += 64) {
             const int row = i / tw, col = i - row * tw;
             const long long p = (long long)(y0 + row) * a.width + x0 + col;
-            accumulate_pixel<C, MAXM, TRANSFORM>(t, p, base + (long long)i * C, stride, S);
+            accumulate_pixel<C, MAXM, TRANSFORM, ST>(t, p, base + (long long)i * C, stride, S);
         }
     }
 }
@@ -1344,22 +1407,75 @@ __global__ __launch_bounds__(kBlock) void accumulate_tiles_kernel(AccumulateTile
         if (S <= 0 || x1 <= x0 || y1 <= y0) continue;
         const AccumulateType &t = a.t[ti];
         acc_dispatch_type(t, [&](auto c, auto maxm, auto transform) {
-            accumulate_tile<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, UMUL, DMA>(t, a, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
+            accumulate_tile<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, UMUL, DMA>(t, a, a.vec != 0, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
         });
+    }
+}
+
+// Launches in which at least one type's arena is IEEE half (statmc_accumulate_tiles_formats; a.half_mask: bit i = type i): a
+// kernel of its own, so that accumulate_tiles_kernel stays the code object it was.  The format of an item's type is a
+// wave-uniform choice in front of the type dispatch.  A half type's rows come through the half loaders of accumulate_lane /
+// accumulate_pixel and widen exactly, so the fold sees what it would see had the caller widened the arena.  DMA > 0: the RGB
+// rows of the launch, fp32 and half, arrive by LDS-DMA in the wave's ring (a half slot holds two samples: accumulate_lane);
+// DMA = 0 (statmc_debug_accumulate_dma(0)): every row by register loads, 8-byte pieces for half.  The vector path is a type's own here (a.vec: bit i = type i), since a half arena asks for 8-byte alignment only.
+template <int UMUL, int DMA>
+__global__ __launch_bounds__(kBlock) void accumulate_tiles_half_kernel(AccumulateTilesArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float acc_lds[];
+    float *ring = DMA ? acc_lds + (threadIdx.x >> 6) * acc_ring_floats(DMA) : nullptr;
+    // (the item walk of accumulate_tiles_kernel, a.order as there: its own copy -- handing both kernels one function for it
+    // changes the fp32 kernels' code, 23 511 -> 23 287 instructions without the ring, 18 398 -> 18 181 with it)
+    const long long n_items = a.order == 2 ? (((long long)a.n_tiles + 3) >> 2) * 4 * a.n_types : (long long)a.n_tiles * a.n_types;
+    const long long n_waves = (long long)gridDim.x * (kBlock / 64);
+    for (long long item = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); item < n_items; item += n_waves) {
+        int tile = __builtin_amdgcn_readfirstlane(a.order ? (int)(item % a.n_tiles) : (int)(item / a.n_types));
+        int ti = __builtin_amdgcn_readfirstlane(a.order ? (int)(item / a.n_tiles) : (int)(item % a.n_types));
+        if (a.order == 2) {
+            const long long q = item >> 2;
+            ti = __builtin_amdgcn_readfirstlane((int)(q % a.n_types));
+            tile = __builtin_amdgcn_readfirstlane((int)(q / a.n_types) * 4 + (int)(item & 3));
+            if (tile >= a.n_tiles) continue;
+        }
+        const int x0 = a.tile_bounds[4 * tile], y0 = a.tile_bounds[4 * tile + 1];
+        const int x1 = a.tile_bounds[4 * tile + 2], y1 = a.tile_bounds[4 * tile + 3];
+        const int S = a.tile_samples[tile];
+        if (S <= 0 || x1 <= x0 || y1 <= y0) continue;
+        const AccumulateType &t = a.t[ti];
+        const bool vec = (a.vec >> ti) & 1;
+        if ((a.half_mask >> ti) & 1) {
+            acc_dispatch_type(t, [&](auto c, auto maxm, auto transform) {
+                accumulate_tile<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, UMUL, DMA, _Float16>(t, a, vec, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
+            });
+        } else {
+            acc_dispatch_type(t, [&](auto c, auto maxm, auto transform) {
+                accumulate_tile<decltype(c)::value, decltype(maxm)::value, decltype(transform)::value, UMUL, DMA>(t, a, vec, x0, y0, x1 - x0, y1 - y0, a.tile_offsets[tile], S, ring);
+            });
+        }
     }
 }
 
 hipError_t launch_accumulate_tiles(const AccumulateTilesArgs &a_in, hipStream_t s) {
     AccumulateTilesArgs a = a_in;
-    bool vec = true;
-    for (int i = 0; i < a.n_types; i++) vec = vec && acc_type_vectorizable(a.t[i], false, false);
-    a.vec = vec ? 1 : 0;
+    int vec_mask = 0;
+    for (int i = 0; i < a.n_types; i++)
+        if (acc_type_vectorizable(a.t[i], (a.half_mask >> i) & 1, false)) vec_mask |= 1 << i;
+    // fp32 launches: all types or none (the ring is the launch's); the half kernel: a bit per type
+    a.vec = a.half_mask != 0 ? vec_mask : vec_mask == (1 << a.n_types) - 1 ? 1 : 0;
     const long long items = a.order == 2 ? (((long long)a.n_tiles + 3) >> 2) * 4 * a.n_types : (long long)a.n_tiles * a.n_types;
     // one wave per item; films up to ~ 4 Mpixels: at most 8 workgroups per CU, walking the items with a grid stride; larger ones
     // (4K: 32 400 tiles): every wave ONE item, the dispatcher hands the workgroups out -- + 1 - 4 % at 4 .. 64 samples per tile there,
     // - 1 - 2 % at 1080p (profiles/r05_tiles_first.log; the film-major launch has the same rule, plan_accumulate)
     const bool big = a.n_tiles >= 16384;
     const int grid = grid_for(items * 64, a.wg_per_cu > 0 ? 256 * a.wg_per_cu : big ? (1 << 30) : 256 * 8);
+    if (a.half_mask != 0) {   // (the ring serves the launch's RGB types, fp32 and half; a launch without one asks for no LDS)
+        bool rgb = false;
+        for (int i = 0; i < a.n_types; i++) rgb = rgb || a.t[i].channels == 3;
+        if (!rgb) a.dma = 0;
+        if (a.dma && a.umul == 2) hipLaunchKernelGGL((accumulate_tiles_half_kernel<2, kAccTilesDmaD>), dim3(grid), dim3(kBlock), acc_lds_bytes(kAccTilesDmaD), s, a);
+        else if (a.dma) hipLaunchKernelGGL((accumulate_tiles_half_kernel<1, kAccTilesDmaD>), dim3(grid), dim3(kBlock), acc_lds_bytes(kAccTilesDmaD), s, a);
+        else if (a.umul == 2) hipLaunchKernelGGL((accumulate_tiles_half_kernel<2, 0>), dim3(grid), dim3(kBlock), 0, s, a);
+        else hipLaunchKernelGGL((accumulate_tiles_half_kernel<1, 0>), dim3(grid), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    }
     // (the DMA walk needs the vector path: a.vec; the scalar path of unaligned images never touches the ring)
     if (a.vec && a.dma && a.umul == 2) hipLaunchKernelGGL((accumulate_tiles_kernel<2, kAccTilesDmaD>), dim3(grid), dim3(kBlock), acc_lds_bytes(kAccTilesDmaD), s, a);
     else if (a.vec && a.dma) hipLaunchKernelGGL((accumulate_tiles_kernel<1, kAccTilesDmaD>), dim3(grid), dim3(kBlock), acc_lds_bytes(kAccTilesDmaD), s, a);

@@ -20,8 +20,10 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--placed]
+//                     [--adaptive] [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
+// --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
+//                   half (Estimator::SetSampleFormat); radiance stays fp32.  "Staged bytes:" at the end counts what went up.
 // --config denoise: Render<Vec3>, RGB radiance + normal + albedo, filter<float3> (scenes/render-denoise.pbrt).
 // --config acrr:    Render<Float>, "multichannelstats" false: the luminance of the path prefix up to each
 //                   of the tracked bounces is one float stat buffer, filtered together by filter<float>
@@ -106,7 +108,7 @@ struct Options {
     unsigned seed = 1;
     float filterSD = 10.f;
     int filterRadius = 20;
-    bool denoise = true, acrr = false, smis = false, warmUp = false, tileStats = false, adaptive = false;
+    bool denoise = true, acrr = false, smis = false, warmUp = false, tileStats = false, adaptive = false, halfFeatures = false;
     std::string stem, outputRegex = ".*";
 };
 
@@ -129,6 +131,9 @@ static void Render(const Options &o) {
     BufferRegistry reg(film);
     Estimator estimator(film, sCfgs, o.filterSD, (unsigned char)o.filterRadius, /*denoiseFilm=*/false, o.acrr, o.smis, reg);
     estimator.AllocateBuffers(reg);
+    if (o.halfFeatures)
+        for (unsigned char t = 0; t < estimator.statTypeConfigs.nEnabled; t++)
+            if (!estimator.statTypeConfigs.configs[t].transform) estimator.SetSampleFormat(t, STATMC_SAMPLES_F16);
     estimator.EnableDeviceAccumulation((size_t)o.stageMb << 20);
 
     std::vector<StatTypeConfig> enabledRGBFeatureCfgs;  // statpath.cpp:160-163
@@ -314,6 +319,7 @@ static void Render(const Options &o) {
         tileNoise.clear();
     }
     RenderLoop(o.iterations, true);
+    std::cout << "Staged bytes: " << estimator.stagedBytes() << std::endl;   // sample bytes handed to the device, warm-up included
 }
 
 int main(int argc, char **argv) {
@@ -343,6 +349,7 @@ int main(int argc, char **argv) {
         else if (a == "--warmup") o.warmUp = true;
         else if (a == "--tilestats") o.tileStats = true;
         else if (a == "--adaptive") o.adaptive = true;
+        else if (a == "--half-features") o.halfFeatures = true;
         else if (a == "--placed") statmc::usePlacedMemory() = true;   // device images and sample arenas from statmc_malloc_placed
         else if (a == "--config") {
             const std::string c = next();

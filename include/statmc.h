@@ -485,6 +485,48 @@ int statmc_accumulate_tiles_formats(uint16_t width, uint16_t height, const statm
                                     int n_types, const int32_t *tile_bounds, const int64_t *tile_offsets,
                                     const int32_t *tile_samples, int n_tiles, void *stream);
 
+/* ---- arenas in which every pixel has its own sample count: what a renderer leaves that spends its samples by a per-pixel noise
+ * estimate, writes the dense arena of the entries above and simply stops early on most pixels.  Everything but sample_counts means
+ * what it means for statmc_accumulate_formats / statmc_accumulate_tiles_formats: arena layouts, formats (NULL = all fp32), row
+ * ranges, tile tables, state pointers and the optional mean_corr / discriminator epilogue.  n_samples and tile_samples[k] become the
+ * CAPACITY S of the arena or block, which keeps its dense layout.
+ *   sample_counts   device image [height][width] of int32, tightly packed, indexed by film pixel in both entries.  Pixel p's
+ *                   effective count is c(p) = min(max(sample_counts[p], 0), S), S = n_samples, or tile_samples[k] of the tile
+ *                   that holds p.  The clamp happens before anything is derived from the count: a count outside [0, S] never
+ *                   becomes an address and never reaches n.
+ * Sample s of pixel p is folded iff s < c(p), in ascending s.  Arena slots with s >= c(p) may be read -- they are memory that
+ * exists -- but whatever they hold (NaN, inf, uninitialised bits) reaches no state image.
+ * DEFINITION, per pixel: the call leaves, bit for bit, what statmc_accumulate_tiles_formats leaves when that pixel is handed over
+ * as a 1 x 1 tile with tile_samples = c(p) whose block holds the pixel's first c(p) samples in order -- equally what
+ * statmc_accumulate_records leaves for those samples in that order: n (+= c(p)), every moment, the film chain and the epilogue.
+ * Hence:
+ *   - where every count is >= S the result is statmc_accumulate_formats' / statmc_accumulate_tiles_formats', bit for bit;
+ *   - a pixel with c(p) == 0 keeps every bit of every image, mean_corr / discriminator included;
+ *   - a batch may be split anywhere along s into two calls (counts min(c, k), then max(c - k, 0) on the arena advanced by k planes);
+ *   - the same inputs give the same bits on every run;
+ *   - the call is asynchronous on `stream`, reads nothing back and allocates nothing: no sort, no tables, no workspace.
+ * sample_counts == NULL: the call IS statmc_accumulate_formats / statmc_accumulate_tiles_formats, the same launch.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: a sample_counts address that is not 4-byte
+ * aligned, and every rule the uncounted entries enforce (sample_formats, a 16-bit arena at an odd address, n_types, n_ranges, the
+ * tile limits).  STATMC_ERR_NO_DEVICE before statmc_setup, after those argument checks.  Zero types, zero samples or zero tiles is
+ * a no-op.
+ * The vector path (a lane owns 4 consecutive pixels) needs what it needs in the uncounted entries plus a 16-byte aligned counts
+ * image; everything else goes element by element, with the same bits.
+ * Cost: a lane walks to the largest of its 4 counts and a wave to its longest lane, and a wave whose lanes stop at different s
+ * still pulls whole memory lines of the planes it walks: the time follows the spatial coherence of the counts, not only their
+ * sum.  Measured at 1920 x 1080, 11 channels, capacity 64 (profiles/accumulate_counted.jsonl): every count 64,
+ * 1.09 x the time of statmc_accumulate on the same arena (1.04 against 0.95 ms: register loads where that launch streams its RGB
+ * rows through LDS-DMA); one count per 16 x 16 tile, 64 on every fourth tile and 4 on the rest, 0.63 ms -- 0.32 x
+ * statmc_accumulate_records on exactly the live samples (1.98 ms) and 0.66 x a launch over all 64 planes; every pixel its own
+ * count, independent and uniform in 1 .. 64, 1.98 ms -- 0.61 x the records entry (3.23 ms), but 2.08 x a launch over all 64
+ * planes: with incoherent counts nearly every wave walks the whole arena and most of its samples take the predicated fold.
+ * The entry is ahead of the records entry on dense arenas, coherent or not; it pays off most where the counts are coherent. */
+int statmc_accumulate_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
+                              int n_types, const int32_t *sample_counts, const int32_t *ranges, int n_ranges, void *stream);
+int statmc_accumulate_tiles_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
+                                    int n_types, const int32_t *tile_bounds, const int64_t *tile_offsets,
+                                    const int32_t *tile_samples, int n_tiles, const int32_t *sample_counts, void *stream);
+
 /* ---- samples that finish anywhere: unordered (pixel, sample) records (no counterpart in the reference, whose tiles own their
  * pixels).  statmc_accumulate wants the same count for every pixel of the film, statmc_accumulate_tiles for every pixel of a
  * tile, statmc::device::PixelStats one thread that owns the pixel.  A wavefront path tracer, per-pixel adaptive sampling or a

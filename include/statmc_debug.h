@@ -55,6 +55,13 @@ int statmc_debug_accumulate_umul(int umul);
 /* Tile-fed accumulation: prefetch depth of the mean-only types (1 | 2, default 2), item order, workgroups per CU. */
 int statmc_debug_accumulate_tiles_variant(int umul, int order, int wg_per_cu);
 
+/* Whether the calling thread's last accumulate call (statmc_accumulate and its _rows / _row_ranges / _formats forms,
+ * statmc_accumulate_tiles[_formats], statmc_accumulate[_tiles]_counted) launched a counted kernel, and on which path: 0 = none (an
+ * uncounted entry that got as far as its launch, sample_counts == NULL, a counted call that was a no-op or was refused), 1 = a
+ * counted kernel on the vector path, 2 = a counted kernel element by element.  Tile launches: 1 when every type's images, its arena and the counts image are aligned for the vector path
+ * and the film's width is a multiple of 4 (a tile whose own rows do not split into 4-pixel groups still goes element by element). */
+int statmc_debug_last_accumulate_counted(void);
+
 /* statmc_accumulate_records, for timing its two steps apart (tools/time_accumulate_records.py): 1 = the grouping only, 2 = the
  * fold only, over the index that the last full or grouping-only call with the same pixels and record count left in the
  * stream's workspace, 3 = both (default).  Any other value: STATMC_ERR_INVALID.  Applies to statmc_accumulate_records_split and

@@ -1076,7 +1076,10 @@ class Estimator {
 
     // estimator.cpp:341-407.  Thread-safe (Render calls them from its worker threads, one tile
     // each, statpath.cpp:381-388).  The samples recorded in the tile since its last merge are copied
-    // to the staging arena of (statTypeIndex, bounceIndex) and the tile is emptied.
+    // to the staging arena of (statTypeIndex, bounceIndex) and the tile is emptied.  The pixels of a tile may hold different
+    // numbers of samples (a per-pixel sample budget): the block is staged dense up to the largest count, the per-pixel counts
+    // go with it and the flush takes statmc_accumulate_tiles_counted -- per pixel the bits of its samples in recorded order.
+    // The stat types merged for one tile must agree on those counts (STATMC_ERR_UNSUPPORTED otherwise).
     template <typename T>
     void MergeTile(const StatTile<T> &tile, const unsigned char statTypeIndex, const unsigned char bounceIndex) const {
         mergeRecorded(tile, statTypeIndex, bounceIndex);
@@ -1237,6 +1240,13 @@ class Estimator {
         bool withPrepass = false;
     };
     void AccumulateFilm(int nSamples, const std::vector<FilmSamples> &buffers) {
+        AccumulateFilm(nSamples, buffers, nullptr);    // (no counts: statmc_accumulate_counted IS statmc_accumulate_formats then)
+    }
+    // ... of a renderer that spends its samples by a per-pixel budget (statmc_accumulate_counted): d_counts is an int32 image
+    // [height][width] on this Estimator's device, tightly packed and 4-byte aligned; pixel p folds its first
+    // min(max(d_counts[p], 0), nSamples) samples only and keeps every bit where that is 0.  nSamples is the arenas' capacity.  The
+    // bits Merge*Tile(s) leave for the same samples; d_counts == nullptr is the call above.
+    void AccumulateFilm(int nSamples, const std::vector<FilmSamples> &buffers, const int32_t *d_counts) {
         std::vector<statmc_stat_type> types;
         std::vector<int32_t> formats;
         for (const FilmSamples &b : buffers) {
@@ -1247,7 +1257,7 @@ class Estimator {
             formats.push_back(b.format);
         }
         check(statmc_set_device(device));
-        check(statmc_accumulate_formats(width, height, types.data(), formats.data(), (int)types.size(), nullptr, 0, stream.handle()));
+        check(statmc_accumulate_counted(width, height, types.data(), formats.data(), (int)types.size(), d_counts, nullptr, 0, stream.handle()));
     }
 
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
@@ -1257,6 +1267,9 @@ class Estimator {
     // up to a multiple of 4 pixel-samples on top)
     size_t stagedBytes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedBytes; }
     size_t flushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nFlushes; }
+    // ... of which had at least one ragged tile (pixels of one tile with different counts) and went through the per-pixel
+    // count image and statmc_accumulate_tiles_counted; a flush of uniform tiles stages no counts
+    size_t countedFlushes() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.nCountedFlushes; }
     // Statistics images device -> host mats (dumps, OutputBufferSelection::Write); asynchronous.
     void DownloadStatistics() {
         joinUploads();
@@ -1548,13 +1561,14 @@ class Estimator {
     struct Slot {
         int32_t x0, y0, x1, y1, samples;
         int64_t offset;                  // in pixel-samples, a multiple of 4
+        std::vector<int32_t> counts;     // a ragged tile's per-pixel counts, row-major over the rectangle; empty: `samples` everywhere
     };
     struct Accumulation {
         std::mutex mu;
         std::condition_variable idle;    // signalled when the last unlocked copy has finished
         int writers = 0;                 // merges copying into the arenas right now (outside the lock)
         bool enabled = false, uploadInFlight = false, dry = false;
-        size_t flushedMerges = 0, nFlushes = 0, flushedBytes = 0;
+        size_t flushedMerges = 0, nFlushes = 0, flushedBytes = 0, nCountedFlushes = 0;
         int64_t capacity = 0;            // pixel-samples per arena
         std::vector<int> formats;        // [statTypeIndex]: what the type's arenas hold (sampleFormats when the staging was sized)
         std::vector<std::vector<Arena>> arenas;  // [statTypeIndex][bounceIndex]
@@ -1562,6 +1576,8 @@ class Estimator {
         std::map<std::array<int32_t, 4>, uint32_t> slotOf;
         int64_t nextOffset = 0;
         DeviceBytes tables;
+        PinnedFloats countsHost;         // flushes with a ragged slot: a page-locked film-sized int32 image of per-pixel counts ...
+        DeviceBytes countsDev;           // ... and its device copy (both allocated by the first such flush)
         std::unordered_set<const Buffer *> deviceProduced;
     };
     mutable Accumulation acc;
@@ -1587,8 +1603,11 @@ class Estimator {
     template <typename T>
     void mergeRecorded(const StatTile<T> &tile, const unsigned char ti, const unsigned char bj) const {
         constexpr int C = stat_denoiser::detail::channels<T>::value;
-        // every pixel that received samples received the same number, and those pixels form a
-        // rectangle (the whole tile, or its part inside the integrator's pixelbounds, statpath.cpp:261)
+        // The slot is the bounding rectangle of the pixels that received samples (the whole tile, or its part inside the
+        // integrator's pixelbounds, statpath.cpp:261) and S the largest count.  Usually every pixel of the rectangle holds S
+        // samples; a renderer that spends its samples by a per-pixel budget leaves a RAGGED tile: the block is staged dense all
+        // the same -- planes beyond a pixel's count hold whatever the recorder holds, they are never folded -- and the
+        // rectangle's counts go with the slot (flushLocked hands them to statmc_accumulate_tiles_counted).
         uint32_t S = 0;
         for (uint32_t c : tile.counts) S = std::max(S, c);
         if (S == 0) return;
@@ -1600,12 +1619,19 @@ class Estimator {
                     rx0 = std::min(rx0, x); rx1 = std::max(rx1, x + 1);
                     ry0 = std::min(ry0, y); ry1 = std::max(ry1, y + 1);
                 }
-        for (int y = 0; y < th; y++)
-            for (int x = 0; x < tw; x++) {
-                const bool inside = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
-                if (tile.counts[(size_t)y * tw + x] != (inside ? S : 0u))
-                    throw Error(STATMC_ERR_UNSUPPORTED, "Merge*Tile: pixels of one tile hold different sample counts");
-            }
+        bool ragged = false;
+        for (int y = ry0; y < ry1 && !ragged; y++)
+            for (int x = rx0; x < rx1; x++)
+                if (tile.counts[(size_t)y * tw + x] != S) {
+                    ragged = true;
+                    break;
+                }
+        std::vector<int32_t> pixelCounts;          // row-major over the rectangle; empty: every pixel holds S
+        if (ragged) {
+            pixelCounts.reserve((size_t)(rx1 - rx0) * (ry1 - ry0));
+            for (int y = ry0; y < ry1; y++)
+                for (int x = rx0; x < rx1; x++) pixelCounts.push_back((int32_t)tile.counts[(size_t)y * tw + x]);
+        }
         const std::array<int32_t, 4> key = {tile.pixelBounds.pMin.x + rx0, tile.pixelBounds.pMin.y + ry0,
                                             tile.pixelBounds.pMin.x + rx1, tile.pixelBounds.pMin.y + ry1};
         if (key[0] < 0 || key[1] < 0 || key[2] > width || key[3] > height)
@@ -1631,13 +1657,14 @@ class Estimator {
             uint32_t slot;
             if (it == acc.slotOf.end()) {
                 slot = (uint32_t)acc.slots.size();
-                acc.slots.push_back(Slot{key[0], key[1], key[2], key[3], (int32_t)S, acc.nextOffset});
+                acc.slots.push_back(Slot{key[0], key[1], key[2], key[3], (int32_t)S, acc.nextOffset, std::move(pixelCounts)});
                 acc.slotOf.emplace(key, slot);
                 acc.nextOffset += need;
             } else {
                 slot = it->second;
-                if (acc.slots[slot].samples != (int32_t)S)
-                    throw Error(STATMC_ERR_UNSUPPORTED, "Merge*Tile: the stat types of one tile hold different sample counts");
+                // (every camera sample feeds every type, statpath.cpp:355-371: one count image serves all types of a flush)
+                if (acc.slots[slot].samples != (int32_t)S || acc.slots[slot].counts != pixelCounts)
+                    throw Error(STATMC_ERR_UNSUPPORTED, "Merge*Tile: the stat types of one tile hold different per-pixel counts");
             }
             Arena &A = acc.arenas[ti][bj];
             if (A.merged.size() <= slot) A.merged.resize((size_t)slot + 1, 0);
@@ -1702,11 +1729,38 @@ class Estimator {
                     acc.flushedBytes += (size_t)s.samples * (size_t)(s.x1 - s.x0) * (size_t)(s.y1 - s.y0) * statTypeConfigs.configs[i].nChannels * sampleBytes(i);
                 }
             }
+        // A flush in which every slot is uniform makes the calls it always made.  One with a ragged slot writes the counts of ALL
+        // its slots into the film-sized count image, uploads the rows those slots span and takes the counted entry.  (The image
+        // may be rewritten here: a slot exists only behind a merge, and every merge waits for the previous flush's copies.)
+        bool counted = false;
+        for (const Slot &s : acc.slots) counted = counted || !s.counts.empty();
+        int32_t *hostCounts = nullptr;
+        int rowsFrom = height, rowsTo = 0;
+        if (counted) {
+            acc.nCountedFlushes++;
+            acc.countsHost.allocate((size_t)width * height, !acc.dry);
+            hostCounts = reinterpret_cast<int32_t *>(acc.countsHost.ptr);
+            for (const Slot &s : acc.slots) {
+                rowsFrom = std::min<int>(rowsFrom, s.y0);
+                rowsTo = std::max<int>(rowsTo, s.y1);
+                const int rw = s.x1 - s.x0;
+                for (int y = s.y0; y < s.y1; y++)
+                    for (int x = s.x0; x < s.x1; x++)
+                        hostCounts[(size_t)y * width + x] = s.counts.empty() ? s.samples : s.counts[(size_t)(y - s.y0) * rw + (x - s.x0)];
+            }
+        }
         if (acc.dry) {
             resetEpochLocked();
             return;
         }
         check(statmc_set_device(device));  // a render worker thread may be the one that flushes
+        const int32_t *devCounts = nullptr;
+        if (counted) {
+            acc.countsDev.reserve((size_t)width * height * sizeof(int32_t));
+            devCounts = static_cast<const int32_t *>(acc.countsDev.ptr);
+            check(statmc_upload(static_cast<int32_t *>(acc.countsDev.ptr) + (size_t)rowsFrom * width, hostCounts + (size_t)rowsFrom * width,
+                                (size_t)(rowsTo - rowsFrom) * width * sizeof(int32_t), stream.handle()));
+        }
         const size_t used = (size_t)acc.nextOffset;  // pixel-samples staged in every arena
         const size_t n = acc.slots.size();
         // tile tables: bounds (int32 x 4), offsets (int64), samples (int32), one device block
@@ -1755,17 +1809,18 @@ class Estimator {
                     check(statmc_upload(p, o.data(), m * 8, stream.handle()));
                     check(statmc_upload(p + m * 8, b.data(), m * 16, stream.handle()));
                     check(statmc_upload(p + m * 24, sm.data(), m * 4, stream.handle()));
-                    check(statmc_accumulate_tiles_formats(width, height, &t, &format, 1, reinterpret_cast<const int32_t *>(p + m * 8),
+                    // (devCounts == NULL, a uniform flush: the call IS statmc_accumulate_tiles_formats)
+                    check(statmc_accumulate_tiles_counted(width, height, &t, &format, 1, reinterpret_cast<const int32_t *>(p + m * 8),
                                                           reinterpret_cast<const int64_t *>(p), reinterpret_cast<const int32_t *>(p + m * 24),
-                                                          (int)m, stream.handle()));
+                                                          (int)m, devCounts, stream.handle()));
                     check(statmc_synchronize(stream.handle()));  // `own` is freed on scope exit
                 }
             }
         for (size_t first = 0; first < full.size(); first += 8) {  // kMaxStatTypes per launch
             const int cnt = (int)std::min<size_t>(8, full.size() - first);
-            check(statmc_accumulate_tiles_formats(width, height, full.data() + first, fullFormats.data() + first, cnt,
+            check(statmc_accumulate_tiles_counted(width, height, full.data() + first, fullFormats.data() + first, cnt,
                                                   reinterpret_cast<const int32_t *>(tab + n * 8), reinterpret_cast<const int64_t *>(tab),
-                                                  reinterpret_cast<const int32_t *>(tab + n * 24), (int)n, stream.handle()));
+                                                  reinterpret_cast<const int32_t *>(tab + n * 24), (int)n, devCounts, stream.handle()));
         }
         resetEpochLocked();
     }

@@ -109,7 +109,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -190,6 +190,11 @@ def load():
                                             C.c_void_p, C.c_int, C.c_void_p]
     lib.statmc_accumulate_tiles_formats.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_int, C.c_void_p]
+    lib.statmc_accumulate_counted.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.c_void_p,
+                                              C.POINTER(C.c_int32), C.c_int, C.c_void_p]
+    lib.statmc_accumulate_tiles_counted.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.statmc_debug_last_accumulate_counted.restype = C.c_int
     lib.statmc_accumulate_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     lib.statmc_debug_accumulate_records_phases.argtypes = [C.c_int]
     lib.statmc_accumulate_records_interleaved.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
@@ -633,23 +638,47 @@ def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_
     return t
 
 
-def accumulate(width, height, stat_types, stream=None, rows=None, sample_formats=None):
+def _counts_pointer(sample_counts, width, height, who):
+    """The address of a per-pixel count image: an int32 CUDA tensor of height * width elements, packed (a view that starts
+    anywhere in a larger tensor is fine -- the entry wants 4-byte alignment, the vector path 16)."""
+    tc = _torch()
+    if sample_counts.dtype != tc.int32 or not sample_counts.is_cuda or not sample_counts.is_contiguous():
+        raise ValueError("%s: sample_counts must be a contiguous int32 CUDA tensor" % who)
+    if sample_counts.numel() != int(width) * int(height):
+        raise ValueError("%s: sample_counts holds %d counts, the film %d pixels" % (who, sample_counts.numel(), int(width) * int(height)))
+    return sample_counts.data_ptr()
+
+
+def last_accumulate_counted():
+    """statmc_debug_last_accumulate_counted: 0 = the calling thread's last accumulate call launched no counted kernel, 1 = a counted
+    kernel on the vector path, 2 = a counted kernel element by element."""
+    return int(load().statmc_debug_last_accumulate_counted())
+
+
+def accumulate(width, height, stat_types, stream=None, rows=None, sample_formats=None, sample_counts=None):
     """rows = (y0, y1): only those rows of the film (statmc_accumulate_rows); rows = [(y0, y1), ...]: several disjoint
     ranges in one launch (statmc_accumulate_row_ranges).  sample_formats = [SAMPLES_F32 | SAMPLES_F16, ...], one per stat
-    type: what each type's sample arena holds (statmc_accumulate_formats)."""
+    type: what each type's sample arena holds (statmc_accumulate_formats).  sample_counts = int32 CUDA tensor [height, width]:
+    pixel p folds its first min(max(count, 0), n_samples) samples only (statmc_accumulate_counted)."""
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
     st = stream if stream is not None else current_stream_handle()
-    if sample_formats is not None:
-        if len(sample_formats) != len(stat_types):
-            raise ValueError("accumulate: one sample format per stat type")
-        fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
+    if sample_formats is not None or sample_counts is not None:
+        fmts = None
+        if sample_formats is not None:
+            if len(sample_formats) != len(stat_types):
+                raise ValueError("accumulate: one sample format per stat type")
+            fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
         if rows is None:
             flat, n_ranges = None, 0
         else:
             if len(rows) == 2 and not hasattr(rows[0], "__len__"):
                 rows = [rows]
             flat, n_ranges = (C.c_int32 * (2 * len(rows)))(*[int(v) for r in rows for v in r]), len(rows)
-        check(load().statmc_accumulate_formats(width, height, arr, fmts, len(stat_types), flat, n_ranges, st))
+        if sample_counts is not None:
+            check(load().statmc_accumulate_counted(width, height, arr, fmts, len(stat_types), _counts_pointer(sample_counts, width, height, "accumulate"),
+                                                   flat, n_ranges, st))
+        else:
+            check(load().statmc_accumulate_formats(width, height, arr, fmts, len(stat_types), flat, n_ranges, st))
     elif rows is None:
         check(load().statmc_accumulate(width, height, arr, len(stat_types), st))
     elif len(rows) == 2 and not hasattr(rows[0], "__len__"):
@@ -659,13 +688,25 @@ def accumulate(width, height, stat_types, stream=None, rows=None, sample_formats
         check(load().statmc_accumulate_row_ranges(width, height, arr, len(stat_types), flat, len(rows), st))
 
 
-def accumulate_tiles(width, height, stat_types, tile_bounds, tile_offsets, tile_samples, stream=None, sample_formats=None):
+def accumulate_tiles(width, height, stat_types, tile_bounds, tile_offsets, tile_samples, stream=None, sample_formats=None, sample_counts=None):
     """stat_types: make_stat_type_arena(arena, ...) per type, `arena` a flat device tensor holding the
     tiles' sample blocks; tile_bounds int32 [n,4], tile_offsets int64 [n] (pixel-samples),
     tile_samples int32 [n]: device tensors.  sample_formats = [SAMPLES_F32 | SAMPLES_F16, ...], one per stat type: what each
-    type's arena holds (statmc_accumulate_tiles_formats); None: fp32 arenas, the existing entry."""
+    type's arena holds (statmc_accumulate_tiles_formats); None: fp32 arenas, the existing entry.  sample_counts = int32 CUDA
+    tensor [height, width] indexed by film pixel: a pixel folds its first min(max(count, 0), tile_samples) samples only
+    (statmc_accumulate_tiles_counted)."""
     arr = (StatType * max(len(stat_types), 1))(*stat_types)
     st = stream if stream is not None else current_stream_handle()
+    if sample_counts is not None:
+        fmts = None
+        if sample_formats is not None:
+            if len(sample_formats) != len(stat_types):
+                raise ValueError("accumulate_tiles: one sample format per stat type")
+            fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
+        check(load().statmc_accumulate_tiles_counted(width, height, arr, fmts, len(stat_types), tile_bounds.data_ptr(), tile_offsets.data_ptr(),
+                                                     tile_samples.data_ptr(), tile_bounds.shape[0],
+                                                     _counts_pointer(sample_counts, width, height, "accumulate_tiles"), st))
+        return
     if sample_formats is None:
         check(load().statmc_accumulate_tiles(width, height, arr, len(stat_types), tile_bounds.data_ptr(),
                                              tile_offsets.data_ptr(), tile_samples.data_ptr(), tile_bounds.shape[0], st))

@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
-           "statmc_records.hip"]
-HEADERS = ["statmc_device.h", "statmc_records_plan.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+           "statmc_records.hip", "statmc_counted.hip"]
+HEADERS = ["statmc_device.h", "statmc_accumulate_fold.h", "statmc_records_plan.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -99,6 +99,7 @@ REC_ILV_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_interleaved_
 REC_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_interleaved")   # tests/cpp/test_accumulate_records_interleaved.cpp: Estimator::AccumulateRecordsInterleaved
 REC_SPLIT_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_split_plan")   # tests/cpp/test_records_split_plan.cpp: the split entries' chunk rule, no device, no library
 REC_SPLIT_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_split")   # tests/cpp/test_accumulate_records_split.cpp: Estimator::AccumulateRecords(..., splitAbove)
+ACC_COUNTED_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_counted")   # tests/cpp/test_accumulate_counted.cpp: ragged StatTiles, Estimator::AccumulateFilm(..., d_counts)
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
@@ -108,7 +109,8 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          REC_ILV_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_interleaved_plan.cpp"),
          REC_ILV_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_interleaved.cpp"),
          REC_SPLIT_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_split_plan.cpp"),
-         REC_SPLIT_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_split.cpp")}
+         REC_SPLIT_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_split.cpp"),
+         ACC_COUNTED_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_counted.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")

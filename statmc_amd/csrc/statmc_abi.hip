@@ -27,6 +27,7 @@ thread_local char g_variant[96] = "none";
 thread_local int g_last_parts = 0, g_last_parts_hi = 0, g_last_tail_rows = 0;
 thread_local const int *g_last_redo = nullptr;   // the item flags of the calling thread's last Welch launch (device memory)
 thread_local int g_last_redo_n = 0;
+thread_local int g_last_acc_counted = 0;    // the calling thread's last accumulate call: 0 no counted kernel, 1 counted, vector path, 2 counted, element by element
 thread_local int g_last_rec_ilv_path = 0;   // the fold the calling thread's last statmc_accumulate_records_interleaved call planned (0: none)
 std::mutex g_mu;
 
@@ -1233,17 +1234,13 @@ int statmc_accumulate_formats(uint16_t width, uint16_t height, const statmc_stat
             return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
     return accumulate_row_ranges_impl(width, height, types, sample_formats, n_types, ranges, n_ranges, stream);
 }
-static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
-                                      const int32_t *ranges, int n_ranges, void *stream) {
-    NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "stat types x row ranges must be in [0,%d]", statmc::kMaxStatTypes);
-    if (n_types == 0 || n_ranges == 0) return STATMC_OK;
-    if (!types || !ranges) return fail(STATMC_ERR_INVALID, "null types or ranges");
-    statmc::AccumulateArgs k;
-    memset(&k, 0, sizeof(k));
-    k.n_types = 0;
+// The entries of a film-major launch: one per (row range, stat type), every pointer advanced to the range's first row.  Validates
+// the ranges and the types; counts (statmc_accumulate_counted, else NULL): the film's count image, advanced likewise.
+static int fill_row_range_entries(const DeviceState &ds, uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats,
+                                  int n_types, const int32_t *ranges, int n_ranges, statmc::AccumulateType *out, int &n_out, int &half_mask,
+                                  const int32_t *counts, const int32_t **counts_out) {
+    n_out = 0;
+    half_mask = 0;
     for (int r = 0; r < n_ranges; r++) {
         const int y0 = ranges[2 * r], y1 = ranges[2 * r + 1];
         if (y0 < 0 || y1 > height || y0 > y1) return fail(STATMC_ERR_INVALID, "rows [%d,%d) outside the %d-row image", y0, y1, (int)height);
@@ -1251,12 +1248,12 @@ static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const sta
             if (y0 < ranges[2 * q + 1] && ranges[2 * q] < y1) return fail(STATMC_ERR_INVALID, "row ranges %d and %d overlap", q, r);
         if (y0 == y1) continue;
         for (int i = 0; i < n_types; i++) {
-            statmc::AccumulateType &d = k.t[k.n_types];
-            if (int rc = fill_stat_type(dstate, types[i], i, width, height, true, d)) return rc;
+            statmc::AccumulateType &d = out[n_out];
+            if (int rc = fill_stat_type(ds, types[i], i, width, height, true, d)) return rc;
             const long long px0 = (long long)y0 * width, e0 = px0 * d.channels;
             const bool half = formats && formats[i] == STATMC_SAMPLES_F16;
             if (d.samples) d.samples = half ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(d.samples) + e0) : d.samples + e0;
-            if (half) k.half_mask |= 1 << k.n_types;
+            if (half) half_mask |= 1 << n_out;
             d.n += px0;
             d.mean += e0;
             if (d.m2) d.m2 += e0;
@@ -1265,9 +1262,24 @@ static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const sta
             if (d.film_m2) d.film_m2 += e0;
             if (d.mean_corr) { d.mean_corr += e0; d.disc += e0; }
             d.n_elems = (long long)(y1 - y0) * width * d.channels;   // d.stride stays the whole film's plane
-            k.n_types++;
+            if (counts_out) counts_out[n_out] = counts + px0;
+            n_out++;
         }
     }
+    return STATMC_OK;
+}
+static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
+                                      const int32_t *ranges, int n_ranges, void *stream) {
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "stat types x row ranges must be in [0,%d]", statmc::kMaxStatTypes);
+    if (n_types == 0 || n_ranges == 0) return STATMC_OK;
+    if (!types || !ranges) return fail(STATMC_ERR_INVALID, "null types or ranges");
+    g_last_acc_counted = 0;
+    statmc::AccumulateArgs k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = fill_row_range_entries(dstate, width, height, types, formats, n_types, ranges, n_ranges, k.t, k.n_types, k.half_mask, nullptr, nullptr)) return rc;
     if (k.n_types == 0) return STATMC_OK;
     k.resident_blocks = dstate.acc_resident_blocks;
     k.cus = dstate.cus;
@@ -1508,6 +1520,7 @@ static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_s
     if (n_tiles < 0) return fail(STATMC_ERR_INVALID, "negative tile count");
     if (n_types == 0 || n_tiles == 0) return STATMC_OK;
     if (!types || !tile_bounds || !tile_offsets || !tile_samples) return fail(STATMC_ERR_INVALID, "null pointer");
+    g_last_acc_counted = 0;
     statmc::AccumulateTilesArgs k;
     memset(&k, 0, sizeof(k));
     k.n_types = n_types;
@@ -1529,6 +1542,98 @@ static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_s
     HIP_TRY(statmc::launch_accumulate_tiles(k, S(stream)));
     return STATMC_OK;
 }
+
+// Arenas in which every pixel has its own sample count (include/statmc.h; kernels: statmc_counted.hip).  What can be refused
+// without a device is refused first, in the order of the uncounted entries; then the device, then the descriptors.
+static int check_counted_formats(const statmc_stat_type *types, const int32_t *sample_formats, int n_types, const int32_t *sample_counts) {
+    if (reinterpret_cast<uintptr_t>(sample_counts) & 3) return fail(STATMC_ERR_INVALID, "sample_counts is not 4-byte aligned");
+    for (int i = 0; sample_formats && i < n_types; i++)
+        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
+            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
+    if (n_types > 0 && !types) return fail(STATMC_ERR_INVALID, "null types");
+    for (int i = 0; sample_formats && i < n_types; i++)
+        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
+            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
+    return STATMC_OK;
+}
+static int counted_context(const DeviceState &ds, statmc_prepass_context &ctx) {
+    ctx.t_table = statmc::t_table_device_ptr(prepass_table(ds));
+    if (!ctx.t_table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
+    ctx.flags = prepass_flags(ds);
+    ctx.reserved = 0;
+    return STATMC_OK;
+}
+int statmc_accumulate_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                              const int32_t *sample_counts, const int32_t *ranges, int n_ranges, void *stream) {
+    if (!sample_counts) return statmc_accumulate_formats(width, height, types, sample_formats, n_types, ranges, n_ranges, stream);   // the existing call
+    g_last_acc_counted = 0;
+    const int32_t whole[2] = {0, height};
+    if (!ranges || n_ranges == 0) {
+        if (n_ranges != 0) return fail(STATMC_ERR_INVALID, "n_ranges = %d without ranges", n_ranges);
+        ranges = whole;
+        n_ranges = 1;
+    }
+    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
+        return fail(STATMC_ERR_INVALID, "n_types x row ranges (n_ranges) must be in [0,%d]", statmc::kMaxStatTypes);
+    if (int rc = check_counted_formats(types, sample_formats, n_types, sample_counts)) return rc;
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0) return STATMC_OK;
+    statmc::AccumulateCountedArgs k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = fill_row_range_entries(dstate, width, height, types, sample_formats, n_types, ranges, n_ranges, k.t, k.n_types, k.half_mask, sample_counts, k.counts))
+        return rc;
+    int live = 0, live_half = 0;       // (an entry without samples folds nothing: it is not launched)
+    for (int i = 0; i < k.n_types; i++) {
+        if (k.t[i].n_samples == 0) continue;
+        k.t[live] = k.t[i];
+        k.counts[live] = k.counts[i];
+        live_half |= ((k.half_mask >> i) & 1) << live;
+        live++;
+    }
+    k.n_types = live;
+    k.half_mask = live_half;
+    if (k.n_types == 0) return STATMC_OK;
+    if (int rc = counted_context(dstate, k.ctx)) return rc;
+    int path = 0;
+    HIP_TRY(statmc::launch_accumulate_counted(k, S(stream), &path));
+    g_last_acc_counted = path;
+    return STATMC_OK;
+}
+int statmc_accumulate_tiles_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                                    const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles,
+                                    const int32_t *sample_counts, void *stream) {
+    if (!sample_counts)      // the existing call
+        return statmc_accumulate_tiles_formats(width, height, types, sample_formats, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
+    g_last_acc_counted = 0;
+    if (n_types < 0 || n_types > statmc::kMaxStatTypes) return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
+    if (n_tiles < 0) return fail(STATMC_ERR_INVALID, "negative tile count (n_tiles)");
+    if (int rc = check_counted_formats(types, sample_formats, n_types, sample_counts)) return rc;
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0 || n_tiles == 0) return STATMC_OK;
+    if (!tile_bounds || !tile_offsets || !tile_samples) return fail(STATMC_ERR_INVALID, "null pointer");
+    statmc::AccumulateTilesCountedArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_types = n_types;
+    for (int i = 0; i < n_types; i++) {
+        if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, k.t[i])) return rc;
+        if (sample_formats && sample_formats[i] == STATMC_SAMPLES_F16) k.half_mask |= 1 << i;
+    }
+    if (int rc = counted_context(dstate, k.ctx)) return rc;
+    k.counts = sample_counts;
+    k.tile_bounds = tile_bounds;
+    k.tile_offsets = reinterpret_cast<const long long *>(tile_offsets);
+    k.tile_samples = tile_samples;
+    k.n_tiles = n_tiles;
+    k.width = width;
+    k.height = height;
+    int path = 0;
+    HIP_TRY(statmc::launch_accumulate_tiles_counted(k, S(stream), &path));
+    g_last_acc_counted = path;
+    return STATMC_OK;
+}
+int statmc_debug_last_accumulate_counted(void) { return g_last_acc_counted; }
 
 // Samples as unordered (pixel, sample) records (include/statmc.h; kernels and the scheme: statmc_records.hip).
 // split_above: 0 = statmc_accumulate_records; otherwise statmc_accumulate_records_split's argument, checked here

@@ -93,6 +93,34 @@ struct AccumulateTilesArgs {
 static_assert(sizeof(AccumulateTilesArgs) == sizeof(AccumulateType) * kMaxStatTypes + 72 && offsetof(AccumulateTilesArgs, half_mask) + 4 == sizeof(AccumulateTilesArgs),
               "AccumulateTilesArgs: kernel-argument offsets");
 
+// statmc_accumulate_counted / statmc_accumulate_tiles_counted (statmc_counted.hip): the arena of the uncounted entry plus an int32
+// film image that says how many of its planes are live for each pixel.  Argument blocks of their own: AccumulateArgs and
+// AccumulateTilesArgs above, and the kernels that take them, stay what they are.
+struct AccumulateCountedArgs {
+    AccumulateType t[kMaxStatTypes];         // as AccumulateArgs::t (stat types x row ranges); n_samples is the arena's capacity S
+    const int32_t *counts[kMaxStatTypes];    // the count of entry i's first pixel (the film image, advanced to the entry's first row)
+    statmc_prepass_context ctx;              // the pre-pass epilogue's table and flags (entries with mean_corr / disc)
+    int n_types;
+    int half_mask;                           // bit i = t[i].samples is an IEEE-half arena
+};
+struct AccumulateTilesCountedArgs {
+    AccumulateType t[kMaxStatTypes];         // as AccumulateTilesArgs::t
+    statmc_prepass_context ctx;
+    const int32_t *counts;                   // [height][width], indexed by film pixel
+    const int32_t *tile_bounds;              // device, {x0, y0, x1, y1} per tile
+    const long long *tile_offsets;           // device, in pixel-samples
+    const int32_t *tile_samples;             // device: the capacity S of tile k's block
+    int n_types, n_tiles, width, height;
+    int vec;                                 // bit i = type i's images, arena and the counts image are aligned for the vector path
+    int half_mask;
+};
+static_assert(sizeof(AccumulateCountedArgs) <= 4096 && sizeof(AccumulateTilesCountedArgs) <= 4096, "passed by value: the kernel-argument limit");
+// path (out): what statmc_debug_last_accumulate_counted reports -- 1 the vector path, 2 element by element
+hipError_t launch_accumulate_counted(const AccumulateCountedArgs &a, hipStream_t s, int *path);
+hipError_t launch_accumulate_tiles_counted(const AccumulateTilesCountedArgs &a, hipStream_t s, int *path);
+// whether a lane can own 4 consecutive pixels of the type as 16-byte pieces (statmc_pointwise.hip; film_major: also the plane sizes)
+bool acc_type_vectorizable(const AccumulateType &t, bool half_arena, bool film_major);
+
 // statmc_combine_statistics: one entry per pair of states.  The counts are read from cnt_dst / cnt_src: the entry's own
 // count images, or those of the entry it borrows them from.  The ABI puts borrowing entries first, so that they read the
 // counts before their owner (later in the same lane) writes n = nA + nB.

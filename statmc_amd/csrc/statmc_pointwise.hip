@@ -23,6 +23,7 @@
 #include "statmc_device.h"
 
 #include "../../include/statmc_device_api.hpp"
+#include "statmc_accumulate_fold.h"
 #include "t_quantiles.h"
 
 namespace statmc {
@@ -104,7 +105,6 @@ __device__ __forceinline__ float t_quantile(int table, int dof) {
 __device__ __forceinline__ float prepass_quantile(int table, int flags, int n) { return (flags & 1) ? 1.f : t_quantile(table, n - 1); }
 
 constexpr int kBlock = 256;
-typedef float vfloat4 __attribute__((ext_vector_type(4)));
 
 static inline int grid_for(long long work_items, int cap = 256 * 16) {
     long long b = (work_items + kBlock - 1) / kBlock;
@@ -232,101 +232,8 @@ hipError_t launch_mean_vars(const MeanVarsArgs &a, hipStream_t s) {
 // (ElemState, refined_rcp, div_by_count, add_sample: include/statmc_device_api.hpp, the definition a renderer's own kernel
 // includes as well)
 
-// The same update on two elements at once (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32: one issue slot for two lanes'
-// worth of IEEE fp32 arithmetic, each component rounded exactly like the scalar instruction, so the bits are those of
-// add_sample).  The kernel holds ~250 VGPRs, i.e. two waves per SIMD, and while one of them waits for memory the other
-// issues one vector instruction per 4 cycles: the radiance type (Box-Cox + three moments + the raw-sample chain, 27
-// instructions per element and sample) was bound by exactly that issue rate (5.1 TB/s on its own); paired, it is
-// bound by the memory like the feature types.
-typedef float v2f __attribute__((ext_vector_type(2)));
-struct PairState {
-    v2f mean, m2, m3, fmean, fm2;
-};
-__device__ __forceinline__ v2f div_by_count2(v2f d, v2f nf, v2f r) {
-    const v2f q0 = d * r;
-    const v2f rem = __builtin_elementwise_fma(-q0, nf, d);
-    return __builtin_elementwise_fma(rem, r, q0);
-}
-// G pairs at a time, stage by stage: consecutive instructions belong to different pairs, so none waits for the one
-// before it (a dependent packed instruction costs a wait state, and the kernel is compiled without the machine scheduler:
-// the source order is the issue order).
-#define STATMC_PAIRS(i) _Pragma("unroll") for (int i = 0; i < G; i++)
-template <int G, int MAXM, bool TRANSFORM>
-__device__ __forceinline__ void add_sample2(PairState *st, const v2f *nf, const v2f *r, const v2f *smp) {
-    v2f v[G], d[G], q0[G], dN[G];
-    if (TRANSFORM) {   // estimator.h:215 -- boxCox(sample, .5f), as in add_sample
-        STATMC_PAIRS(i) v[i] = v2f{__builtin_amdgcn_sqrtf(smp[i].x), __builtin_amdgcn_sqrtf(smp[i].y)};
-        // (root - 1) / .5 in one instruction: fma(root, 2, -2) rounds 2 root - 2 = 2 (root - 1) once, and doubling commutes with
-        // rounding (no overflow: root < 2^64; no underflow: |root - 1| is 0 or at least 2^-24) -- the bits of the two-step form
-        STATMC_PAIRS(i) v[i] = __builtin_elementwise_fma(v[i], v2f{2.f, 2.f}, v2f{-2.f, -2.f});
-    } else {
-        STATMC_PAIRS(i) v[i] = smp[i];
-    }
-    STATMC_PAIRS(i) d[i] = v[i] - st[i].mean;
-    STATMC_PAIRS(i) q0[i] = d[i] * r[i];                                         // div_by_count, three stages
-    STATMC_PAIRS(i) dN[i] = __builtin_elementwise_fma(-q0[i], nf[i], d[i]);
-    STATMC_PAIRS(i) dN[i] = __builtin_elementwise_fma(dN[i], r[i], q0[i]);
-    STATMC_PAIRS(i) st[i].mean += dN[i];
-    if (MAXM >= 2) {
-        v2f t[G];
-        STATMC_PAIRS(i) t[i] = d[i] - dN[i];
-        STATMC_PAIRS(i) t[i] = d[i] * t[i];
-        STATMC_PAIRS(i) st[i].m2 += t[i];
-    }
-    if (MAXM >= 3) {   // m3 += -3 dN m2 + d (d^2 - dN^2), with the m2 already updated (estimator.h:178-180)
-        v2f a[G], b[G];
-        STATMC_PAIRS(i) a[i] = -3.f * dN[i];
-        STATMC_PAIRS(i) b[i] = d[i] * d[i];
-        STATMC_PAIRS(i) dN[i] = dN[i] * dN[i];
-        STATMC_PAIRS(i) a[i] = a[i] * st[i].m2;
-        STATMC_PAIRS(i) b[i] = b[i] - dN[i];
-        STATMC_PAIRS(i) b[i] = d[i] * b[i];
-        STATMC_PAIRS(i) a[i] = a[i] + b[i];
-        STATMC_PAIRS(i) st[i].m3 += a[i];
-    }
-    if (TRANSFORM) {   // the raw-sample chain (estimator.h:217-225)
-        STATMC_PAIRS(i) d[i] = smp[i] - st[i].fmean;
-        STATMC_PAIRS(i) q0[i] = d[i] * r[i];
-        STATMC_PAIRS(i) dN[i] = __builtin_elementwise_fma(-q0[i], nf[i], d[i]);
-        STATMC_PAIRS(i) dN[i] = __builtin_elementwise_fma(dN[i], r[i], q0[i]);
-        STATMC_PAIRS(i) st[i].fmean += dN[i];
-        STATMC_PAIRS(i) dN[i] = d[i] - dN[i];
-        STATMC_PAIRS(i) dN[i] = d[i] * dN[i];
-        STATMC_PAIRS(i) st[i].fm2 += dN[i];
-    }
-}
-#undef STATMC_PAIRS
-
-// One state plane of a lane's 4 consecutive pixels -- C float4 from p on -- into the field of the lane's element pairs (2 i, 2 i + 1)
-// and back.  ON = false: a plane the stat type does not hold; it reads as zeros and is not stored.
-template <int C, bool ON = true>
-__device__ __forceinline__ void load_plane(PairState *st, v2f PairState::*field, const float *p) {
-#pragma unroll
-    for (int k = 0; k < C; k++) {
-        float4 v = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (ON) v = *reinterpret_cast<const float4 *>(p + 4 * k);
-        st[2 * k].*field = v2f{v.x, v.y};
-        st[2 * k + 1].*field = v2f{v.z, v.w};
-    }
-}
-template <int C, bool ON = true>
-__device__ __forceinline__ void store_plane(float *p, const PairState *st, v2f PairState::*field) {
-    if constexpr (ON) {
-#pragma unroll
-        for (int k = 0; k < C; k++) {
-            const vfloat4 v = {(st[2 * k].*field).x, (st[2 * k].*field).y, (st[2 * k + 1].*field).x, (st[2 * k + 1].*field).y};
-            *reinterpret_cast<vfloat4 *>(p + 4 * k) = v;
-        }
-    }
-}
-// The counts of the lane's 4 pixels after the batch: one per pixel, or (NC = 1) the one count a group is known to hold.
-// Merge*Tile casts the tile's uint64 count to int32 (estimator.cpp:347,380)
-template <int NC>
-__device__ __forceinline__ void store_counts(int32_t *n, const int (&n_out)[NC]) {
-    typedef int vint4 __attribute__((ext_vector_type(4)));
-    const vint4 v = {n_out[0], n_out[NC > 1 ? 1 : 0], n_out[NC > 1 ? 2 : 0], n_out[NC > 1 ? 3 : 0]};
-    *reinterpret_cast<vint4 *>(n) = v;
-}
+// (PairState, add_sample2 -- the same update on two elements at once --, load_plane, store_plane, store_counts: statmc_accumulate_fold.h,
+// shared with statmc_counted.hip)
 // Optional epilogue (round 6): the pre-pass of the moments just written, from the registers that hold them -- the same
 // prepass_elem as prepass_kernel, hence the same bits -- instead of a launch that reads 40 B per pixel back.  NC as above: one
 // count, one quantile.  (The caller reads pre_mc, pre_dc, table and flags out of its descriptor BEFORE its first store: see
@@ -1139,7 +1046,7 @@ static bool accumulate_fused_plan(const AccumulateArgs &a, AccumulateFusedArgs &
 // launch, the element count and the sample stride keep every sample plane so.  A half arena wants 8 bytes and whole 4-pixel groups
 // (n_elems % (4 channels)); an fp32 one is asked for n_elems % 4, which says the same of every count the C ABI can hand over
 // (pixels x channels, channels 1 or 3), also of an fp32 type beside half ones.  A tile-fed launch checks its rows tile by tile.
-static bool acc_type_vectorizable(const AccumulateType &t, bool half_arena, bool film_major) {
+bool acc_type_vectorizable(const AccumulateType &t, bool half_arena, bool film_major) {
     const long long whole = half_arena ? 4 * t.channels : 4;
     return (half_arena ? (reinterpret_cast<uintptr_t>(t.samples) & 7) == 0 : aligned16(t.samples)) && aligned16(t.n) && aligned16(t.mean) &&
            (t.max_moment < 2 || aligned16(t.m2)) && (t.max_moment < 3 || aligned16(t.m3)) &&

@@ -67,10 +67,14 @@ class FilmStats:
                 if v is not None:
                     v.zero_()
 
-    def accumulate(self, samples, rows=None):
+    def accumulate(self, samples, rows=None, counts=None):
         """samples: {type: [S, H, W, C]}; one kernel launch covers every stat type.  rows = (y0, y1): only those rows.
         A type's arena is read in the format of its tensor: torch.float32, or torch.float16 (statmc_accumulate_formats: the bits
-        of the same samples widened to fp32)."""
+        of the same samples widened to fp32).  counts: int32 CUDA tensor [H, W] -- pixel p folds only its first
+        min(max(counts[p], 0), S) samples and keeps every bit where that is 0 (statmc_accumulate_counted): the arena of a
+        renderer that spends its samples unevenly."""
+        if counts is not None and tuple(counts.shape) != (self.height, self.width):
+            raise ValueError("FilmStats.accumulate: counts must be [H, W] = [%d, %d]" % (self.height, self.width))
         fuse = self.fused_prepass and rows is None and "radiance" in samples
         sts = [api.make_stat_type(samples[t], self.state[t], STAT_TYPES[t]["transform"], STAT_TYPES[t]["max_moment"],
                                   prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None)
@@ -82,8 +86,13 @@ class FilmStats:
                     raise TypeError("FilmStats.accumulate: samples of %r are %s; torch.float32 or torch.float16" % (t, samples[t].dtype))
                 fmts.append(api.SAMPLES_F16 if samples[t].dtype == torch.float16 else api.SAMPLES_F32)
         # (an all-fp32 batch makes the call it always made)
-        api.accumulate(self.width, self.height, sts, rows=rows, sample_formats=fmts if api.SAMPLES_F16 in fmts else None)
-        self._prepass_current = self._prepass_key() if fuse else None
+        api.accumulate(self.width, self.height, sts, rows=rows, sample_formats=fmts if api.SAMPLES_F16 in fmts else None, sample_counts=counts)
+        if counts is not None and fuse:
+            # pixels without a live sample keep their mean-corr / discriminator: current only if they were current before
+            key = self._prepass_key()
+            self._prepass_current = key if self._prepass_current == key else None
+        else:
+            self._prepass_current = self._prepass_key() if fuse else None
 
     def combine_(self, other):
         """Combines the statistics of `other` -- the same film, its own samples -- into self, so that self holds the

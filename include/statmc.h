@@ -126,8 +126,22 @@ const char *statmc_pinned_from(void);
  * call from the number of tiles of the LOCAL image and the device's CU count, so that the launch fills the chip.  The
  * parts decide how a pixel's 1681 terms are grouped: two calls with a different split agree to <= 1e-6 relative L2, two
  * calls with the same split (and the same film-anchored tile grid, statmc_filter_args::film_x0 / film_y0) agree BIT FOR BIT
- * -- whatever the image shape, the region of interest or the device.  Within one image the split never depends on the
+ * -- whatever the image shape, the region of interest, the image layout (separate images or any packed_inputs layout the
+ * call's G-buffer set may travel in) or the device.  Within one image the split never depends on the
  * region a call filters (bands of the Upload / Denoise / Download pipeline = the whole-image call, bit for bit).
+ * Kernel by kernel (statmc_last_filter_variant()): the pair-symmetric kernel ("sym_...") anchors its tiles and lanes in film
+ * coordinates; the general kernel ("generic") sums every pixel's window in one fixed order and has no split.  The
+ * ONE-SIDED LDS kernel ("lds_...": float buffers under the asymmetric / centre gate, more than two 1-channel G-buffers -- up to six
+ * feature channels in all --, and the last three of an odd number >= 3 of float buffers when the sweep is in one part,
+ * "sym_..._f+lds_..._f") lays its tiles from the corner of the region of interest, not on the film's grid, and ignores
+ * film_x0 / film_y0.  It keeps the promise all the same, with NO alignment condition on the region's corner: a lane adds the
+ * taps of a window row in ascending dx into two running sums, one for the taps with dx + (x - roi_x0) even and one for the odd
+ * ones, over the window rows in ascending dy, and adds the two at the end.  Moving the corner by an odd number of columns swaps
+ * the two sums and nothing else, and their sum does not care; rows, widths, the tile and the lane a pixel falls into never
+ * enter.  What does enter is the KERNEL: the pair-symmetric and the one-sided kernel group a pixel's sums differently (they
+ * agree to 5e-7), so the float-buffer tail makes a buffer's bits depend on the call's buffer count -- compare calls with the
+ * same n_buffers -- and a forced variant (include/statmc_debug.h) is compared with itself.
+ * tests/test_filter_bit_contract_gpu.py holds all of this at the C ABI, layout by layout.
  * A host that needs the blocks of a sharded film and the single-device result to be the same bits pins ONE split on every
  * device involved, the single one included:
  *     statmc_set_filter_split(statmc_filter_split_auto(film_width, film_height, radius)),
@@ -280,6 +294,12 @@ typedef struct statmc_filter_args {
      * When set, statmc_window_filter (T = float3, radius <= 20, n_buffers = 1) reads its inputs from it and ignores
      * mean_corr / discriminator / film / g_buffers (g_dr_factors and, for 17 / 18 channels, g_channel_counts still describe
      * the G-buffers: 15 / 16 channels = two RGB; 17 / 18 = up to two RGB + up to two 1-channel, pair-symmetric kernel only).
+     * A G-buffer set has ONE packed layout per dof rule, so that every block of a film is filtered by the build that filters the
+     * whole film: exactly two RGB G-buffers and no 1-channel one travel in the 15-channel image under STATMC_DOF_PIXEL -- a
+     * 17-channel image that holds just those two is refused with STATMC_ERR_UNSUPPORTED by statmc_window_filter and by the
+     * pack entries below (it would run the eight-plane build, whose sums are grouped otherwise than the whole film's at r = 20
+     * under the symmetric gate) -- and every other set in the 17-channel image.  Under STATMC_DOF_WELCH the two-RGB set may
+     * travel in 16 or in 18 channels: both reproduce the whole film.
      * statmc_pack_filter_inputs / statmc_prepass_pack fill the owned block of such an image; the channel count is the
      * image's row pitch / (cols * 4). */
     statmc_image packed_inputs;
@@ -288,7 +308,8 @@ typedef struct statmc_filter_args {
      * same order whether it is filtered as part of the whole film or of a block + halo image: block-decomposed
      * results equal the single-GPU result bit for bit WHEN BOTH USE THE SAME WINDOW-SWEEP SPLIT (statmc_set_filter_split;
      * the automatic split depends on the local image's shape and the device's CU count), and to <= 1e-6 relative L2
-     * under the automatic split. */
+     * under the automatic split.  (The one-sided LDS kernel does not use the film grid and needs none: the window-sweep split
+     * paragraph above says why its blocks reproduce the whole film from any corner.) */
     int32_t film_x0, film_y0;
 } statmc_filter_args;
 

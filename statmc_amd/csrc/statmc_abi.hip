@@ -246,7 +246,9 @@ inline bool packed_has_scalars(int ch) { return ch == 17 || ch == 18; }
 struct PackedSlots {
     const float *rgb[2] = {nullptr, nullptr}, *sc[2] = {nullptr, nullptr};
 };
-int packed_slots(const statmc_filter_args *a, int ch, int W, int H, PackedSlots &out) {
+// (dof: the device's statmc_filter_spec.dof.  A 17-channel image that holds exactly two RGB G-buffers and no 1-channel one is
+// refused under STATMC_DOF_PIXEL, as plan_window_filter refuses to read it: that set belongs in the 15-channel image.)
+int packed_slots(const statmc_filter_args *a, int ch, int W, int H, int dof, PackedSlots &out) {
     if (ch == 15 || ch == 16) {
         if (a->n_g_buffers != 2 || !a->g_buffers || (a->g_channel_counts && (a->g_channel_counts[0] != 3 || a->g_channel_counts[1] != 3)))
             return fail(STATMC_ERR_INVALID, "a 15- or 16-channel block + halo image holds exactly two RGB G-buffers");
@@ -261,6 +263,7 @@ int packed_slots(const statmc_filter_args *a, int ch, int W, int H, PackedSlots 
         if (int rc = check_image(a->g_buffers[g], W, H, gc, "g_buffers", (int)g)) return rc;
         (gc == 3 ? out.rgb[n_rgb++] : out.sc[n_sc++]) = static_cast<const float *>(a->g_buffers[g].data);
     }
+    if (ch == 17 && dof == STATMC_DOF_PIXEL && n_rgb == 2 && n_sc == 0) return fail(STATMC_ERR_UNSUPPORTED, "%s", statmc::kTwoRgbIn17Channels);
     return STATMC_OK;
 }
 
@@ -718,7 +721,7 @@ int statmc_pack_filter_inputs(const statmc_filter_args *a, const statmc_image *p
     CHECK_IMG(a->discriminator[0], 3, "discriminator", 0);
     CHECK_IMG(colour, 3, "colour", 0);
     PackedSlots gs;
-    if (int rc = packed_slots(a, pch, W, H, gs)) return rc;
+    if (int rc = packed_slots(a, pch, W, H, dstate.spec.dof, gs)) return rc;
     if (dst_x0 < 0 || dst_y0 < 0 || dst_x0 + W > packed->cols || dst_y0 + H > packed->rows)
         return fail(STATMC_ERR_INVALID, "block %dx%d at (%d,%d) does not fit the %dx%d packed image", W, H, dst_x0, dst_y0,
                     packed->cols, packed->rows);
@@ -754,7 +757,7 @@ int statmc_prepass_pack_rows(const statmc_filter_args *a, const statmc_image *pa
     CHECK_IMG(a->m3[0], 3, "m3", 0);
     CHECK_IMG(colour, 3, "colour", 0);
     PackedSlots gs;
-    if (int rc = packed_slots(a, pch, W, H, gs)) return rc;
+    if (int rc = packed_slots(a, pch, W, H, dstate.spec.dof, gs)) return rc;
     float *mc = nullptr, *dc = nullptr;
     if (a->mean_corr && a->discriminator && a->mean_corr[0].data && a->discriminator[0].data) {
         CHECK_IMG(a->mean_corr[0], 3, "mean_corr", 0);

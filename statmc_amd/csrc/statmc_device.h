@@ -366,6 +366,13 @@ struct FilterPlan {
 // STATMC_OK, or STATMC_ERR_UNSUPPORTED (with the message recorded) for a block + halo image no kernel can read.  Fills the
 // layout fields of k: feature scales and slots, parts, the pair-symmetric kernel's tile range and split.
 int plan_window_filter(FilterArgs &k, int channels, int n_buffers, int n_cus, int force_variant, int split, FilterPlan &p);
+// What the planner and the pack entries say to a 17-channel block + halo image that holds exactly two RGB G-buffers and no
+// 1-channel one under STATMC_DOF_PIXEL.  It would run the eight-plane build, which shares the window after read group 6, where the
+// whole film with the same G-buffers -- and its 15-channel image -- runs the G7 build at r = 20 (statmc_filter_sym.hip, gsplit_of):
+// not the same bits.  The set has one packed layout, 15 channels.
+constexpr const char *kTwoRgbIn17Channels =
+    "packed image (17 channels): exactly two RGB G-buffers and no 1-channel one belong in the 15-channel layout under STATMC_DOF_PIXEL "
+    "(the 17-channel image would not reproduce the whole film's bits)";
 hipError_t launch_window_filter(const FilterPlan &p, bool tail, const FilterArgs &a, int channels, hipStream_t s);
 // window-sweep parts per tile for the whole local image (statmc_filter_split_auto: sym, split 0)
 int whole_image_parts(const FilterArgs &a, bool sym, int n_cus, int split);

@@ -1086,6 +1086,8 @@ int plan_window_filter(FilterArgs &k, int channels, int n_buffers, int n_cus, in
         return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (17 / 18 channels): runs on the pair-symmetric kernel only -- radius 1..20, DR factors "
                                                 "finite and <= 0, at most two RGB and two 1-channel G-buffers; 17 channels under STATMC_DOF_PIXEL, "
                                                 "18 under STATMC_DOF_WELCH");
+    if (pch == 17 && k.dof == STATMC_DOF_PIXEL && k.n_g == 2 && k.g[0].channels == 3 && k.g[1].channels == 3)
+        return abi_fail(STATMC_ERR_UNSUPPORTED, "%s", kTwoRgbIn17Channels);
     if (pch == 16 && !sym_ok)
         return abi_fail(STATMC_ERR_UNSUPPORTED, "packed_inputs (16 channels): for STATMC_DOF_WELCH on the pair-symmetric kernel -- radius 1..20, DR "
                                                 "factors finite and <= 0, two RGB G-buffers");

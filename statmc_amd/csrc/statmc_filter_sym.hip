@@ -111,7 +111,7 @@ constexpr bool mode_pair(int m) { return m == 1 /* kModePair */ || m == kModeWel
 // only the housekeeping's place, which changes no sum, is chosen per build.
 // ... with ONE exception, decided by the G-buffer SET and not by the build (the last session of round 6): a call whose G-buffers are
 // exactly two RGB images -- the shipped normal + albedo -- runs a six-plane build whether it filters the whole film or a 15-channel block +
-// halo image, so those calls may have a G of their own: 7 under the default and the pooled test (G7 builds; 1.603 - 1.611 against 1.641 -
+// halo image (its 17-channel image, which would run the eight-plane build, is refused: plan_window_filter), so those calls may have a G of their own: 7 under the default and the pooled test (G7 builds; 1.603 - 1.611 against 1.641 -
 // 1.650 ms in the step at 1080p, three A/B pairs, profiles/r06_ab_g7_step.log).  Every other set keeps 6 in every build.
 // (G itself, 1080p RGB, back to back, one box: 1.440 ms with the dx = 0 split | G = 5 1.42 | 6 1.383 | 7 1.340 | 8 1.442;
 // profiles/r06_ab*.log.)

@@ -10,7 +10,7 @@ SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
            "statmc_records.hip", "statmc_counted.hip"]
-HEADERS = ["statmc_device.h", "statmc_accumulate_fold.h", "statmc_records_plan.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+HEADERS = ["statmc_device.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -99,6 +99,7 @@ REC_ILV_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_interleaved_
 REC_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_interleaved")   # tests/cpp/test_accumulate_records_interleaved.cpp: Estimator::AccumulateRecordsInterleaved
 REC_SPLIT_PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_records_split_plan")   # tests/cpp/test_records_split_plan.cpp: the split entries' chunk rule, no device, no library
 REC_SPLIT_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_records_split")   # tests/cpp/test_accumulate_records_split.cpp: Estimator::AccumulateRecords(..., splitAbove)
+ACC_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_args")   # tests/cpp/test_accumulate_args.cpp: statmc_accumulate_args.h, no device, no library
 ACC_COUNTED_BIN = os.path.join(ROOT, "tools", "bin", "test_accumulate_counted")   # tests/cpp/test_accumulate_counted.cpp: ragged StatTiles, Estimator::AccumulateFilm(..., d_counts)
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
@@ -106,6 +107,7 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          ACC_RECORDS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records.cpp"),
          ACC_FILM_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_film.cpp"),
          ACC_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_plan.cpp"),
+         ACC_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_args.cpp"),
          REC_ILV_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_interleaved_plan.cpp"),
          REC_ILV_BIN: os.path.join("..", "tests", "cpp", "test_accumulate_records_interleaved.cpp"),
          REC_SPLIT_PLAN_BIN: os.path.join("..", "tests", "cpp", "test_records_split_plan.cpp"),
@@ -129,6 +131,7 @@ def tools_hash():
     files = [os.path.join(ROOT, "tools", src) for src in list(TOOLS.values()) + [DEVICE_EXAMPLE_SRC]]
     files += [os.path.join(inc, f) for f in sorted(os.listdir(inc))]
     files.append(os.path.join(CSRC, "statmc_device.h"))    # test_accumulate_plan.cpp reads the library's own argument blocks
+    files.append(os.path.join(CSRC, "statmc_accumulate_args.h"))    # ... test_accumulate_args.cpp the accumulation entries' checks and fills
     files.append(os.path.join(CSRC, "statmc_records_plan.h"))    # ... and test_records_interleaved_plan.cpp the records entries' host decisions
     for path in files:
         with open(path, "rb") as f:
@@ -163,7 +166,7 @@ def build_tools(force=False):
     for binary, src in TOOLS.items():
         tmp = binary + ".tmp%d" % os.getpid()
         extra = ["-L", os.path.dirname(DEVICE_EXAMPLE_SO), "-lstatmc_device_example", "-Wl,-rpath,$ORIGIN"] if binary == DEVICE_ACC_BIN else []
-        if binary == ACC_PLAN_BIN:      # statmc_device.h includes the HIP runtime's header
+        if binary in (ACC_PLAN_BIN, ACC_ARGS_BIN):      # statmc_device.h includes the HIP runtime's header
             extra = ["-D__HIP_PLATFORM_AMD__", "-I", rocm_inc]
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread",
                                "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", src), "-o", tmp,

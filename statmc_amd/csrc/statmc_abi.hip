@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "statmc_device.h"
+#include "statmc_accumulate_args.h"
 #include "statmc_records_plan.h"
 
 #include <atomic>
@@ -62,17 +63,9 @@ DeviceState current_state(int *dev_out = nullptr) {
     return it == g_dev.end() ? DeviceState() : it->second;
 }
 
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace
 namespace statmc {
-int abi_fail(int code, const char *fmt, ...) {
+int abi_fail(int code, const char *fmt, ...) {   // the calling thread's message (statmc_last_error), for every translation unit
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -81,6 +74,7 @@ int abi_fail(int code, const char *fmt, ...) {
 }
 }  // namespace statmc
 namespace {
+int (&fail)(int, const char *, ...) = statmc::abi_fail;   // ... under this file's name for it
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -1140,164 +1134,98 @@ int statmc_calculate_mean_vars(uint8_t n_buffers, uint16_t width, uint16_t heigh
     });
 }
 
-// validates one statmc_stat_type and translates it for the kernels (shared by both accumulate entries)
-static int fill_stat_type(const DeviceState &ds, const statmc_stat_type &t, int i, uint16_t width, uint16_t height, bool batch,
-                          statmc::AccumulateType &d) {
-    if (t.channels != 1 && t.channels != 3) return fail(STATMC_ERR_INVALID, "types[%d]: channels must be 1 or 3", i);
-    if (t.max_moment < 1 || t.max_moment > 3) return fail(STATMC_ERR_INVALID, "types[%d]: max_moment must be 1..3", i);
-    if (batch && t.n_samples < 0) return fail(STATMC_ERR_INVALID, "types[%d]: negative n_samples", i);
-    if (!t.n || !t.mean || ((!batch || t.n_samples) && !t.samples)) return fail(STATMC_ERR_INVALID, "types[%d]: null pointer", i);
-    if (t.max_moment >= 2 && !t.m2) return fail(STATMC_ERR_INVALID, "types[%d]: null m2", i);
-    if (t.max_moment >= 3 && !t.m3) return fail(STATMC_ERR_INVALID, "types[%d]: null m3", i);
-    if (t.transform && (!t.film_mean || !t.film_m2))
-        return fail(STATMC_ERR_INVALID, "types[%d]: transform types need film_mean and film_m2", i);
-    d.samples = t.samples;
-    d.n = t.n;
-    d.mean = t.mean;
-    d.m2 = t.m2;
-    d.m3 = t.m3;
-    d.film_mean = t.film_mean;
-    d.film_m2 = t.film_m2;
-    d.n_elems = (long long)width * height * t.channels;
-    d.stride = d.n_elems;
-    d.channels = t.channels;
-    d.n_samples = t.n_samples;
-    d.transform = t.transform ? 1 : 0;
-    d.max_moment = t.max_moment;
-    // optional epilogue: the pre-pass of the updated moments under the device's current spec and significance level
-    // (statmc_prepass's own PrepassArgs, prepass_impl above)
-    d.mean_corr = nullptr;
-    d.disc = nullptr;
-    d.pre_table = 0;
-    d.pre_flags = 0;
-    if (t.mean_corr || t.discriminator) {
-        if (!t.mean_corr || !t.discriminator) return fail(STATMC_ERR_INVALID, "types[%d]: mean_corr and discriminator come together", i);
-        if (t.max_moment < 3) return fail(STATMC_ERR_INVALID, "types[%d]: the pre-pass epilogue needs max_moment 3 (it reads m2 and m3)", i);
-        d.mean_corr = t.mean_corr;
-        d.disc = t.discriminator;
-        d.pre_table = prepass_table(ds);
-        d.pre_flags = prepass_flags(ds);
-    }
+// ---------------------------------------------------------------- the accumulation entries
+// What they check and fill is statmc_accumulate_args.h's, each rule stated once.  One body per family -- film-major (here), tile-fed
+// and records (below) -- takes a call with its optional arguments, looks at the device once, runs every check, fills the argument
+// block and launches.  What an entry has always refused ahead of the device (the comment above it) it still does, in that order.
+static statmc::Msg why() { return statmc::Msg{g_err, sizeof(g_err)}; }
+#define ARG_TRY(check) do { if (!(check)) return STATMC_ERR_INVALID; } while (0)
+
+// the pre-pass epilogue's table and flags as a context: the counted and records entries' own, and statmc_get_prepass_context's
+// for device code outside the library (include/statmc_device_api.hpp: PixelStats::store with a context)
+static int prepass_context(const DeviceState &ds, statmc_prepass_context &ctx) {
+    const float *table = statmc::t_table_device_ptr(prepass_table(ds));
+    if (!table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
+    ctx = statmc_prepass_context{table, prepass_flags(ds), 0};
     return STATMC_OK;
 }
-
-// what the epilogue of fill_stat_type hands the accumulation kernel, for device code outside the library
-// (include/statmc_device_api.hpp: PixelStats::store with a context)
 int statmc_get_prepass_context(statmc_prepass_context *out) {
     if (!out) return fail(STATMC_ERR_INVALID, "null context");
     NEED_READY();
-    const float *table = statmc::t_table_device_ptr(prepass_table(dstate));
-    if (!table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
-    out->t_table = table;
-    out->flags = prepass_flags(dstate);
-    out->reserved = 0;
+    return prepass_context(dstate, *out);
+}
+
+static void accumulate_knobs(const DeviceState &d, statmc::AccumulateArgs &k) {   // the A/B switches (include/statmc_debug.h)
+    k.resident_blocks = d.acc_resident_blocks;
+    k.cus = d.cus;
+    k.umul = d.acc_umul;
+    k.dma = d.acc_dma;
+    k.grid_mode = d.acc_grid_mode;
+    k.dma_first = d.acc_dma_first;
+    k.fused = d.acc_fused;   // (k.occ: unused, 0)
+}
+static int accumulate_film(statmc::FilmCall c) {
+    int32_t whole[2];
+    if (c.counts) g_last_acc_counted = 0;   // a call with counts resets the counted report whatever becomes of it
+    if (c.whole_film_default) ARG_TRY(statmc::default_row_ranges(c, whole, why()));
+    ARG_TRY(statmc::check_ahead_of_device(c, &c.n_ranges, nullptr, why()));
+    NEED_READY();
+    if (c.width == 0 || c.height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    ARG_TRY(statmc::check_type_limit(c.n_types, &c.n_ranges, why()));
+    if (c.n_types == 0 || c.n_ranges == 0) return STATMC_OK;
+    if (!c.types || !c.ranges) return fail(STATMC_ERR_INVALID, "null types or ranges");
+    ARG_TRY(statmc::check_sample_arenas(c, why()));
+    g_last_acc_counted = 0;
+    if (!c.counts) {
+        statmc::AccumulateArgs k;
+        memset(&k, 0, sizeof(k));
+        ARG_TRY(statmc::fill_row_range_entries(k, prepass_table(dstate), prepass_flags(dstate), c, nullptr, why()));
+        if (k.n_types == 0) return STATMC_OK;
+        accumulate_knobs(dstate, k);
+        // every type's samples in a STREAM block and its moments in a STATE block of the placed allocator: apart by construction
+        k.apart = 1;
+        for (int i = 0; i < k.n_types && k.apart; i++)
+            k.apart = statmc::placement_role_of(k.t[i].samples) == STATMC_MEM_STREAM && statmc::placement_role_of(k.t[i].mean) == STATMC_MEM_STATE;
+        HIP_TRY(statmc::launch_accumulate(k, S(c.stream)));
+        return STATMC_OK;
+    }
+    statmc::AccumulateCountedArgs k;   // every pixel has its own sample count (kernels: statmc_counted.hip)
+    memset(&k, 0, sizeof(k));
+    ARG_TRY(statmc::fill_row_range_entries(k, prepass_table(dstate), prepass_flags(dstate), c, k.counts, why()));
+    if (k.n_types == 0) return STATMC_OK;
+    if (int rc = prepass_context(dstate, k.ctx)) return rc;
+    int path = 0;
+    HIP_TRY(statmc::launch_accumulate_counted(k, S(c.stream), &path));
+    g_last_acc_counted = path;
     return STATMC_OK;
 }
 
+// Ahead of the device: nothing (no ranges: the whole film).
 int statmc_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, void *stream) {
-    return statmc_accumulate_rows(width, height, types, n_types, 0, height, stream);
+    return accumulate_film(statmc::FilmCall{{width, height, types, n_types, nullptr, nullptr, stream}, nullptr, 0, true});
 }
-// Rows [y0, y1) of the film only (per-pixel work: any split into row ranges leaves the same bits).  The multi-GPU step
-// accumulates the r rows next to a neighbour first, hands them to the halo exchange and accumulates the rest while the
-// exchange runs (statmc_amd/pipeline.py).
+// Rows [y0, y1) of the film only: the multi-GPU step accumulates the rows next to a neighbour first and the rest while the halo
+// exchange runs (statmc_amd/pipeline.py).  Ahead of the device: nothing.
 int statmc_accumulate_rows(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, int y0, int y1, void *stream) {
     const int32_t range[2] = {y0, y1};
-    return statmc_accumulate_row_ranges(width, height, types, n_types, range, 1, stream);
+    return accumulate_film(statmc::FilmCall{{width, height, types, n_types, nullptr, nullptr, stream}, range, 1, false});
 }
-// Several disjoint row ranges in ONE launch (the two border strips of a block: a 20-row launch on its own is bound by the
-// latency of its few waves, two of them together cost what one costs).
-static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
-                                      const int32_t *ranges, int n_ranges, void *stream);
+// Several disjoint row ranges in ONE launch (a block's two border strips cost what one costs).  Ahead of the device: nothing.
 int statmc_accumulate_row_ranges(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *ranges,
                                  int n_ranges, void *stream) {
-    return accumulate_row_ranges_impl(width, height, types, nullptr, n_types, ranges, n_ranges, stream);
+    return accumulate_film(statmc::FilmCall{{width, height, types, n_types, nullptr, nullptr, stream}, ranges, n_ranges, false});
 }
-// Samples in the format the renderer holds them in.  Everything that can be refused is refused before the device is looked at.
+// Samples in the format the renderer holds them in.  Ahead of the device: the row-range default; with formats the limit and the
+// format values; with a half arena also null types and odd arenas.
 int statmc_accumulate_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
                               const int32_t *ranges, int n_ranges, void *stream) {
-    const int32_t whole[2] = {0, height};
-    if (!ranges || n_ranges == 0) {
-        if (n_ranges != 0) return fail(STATMC_ERR_INVALID, "n_ranges = %d without ranges", n_ranges);
-        ranges = whole;
-        n_ranges = 1;
-    }
-    if (!sample_formats) return statmc_accumulate_row_ranges(width, height, types, n_types, ranges, n_ranges, stream);   // the existing call
-    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "n_types x row ranges must be in [0,%d]", statmc::kMaxStatTypes);
-    bool any_half = false;
-    for (int i = 0; i < n_types; i++) {
-        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
-            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
-        any_half = any_half || sample_formats[i] == STATMC_SAMPLES_F16;
-    }
-    if (!any_half) return statmc_accumulate_row_ranges(width, height, types, n_types, ranges, n_ranges, stream);        // the existing call
-    if (!types) return fail(STATMC_ERR_INVALID, "null types");
-    for (int i = 0; i < n_types; i++)
-        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
-            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
-    return accumulate_row_ranges_impl(width, height, types, sample_formats, n_types, ranges, n_ranges, stream);
+    return accumulate_film(statmc::FilmCall{{width, height, types, n_types, sample_formats, nullptr, stream}, ranges, n_ranges, true});
 }
-// The entries of a film-major launch: one per (row range, stat type), every pointer advanced to the range's first row.  Validates
-// the ranges and the types; counts (statmc_accumulate_counted, else NULL): the film's count image, advanced likewise.
-static int fill_row_range_entries(const DeviceState &ds, uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats,
-                                  int n_types, const int32_t *ranges, int n_ranges, statmc::AccumulateType *out, int &n_out, int &half_mask,
-                                  const int32_t *counts, const int32_t **counts_out) {
-    n_out = 0;
-    half_mask = 0;
-    for (int r = 0; r < n_ranges; r++) {
-        const int y0 = ranges[2 * r], y1 = ranges[2 * r + 1];
-        if (y0 < 0 || y1 > height || y0 > y1) return fail(STATMC_ERR_INVALID, "rows [%d,%d) outside the %d-row image", y0, y1, (int)height);
-        for (int q = 0; q < r; q++)
-            if (y0 < ranges[2 * q + 1] && ranges[2 * q] < y1) return fail(STATMC_ERR_INVALID, "row ranges %d and %d overlap", q, r);
-        if (y0 == y1) continue;
-        for (int i = 0; i < n_types; i++) {
-            statmc::AccumulateType &d = out[n_out];
-            if (int rc = fill_stat_type(ds, types[i], i, width, height, true, d)) return rc;
-            const long long px0 = (long long)y0 * width, e0 = px0 * d.channels;
-            const bool half = formats && formats[i] == STATMC_SAMPLES_F16;
-            if (d.samples) d.samples = half ? reinterpret_cast<const float *>(reinterpret_cast<const uint16_t *>(d.samples) + e0) : d.samples + e0;
-            if (half) half_mask |= 1 << n_out;
-            d.n += px0;
-            d.mean += e0;
-            if (d.m2) d.m2 += e0;
-            if (d.m3) d.m3 += e0;
-            if (d.film_mean) d.film_mean += e0;
-            if (d.film_m2) d.film_m2 += e0;
-            if (d.mean_corr) { d.mean_corr += e0; d.disc += e0; }
-            d.n_elems = (long long)(y1 - y0) * width * d.channels;   // d.stride stays the whole film's plane
-            if (counts_out) counts_out[n_out] = counts + px0;
-            n_out++;
-        }
-    }
-    return STATMC_OK;
-}
-static int accumulate_row_ranges_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
-                                      const int32_t *ranges, int n_ranges, void *stream) {
-    NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "stat types x row ranges must be in [0,%d]", statmc::kMaxStatTypes);
-    if (n_types == 0 || n_ranges == 0) return STATMC_OK;
-    if (!types || !ranges) return fail(STATMC_ERR_INVALID, "null types or ranges");
-    g_last_acc_counted = 0;
-    statmc::AccumulateArgs k;
-    memset(&k, 0, sizeof(k));
-    if (int rc = fill_row_range_entries(dstate, width, height, types, formats, n_types, ranges, n_ranges, k.t, k.n_types, k.half_mask, nullptr, nullptr)) return rc;
-    if (k.n_types == 0) return STATMC_OK;
-    k.resident_blocks = dstate.acc_resident_blocks;
-    k.cus = dstate.cus;
-    k.umul = dstate.acc_umul;
-    k.dma = dstate.acc_dma;
-    k.grid_mode = dstate.acc_grid_mode;
-    k.dma_first = dstate.acc_dma_first;
-    k.fused = dstate.acc_fused;
-    k.occ = 0;   // (unused)
-    // every type's samples in a STREAM block and its moments in a STATE block of the placed allocator: apart by construction
-    k.apart = 1;
-    for (int i = 0; i < k.n_types && k.apart; i++)
-        k.apart = statmc::placement_role_of(k.t[i].samples) == STATMC_MEM_STREAM && statmc::placement_role_of(k.t[i].mean) == STATMC_MEM_STATE;
-    HIP_TRY(statmc::launch_accumulate(k, S(stream)));
-    return STATMC_OK;
+// ... and every pixel with its own sample count.  Ahead of the device, with counts: the counted report's reset, the row-range
+// default, the limit, the counts' alignment, the format values, null types, odd arenas.  Without counts: as above.
+int statmc_accumulate_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                              const int32_t *sample_counts, const int32_t *ranges, int n_ranges, void *stream) {
+    return accumulate_film(statmc::FilmCall{{width, height, types, n_types, sample_formats, sample_counts, stream}, ranges, n_ranges, true});
 }
 
 // statmc_combine_statistics: validation (include/statmc.h) and the entry order of the launch -- entries that borrow counts
@@ -1486,255 +1414,126 @@ int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_ma
     return STATMC_OK;
 }
 
-static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
-                                 const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream);
-int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
-                            const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples,
-                            int n_tiles, void *stream) {
-    return accumulate_tiles_impl(width, height, types, nullptr, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
+static void tiles_knobs(const DeviceState &d, statmc::AccumulateTilesArgs &k) {   // the A/B switches (include/statmc_debug.h)
+    k.dma = d.acc_dma;
+    k.umul = d.tiles_umul;
+    k.order = d.tiles_order;
+    k.wg_per_cu = d.tiles_wg_per_cu;
+    k.dma_first = d.acc_dma_first;
 }
-// The tile arenas in the format the renderer holds them in.  As statmc_accumulate_formats: what can be refused is refused before
-// the device is looked at, and a call without a half arena is the existing call.
-int statmc_accumulate_tiles_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
-                                    const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples,
-                                    int n_tiles, void *stream) {
-    if (!sample_formats) return statmc_accumulate_tiles(width, height, types, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);   // the existing call
-    if (n_types < 0 || n_types > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
-    bool any_half = false;
-    for (int i = 0; i < n_types; i++) {
-        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
-            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
-        any_half = any_half || sample_formats[i] == STATMC_SAMPLES_F16;
-    }
-    if (!any_half) return statmc_accumulate_tiles(width, height, types, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);        // the existing call
-    if (!types) return fail(STATMC_ERR_INVALID, "null types");
-    for (int i = 0; i < n_types; i++)
-        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
-            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
-    return accumulate_tiles_impl(width, height, types, sample_formats, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
-}
-static int accumulate_tiles_impl(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *formats, int n_types,
-                                 const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream) {
+static int accumulate_tiles(const statmc::TilesCall &c) {
+    if (c.counts) g_last_acc_counted = 0;   // as accumulate_film
+    ARG_TRY(statmc::check_ahead_of_device(c, nullptr, &c.n_tiles, why()));
     NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types < 0 || n_types > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
-    if (n_tiles < 0) return fail(STATMC_ERR_INVALID, "negative tile count");
-    if (n_types == 0 || n_tiles == 0) return STATMC_OK;
-    if (!types || !tile_bounds || !tile_offsets || !tile_samples) return fail(STATMC_ERR_INVALID, "null pointer");
+    if (c.width == 0 || c.height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    ARG_TRY(statmc::check_type_limit(c.n_types, nullptr, why()));
+    ARG_TRY(statmc::check_n_tiles(c.n_tiles, why()));
+    if (c.n_types == 0 || c.n_tiles == 0) return STATMC_OK;
+    if (!c.types || !c.tile_bounds || !c.tile_offsets || !c.tile_samples) return fail(STATMC_ERR_INVALID, "null pointer");
+    ARG_TRY(statmc::check_sample_arenas(c, why()));
     g_last_acc_counted = 0;
-    statmc::AccumulateTilesArgs k;
-    memset(&k, 0, sizeof(k));
-    k.n_types = n_types;
-    for (int i = 0; i < n_types; i++)
-        if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, k.t[i])) return rc;
-    for (int i = 0; formats && i < n_types; i++)
-        if (formats[i] == STATMC_SAMPLES_F16) k.half_mask |= 1 << i;
-    k.tile_bounds = tile_bounds;
-    k.tile_offsets = reinterpret_cast<const long long *>(tile_offsets);
-    k.tile_samples = tile_samples;
-    k.n_tiles = n_tiles;
-    k.width = width;
-    k.height = height;
-    k.dma = dstate.acc_dma;
-    k.umul = dstate.tiles_umul;
-    k.order = dstate.tiles_order;
-    k.wg_per_cu = dstate.tiles_wg_per_cu;
-    k.dma_first = dstate.acc_dma_first;
-    HIP_TRY(statmc::launch_accumulate_tiles(k, S(stream)));
-    return STATMC_OK;
-}
-
-// Arenas in which every pixel has its own sample count (include/statmc.h; kernels: statmc_counted.hip).  What can be refused
-// without a device is refused first, in the order of the uncounted entries; then the device, then the descriptors.
-static int check_counted_formats(const statmc_stat_type *types, const int32_t *sample_formats, int n_types, const int32_t *sample_counts) {
-    if (reinterpret_cast<uintptr_t>(sample_counts) & 3) return fail(STATMC_ERR_INVALID, "sample_counts is not 4-byte aligned");
-    for (int i = 0; sample_formats && i < n_types; i++)
-        if (sample_formats[i] != STATMC_SAMPLES_F32 && sample_formats[i] != STATMC_SAMPLES_F16)
-            return fail(STATMC_ERR_INVALID, "sample_formats[%d] = %d: STATMC_SAMPLES_F32 (0) or STATMC_SAMPLES_F16 (1)", i, (int)sample_formats[i]);
-    if (n_types > 0 && !types) return fail(STATMC_ERR_INVALID, "null types");
-    for (int i = 0; sample_formats && i < n_types; i++)
-        if (sample_formats[i] == STATMC_SAMPLES_F16 && (reinterpret_cast<uintptr_t>(types[i].samples) & 1))
-            return fail(STATMC_ERR_INVALID, "types[%d]: a 16-bit sample arena at an odd address", i);
-    return STATMC_OK;
-}
-static int counted_context(const DeviceState &ds, statmc_prepass_context &ctx) {
-    ctx.t_table = statmc::t_table_device_ptr(prepass_table(ds));
-    if (!ctx.t_table) return fail(STATMC_ERR_HIP, "the quantile tables of the current device cannot be located");
-    ctx.flags = prepass_flags(ds);
-    ctx.reserved = 0;
-    return STATMC_OK;
-}
-int statmc_accumulate_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
-                              const int32_t *sample_counts, const int32_t *ranges, int n_ranges, void *stream) {
-    if (!sample_counts) return statmc_accumulate_formats(width, height, types, sample_formats, n_types, ranges, n_ranges, stream);   // the existing call
-    g_last_acc_counted = 0;
-    const int32_t whole[2] = {0, height};
-    if (!ranges || n_ranges == 0) {
-        if (n_ranges != 0) return fail(STATMC_ERR_INVALID, "n_ranges = %d without ranges", n_ranges);
-        ranges = whole;
-        n_ranges = 1;
+    if (!c.counts) {
+        statmc::AccumulateTilesArgs k;
+        memset(&k, 0, sizeof(k));
+        ARG_TRY(statmc::fill_tiles_args(k, prepass_table(dstate), prepass_flags(dstate), c, why()));
+        tiles_knobs(dstate, k);
+        HIP_TRY(statmc::launch_accumulate_tiles(k, S(c.stream)));
+        return STATMC_OK;
     }
-    if (n_types < 0 || n_ranges < 0 || (long long)n_types * n_ranges > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "n_types x row ranges (n_ranges) must be in [0,%d]", statmc::kMaxStatTypes);
-    if (int rc = check_counted_formats(types, sample_formats, n_types, sample_counts)) return rc;
-    NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types == 0) return STATMC_OK;
-    statmc::AccumulateCountedArgs k;
+    statmc::AccumulateTilesCountedArgs k;   // every pixel has its own sample count (kernels: statmc_counted.hip)
     memset(&k, 0, sizeof(k));
-    if (int rc = fill_row_range_entries(dstate, width, height, types, sample_formats, n_types, ranges, n_ranges, k.t, k.n_types, k.half_mask, sample_counts, k.counts))
-        return rc;
-    int live = 0, live_half = 0;       // (an entry without samples folds nothing: it is not launched)
-    for (int i = 0; i < k.n_types; i++) {
-        if (k.t[i].n_samples == 0) continue;
-        k.t[live] = k.t[i];
-        k.counts[live] = k.counts[i];
-        live_half |= ((k.half_mask >> i) & 1) << live;
-        live++;
-    }
-    k.n_types = live;
-    k.half_mask = live_half;
-    if (k.n_types == 0) return STATMC_OK;
-    if (int rc = counted_context(dstate, k.ctx)) return rc;
+    ARG_TRY(statmc::fill_tiles_args(k, prepass_table(dstate), prepass_flags(dstate), c, why()));
+    if (int rc = prepass_context(dstate, k.ctx)) return rc;
+    k.counts = c.counts;
     int path = 0;
-    HIP_TRY(statmc::launch_accumulate_counted(k, S(stream), &path));
+    HIP_TRY(statmc::launch_accumulate_tiles_counted(k, S(c.stream), &path));
     g_last_acc_counted = path;
     return STATMC_OK;
 }
+// Ahead of the device: nothing.
+int statmc_accumulate_tiles(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *tile_bounds,
+                            const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream) {
+    return accumulate_tiles(statmc::TilesCall{{width, height, types, n_types, nullptr, nullptr, stream}, tile_bounds, tile_offsets, tile_samples, n_tiles});
+}
+// The tile arenas in the format the renderer holds them in.  Ahead of the device: with formats the limit and the format values;
+// with a half arena also null types and odd arenas.
+int statmc_accumulate_tiles_formats(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                                    const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles, void *stream) {
+    return accumulate_tiles(statmc::TilesCall{{width, height, types, n_types, sample_formats, nullptr, stream}, tile_bounds, tile_offsets, tile_samples, n_tiles});
+}
+// ... and every pixel with its own sample count.  Ahead of the device, with counts: the counted report's reset, the limit, n_tiles,
+// the counts' alignment, the format values, null types, odd arenas.  Without counts: as above.
 int statmc_accumulate_tiles_counted(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
                                     const int32_t *tile_bounds, const int64_t *tile_offsets, const int32_t *tile_samples, int n_tiles,
                                     const int32_t *sample_counts, void *stream) {
-    if (!sample_counts)      // the existing call
-        return statmc_accumulate_tiles_formats(width, height, types, sample_formats, n_types, tile_bounds, tile_offsets, tile_samples, n_tiles, stream);
-    g_last_acc_counted = 0;
-    if (n_types < 0 || n_types > statmc::kMaxStatTypes) return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
-    if (n_tiles < 0) return fail(STATMC_ERR_INVALID, "negative tile count (n_tiles)");
-    if (int rc = check_counted_formats(types, sample_formats, n_types, sample_counts)) return rc;
-    NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types == 0 || n_tiles == 0) return STATMC_OK;
-    if (!tile_bounds || !tile_offsets || !tile_samples) return fail(STATMC_ERR_INVALID, "null pointer");
-    statmc::AccumulateTilesCountedArgs k;
-    memset(&k, 0, sizeof(k));
-    k.n_types = n_types;
-    for (int i = 0; i < n_types; i++) {
-        if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, k.t[i])) return rc;
-        if (sample_formats && sample_formats[i] == STATMC_SAMPLES_F16) k.half_mask |= 1 << i;
-    }
-    if (int rc = counted_context(dstate, k.ctx)) return rc;
-    k.counts = sample_counts;
-    k.tile_bounds = tile_bounds;
-    k.tile_offsets = reinterpret_cast<const long long *>(tile_offsets);
-    k.tile_samples = tile_samples;
-    k.n_tiles = n_tiles;
-    k.width = width;
-    k.height = height;
-    int path = 0;
-    HIP_TRY(statmc::launch_accumulate_tiles_counted(k, S(stream), &path));
-    g_last_acc_counted = path;
-    return STATMC_OK;
+    return accumulate_tiles(statmc::TilesCall{{width, height, types, n_types, sample_formats, sample_counts, stream}, tile_bounds, tile_offsets, tile_samples, n_tiles});
 }
 int statmc_debug_last_accumulate_counted(void) { return g_last_acc_counted; }
 
-// Samples as unordered (pixel, sample) records (include/statmc.h; kernels and the scheme: statmc_records.hip).
-// split_above: 0 = statmc_accumulate_records; otherwise statmc_accumulate_records_split's argument, checked here
-static int accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels, int64_t n_records,
-                              bool split, int32_t split_above, void *stream) {
-    // the limits first: an argument error is reported whether or not a device has been set up
-    if (n_types < 0 || n_types > statmc::kMaxStatTypes)
-        return fail(STATMC_ERR_INVALID, "n_types must be in [0,%d]", statmc::kMaxStatTypes);
-    if (n_records < 0 || n_records > (int64_t)INT32_MAX) return fail(STATMC_ERR_INVALID, "n_records must be in [0, 2^31)");
-    char why_split[96];
-    if (split && !statmc::check_records_split_above(split_above, why_split, sizeof(why_split))) return fail(STATMC_ERR_INVALID, "%s", why_split);
-    NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types == 0 || n_records == 0) return STATMC_OK;
-    if (!types || !pixels) return fail(STATMC_ERR_INVALID, "null types or pixels");
-    statmc::RecordsArgs k;
-    memset(&k, 0, sizeof(k));
-    k.n_types = n_types;
-    k.n_records = n_records;
-    k.n_px = (long long)width * height;
-    bool epilogue = false;
-    for (int i = 0; i < n_types; i++) {
-        statmc::AccumulateType checked;   // the validation of every accumulate entry; n_samples is ignored here
-        if (int rc = fill_stat_type(dstate, types[i], i, width, height, false, checked)) return rc;
-        k.t[i] = types[i];
-        k.t[i].transform = types[i].transform ? 1 : 0;
-        epilogue = epilogue || types[i].mean_corr != nullptr;
+// Unordered (pixel, sample) records (kernels and the scheme: statmc_records.hip; interleaved layouts and which fold runs:
+// statmc_records_plan.h).  Never touches what statmc_debug_last_accumulate_counted reports.
+static int accumulate_records(const statmc::RecordsCall &c) {
+    // the limits, the layout and split_above first: an argument error is reported whether or not a device has been set up
+    if (c.interleaved) {
+        g_last_rec_ilv_path = 0;
+        ARG_TRY(statmc::check_records_interleaved(c.types, c.n_types, c.records, c.layout, c.n_records, g_err, sizeof(g_err)));
+    } else {
+        ARG_TRY(statmc::check_type_limit(c.n_types, nullptr, why()));
+        if (c.n_records < 0 || c.n_records > (int64_t)INT32_MAX) return fail(STATMC_ERR_INVALID, "n_records must be in [0, 2^31)");
     }
-    if (epilogue)
-        if (int rc = statmc_get_prepass_context(&k.ctx)) return rc;
-    statmc::RecordsWorkspace w;
-    HIP_TRY(statmc::records_workspace_layout(k.n_records, k.n_px, w));
-    char *ws = nullptr;
-    if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
-    HIP_TRY(statmc::launch_accumulate_records(k, pixels, w, ws, dstate.rec_phases, split ? split_above : 0, S(stream)));
-    return STATMC_OK;
-}
-int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
-                              int64_t n_records, void *stream) {
-    return accumulate_records(width, height, types, n_types, pixels, n_records, false, 0, stream);
-}
-// ... with a pixel's run of more than split_above records folded by the 64 lanes of a wave (include/statmc.h)
-int statmc_accumulate_records_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
-                                    int64_t n_records, int32_t split_above, void *stream) {
-    return accumulate_records(width, height, types, n_types, pixels, n_records, true, split_above, stream);
-}
-
-// The same queue as interleaved records (include/statmc.h; what is valid and which fold runs: statmc_records_plan.h).
-static int accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
-                                          const statmc_record_layout *layout, int64_t n_records, bool split, int32_t split_above, void *stream) {
-    // the limits and the layout first: an argument error is reported whether or not a device has been set up
-    g_last_rec_ilv_path = 0;
-    char why[256];
-    if (!statmc::check_records_interleaved(types, n_types, records, layout, n_records, why, sizeof(why))) return fail(STATMC_ERR_INVALID, "%s", why);
-    if (split && !statmc::check_records_split_above(split_above, why, sizeof(why))) return fail(STATMC_ERR_INVALID, "%s", why);
+    if (c.split_above) ARG_TRY(statmc::check_records_split_above(*c.split_above, g_err, sizeof(g_err)));
     NEED_READY();
-    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
-    if (n_types == 0 || n_records == 0) return STATMC_OK;
-    if (!records) return fail(STATMC_ERR_INVALID, "null records");
+    if (c.width == 0 || c.height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (c.n_types == 0 || c.n_records == 0) return STATMC_OK;
+    if (c.interleaved ? !c.records : (!c.types || !c.pixels)) return fail(STATMC_ERR_INVALID, c.interleaved ? "null records" : "null types or pixels");
+    const int split = c.split_above ? *c.split_above : 0;
+    bool epilogue = false;
+    statmc::RecordsWorkspace w;
+    char *ws = nullptr;
+    if (!c.interleaved) {
+        statmc::RecordsArgs k;
+        memset(&k, 0, sizeof(k));
+        ARG_TRY(statmc::fill_records_args(k, c, epilogue, why()));
+        if (int rc = epilogue ? prepass_context(dstate, k.ctx) : STATMC_OK) return rc;
+        HIP_TRY(statmc::records_workspace_layout(k.n_records, k.n_px, w));
+        if (int rc = records_workspace(w.bytes, c.stream, &ws)) return rc;
+        HIP_TRY(statmc::launch_accumulate_records(k, c.pixels, w, ws, dstate.rec_phases, split, S(c.stream)));
+        return STATMC_OK;
+    }
     statmc::RecordsInterleavedArgs k;
     memset(&k, 0, sizeof(k));
-    k.n_types = n_types;
-    k.n_records = n_records;
-    k.n_px = (long long)width * height;
-    k.records = static_cast<const char *>(records);
-    k.stride = layout->stride;
-    k.pixel_off = layout->pixel_offset;
-    bool epilogue = false;
-    for (int i = 0; i < n_types; i++) {
-        statmc::AccumulateType checked;   // the validation of every accumulate entry; samples and n_samples are ignored here
-        statmc_stat_type t = types[i];
-        t.samples = static_cast<const float *>(records);
-        if (int rc = fill_stat_type(dstate, t, i, width, height, false, checked)) return rc;
-        k.t[i] = t;
-        k.t[i].samples = nullptr;
-        k.t[i].transform = t.transform ? 1 : 0;
-        k.off[i] = layout->sample_offset[i];
-        if (layout->sample_format[i] == STATMC_SAMPLES_F16) k.half_mask |= 1u << i;
-        epilogue = epilogue || t.mean_corr != nullptr;
+    ARG_TRY(statmc::fill_records_args(k, c, epilogue, why()));
+    if (int rc = epilogue ? prepass_context(dstate, k.ctx) : STATMC_OK) return rc;
+    k.records = static_cast<const char *>(c.records);
+    k.stride = c.layout->stride;
+    k.pixel_off = c.layout->pixel_offset;
+    for (int i = 0; i < c.n_types; i++) {
+        k.off[i] = c.layout->sample_offset[i];
+        if (c.layout->sample_format[i] == STATMC_SAMPLES_F16) k.half_mask |= 1u << i;
     }
-    if (epilogue)
-        if (int rc = statmc_get_prepass_context(&k.ctx)) return rc;
-    const statmc::RecordsInterleavedPlan plan = statmc::plan_records_interleaved(k.t, n_types, *layout, dstate.rec_ilv_path);
-    statmc::RecordsWorkspace w;
+    const statmc::RecordsInterleavedPlan plan = statmc::plan_records_interleaved(k.t, c.n_types, *c.layout, dstate.rec_ilv_path);
     HIP_TRY(statmc::records_interleaved_workspace_layout(k.n_records, k.n_px, w));
-    char *ws = nullptr;
-    if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
-    HIP_TRY(statmc::launch_accumulate_records_interleaved(k, plan, w, ws, dstate.rec_phases, split ? split_above : 0, S(stream)));
+    if (int rc = records_workspace(w.bytes, c.stream, &ws)) return rc;
+    HIP_TRY(statmc::launch_accumulate_records_interleaved(k, plan, w, ws, dstate.rec_phases, split, S(c.stream)));
     g_last_rec_ilv_path = plan.path;
     return STATMC_OK;
 }
+// Ahead of the device, all four: the limit and n_records (interleaved: every rule of check_records_interleaved), then split_above.
+int statmc_accumulate_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
+                              int64_t n_records, void *stream) {
+    return accumulate_records(statmc::RecordsCall{width, height, types, n_types, pixels, nullptr, nullptr, false, n_records, nullptr, stream});
+}
+int statmc_accumulate_records_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels,
+                                    int64_t n_records, int32_t split_above, void *stream) {
+    return accumulate_records(statmc::RecordsCall{width, height, types, n_types, pixels, nullptr, nullptr, false, n_records, &split_above, stream});
+}
 int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
                                           const statmc_record_layout *layout, int64_t n_records, void *stream) {
-    return accumulate_records_interleaved(width, height, types, n_types, records, layout, n_records, false, 0, stream);
+    return accumulate_records(statmc::RecordsCall{width, height, types, n_types, nullptr, records, layout, true, n_records, nullptr, stream});
 }
 int statmc_accumulate_records_interleaved_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
                                                 const statmc_record_layout *layout, int64_t n_records, int32_t split_above, void *stream) {
-    return accumulate_records_interleaved(width, height, types, n_types, records, layout, n_records, true, split_above, stream);
+    return accumulate_records(statmc::RecordsCall{width, height, types, n_types, nullptr, records, layout, true, n_records, &split_above, stream});
 }
 
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,

@@ -736,6 +736,55 @@ typedef struct statmc_combine_many_entry {
 int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_many_entry *entries, int n_entries,
                         int n_sources, void *stream);
 
+/* ---- pooling k x k blocks of pixels into a coarser film (no counterpart in the reference): the statistics of the samples of
+ * NEIGHBOURING pixels put together, where the two calls above put together samples of the same pixel.  k is 2, 4 or 8.  The fine
+ * film (src) has width x height pixels, the coarse one (dst) Wc x Hc with Wc = ceil(width / k), Hc = ceil(height / k); both are
+ * packed planes like every image of this header.
+ * DEFINITION.  Coarse pixel (X, Y) has k * k slots.  Slot j holds the state of fine pixel (k X + dx, k Y + dy) with
+ * j = Morton(dx, dy): bit i of dx is bit 2 i of j, bit i of dy is bit 2 i + 1 (k = 2: slots 0 .. 3 are (0,0) (1,0) (0,1) (1,1)).
+ * A slot whose fine pixel lies outside the film holds the state of no samples (n = 0, every field 0).  The coarse state is the
+ * balanced tree of statmc::device::merge_lanes (include/statmc_device_api.hpp) over those slots:
+ *     for stride = 1, 2, 4, ... < k * k:
+ *         for every slot j with j % (2 stride) == 0:   slot[j].merge(slot[j + stride])        (A = slot j, B = slot j + stride)
+ * with slot 0's result stored.  Through the other entries: the result is, bit for bit, what k * k part states of size Wc x Hc --
+ * part j holding slot j of every coarse pixel -- give when combined by two-part statmc_combine_statistics calls in exactly that
+ * order (dst = part j, src = part j + stride).  Every rule of that call holds per merge: nB == 0 keeps A's bits, otherwise
+ * nA == 0 takes B's, n is the integer sum; counts must sum below 2^24 per block, which is not checked.  Hence:
+ *   - dst.n is the sum of the block's counts;
+ *   - a block with one live pixel is a bit copy of that pixel's state, wherever in the block it lies;
+ *   - a block without a live sample keeps the bits of its slot 0, fine pixel (k X, k Y), which always lies inside the film;
+ *   - the slots are in Morton order, so the tree's levels alternate pairs along x and pairs along y, and pooling by 2 and
+ *     pooling the result by 2 again IS the tree of pooling by 4: pool_a(pool_b(film)) == pool_ab(film) bit for bit for
+ *     a b <= 8, partial blocks at the right and bottom edge included.  A pyramid holds the same bits whichever way it was built
+ *     (a row-major slot order would not give this);
+ *   - it is NOT the left fold in slot order that statmc_combine_many computes from the same parts: fp32 addition is not
+ *     associative, and the two orders differ in the last bits.
+ * Each entry reuses statmc_stat_type for both sides as statmc_combine_entry does: channels and max_moment pick the planes and
+ * must agree; film_mean / film_m2 are pooled when non-NULL and not the same pointers as mean / m2, and dst and src agree on which
+ * of them they have; samples, n_samples and transform are ignored, as are src.mean_corr / src.discriminator.  dst is WRITTEN:
+ * what it held is not read.  count_of = -1: the entry owns src.n and dst.n.  count_of = q >= 0: every merge of the entry is
+ * weighed with entry q's counts of the same two sub-trees (the slots' counts are read from entry q's src.n); dst.n and src.n are
+ * NULL and entry q has count_of = -1 -- the "film" RGB image and the G-buffer means of a dump without counts, as for
+ * statmc_combine_statistics.  dst.mean_corr / dst.discriminator (both or neither; max_moment 3 and own counts): the epilogue
+ * writes the pre-pass of the pooled moments under the device's current spec and significance level, the bits statmc_prepass
+ * computes from the pooled images.
+ * One launch serves all entries; n_entries <= 16, n_entries = 0 is a no-op.  Asynchronous on `stream`, nothing is allocated or
+ * read back; both films on the current device.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: k not 2, 4 or 8; a zero width or height;
+ * n_entries outside [0, 16] or NULL entries with n_entries > 0; channels not 1 or 3, max_moment not 1..3; dst and src
+ * disagreeing on channels, max_moment or their film planes; a NULL plane the entry needs; film_m2 without a film_mean of its own;
+ * a broken count_of rule; one of mean_corr / discriminator alone, or either with max_moment < 3 or borrowed counts; the byte range
+ * of any dst plane (coarse size) overlapping that of any src plane (fine size) of any entry; two entries writing the same dst
+ * plane or owning the same dst count image.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 on the 11-channel set plus "film": DESIGN.md 4.2b, profiles/pool_statistics.jsonl. */
+typedef struct statmc_pool_entry {
+    statmc_stat_type dst; /* coarse film, ceil(width/k) x ceil(height/k), WRITTEN: what it held is not read */
+    statmc_stat_type src; /* fine film, width x height, read only */
+    int32_t count_of;     /* as in statmc_combine_entry */
+} statmc_pool_entry;
+
+int statmc_pool_statistics(uint16_t width, uint16_t height, int k, const statmc_pool_entry *entries, int n_entries, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

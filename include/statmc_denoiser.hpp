@@ -1302,7 +1302,103 @@ class Estimator {
                          borrowCounts, true);
     }
 
+    // Pools the statistics of every k x k block of this Estimator's pixels into one pixel of `coarse` (statmc_pool_statistics;
+    // include/statmc.h has the definition: the Morton-ordered tree of two-part combines, k = 2, 4 or 8): a preview film with a
+    // 1 / k^2 of the pixels and k^2 times the samples per pixel, or one level of a statistics pyramid.  `coarse` has
+    // ceil(width / k) x ceil(height / k) pixels, this Estimator's configuration and device, and device images; what its
+    // statistics images and its "film" image held is overwritten.  Every enabled (type, bounce) is pooled with its own counts,
+    // the "film" image with the counts of the first (type, bounce); the types listed in `borrowCounts` take those counts as
+    // well, as for CombineStatistics.  Pending device-accumulation samples are flushed first; the call is ordered behind
+    // everything enqueued on this Estimator's stream and is asynchronous on `coarse`'s.  This Estimator is only read;
+    // coarse.Denoise() and coarse.Download() then work as usual.
+    void PoolStatistics(Estimator &coarse, int k, const std::vector<unsigned char> &borrowCounts = {}) {
+        const auto &a = statTypeConfigs;
+        if (k != 2 && k != 4 && k != 8) throw Error(STATMC_ERR_INVALID, "PoolStatistics: k must be 2, 4 or 8");
+        if (&coarse == this) throw Error(STATMC_ERR_INVALID, "PoolStatistics: an Estimator cannot be pooled into itself");
+        if (!allocateDevice || !coarse.allocateDevice) throw Error(STATMC_ERR_INVALID, "PoolStatistics needs device images");
+        if (coarse.device != device) throw Error(STATMC_ERR_INVALID, "PoolStatistics: both Estimators must be on one device");
+        if (coarse.width != (width + k - 1) / k || coarse.height != (height + k - 1) / k)
+            throw Error(STATMC_ERR_INVALID, "PoolStatistics: the coarse film must have ceil(width / k) x ceil(height / k) pixels");
+        if (!sameConfiguration(coarse)) throw Error(STATMC_ERR_INVALID, "PoolStatistics: the Estimators have different stat type configurations");
+        if (a.nEnabled == 0 || nBuffers.empty() || nBuffers[0].empty() || coarse.nBuffers.empty() || coarse.nBuffers[0].empty())
+            throw Error(STATMC_ERR_INVALID, "PoolStatistics: no statistics (call AllocateBuffers first)");
+        for (unsigned char t : borrowCounts)
+            if (t == 0 || t >= a.nEnabled) throw Error(STATMC_ERR_INVALID, "PoolStatistics: borrowCounts names type " + std::to_string(t));
+        check(statmc_set_device(device));
+        if (acc.enabled) FlushSamples();
+        if (coarse.acc.enabled) coarse.FlushSamples();
+        joinUploads();
+        coarse.joinUploads();
+        if (!combineEvent) {
+            void *ev = nullptr;
+            check(statmc_event_create(&ev));
+            combineEvent.reset(ev, [](void *e) { statmc_event_destroy(e); });
+        }
+        check(statmc_event_record(combineEvent.get(), stream.handle()));
+        check(statmc_stream_wait_event(coarse.stream.handle(), combineEvent.get()));
+        // the owner of the borrowed counts and everything that borrows them go into the first call (count_of is an index of the call)
+        std::vector<statmc_pool_entry> first, rest;
+        auto entry = [&](unsigned char i, unsigned char j, bool own) {
+            statmc_pool_entry e;
+            e.dst = statSide(coarse, i, j, own);
+            e.src = statSide(*this, i, j, own);
+            e.count_of = own ? -1 : 0;
+            return e;
+        };
+        first.push_back(entry(0, 0, true));
+        for (unsigned char i = 0; i < a.nEnabled; i++) {
+            const bool borrow = std::find(borrowCounts.begin(), borrowCounts.end(), i) != borrowCounts.end();
+            for (unsigned char j = 0; j < a[i].nBounces; j++) {
+                if (i == 0 && j == 0) continue;
+                (borrow ? first : rest).push_back(entry(i, j, !borrow));
+            }
+        }
+        if (filmBuffer.gpuMat.data() && coarse.filmBuffer.gpuMat.data()) {   // the colour image: an M1 mean weighted by t0-b0-n
+            statmc_pool_entry e;
+            std::memset(&e, 0, sizeof(e));
+            e.dst.channels = e.src.channels = 3;
+            e.dst.max_moment = e.src.max_moment = 1;
+            e.dst.mean = static_cast<float *>(coarse.filmBuffer.gpuMat.data());
+            e.src.mean = static_cast<float *>(filmBuffer.gpuMat.data());
+            e.count_of = 0;
+            first.push_back(e);
+        }
+        const size_t cap = 16;   // entries per call
+        if (first.size() > cap) throw Error(STATMC_ERR_INVALID, "PoolStatistics: more than 16 images borrow the first type's counts");
+        while (first.size() < cap && !rest.empty()) {
+            first.push_back(rest.back());
+            rest.pop_back();
+        }
+        check(statmc_pool_statistics(width, height, k, first.data(), (int)first.size(), coarse.stream.handle()));
+        for (size_t q = 0; q < rest.size(); q += cap)
+            check(statmc_pool_statistics(width, height, k, rest.data() + q, (int)std::min(cap, rest.size() - q), coarse.stream.handle()));
+    }
+
   private:
+    bool sameConfiguration(const Estimator &other) const {
+        const auto &a = statTypeConfigs, &b = other.statTypeConfigs;
+        bool same = a.nEnabled == b.nEnabled;
+        for (unsigned char i = 0; same && i < a.nEnabled; i++)
+            same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
+                   a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
+        return same;
+    }
+    // one side of a combine or pool entry: the device images of (type i, bounce j) of Estimator e
+    static statmc_stat_type statSide(Estimator &e, unsigned char i, unsigned char j, bool own) {
+        const StatTypeConfig &c = e.statTypeConfigs[i];
+        statmc_stat_type s;
+        std::memset(&s, 0, sizeof(s));
+        s.channels = c.nChannels;
+        s.transform = c.transform;
+        s.max_moment = c.maxMoment;
+        s.n = own ? static_cast<int32_t *>(e.nBuffers[i][j].gpuMat.data()) : nullptr;
+        s.mean = static_cast<float *>(e.meanBuffers[i][j].gpuMat.data());
+        s.m2 = static_cast<float *>(e.m2Buffers[i][j].gpuMat.data());
+        s.m3 = static_cast<float *>(e.m3Buffers[i][j].gpuMat.data());
+        s.film_mean = static_cast<float *>(e.filmBuffers[i][j].gpuMat.data());   // non-transform types: the mean's own storage (combined once)
+        s.film_m2 = static_cast<float *>(e.filmM2Buffers[i][j].gpuMat.data());
+        return s;
+    }
     void combineChecks(const std::vector<Estimator *> &others, const std::vector<unsigned char> &borrowCounts) const {
         const auto &a = statTypeConfigs;
         for (size_t k = 0; k < others.size(); k++) {
@@ -1314,12 +1410,7 @@ class Estimator {
             if (!allocateDevice || !other.allocateDevice) throw Error(STATMC_ERR_INVALID, "CombineStatistics needs device images");
             if (other.device != device) throw Error(STATMC_ERR_INVALID, "CombineStatistics: both Estimators must be on one device");
             if (other.width != width || other.height != height) throw Error(STATMC_ERR_INVALID, "CombineStatistics: film sizes differ");
-            const auto &b = other.statTypeConfigs;
-            bool same = a.nEnabled == b.nEnabled;
-            for (unsigned char i = 0; same && i < a.nEnabled; i++)
-                same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
-                       a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
-            if (!same) throw Error(STATMC_ERR_INVALID, "CombineStatistics: the Estimators have different stat type configurations");
+            if (!sameConfiguration(other)) throw Error(STATMC_ERR_INVALID, "CombineStatistics: the Estimators have different stat type configurations");
         }
         if (a.nEnabled == 0 || nBuffers.empty() || nBuffers[0].empty())
             throw Error(STATMC_ERR_INVALID, "CombineStatistics: no statistics (call AllocateBuffers first)");
@@ -1347,20 +1438,6 @@ class Estimator {
             check(statmc_stream_wait_event(stream.handle(), combineEvent.get()));
         }
 
-        auto side = [](const StatTypeConfig &c, Buffer &n, Buffer &mean, Buffer &m2, Buffer &m3, Buffer &fm, Buffer &fm2, bool own) {
-            statmc_stat_type s;
-            std::memset(&s, 0, sizeof(s));
-            s.channels = c.nChannels;
-            s.transform = c.transform;
-            s.max_moment = c.maxMoment;
-            s.n = own ? static_cast<int32_t *>(n.gpuMat.data()) : nullptr;
-            s.mean = static_cast<float *>(mean.gpuMat.data());
-            s.m2 = static_cast<float *>(m2.gpuMat.data());
-            s.m3 = static_cast<float *>(m3.gpuMat.data());
-            s.film_mean = static_cast<float *>(fm.gpuMat.data());   // non-transform types: the mean's own storage (combined once)
-            s.film_m2 = static_cast<float *>(fm2.gpuMat.data());
-            return s;
-        };
         // an entry: dst, one src per part, count_of.  The owner of the borrowed counts and everything that borrows them go into
         // the first call: a later call would see the counts already summed
         struct Entry {
@@ -1370,12 +1447,9 @@ class Estimator {
         };
         std::vector<Entry> first, rest;
         auto entry = [&](unsigned char i, unsigned char j, bool own) {
-            const StatTypeConfig &c = a[i];
             Entry e;
-            e.dst = side(c, nBuffers[i][j], meanBuffers[i][j], m2Buffers[i][j], m3Buffers[i][j], filmBuffers[i][j], filmM2Buffers[i][j], own);
-            for (Estimator *o : others)
-                e.srcs.push_back(side(c, o->nBuffers[i][j], o->meanBuffers[i][j], o->m2Buffers[i][j], o->m3Buffers[i][j], o->filmBuffers[i][j],
-                                      o->filmM2Buffers[i][j], own));
+            e.dst = statSide(*this, i, j, own);
+            for (Estimator *o : others) e.srcs.push_back(statSide(*o, i, j, own));
             e.count_of = own ? -1 : 0;
             return e;
         };

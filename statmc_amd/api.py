@@ -99,6 +99,11 @@ class CombineManyEntry(C.Structure):
     _fields_ = [("dst", StatType), ("srcs", C.POINTER(StatType)), ("count_of", C.c_int32)]
 
 
+class PoolEntry(C.Structure):
+    """statmc_pool_entry: the coarse film (dst, written) and the fine film (src) of one set of statistics."""
+    _fields_ = [("dst", StatType), ("src", StatType), ("count_of", C.c_int32)]
+
+
 MAX_COMBINE_SOURCES = 15
 
 EXPORTS = [
@@ -109,7 +114,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -207,6 +212,7 @@ def load():
     lib.statmc_get_prepass_context.argtypes = [C.POINTER(PrepassContext)]
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
+    lib.statmc_pool_statistics.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.POINTER(PoolEntry), C.c_int, C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -625,6 +631,34 @@ def combine_many(width, height, entries, n_sources=None, stream=None):
     arr = (CombineManyEntry * max(len(entries), 1))(*entries)
     check(load().statmc_combine_many(int(width), int(height), arr, len(entries), int(n_sources),
                                      stream if stream is not None else current_stream_handle()))
+
+
+def pooled_size(width, height, k):
+    """The coarse film of statmc_pool_statistics: (ceil(width / k), ceil(height / k))."""
+    return -(-int(width) // int(k)), -(-int(height) // int(k))
+
+
+def make_pool_entry(dst, src, channels, max_moment, count_of=-1, prepass_into=None):
+    """One statmc_pool_entry: dst (the coarse film, written) and src (the fine film) are state dicts of device tensors as for
+    make_combine_entry.  count_of = q >= 0: every merge is weighed with entry q's fine counts ("n" is not passed then).
+    prepass_into = (mean_corr, discriminator) of the coarse size: the epilogue writes the pre-pass of the pooled moments there
+    (max_moment 3, own counts)."""
+    e = PoolEntry()
+    own = count_of < 0
+    e.dst = _state_side(dst, channels, max_moment, own)
+    e.src = _state_side(src, channels, max_moment, own)
+    e.count_of = -1 if own else int(count_of)
+    if prepass_into is not None:
+        e.dst.mean_corr, e.dst.discriminator = prepass_into[0].data_ptr(), prepass_into[1].data_ptr()
+    return e
+
+
+def pool_statistics(width, height, k, entries, stream=None):
+    """statmc_pool_statistics: the statistics of every k x k block of the width x height film in every entry's src pooled into
+    one pixel of its dst, in one launch (include/statmc.h: the Morton-ordered tree of two-part combines; k = 2, 4 or 8)."""
+    arr = (PoolEntry * max(len(entries), 1))(*entries)
+    check(load().statmc_pool_statistics(int(width), int(height), int(k), arr, len(entries),
+                                        stream if stream is not None else current_stream_handle()))
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):

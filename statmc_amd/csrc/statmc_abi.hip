@@ -15,6 +15,7 @@
 #include "statmc_device.h"
 #include "statmc_accumulate_args.h"
 #include "statmc_records_plan.h"
+#include "statmc_pool_args.h"
 
 #include <atomic>
 
@@ -1411,6 +1412,23 @@ int statmc_combine_many(uint16_t width, uint16_t height, const statmc_combine_ma
         }
         HIP_TRY(statmc::launch_combine_many(k, S(stream)));
     }
+    return STATMC_OK;
+}
+
+// statmc_pool_statistics: every rule of include/statmc.h ahead of the device (statmc_pool_args.h), then one launch for all entries.
+// Entries that borrow counts read their owner's FINE counts, which no entry writes: the entry order does not matter here.
+int statmc_pool_statistics(uint16_t width, uint16_t height, int k, const statmc_pool_entry *entries, int n_entries, void *stream) {
+    ARG_TRY(statmc::check_pool_call(width, height, k, entries, n_entries, statmc::PoolMsg{g_err, sizeof(g_err)}));
+    if (n_entries == 0) return STATMC_OK;
+    NEED_READY();
+    statmc::PoolArgs a;
+    statmc::fill_pool_args(a, width, height, k, entries, n_entries);
+    for (int i = 0; i < n_entries; i++)
+        if (a.e[i].mean_corr) {
+            if (int rc = prepass_context(dstate, a.ctx)) return rc;
+            break;
+        }
+    HIP_TRY(statmc::launch_pool(a, S(stream)));
     return STATMC_OK;
 }
 

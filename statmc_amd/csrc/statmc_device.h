@@ -206,6 +206,10 @@ hipError_t records_interleaved_workspace_layout(long long n_records, long long n
 hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w, char *ws,
                                                  int phases, int split_above, hipStream_t s);
 
+// statmc_pool_statistics (statmc_pool.hip): the argument block and its checks are statmc_pool_args.h's, a host-only header
+struct PoolArgs;
+hipError_t launch_pool(const PoolArgs &a, hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

@@ -130,6 +130,26 @@ class FilmStats:
         if others:
             self._prepass_current = self._prepass_key() if fuse else None
 
+    def pooled(self, k):
+        """A new FilmStats of ceil(width / k) x ceil(height / k) pixels whose every pixel holds the statistics of all samples of
+        a k x k block of this film (statmc_pool_statistics: one launch; k = 2, 4 or 8; this film is only read).  Every stat
+        type is pooled with its own counts, the colour image `film` with the radiance counts.  With fused_prepass the launch's
+        epilogue writes mean-corr / discriminator of the pooled radiance moments, so pooled(k).denoise() works as on any film."""
+        wc, hc = api.pooled_size(self.width, self.height, k)
+        coarse = FilmStats(wc, hc, self.device, types=self.types, filter_sd=self.filter_sd, radius=self.radius,
+                           g_buffers=self.g_names, g_sds=self.g_sds, placed=self.placed, fused_prepass=self.fused_prepass)
+        fuse = self.fused_prepass and "radiance" in self.types
+        entries = []
+        for t in self.types:
+            cfg = STAT_TYPES[t]
+            entries.append(api.make_pool_entry(coarse.state[t], self.state[t], cfg["channels"], cfg["max_moment"],
+                                               prepass_into=(coarse.mean_corr, coarse.disc) if (fuse and t == "radiance") else None))
+        if "radiance" in self.types and self.film is not None:
+            entries.append(api.make_pool_entry({"mean": coarse.film}, {"mean": self.film}, 3, 1, count_of=self.types.index("radiance")))
+        api.pool_statistics(self.width, self.height, k, entries)
+        coarse._prepass_current = coarse._prepass_key() if fuse else None
+        return coarse
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

@@ -10,6 +10,7 @@
 //                  [--grid GXxGY [--devices 0,1,..]]   the denoise pass over film blocks with a halo exchange (C++ only)
 //                  [--placed]                          device images from statmc_malloc_placed (statmc::usePlacedMemory())
 //                  [--combine S1[,S2,..] --output-stem O [--write-combined] [--combine-mem GiB]]   dumps of independent renders, combined
+//                  [--pool 2|4|8 [--output-stem O]]    k x k pixel blocks pooled into a coarser film, which is denoised and written
 //   statmc_denoise --catalogue [--config denoise|acrr|smis|proden|ours] [--width W --height H]
 //
 // Per iteration it reads "<stem>-<spp>-film.pfm" and every "<stem>-<spp>-t<i>-b<j>-<suffix>.pfm"
@@ -31,6 +32,10 @@
 // t0-b0-n; input mean-corr / discriminator dumps are not read (Denoise recomputes them).  The outputs go to
 // "<O>-<spp * (1 + k)>-<buffer>.pfm"; --write-combined also writes every combined statistics buffer that was read under the
 // same names: a dump `statmc_denoise --stem O --spp <total>` (or pbrt --denoise) reads like any other.
+// --pool k: after the upload (and after --combine) the statistics of every k x k block of pixels are pooled into one pixel of a
+// film of ceil(width / k) x ceil(height / k) pixels (Estimator::PoolStatistics, statmc_pool_statistics: k^2 times the samples per
+// pixel, 1 / k^2 of the pixels); that film is denoised and the selected buffers are written at its size, under the input's names
+// or under "<O>-<spp>-<buffer>.pfm" with --output-stem.  Types without an n file are pooled with t0-b0-n, as under --combine.
 #include <chrono>
 #include <memory>
 #include <cmath>
@@ -128,7 +133,7 @@ int main(int argc, char **argv) {
         bool noWrite = false, writeCombined = false;
         std::string combineText, outputStem;
         size_t combineMemBytes = 8ull << 30;   // --combine-mem GiB: the images of the other stems held at once
-        int forceParts = 0, bands = 0;
+        int forceParts = 0, bands = 0, pool = 0;
         std::string kernel, sweep, sweepSignificance = "0,1,2";
         int significance = 0;
         StatPathParams params = shippedConfig("denoise");
@@ -169,6 +174,7 @@ int main(int argc, char **argv) {
             else if (a == "--output-stem") outputStem = next();
             else if (a == "--combine-mem") combineMemBytes = (size_t)(std::stod(next()) * (double)(1ull << 30));
             else if (a == "--write-combined") writeCombined = true;
+            else if (a == "--pool") pool = std::stoi(next());
             else if (a == "--width") width = std::stoi(next());
             else if (a == "--height") height = std::stoi(next());
             else throw std::runtime_error("unknown option " + a);
@@ -179,8 +185,13 @@ int main(int argc, char **argv) {
             if (outputStem.empty()) throw std::runtime_error("--combine needs --output-stem (where the combined results go)");
             if (!gridText.empty()) throw std::runtime_error("--combine cannot be used with --grid (the combine runs on one device)");
             if (!sweep.empty()) throw std::runtime_error("--combine cannot be used with --sweep");
-        } else if (!outputStem.empty() || writeCombined) {
-            throw std::runtime_error("--output-stem and --write-combined go with --combine");
+        } else if ((!outputStem.empty() && !pool) || writeCombined) {
+            throw std::runtime_error("--output-stem goes with --combine or --pool, --write-combined with --combine");
+        }
+        if (pool) {
+            if (pool != 2 && pool != 4 && pool != 8) throw std::runtime_error("--pool 2 | 4 | 8");
+            if (!gridText.empty()) throw std::runtime_error("--pool cannot be used with --grid (the coarse film is denoised on one device)");
+            if (writeCombined) throw std::runtime_error("--pool cannot be used with --write-combined (the combined statistics have the fine size)");
         }
         if (configGiven) {
             StatPathParams c = shippedConfig(config);
@@ -232,7 +243,25 @@ int main(int argc, char **argv) {
         Estimator est(film, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr, params.smis, reg);
         est.AllocateBuffers(reg);
         // --combine: the combine sits between the uploads and Denoise, so the row-band pipeline is off
-        est.SetPipelineBands(combineStems.empty() ? bands : 1);
+        // ... and so does the pooling, which reads the uploaded images as a whole
+        est.SetPipelineBands(combineStems.empty() && !pool ? bands : 1);
+        // --pool: the coarse film, an Estimator like any other; the denoise pass and the outputs below are its
+        std::unique_ptr<Buffer> coarseFilm;
+        std::unique_ptr<BufferRegistry> coarseReg;
+        std::unique_ptr<Estimator> coarseEst;
+        if (pool) {
+            const int wc = (width + pool - 1) / pool, hc = (height + pool - 1) / pool;
+            coarseFilm.reset(new Buffer("film", HostImage(hc, wc, F32C3)));
+            coarseReg.reset(new BufferRegistry(*coarseFilm));
+            coarseEst.reset(new Estimator(*coarseFilm, cfgs, params.filterSD, params.filterRadius, params.denoiseImage, params.acrr,
+                                          params.smis, *coarseReg));
+            coarseEst->AllocateBuffers(*coarseReg);
+            coarseEst->SetPipelineBands(1);
+            std::cout << "pool: " << width << " x " << height << " pooled " << pool << " x " << pool << " into " << wc << " x " << hc << std::endl;
+        }
+        Estimator &work = pool ? *coarseEst : est;                 // what is denoised and written
+        const BufferRegistry &workReg = pool ? *coarseReg : reg;
+        const int outWidth = work.width, outHeight = work.height;
         // --combine: the dumps of up to STATMC_MAX_COMBINE_SOURCES other stems at a time, as many as fit the memory bound
         struct Part {
             std::unique_ptr<Buffer> film;
@@ -350,12 +379,12 @@ int main(int argc, char **argv) {
             const std::string prefix = stem + "-" + spp + "-";
             std::string outPrefix = prefix;
             combinedNames = readDump(prefix, est);
+            // a type whose counts are not in the dump (G-buffer means of a for-ours dump) is weighed with t0-b0-n
+            std::vector<unsigned char> borrow;
+            for (unsigned char i = 1; i < est.statTypeConfigs.nEnabled; i++)
+                if (!est.nBuffers[i].empty() && !fileExists(prefix + est.nBuffers[i][0].name + ".pfm")) borrow.push_back(i);
+            if (!combineStems.empty() || pool) uploadAll(est, reg, combinedNames);
             if (!combineStems.empty()) {
-                uploadAll(est, reg, combinedNames);
-                // a type whose counts are not in the dump (G-buffer means of a for-ours dump) is weighed with t0-b0-n
-                std::vector<unsigned char> borrow;
-                for (unsigned char i = 1; i < est.statTypeConfigs.nEnabled; i++)
-                    if (!est.nBuffers[i].empty() && !fileExists(prefix + est.nBuffers[i][0].name + ".pfm")) borrow.push_back(i);
                 // the buffer files every stem must carry: the ones of the first
                 std::vector<std::string> candidates{"film"};
                 for (const auto &r : reg.buffers) candidates.push_back(r.name);
@@ -385,18 +414,21 @@ int main(int argc, char **argv) {
                     for (Estimator *e : group) e->Synchronize();
                 }
                 outPrefix = outputStem + "-" + std::to_string(std::stoll(spp) * (long long)(1 + combineStems.size())) + "-";
+            } else if (!outputStem.empty()) {
+                outPrefix = outputStem + "-" + spp + "-";
             }
+            if (pool) est.PoolStatistics(*coarseEst, pool, borrow);   // (enqueued on the coarse Estimator's stream, behind est's)
             auto t1 = clk::now();
             std::cout << "I/O time [ns]: " << std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() << std::endl;
             t0 = clk::now();
-            if (combineStems.empty()) est.Upload();   // (--combine: uploaded and combined above)
+            if (combineStems.empty() && !pool) est.Upload();   // (--combine, --pool: uploaded above)
             const auto tu = clk::now();
             if (shards) shards->Denoise();   // film blocks + halo exchange (statmc_halo_exchange), same result bit for bit
-            else est.Denoise();
+            else work.Denoise();
             const auto td = clk::now();
-            est.Download();
+            work.Download();
             const auto tl = clk::now();
-            est.Synchronize();
+            work.Synchronize();
             t1 = clk::now();
             std::cout << "HIP time [ns]: " << std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() << std::endl;
             // how long the host spent ENQUEUEING each phase (all four calls only enqueue; a long time here is the runtime
@@ -406,19 +438,19 @@ int main(int argc, char **argv) {
                       << ns(tl, t1) << std::endl;
             if (!write) return;
             for (const auto &name : outputs) {
-                const Buffer *b = reg.find(name);
+                const Buffer *b = workReg.find(name);
                 if (!b) throw std::runtime_error("no buffer named " + name);
                 HostImage host = b->mat;
-                if (std::find(est.downloadBuffers.begin(), est.downloadBuffers.end(), b) == est.downloadBuffers.end() &&
-                    (name.find("mean-corr") != std::string::npos || name.find("discriminator") != std::string::npos)) {
-                    // device-only outputs: fetch them explicitly
-                    b->gpuMat.download(host, est.stream);
-                    est.Synchronize();
+                const bool downloaded = std::find(work.downloadBuffers.begin(), work.downloadBuffers.end(), b) != work.downloadBuffers.end();
+                if (!downloaded && (pool || name.find("mean-corr") != std::string::npos || name.find("discriminator") != std::string::npos)) {
+                    // device-only outputs and, under --pool, every pooled image: fetch them explicitly
+                    b->gpuMat.download(host, work.stream);
+                    work.Synchronize();
                 }
                 std::vector<float> tmp;
                 const float *pixels = host.type == I32C1 ? nullptr : host.ptr<float>();
                 if (host.type == I32C1) {
-                    tmp.resize((size_t)width * height);
+                    tmp.resize((size_t)outWidth * outHeight);
                     for (size_t i = 0; i < tmp.size(); i++) tmp[i] = (float)host.ptr<int32_t>()[i];
                     pixels = tmp.data();
                 }
@@ -426,8 +458,8 @@ int main(int argc, char **argv) {
                 // CUDA build's outputs sit next to its inputs, tools/pin_from_dumps.sh)
                 const std::string mine = outPrefix + name + ".pfm", theirs = compareStem + "-" + spp + "-" + name + ".pfm";
                 const bool comparing = !compareStem.empty() && fileExists(theirs);
-                if (comparing) compareImages(name, readPfm(theirs), width, height, host.channels(), pixels);
-                if (!noWrite && !(comparing && theirs == mine)) writePfm(mine, width, height, host.channels(), pixels);
+                if (comparing) compareImages(name, readPfm(theirs), outWidth, outHeight, host.channels(), pixels);
+                if (!noWrite && !(comparing && theirs == mine)) writePfm(mine, outWidth, outHeight, host.channels(), pixels);
             }
             if (writeCombined && !noWrite) {   // the combined statistics: a dump of the union of the renders' samples
                 est.DownloadStatistics();

@@ -785,6 +785,81 @@ typedef struct statmc_pool_entry {
 
 int statmc_pool_statistics(uint16_t width, uint16_t height, int k, const statmc_pool_entry *entries, int n_entries, void *stream);
 
+/* ---- planning per-pixel sample counts from the statistics (no counterpart in the reference): what feeds the sample_counts of
+ * statmc_accumulate_counted / statmc_accumulate_tiles_counted.  Two entries: a pointwise noise score, and the allocation of a
+ * budget by a score image.  Minimising the summed variance of the mean, sum_p s_p^2 / (n_p + c_p), under a fixed sum of c_p gives
+ * n_p + c_p proportional to s_p, clamped per pixel: one scalar level, found by water-filling.  All images are packed
+ * width x height planes like every image of this header.
+ *
+ * statmc_sample_scores: statistics -> score image.  channels is 1 or 3; film_mean / film_m2 are the raw-sample Welford planes of a
+ * stat type (for a non-transform type its mean / m2).
+ * DEFINITION, per pixel; every operation is one fp32 rounding in this order, nothing is contracted, `/` and sqrt are the correctly
+ * rounded IEEE quotient and root:
+ *     n < 2:      score = +inf                    (a pixel nobody can judge yet takes the maximum)
+ *     otherwise   fn = (float)(n - 1);  v = film_m2[0] / fn  (+ film_m2[1] / fn) (+ film_m2[2] / fn), added in channel order;
+ *                 sd = sqrt(v)
+ *       STATMC_SCORE_ABSOLUTE   score = sd
+ *       STATMC_SCORE_RELATIVE   score = sd / (eps + a),  a = |film_mean[0]| (+ |film_mean[1]|) (+ |film_mean[2]|) in channel order
+ * Non-finite or negative statistics pass through as the arithmetic has it (NaN stays NaN, sqrt of a negative sum is NaN);
+ * statmc_plan_samples says what such a score means.  So a numpy float32 restatement gives the same bits.  Planes that are all
+ * 16-byte aligned move four pixels per lane; any other alignment, and the film's last partial group of four, go pixel by pixel to
+ * the same bits.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: a zero width or height; channels not 1 or 3; a
+ * metric other than the two; with STATMC_SCORE_RELATIVE an eps that is not positive and finite (eps is ignored otherwise); a NULL or
+ * not 4-byte aligned image; score overlapping n, film_mean or film_m2.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Asynchronous on `stream`. */
+#define STATMC_SCORE_ABSOLUTE 0
+#define STATMC_SCORE_RELATIVE 1
+int statmc_sample_scores(uint16_t width, uint16_t height, int channels, int metric, float eps,
+                         const int32_t *n, const float *film_mean, const float *film_m2,
+                         float *score, void *stream);
+
+/* statmc_plan_samples: score image + counts so far + budget -> count image.  `score` is statmc_sample_scores' or the renderer's own
+ * metric; n is the per-pixel count so far, NULL meaning 0 everywhere; 0 <= c_min <= c_max <= 2^20 and budget >= 0.
+ * DEFINITION.  A pixel's class by its score s:  saturated  s > 2^60 (+inf included);  live  2^-60 <= s <= 2^60;  dead  everything
+ * else (0, negative, tiny, NaN).  A level is the float of bit pattern u in [U_LO, U_HI] = [0x20000000, 0x5F000000], 2^-63 .. 2^63, so
+ * every product below is a normal number and denormal modes reach no bit.  Per pixel p:
+ *     live:       t = fl32(float_from_bits(u) * s);   N = (t >= 2^30) ? 2^30 : (int)ceil(t);
+ *                 c_p(u) = clamp(N - clamp(n_p, 0, 2^30), c_min, c_max)
+ *     saturated:  c_p(u) = c_max            dead:  c_p(u) = c_min
+ * T(u) = sum_p c_p(u) is an exact integer, non-decreasing in u (rounded multiplication, ceil and clamp are monotone).
+ *     budget <= T(U_LO):   sample_counts = c(U_LO), status 1, level_bits = U_LO   (the floor already spends the budget or more)
+ *     budget >  T(U_HI):   sample_counts = c(U_HI), status 2, level_bits = U_HI   (the ceiling cannot spend it)
+ *     otherwise:           u* = the smallest u with T(u) >= budget, level_bits = u*, status 0, and the overshoot of that last float
+ *                          step is trimmed in raster order:  base_p = c_p(u* - 1),  d_p = c_p(u*) - base_p,  R = budget - T(u* - 1),
+ *                          E_p = the sum of d_q over the pixels q < p in row-major order,
+ *                          sample_counts[p] = base_p + clamp(R - E_p, 0, d_p)
+ * result->total is the sum of sample_counts, n_live / n_saturated the number of pixels of those classes.  Hence:
+ *   - with status 0, total == budget to the sample: a renderer sizes its arena or its record queue by it;
+ *   - every count lies in [c_min, c_max];
+ *   - the same inputs give the same bits on every run: every reduction is an integer sum, so no order reaches a bit;
+ *   - on a film of one constant live score all pixels step together, and the trim hands the last samples to the first pixels in
+ *     raster order;
+ *   - the image is what statmc_accumulate_counted / statmc_accumulate_tiles_counted take as sample_counts.
+ * Asynchronous on `stream`; nothing is read back and nothing allocated.  The caller owns `workspace`, at least
+ * statmc_plan_samples_workspace(width, height) bytes (a pure function, no device needed) and 8-byte aligned; the call zeroes it on
+ * `stream` and leaves nothing of use in it.  `result` is device memory, 8-byte aligned, written by the call.  The search runs on the
+ * device: five passes that evaluate T at 64 levels each, every workgroup deriving its levels from the totals of the pass before,
+ * then a three-launch prefix sum; no kernel waits for another workgroup.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: a zero width or height; NULL score, sample_counts,
+ * result or workspace; score, n or sample_counts not 4-byte aligned, result or workspace not 8-byte aligned; c_min / c_max outside
+ * 0 <= c_min <= c_max <= 2^20; a negative budget; workspace_bytes below the helper's answer; sample_counts overlapping score, n,
+ * result or the workspace, or result overlapping the workspace.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2c, profiles/plan_samples.jsonl. */
+typedef struct statmc_plan_result { /* device, written by the call */
+    int64_t total;       /* sum of sample_counts */
+    int64_t budget;      /* as asked */
+    uint32_t level_bits; /* the level u* (U_LO with status 1, U_HI with status 2) */
+    int32_t status;      /* 0 exact; 1 budget below the floor; 2 budget above the ceiling */
+    int32_t n_live, n_saturated;
+} statmc_plan_result;
+
+size_t statmc_plan_samples_workspace(uint16_t width, uint16_t height); /* bytes; pure, no device needed */
+int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, const int32_t *n,
+                        int64_t budget, int32_t c_min, int32_t c_max,
+                        int32_t *sample_counts, statmc_plan_result *result,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

@@ -1260,6 +1260,40 @@ class Estimator {
         check(statmc_accumulate_counted(width, height, types.data(), formats.data(), (int)types.size(), d_counts, nullptr, 0, stream.handle()));
     }
 
+    // ---- the per-pixel budget of the NEXT samples, planned on the device from the statistics as they stand (statmc_sample_scores +
+    // statmc_plan_samples; include/statmc.h has both definitions).  The noise score of (type, bounce) -- metric STATMC_SCORE_RELATIVE
+    // or STATMC_SCORE_ABSOLUTE over its raw-sample Welford planes -- spends `budget` samples so that n + count is proportional to the
+    // score, every count in [cMin, cMax] and, with result.status == 0, the counts summing to the budget to the sample.  d_counts is
+    // what AccumulateFilm(nSamples, buffers, d_counts) takes; it, the score image and the workspace are members allocated by the first
+    // call, and d_counts stays valid and unchanged until the next PlanSamples.  Needs EnableDeviceAccumulation(); staged samples are
+    // flushed first; the launches go to DeviceStream() and the call blocks until the 32 bytes of the result are back.
+    struct SamplePlan {
+        const int32_t *d_counts;      // device, int32 [height][width]
+        statmc_plan_result result;
+    };
+    SamplePlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, int64_t budget, int32_t cMin, int32_t cMax,
+                           int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+        const statmc_stat_type t = DeviceStatistics(statTypeIndex, bounceIndex);   // validates, flushes staged samples
+        joinUploads();
+        check(statmc_set_device(device));
+        const size_t px = (size_t)width * height, wsBytes = statmc_plan_samples_workspace((uint16_t)width, (uint16_t)height);
+        plan.scores.reserve(px * sizeof(float));
+        plan.counts.reserve(px * sizeof(int32_t));
+        plan.workspace.reserve(wsBytes);
+        plan.result.reserve(sizeof(statmc_plan_result));
+        float *scores = static_cast<float *>(plan.scores.ptr);
+        int32_t *counts = static_cast<int32_t *>(plan.counts.ptr);
+        statmc_plan_result *d_result = static_cast<statmc_plan_result *>(plan.result.ptr);
+        check(statmc_sample_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, t.n, t.film_mean ? t.film_mean : t.mean,
+                                   t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
+        check(statmc_plan_samples((uint16_t)width, (uint16_t)height, scores, t.n, budget, cMin, cMax, counts, d_result, plan.workspace.ptr, wsBytes,
+                                  stream.handle()));
+        SamplePlan out{counts, statmc_plan_result{}};
+        check(statmc_download(&out.result, d_result, sizeof(out.result), stream.handle()));
+        Synchronize();
+        return out;
+    }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     // bytes of samples the flushes have handed to the device (dryRun: would have) since EnableDeviceAccumulation(): per merged
@@ -1655,6 +1689,10 @@ class Estimator {
         std::unordered_set<const Buffer *> deviceProduced;
     };
     mutable Accumulation acc;
+    struct Planning {                    // PlanSamples: allocated by the first call, kept
+        DeviceBytes scores, counts, workspace, result;
+    };
+    Planning plan;
     // tests of the staging (tests/cpp/test_tile_half.cpp defines it): the capacity of the arenas, and the host staging itself,
     // which is no part of the interface -- worker threads write it outside the lock
     friend struct EstimatorTestAccess;

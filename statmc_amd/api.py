@@ -104,6 +104,15 @@ class PoolEntry(C.Structure):
     _fields_ = [("dst", StatType), ("src", StatType), ("count_of", C.c_int32)]
 
 
+class PlanResult(C.Structure):
+    """statmc_plan_result: what statmc_plan_samples writes to device memory next to the count image."""
+    _fields_ = [("total", C.c_int64), ("budget", C.c_int64), ("level_bits", C.c_uint32), ("status", C.c_int32),
+                ("n_live", C.c_int32), ("n_saturated", C.c_int32)]
+
+
+SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
+PLAN_LEVEL_LO, PLAN_LEVEL_HI = 0x20000000, 0x5F000000   # statmc_plan_samples' level range [U_LO, U_HI]: 2^-63 .. 2^63
+PLAN_MAX_COUNT = 1 << 20
 MAX_COMBINE_SOURCES = 15
 
 EXPORTS = [
@@ -114,7 +123,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -213,6 +222,11 @@ def load():
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
     lib.statmc_pool_statistics.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.POINTER(PoolEntry), C.c_int, C.c_void_p]
+    lib.statmc_sample_scores.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.statmc_plan_samples_workspace.argtypes = [C.c_uint16, C.c_uint16]
+    lib.statmc_plan_samples_workspace.restype = C.c_size_t
+    lib.statmc_plan_samples.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.POINTER(PlanResult), C.c_void_p, C.c_size_t, C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -659,6 +673,83 @@ def pool_statistics(width, height, k, entries, stream=None):
     arr = (PoolEntry * max(len(entries), 1))(*entries)
     check(load().statmc_pool_statistics(int(width), int(height), int(k), arr, len(entries),
                                         stream if stream is not None else current_stream_handle()))
+
+
+_METRICS = {"absolute": SCORE_ABSOLUTE, "relative": SCORE_RELATIVE}
+
+
+def sample_scores(n, film_mean, film_m2, metric="relative", eps=1e-3, out=None, stream=None):
+    """statmc_sample_scores: the per-pixel noise score of the running statistics n [H, W] int32 and film_mean / film_m2 [H, W, C]
+    float32 (C = 1 or 3; a [H, W] image is one channel) -- "absolute": the sample standard deviation summed over the channels'
+    variances; "relative": that over eps + sum |film_mean|; +inf where n < 2.  Returns the float32 score image [H, W] (`out`, or a new
+    tensor)."""
+    tc = _torch()
+    h, w = int(n.shape[0]), int(n.shape[1])
+    ch = int(film_mean.shape[2]) if film_mean.dim() == 3 else 1
+    for name, t, dt in (("n", n, tc.int32), ("film_mean", film_mean, tc.float32), ("film_m2", film_m2, tc.float32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("sample_scores: %s must be a contiguous %s CUDA tensor" % (name, dt))
+    if film_mean.numel() != h * w * ch or film_m2.numel() != h * w * ch:
+        raise ValueError("sample_scores: film_mean and film_m2 must hold [H, W, C] = [%d, %d, %d] values" % (h, w, ch))
+    if out is None:
+        out = tc.empty(h, w, dtype=tc.float32, device=n.device)
+    elif out.dtype != tc.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() != h * w:
+        raise ValueError("sample_scores: out must be a contiguous float32 CUDA tensor of H * W values")
+    m = _METRICS[metric] if isinstance(metric, str) else int(metric)
+    check(load().statmc_sample_scores(w, h, ch, m, float(eps), n.data_ptr(), film_mean.data_ptr(), film_m2.data_ptr(), out.data_ptr(),
+                                      stream if stream is not None else current_stream_handle()))
+    return out
+
+
+def plan_samples_workspace(width, height):
+    """statmc_plan_samples_workspace: the bytes of workspace statmc_plan_samples wants for a width x height film (no device needed)."""
+    return int(load().statmc_plan_samples_workspace(int(width), int(height)))
+
+
+_plan_scratch = {}    # (device index, stream handle) -> (workspace, result): alive while kernels of that stream may still use them
+
+
+def plan_result_dict(result):
+    """The statmc_plan_result a plan_samples call wrote into the int64 [4] device tensor `result`, as a dict (a device-to-host copy:
+    synchronises with the work that wrote it on the current stream; after a call on another stream synchronise that one first)."""
+    r = PlanResult.from_buffer_copy(result.cpu().numpy().tobytes())
+    return {k: int(getattr(r, k)) for k, _ in PlanResult._fields_}
+
+
+def plan_samples(score, budget, c_min, c_max, n=None, out=None, workspace=None, result=None, stream=None, return_result=False):
+    """statmc_plan_samples: spends `budget` samples over the film by the float32 score image [H, W] -- n + counts proportional to the
+    score, every count in [c_min, c_max], the sum equal to the budget to the sample wherever the bounds allow it (include/statmc.h).
+    n: int32 [H, W] counts so far, None = 0 everywhere.  Returns the int32 count image [H, W] (`out`, or a new tensor): what
+    accumulate(..., sample_counts=) takes as it is.  Asynchronous; workspace (uint8, at least plan_samples_workspace bytes) and result
+    (int64 [4], the statmc_plan_result's 32 bytes) are the caller's or, if None, tensors kept per (device, stream) until the next call on
+    that stream.  return_result=True: waits for the call and returns (counts, result as a dict)."""
+    tc = _torch()
+    if score.dtype != tc.float32 or not score.is_cuda or not score.is_contiguous() or score.dim() != 2:
+        raise ValueError("plan_samples: score must be a contiguous float32 CUDA tensor [H, W]")
+    h, w = int(score.shape[0]), int(score.shape[1])
+    if n is not None and (n.dtype != tc.int32 or not n.is_cuda or not n.is_contiguous() or n.numel() != h * w):
+        raise ValueError("plan_samples: n must be a contiguous int32 CUDA tensor of H * W counts")
+    if out is None:
+        out = tc.empty(h, w, dtype=tc.int32, device=score.device)
+    else:
+        _counts_pointer(out, w, h, "plan_samples")
+    st = stream if stream is not None else current_stream_handle()
+    need = plan_samples_workspace(w, h)
+    if workspace is None or result is None:
+        key = (score.device.index, st.value if hasattr(st, "value") else int(st or 0))
+        held = _plan_scratch.get(key)
+        if held is None or held[0].numel() < need:
+            held = (tc.empty(need, dtype=tc.uint8, device=score.device), tc.empty(4, dtype=tc.int64, device=score.device))
+            _plan_scratch[key] = held
+        workspace = workspace if workspace is not None else held[0]
+        result = result if result is not None else held[1]
+    check(load().statmc_plan_samples(w, h, score.data_ptr(), n.data_ptr() if n is not None else None, int(budget), int(c_min), int(c_max),
+                                     out.data_ptr(), C.cast(result.data_ptr(), C.POINTER(PlanResult)), workspace.data_ptr(),
+                                     workspace.numel() * workspace.element_size(), st))
+    if not return_result:
+        return out
+    check(load().statmc_synchronize(st))
+    return out, plan_result_dict(result)
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):

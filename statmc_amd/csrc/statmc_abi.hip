@@ -16,6 +16,7 @@
 #include "statmc_accumulate_args.h"
 #include "statmc_records_plan.h"
 #include "statmc_pool_args.h"
+#include "statmc_plan_args.h"
 
 #include <atomic>
 
@@ -1429,6 +1430,29 @@ int statmc_pool_statistics(uint16_t width, uint16_t height, int k, const statmc_
             break;
         }
     HIP_TRY(statmc::launch_pool(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_sample_scores / statmc_plan_samples: every rule of include/statmc.h ahead of the device (statmc_plan_args.h), then the
+// launches of statmc_plan.hip on `stream`; nothing is allocated and nothing read back.
+int statmc_sample_scores(uint16_t width, uint16_t height, int channels, int metric, float eps, const int32_t *n, const float *film_mean,
+                         const float *film_m2, float *score, void *stream) {
+    ARG_TRY(statmc::check_scores_call(width, height, channels, metric, eps, n, film_mean, film_m2, score, statmc::PlanMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::ScoreArgs a;
+    statmc::fill_score_args(a, width, height, channels, metric, eps, n, film_mean, film_m2, score);
+    HIP_TRY(statmc::launch_sample_scores(a, S(stream)));
+    return STATMC_OK;
+}
+
+int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, const int32_t *n, int64_t budget, int32_t c_min, int32_t c_max,
+                        int32_t *sample_counts, statmc_plan_result *result, void *workspace, size_t workspace_bytes, void *stream) {
+    ARG_TRY(statmc::check_plan_call(width, height, score, n, budget, c_min, c_max, sample_counts, result, workspace, workspace_bytes,
+                                    statmc::PlanMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::PlanArgs a;
+    statmc::fill_plan_args(a, width, height, score, n, budget, c_min, c_max, sample_counts, result, workspace);
+    HIP_TRY(statmc::launch_plan_samples(a, statmc::plan_workspace_bytes(width, height), S(stream)));
     return STATMC_OK;
 }
 

@@ -210,6 +210,12 @@ hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a
 struct PoolArgs;
 hipError_t launch_pool(const PoolArgs &a, hipStream_t s);
 
+// statmc_sample_scores / statmc_plan_samples (statmc_plan.hip): argument blocks and checks are statmc_plan_args.h's, host-only
+struct ScoreArgs;
+struct PlanArgs;
+hipError_t launch_sample_scores(const ScoreArgs &a, hipStream_t s);
+hipError_t launch_plan_samples(const PlanArgs &a, size_t workspace_bytes, hipStream_t s);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

@@ -150,6 +150,17 @@ class FilmStats:
         coarse._prepass_current = coarse._prepass_key() if fuse else None
         return coarse
 
+    def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False):
+        """The per-pixel sample counts of the next accumulation: `budget` samples spent by the noise of stat type `type` as it stands
+        (statmc_sample_scores over its n and raw-sample Welford planes, then statmc_plan_samples with its n as the counts so far).
+        Returns an int32 tensor [H, W] that accumulate(samples, counts=) takes as it is; with return_result=True, (counts, the
+        statmc_plan_result as a dict) after a synchronisation.  The film is only read."""
+        st = self.state[type]
+        film_mean = st["film_mean"] if st["film_mean"] is not None else st["mean"]
+        film_m2 = st["film_m2"] if st["film_m2"] is not None else st["m2"]
+        score = api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+        return api.plan_samples(score, budget, c_min, c_max, n=st["n"], return_result=return_result)
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

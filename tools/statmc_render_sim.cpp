@@ -20,8 +20,9 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--placed] [--half-features]
+//                     [--adaptive] [--adaptive-pixels] [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
+// --adaptive-pixels: per-pixel sample budgets planned on the device (Estimator::PlanSamples); see RenderLoop.
 // --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
 //                   half (Estimator::SetSampleFormat); radiance stays fp32.  "Staged bytes:" at the end counts what went up.
 // --config denoise: Render<Vec3>, RGB radiance + normal + albedo, filter<float3> (scenes/render-denoise.pbrt).
@@ -108,7 +109,7 @@ struct Options {
     unsigned seed = 1;
     float filterSD = 10.f;
     int filterRadius = 20;
-    bool denoise = true, acrr = false, smis = false, warmUp = false, tileStats = false, adaptive = false, halfFeatures = false;
+    bool denoise = true, acrr = false, smis = false, warmUp = false, tileStats = false, adaptive = false, adaptivePixels = false, halfFeatures = false;
     std::string stem, outputRegex = ".*";
 };
 
@@ -176,6 +177,13 @@ static void Render(const Options &o) {
     // schedule's samples per pixel, the quietest quarter half of them (at least one).  Counts then differ from tile to tile.
     std::vector<unsigned> tileDone(nTilesTotal, 0u);      // samples per pixel so far, tile by tile
     std::vector<float> tileNoise;                          // of the last iteration (empty: no ranking yet)
+    // --adaptive-pixels (no counterpart in the reference either): after every iteration but the last the NEXT iteration's
+    // width * height * target samples are planned per pixel on the device from the radiance statistics as they stand
+    // (Estimator::PlanSamples: statmc_sample_scores, relative metric, then statmc_plan_samples with 1 .. 4 * target samples per
+    // pixel); only the count image comes back.  The tiles of the next iteration are then ragged, and Merge*Tile(s) take them as
+    // they are.  Every stat type of a pixel gets the same samples.
+    std::vector<int32_t> pixelTarget;                      // the plan of this iteration (empty: the schedule's target everywhere)
+    std::vector<unsigned> pixelDone(o.adaptivePixels ? (size_t)width * height : 0, 0u);   // samples so far, pixel by pixel
     auto RenderLoop = [&](const int nIterations, const bool writeOutput) {
     for (int i = 1; i <= nIterations; i++) {
         const unsigned target = i == 1 ? (unsigned)o.spp : (unsigned)o.spp << std::max(i - 2, 0);  // statpath.cpp:272-279
@@ -200,13 +208,15 @@ static void Render(const Options &o) {
                 std::vector<Vec3> Ls(nLs);
                 for (int t = nextTile.fetch_add(1); t < nTilesTotal; t = nextTile.fetch_add(1)) {
                     const Bounds2i tb = tileBoundsOf(t);
-                    const unsigned target = tileTarget[t], done = tileDone[t];   // (shadow the schedule's: this tile's)
                     std::vector<StatTile<T>> &tileLs = lTiles[t];
                     std::vector<std::vector<StatTile<Vec3>>> &tileRGBFeatures = rgbFeatureTiles[t];
                     std::vector<std::vector<StatTile<float>>> &tileMISTallies = misTallyTiles[t];
                     for (int y = tb.pMin.y; y < tb.pMax.y; y++)
                         for (int x = tb.pMin.x; x < tb.pMax.x; x++) {
                             const Point2i actualPixel(x, y);
+                            const size_t pixel = (size_t)y * width + x;
+                            const unsigned target = pixelTarget.empty() ? tileTarget[t] : (unsigned)pixelTarget[pixel];   // (this pixel's)
+                            const unsigned done = o.adaptivePixels ? pixelDone[pixel] : tileDone[t];
                             for (unsigned s = 0; s < target; s++) {  // do { ... } while (StartNextSample())
                                 const PixelSample smp = makeSample(o.seed, x, y, done + s);
                                 // Li() leaves the radiance gathered up to bounce j in Ls[j]; here a fixed share
@@ -244,6 +254,16 @@ static void Render(const Options &o) {
         if (failed) throw std::runtime_error(failure);
         done += target;
         for (int t = 0; t < nTilesTotal; t++) tileDone[t] += tileTarget[t];
+        if (o.adaptivePixels) {
+            unsigned long long spent = 0;
+            for (size_t p = 0; p < pixelDone.size(); p++) {
+                const unsigned c = pixelTarget.empty() ? target : (unsigned)pixelTarget[p];
+                pixelDone[p] += c;
+                spent += c;
+            }
+            std::cout << "Target: " << target << " spp" << std::endl;
+            std::cout << "Spent: " << spent << " samples" << std::endl;
+        }
         auto end = std::chrono::steady_clock::now();
         std::cout << "Iteration: " << i << std::endl;
         std::cout << "SPP: " << target << std::endl;
@@ -263,6 +283,19 @@ static void Render(const Options &o) {
             unsigned lo = ~0u, hi = 0;
             for (unsigned v : tileDone) { lo = std::min(lo, v); hi = std::max(hi, v); }
             std::cout << "Adaptive: samples per pixel so far " << lo << " .. " << hi << " over " << nTilesTotal << " tiles" << std::endl;
+        }
+
+        if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations) {
+            const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
+            const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next));
+            pixelTarget.resize((size_t)width * height);
+            check(statmc_download(pixelTarget.data(), plan.d_counts, pixelTarget.size() * sizeof(int32_t), estimator.DeviceStream()));
+            estimator.Synchronize();
+            int32_t lo = pixelTarget[0], hi = pixelTarget[0];
+            for (int32_t v : pixelTarget) { lo = std::min(lo, v); hi = std::max(hi, v); }
+            char level[16];
+            std::snprintf(level, sizeof(level), "%08x", (unsigned)plan.result.level_bits);
+            std::cout << "Planned: " << plan.result.total << " samples, " << lo << " .. " << hi << " per pixel, level 0x" << level << std::endl;
         }
 
         begin = std::chrono::steady_clock::now();
@@ -317,6 +350,8 @@ static void Render(const Options &o) {
         done = 0;
         std::fill(tileDone.begin(), tileDone.end(), 0u);
         tileNoise.clear();
+        pixelTarget.clear();
+        std::fill(pixelDone.begin(), pixelDone.end(), 0u);
     }
     RenderLoop(o.iterations, true);
     std::cout << "Staged bytes: " << estimator.stagedBytes() << std::endl;   // sample bytes handed to the device, warm-up included
@@ -349,6 +384,7 @@ int main(int argc, char **argv) {
         else if (a == "--warmup") o.warmUp = true;
         else if (a == "--tilestats") o.tileStats = true;
         else if (a == "--adaptive") o.adaptive = true;
+        else if (a == "--adaptive-pixels") o.adaptivePixels = true;
         else if (a == "--half-features") o.halfFeatures = true;
         else if (a == "--placed") statmc::usePlacedMemory() = true;   // device images and sample arenas from statmc_malloc_placed
         else if (a == "--config") {

@@ -384,7 +384,9 @@ int statmc_copy_rect(const statmc_image *dst, int dst_device, int dst_x, int dst
 /* Replaces cv::cuda::stat_denoiser::calculateMeanVars<T> (commented-out call,
  * src/statistics/estimator.cpp:501-521) and its CPU stand-in (estimator.cpp:524-568):
  * film_var = film_m2 / ((n-1)*n).  row_n_quirk != 0 reproduces the CPU loop reading n once
- * per row (estimator.cpp:540,558). */
+ * per row (estimator.cpp:540,558).  n_buffers is the reference's uchar and every value of it is served, 0 (nothing to do) and
+ * those above STATMC_MAX_BUFFERS included (the filter entries' limit does not apply here), with packed and with pitched images
+ * alike; the buffers are computed in order, each by a launch of its own. */
 int statmc_calculate_mean_vars(uint8_t n_buffers, uint16_t width, uint16_t height, int channels,
                                const statmc_image *n, const statmc_image *film_m2,
                                const statmc_image *film_var, int row_n_quirk, void *stream);
@@ -863,7 +865,11 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,
- * int32 x4), tile_offsets = index of each tile's first pixel in tile_pixels (device). */
+ * int32 x4), tile_offsets = index of each tile's first pixel in tile_pixels (device), in any order.  n takes the low 32 bits of
+ * the 64-bit count, every other field is copied bit for bit; pixels no tile covers, and without `transform` the film images
+ * (which may then be null), are left as they are.  max_tile_pixels sizes the launch -- the pixel count of the largest tile is the
+ * value to pass -- and a tile with more pixels than that is still scattered whole.  At most 65535 tiles per call: more are
+ * refused with STATMC_ERR_UNSUPPORTED and nothing is written. */
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform,
                        const void *tile_pixels, const int32_t *tile_bounds,
                        const int64_t *tile_offsets, int n_tiles, int max_tile_pixels,

@@ -1121,19 +1121,28 @@ static int mean_vars_impl(uint8_t n_buffers, uint16_t width, uint16_t height, in
 int statmc_calculate_mean_vars(uint8_t n_buffers, uint16_t width, uint16_t height, int channels,
                                const statmc_image *n, const statmc_image *film_m2, const statmc_image *film_var,
                                int row_n_quirk, void *stream) {
-    // pitched images: the three tables ride through the packed-twin helper in the slots of a filter call
-    statmc_filter_args f;
-    memset(&f, 0, sizeof(f));
-    f.n_buffers = n_buffers;
-    f.width = width;
-    f.height = height;
-    f.n = n;
-    f.mean = film_m2;
-    f.mean_corr = film_var;
-    f.stream = stream;
-    return with_packed_rows(&f, channels, true, false, [&](const statmc_filter_args *p) {
-        return mean_vars_impl(n_buffers, width, height, channels, p->n, p->mean, p->mean_corr, row_n_quirk, stream);
-    });
+    // pitched images: the three tables ride through the packed-twin helper in the slots of a filter call.  That helper twins at
+    // most STATMC_MAX_BUFFERS buffers per call and the reference passes a uchar here, so a longer table goes through it in runs
+    // of that many: packed or pitched, every count up to 255 is served the same way.
+    if (n_buffers == 0 || !n || !film_m2 || !film_var)
+        return mean_vars_impl(n_buffers, width, height, channels, n, film_m2, film_var, row_n_quirk, stream);   // its checks report it
+    for (int b0 = 0; b0 < n_buffers; b0 += STATMC_MAX_BUFFERS) {
+        const uint8_t nb = (uint8_t)(n_buffers - b0 < STATMC_MAX_BUFFERS ? n_buffers - b0 : STATMC_MAX_BUFFERS);
+        statmc_filter_args f;
+        memset(&f, 0, sizeof(f));
+        f.n_buffers = nb;
+        f.width = width;
+        f.height = height;
+        f.n = n + b0;
+        f.mean = film_m2 + b0;
+        f.mean_corr = film_var + b0;
+        f.stream = stream;
+        const int rc = with_packed_rows(&f, channels, true, false, [&](const statmc_filter_args *p) {
+            return mean_vars_impl(nb, width, height, channels, p->n, p->mean, p->mean_corr, row_n_quirk, stream);
+        });
+        if (rc) return rc;
+    }
+    return STATMC_OK;
 }
 
 // ---------------------------------------------------------------- the accumulation entries

@@ -862,6 +862,55 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
                         int32_t *sample_counts, statmc_plan_result *result,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the compact arena of a planned iteration: every pixel's samples back to back, pixels in raster order (CSR).  Pixel p owns
+ * positions [offsets[p], offsets[p + 1]) of a sample-major [total][channels] array per stat type: no pixel index per sample, no
+ * sort, no dead slots, `total` samples of memory.  The loop: statmc_plan_samples -> statmc_compact_offsets -> the renderer writes
+ * pixel p's sample s at position offsets[p] + s -> statmc_compact_accumulate.
+ *
+ * statmc_compact_offsets: count image -> offsets, and optionally owners.
+ *     c(p) = min(max(sample_counts[p], 0), cap),  cap >= 0, INT32_MAX: no cap
+ *     offsets[p] = the sum of c(q) over q < p in raster order, int64, p = 0 .. width * height; offsets[width * height] is the total.
+ *     owners != NULL:  owners[i] = p for offsets[p] <= i < min(offsets[p + 1], owners_capacity), -1 for every i in
+ *                      [total, owners_capacity).
+ * Every sum is an integer sum: the same bits on every run.  The total stays on the device; nothing is read back, nothing is
+ * allocated.  owners is a valid pixels[] of the records entries (-1: a skipped record) and the slot-to-pixel map of a renderer that
+ * runs one thread per sample.  Three launches like statmc_plan_samples' trim (block sums, one workgroup over them, apply) and one
+ * more over the owner slots; no kernel waits for another workgroup.  The caller owns `workspace`, at least
+ * statmc_compact_offsets_workspace(width, height) bytes (pure, no device needed; a multiple of 8, monotone in the pixel count) and
+ * 8-byte aligned.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: a zero width or height; NULL sample_counts, offsets
+ * or workspace; sample_counts or owners not 4-byte aligned, offsets or workspace not 8-byte aligned; cap < 0; owners_capacity < 0,
+ * or non-zero with NULL owners; workspace_bytes below the helper's answer; offsets or owners overlapping sample_counts, the
+ * workspace or each other.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.  Asynchronous on `stream`. */
+size_t statmc_compact_offsets_workspace(uint16_t width, uint16_t height); /* bytes; pure, no device needed */
+int statmc_compact_offsets(uint16_t width, uint16_t height, const int32_t *sample_counts, int32_t cap,
+                           int64_t *offsets, int32_t *owners, int64_t owners_capacity,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* statmc_compact_accumulate: the fold of a compact arena.  types[t].samples is sample-major [n_samples][channels], fp32 or IEEE half
+ * as sample_formats[t] says (STATMC_SAMPLES_F32 / STATMC_SAMPLES_F16; NULL: every type fp32); n_samples is the arena's length in
+ * samples, given by the host who sized it; types[t].n_samples is ignored.
+ * DEFINITION, per pixel p:  start = clamp(offsets[p], 0, n_samples),  end = clamp(offsets[p + 1], start, n_samples),  c = end - start.
+ * The clamp comes before anything is derived from an offset: no value of offsets[], however wrong, becomes an address outside
+ * [0, n_samples).  Apart from that, non-monotone or out-of-range offsets have no defined result.
+ *   c <= split_above  the pixel holds, bit for bit, what statmc_accumulate_records leaves for samples start .. end - 1 in that
+ *                     order, half samples widened first: n, every moment, the film chain and the mean_corr / discriminator
+ *                     epilogue where asked.  c == 0 keeps every bit of every image.
+ *   c >  split_above  the pixel holds, bit for bit, what statmc_accumulate_records_split leaves for that run: 64 chunks of
+ *                     ceil(c / 64) samples, slot 0 continuing the stored state, merged by the fixed tree of merge_lanes<64>.
+ *                     split_above < 1 is refused; INT32_MAX: never split; STATMC_RECORDS_SPLIT_DEFAULT is the documented choice.
+ * Hence: the call equals the records entries on (owners, samples) of statmc_compact_offsets, bit for bit; the same inputs give the
+ * same bits on every run; the call is asynchronous on `stream`, reads nothing back and allocates nothing -- no workspace, no sort.
+ * Positions are 64-bit throughout: there is no 2^31 limit on n_samples (a 4K film at 256 spp has 2.1 G samples).  A pixel's count
+ * stays below 2^24, as everywhere else.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: n_types outside [0, 16]; NULL types or offsets
+ * with work to do; n_samples < 0; a sample format other than the two; a half arena at an odd address; an fp32 arena not 4-byte or
+ * offsets not 8-byte aligned; split_above < 1.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks; then a zero width or
+ * height and the descriptors' own rules (statmc_accumulate_records').  Zero types or zero samples is a no-op.
+ * Measured at 1920 x 1080: DESIGN.md 4.1j, profiles/accumulate_compact.jsonl. */
+int statmc_compact_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
+                              int n_types, const int64_t *offsets, int64_t n_samples, int32_t split_above, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

@@ -77,6 +77,23 @@ int statmc_debug_accumulate_records_interleaved_path(int path);
  * it has not planned one (no call yet, a no-op, a refused call). */
 int statmc_debug_last_accumulate_records_interleaved_path(void);
 
+/* statmc_compact_accumulate, the kernel of its fold: 0 = the default (DESIGN.md 4.1j says which and why); 1 = staged, a wave
+ * streaming the contiguous span of its 64 pixels through LDS, where the library has it -- elsewhere, and for whatever the staged
+ * kernel does not take, the direct one; 2 = direct, one lane per pixel and stat type straight from global memory: the A/B
+ * yardstick and the fallback.  Same bits either way.  Any other value: STATMC_ERR_INVALID. */
+#define STATMC_COMPACT_PATH_STAGED 1
+#define STATMC_COMPACT_PATH_DIRECT 2
+#define STATMC_COMPACT_PATH_SPLIT 4
+int statmc_debug_compact_path(int path);
+/* What the calling thread's last statmc_compact_accumulate call launched: STATMC_COMPACT_PATH_STAGED or _DIRECT, plus
+ * STATMC_COMPACT_PATH_SPLIT when the call had a split_above below INT32_MAX (runs above it folded by the 64 lanes of a wave); 0 if
+ * it launched nothing (no call yet, a no-op, a refused call).  The report names the KERNEL of the launch, not what each wave did:
+ * inside the staged kernel a wave stages only where the span of its 64 pixels fits 12 KiB, holds no run above split_above and
+ * its clamped runs tile that span; every other wave of the launch takes the direct fold there.  Which waves those are follows
+ * from the offsets alone (tools/time_accumulate_compact.py restates the rule as `staged_wave_share`); the library keeps no
+ * per-wave count. */
+int statmc_debug_last_compact_path(void);
+
 /* The placed allocator's probe (statmc_amd/csrc/statmc_placement.hip) on memory of the caller's: streams [stream_ptr, + stream_bytes)
  * while every fourth step read-modify-writes 16 bytes inside [rmw_ptr, + rmw_bytes) -- the words there change.  Best of five, ms.
  * Two buffers in the same interference class: ~ 9 % slower than two in different ones (1-GiB stream, 64-MiB window). */

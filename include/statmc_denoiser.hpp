@@ -1294,6 +1294,41 @@ class Estimator {
         return out;
     }
 
+    // ---- the compact arena of a planned iteration (statmc_compact_offsets + statmc_compact_accumulate; include/statmc.h).  The
+    // loop: PlanSamples -> CompactOffsets(plan.d_counts, cap, d_offsets) -> the renderer writes pixel p's sample s at position
+    // d_offsets[p] + s of every arena -> AccumulateCompact(nSamples, buffers, d_offsets).  d_offsets (int64 [width * height + 1])
+    // and d_owners (int32 [ownersCapacity], optional: slot i's pixel, -1 at and behind the total -- a d_pixels of AccumulateRecords)
+    // are the caller's device arrays; the workspace is a member allocated by the first call.  Both run on DeviceStream() and
+    // return without waiting: the total stays on the device in d_offsets[width * height] (with PlanSamples' status 0 it is the
+    // budget).  cap = INT32_MAX: no cap.
+    void CompactOffsets(const int32_t *d_counts, int32_t cap, int64_t *d_offsets, int32_t *d_owners = nullptr, int64_t ownersCapacity = 0) {
+        check(statmc_set_device(device));
+        const size_t wsBytes = statmc_compact_offsets_workspace((uint16_t)width, (uint16_t)height);
+        compactWorkspace.reserve(wsBytes);
+        check(statmc_compact_offsets((uint16_t)width, (uint16_t)height, d_counts, cap, d_offsets, d_owners, ownersCapacity, compactWorkspace.ptr, wsBytes,
+                                     stream.handle()));
+    }
+    // Per listed (type, bounce) a compact arena [nSamples][channels of the type] on this Estimator's device, fp32 or IEEE half as
+    // `format` says: pixel p folds positions [d_offsets[p], d_offsets[p + 1]), clamped into [0, nSamples), in ascending order -- the
+    // bits AccumulateRecords leaves for the same samples, and with more than splitAbove of them the bits of
+    // AccumulateRecords(..., splitAbove).  A pixel with an empty run keeps every bit.  Needs EnableDeviceAccumulation(); staged
+    // samples are flushed first; one launch on DeviceStream(), no workspace, no sort: the arenas and d_offsets must stay valid and
+    // unchanged until work enqueued there behind this call has run.  withPrepass as in AccumulateRecords.  At most 16 buffers.
+    void AccumulateCompact(int64_t nSamples, const std::vector<FilmSamples> &buffers, const int64_t *d_offsets,
+                           int splitAbove = STATMC_RECORDS_SPLIT_DEFAULT) {
+        std::vector<statmc_stat_type> types;
+        std::vector<int32_t> formats;
+        for (const FilmSamples &b : buffers) {
+            statmc_stat_type t = DeviceStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
+            t.samples = static_cast<const float *>(b.d_samples);
+            types.push_back(t);
+            formats.push_back(b.format);
+        }
+        check(statmc_set_device(device));
+        check(statmc_compact_accumulate((uint16_t)width, (uint16_t)height, types.data(), formats.data(), (int)types.size(), d_offsets, nSamples, splitAbove,
+                                        stream.handle()));
+    }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     // bytes of samples the flushes have handed to the device (dryRun: would have) since EnableDeviceAccumulation(): per merged
@@ -1693,6 +1728,7 @@ class Estimator {
         DeviceBytes scores, counts, workspace, result;
     };
     Planning plan;
+    DeviceBytes compactWorkspace;        // CompactOffsets: allocated by the first call, kept
     // tests of the staging (tests/cpp/test_tile_half.cpp defines it): the capacity of the arenas, and the host staging itself,
     // which is no part of the interface -- worker threads write it outside the lock
     friend struct EstimatorTestAccess;

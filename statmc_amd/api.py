@@ -123,7 +123,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -227,6 +227,14 @@ def load():
     lib.statmc_plan_samples_workspace.restype = C.c_size_t
     lib.statmc_plan_samples.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                         C.POINTER(PlanResult), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
+    lib.statmc_compact_offsets_workspace.restype = C.c_size_t
+    lib.statmc_compact_offsets.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]
+    lib.statmc_compact_accumulate.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64,
+                                              C.c_int32, C.c_void_p]
+    lib.statmc_debug_compact_path.argtypes = [C.c_int]
+    lib.statmc_debug_last_compact_path.restype = C.c_int
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -970,6 +978,98 @@ def accumulate_records_interleaved_path(path):
 def last_accumulate_records_interleaved_path():
     """The fold the calling thread's last accumulate_records_interleaved planned: RECORDS_PATH_GENERAL | _FUSED (0: none)."""
     return int(load().statmc_debug_last_accumulate_records_interleaved_path())
+
+
+INT32_MAX = 2 ** 31 - 1
+COMPACT_PATH_AUTO, COMPACT_PATH_STAGED, COMPACT_PATH_DIRECT, COMPACT_PATH_SPLIT = 0, 1, 2, 4   # include/statmc_debug.h
+
+
+def compact_offsets_workspace(width, height):
+    """statmc_compact_offsets_workspace: the bytes of workspace statmc_compact_offsets wants for a width x height film (no device needed)."""
+    return int(load().statmc_compact_offsets_workspace(int(width), int(height)))
+
+
+_compact_scratch = {}    # (device index, stream handle) -> workspace: alive while kernels of that stream may still use it
+
+
+def compact_offsets(counts, cap=None, owners_capacity=0, out=None, workspace=None, stream=None):
+    """statmc_compact_offsets: the int32 count image [H, W] (statmc_plan_samples' or the renderer's own) -> (offsets, owners).
+    offsets: int64 [H * W + 1], the exclusive prefix sum of min(max(counts, 0), cap) in raster order (cap None: no cap), the last
+    entry the total, which stays on the device.  owners: int32 [owners_capacity], slot i's pixel, -1 at and behind the total (None
+    with owners_capacity 0): a pixels[] for accumulate_records.  out = (offsets, owners) to write into the caller's tensors.
+    Asynchronous; the workspace (uint8, compact_offsets_workspace bytes) is the caller's or one kept per (device, stream)."""
+    tc = _torch()
+    if counts.dim() != 2:
+        raise ValueError("compact_offsets: counts must be an int32 CUDA tensor [H, W]")
+    h, w = int(counts.shape[0]), int(counts.shape[1])
+    _counts_pointer(counts, w, h, "compact_offsets")
+    offsets, owners = out if out is not None else (None, None)
+    owners_capacity = int(owners_capacity)
+    if offsets is None:
+        offsets = tc.empty(h * w + 1, dtype=tc.int64, device=counts.device)
+    elif offsets.dtype != tc.int64 or not offsets.is_cuda or not offsets.is_contiguous() or offsets.numel() != h * w + 1:
+        raise ValueError("compact_offsets: offsets must be a contiguous int64 CUDA tensor of H * W + 1 entries")
+    if owners is None and owners_capacity > 0:
+        owners = tc.empty(owners_capacity, dtype=tc.int32, device=counts.device)
+    elif owners is not None and (owners.dtype != tc.int32 or not owners.is_cuda or not owners.is_contiguous() or owners.numel() < owners_capacity):
+        raise ValueError("compact_offsets: owners must be a contiguous int32 CUDA tensor of at least owners_capacity entries")
+    st = stream if stream is not None else current_stream_handle()
+    need = compact_offsets_workspace(w, h)
+    if workspace is None:
+        key = (counts.device.index, st.value if hasattr(st, "value") else int(st or 0))
+        workspace = _compact_scratch.get(key)
+        if workspace is None or workspace.numel() < need:
+            workspace = _compact_scratch[key] = tc.empty(need, dtype=tc.uint8, device=counts.device)
+    check(load().statmc_compact_offsets(w, h, counts.data_ptr(), INT32_MAX if cap is None else int(cap), offsets.data_ptr(),
+                                        owners.data_ptr() if owners is not None else None, owners_capacity, workspace.data_ptr(),
+                                        workspace.numel() * workspace.element_size(), st))
+    return offsets, owners
+
+
+def make_stat_type_compact(samples, channels, state, transform, max_moment, prepass_into=None):
+    """Stat type whose samples lie in a compact arena (compact_accumulate): `samples` is a contiguous sample-major device tensor,
+    [n_samples, channels] or flat, torch.float32 or -- with SAMPLES_F16 as the type's sample format -- torch.float16."""
+    if not samples.is_contiguous():   # the descriptor holds the address: a reshaped copy would be gone before the call
+        raise ValueError("make_stat_type_compact: samples must be contiguous")
+    t = make_stat_type_arena(samples.view(-1), channels, state, transform, max_moment, prepass_into=prepass_into)
+    t.n_samples = min(samples.numel() // int(channels), INT32_MAX)   # ignored by the entry: compact_accumulate's default n_samples
+    return t
+
+
+def compact_accumulate(width, height, stat_types, offsets, n_samples=None, sample_formats=None, split_above=None, stream=None):
+    """statmc_compact_accumulate (include/statmc.h): pixel p folds positions [offsets[p], offsets[p + 1]) -- clamped into
+    [0, n_samples) -- of every stat type's arena (make_stat_type_compact) in ascending order: the bits of accumulate_records on the
+    same samples.  offsets: int64 CUDA tensor of width * height + 1 entries (compact_offsets).  n_samples: the arenas' length in
+    samples; None: the shortest of the tensors make_stat_type_compact was given (arenas beyond 2^31 - 1 samples: pass it).
+    sample_formats = [SAMPLES_F32 | SAMPLES_F16, ...] per stat type (None: fp32).  split_above: a run of more samples is
+    folded by the 64 lanes of a wave (the bits of accumulate_records(..., split_above=)); None: RECORDS_SPLIT_DEFAULT."""
+    tc = _torch()
+    if offsets.dtype != tc.int64 or not offsets.is_cuda or not offsets.is_contiguous() or offsets.numel() != int(width) * int(height) + 1:
+        raise ValueError("compact_accumulate: offsets must be a contiguous int64 CUDA tensor of width * height + 1 entries")
+    if n_samples is None:
+        n_samples = min([int(t.n_samples) for t in stat_types], default=0)
+        if n_samples == INT32_MAX:
+            raise ValueError("compact_accumulate: arenas this long need n_samples given")
+    fmts = None
+    if sample_formats is not None:
+        if len(sample_formats) != len(stat_types):
+            raise ValueError("compact_accumulate: one sample format per stat type")
+        fmts = (C.c_int32 * max(len(stat_types), 1))(*[int(f) for f in sample_formats])
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    check(load().statmc_compact_accumulate(int(width), int(height), arr, fmts, len(stat_types), offsets.data_ptr(), int(n_samples),
+                                           RECORDS_SPLIT_DEFAULT if split_above is None else int(split_above),
+                                           stream if stream is not None else current_stream_handle()))
+
+
+def compact_path(path):
+    """statmc_debug_compact_path: COMPACT_PATH_AUTO | _STAGED | _DIRECT."""
+    check(load().statmc_debug_compact_path(int(path)))
+
+
+def last_compact_path():
+    """What the calling thread's last compact_accumulate launched: COMPACT_PATH_STAGED or _DIRECT, plus COMPACT_PATH_SPLIT when the
+    call's split_above was below INT32_MAX (0: nothing)."""
+    return int(load().statmc_debug_last_compact_path())
 
 
 def calculate_mean_vars(n, film_m2, film_var, row_n_quirk=True, stream=None):

@@ -17,6 +17,7 @@
 #include "statmc_records_plan.h"
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
+#include "statmc_compact_args.h"
 
 #include <atomic>
 
@@ -31,6 +32,7 @@ thread_local int g_last_parts = 0, g_last_parts_hi = 0, g_last_tail_rows = 0;
 thread_local const int *g_last_redo = nullptr;   // the item flags of the calling thread's last Welch launch (device memory)
 thread_local int g_last_redo_n = 0;
 thread_local int g_last_acc_counted = 0;    // the calling thread's last accumulate call: 0 no counted kernel, 1 counted, vector path, 2 counted, element by element
+thread_local int g_last_compact_path = 0;   // what the calling thread's last statmc_compact_accumulate call launched (0: nothing)
 thread_local int g_last_rec_ilv_path = 0;   // the fold the calling thread's last statmc_accumulate_records_interleaved call planned (0: none)
 std::mutex g_mu;
 
@@ -51,6 +53,7 @@ struct DeviceState {
     int acc_fused = 0;                                        // the type-fused walk: 0 by shape, 1 whenever eligible, -1 never (statmc_debug_accumulate_fused)
     int rec_phases = 3;                                       // statmc_accumulate_records: 1 grouping, 2 fold, 3 both (statmc_debug_accumulate_records_phases; timing)
     int rec_ilv_path = 0;                                     // statmc_accumulate_records_interleaved's fold: 0 by the type set, 1 general, 2 fused where eligible (statmc_debug_accumulate_records_interleaved_path)
+    int compact_path = 0;                                     // statmc_compact_accumulate's kernel: 0 the default, 1 staged, 2 direct (statmc_debug_compact_path)
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
 std::unordered_map<int, DeviceState> g_dev;  // guarded by g_mu
@@ -1587,6 +1590,35 @@ int statmc_accumulate_records_interleaved_split(uint16_t width, uint16_t height,
     return accumulate_records(statmc::RecordsCall{width, height, types, n_types, nullptr, records, layout, true, n_records, &split_above, stream});
 }
 
+// statmc_compact_offsets / statmc_compact_accumulate: every rule of include/statmc.h ahead of the device (statmc_compact_args.h),
+// then the launches of statmc_compact.hip on `stream`; nothing is allocated and nothing read back.
+int statmc_compact_offsets(uint16_t width, uint16_t height, const int32_t *sample_counts, int32_t cap, int64_t *offsets, int32_t *owners,
+                           int64_t owners_capacity, void *workspace, size_t workspace_bytes, void *stream) {
+    ARG_TRY(statmc::check_compact_offsets_call(width, height, sample_counts, cap, offsets, owners, owners_capacity, workspace, workspace_bytes, why()));
+    NEED_READY();
+    statmc::CompactOffsetsArgs a;
+    statmc::fill_compact_offsets_args(a, width, height, sample_counts, cap, offsets, owners, owners_capacity, workspace);
+    HIP_TRY(statmc::launch_compact_offsets(a, S(stream)));
+    return STATMC_OK;
+}
+int statmc_compact_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats, int n_types,
+                              const int64_t *offsets, int64_t n_samples, int32_t split_above, void *stream) {
+    g_last_compact_path = 0;
+    ARG_TRY(statmc::check_compact_accumulate_call(types, sample_formats, n_types, offsets, n_samples, split_above, why()));
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0 || n_samples == 0) return STATMC_OK;
+    statmc::CompactArgs k;
+    memset(&k, 0, sizeof(k));
+    bool epilogue = false;
+    ARG_TRY(statmc::fill_compact_args(k, width, height, types, sample_formats, n_types, offsets, n_samples, split_above, epilogue, why()));
+    if (int rc = epilogue ? prepass_context(dstate, k.ctx) : STATMC_OK) return rc;
+    int path = 0;
+    HIP_TRY(statmc::launch_compact_accumulate(k, dstate.compact_path, S(stream), &path));
+    g_last_compact_path = path;
+    return STATMC_OK;
+}
+
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,
                        const int32_t *tile_bounds, const int64_t *tile_offsets, int n_tiles, int max_tile_pixels,
                        int32_t *n, float *mean, float *m2, float *m3, float *film_mean, float *film_m2, void *stream) {
@@ -1707,6 +1739,11 @@ int statmc_debug_accumulate_records_interleaved_path(int path) {   // the interl
     STATMC_DEBUG_SET(d.rec_ilv_path = path);
 }
 int statmc_debug_last_accumulate_records_interleaved_path(void) { return g_last_rec_ilv_path; }
+int statmc_debug_compact_path(int path) {   // statmc_compact_accumulate's kernel: 0 the default, 1 staged, 2 direct
+    if (path < 0 || path > 2) return fail(STATMC_ERR_INVALID, "statmc_debug_compact_path(%d): 0, 1 or 2", path);
+    STATMC_DEBUG_SET(d.compact_path = path);
+}
+int statmc_debug_last_compact_path(void) { return g_last_compact_path; }
 int statmc_debug_force_filter_parts(int k) { return statmc_set_filter_split(k < 0 ? 0 : k); }   // the older name of the pin
 int statmc_debug_last_filter_parts(void) { return g_last_parts; }
 // the tail split of the calling thread's last pair-symmetric launch: parts of the last `*tail_rows` tile rows (0: uniform)

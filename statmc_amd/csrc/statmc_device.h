@@ -216,6 +216,13 @@ struct PlanArgs;
 hipError_t launch_sample_scores(const ScoreArgs &a, hipStream_t s);
 hipError_t launch_plan_samples(const PlanArgs &a, size_t workspace_bytes, hipStream_t s);
 
+// statmc_compact_offsets / statmc_compact_accumulate (statmc_compact.hip): argument blocks and checks are statmc_compact_args.h's
+struct CompactOffsetsArgs;
+struct CompactArgs;
+hipError_t launch_compact_offsets(const CompactOffsetsArgs &a, hipStream_t s);
+// force: statmc_debug_compact_path's value; path (out): what statmc_debug_last_compact_path reports
+hipError_t launch_compact_accumulate(const CompactArgs &a, int force, hipStream_t s, int *path);
+
 struct MergeTilesArgs {
     const void *tile_pixels;
     const int32_t *tile_bounds;

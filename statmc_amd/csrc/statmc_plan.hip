@@ -15,6 +15,7 @@
 // score and n are 8 B/px and are read once per launch: 16.6 MB at 1080p, resident in the last-level cache between them.
 #include "statmc_device.h"
 #include "statmc_plan_args.h"
+#include "statmc_scan.h"
 
 namespace statmc {
 
@@ -115,33 +116,7 @@ __device__ __forceinline__ long long wave_sum(long long v) {
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
-template <typename T>
-__device__ __forceinline__ T wave_inclusive_scan(T v) {
-    const int lane = (int)(threadIdx.x & 63);
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T t = __shfl_up(v, off, 64);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-// exclusive prefix of v over the workgroup's kPlanBlock threads in thread order, and the workgroup's total
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T (&wave_tot)[kPlanBlock / 64], T &total) {
-    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
-    const T incl = wave_inclusive_scan(v);
-    __syncthreads();   // the previous use of wave_tot is over
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < kPlanBlock / 64; w++) {
-        if (w < wave) before += wave_tot[w];
-        total += wave_tot[w];
-    }
-    return before + incl - v;
-}
+// (wave_inclusive_scan and block_exclusive_scan, the trim's block step: statmc_scan.h)
 
 // ---------------------------------------------------------------- a search pass
 // The wave's sums of all 64 candidates in 63 exchanges, not 64 x 6: a reduce-scatter.  At the step of half h the lanes whose bit h

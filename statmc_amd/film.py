@@ -94,6 +94,28 @@ class FilmStats:
         else:
             self._prepass_current = self._prepass_key() if fuse else None
 
+    def accumulate_compact(self, samples, offsets, n_samples=None, split_above=None):
+        """samples: {type: [n_samples, C]} compact arenas -- every pixel's samples back to back, pixels in raster order -- in
+        torch.float32 or torch.float16; offsets: int64 CUDA tensor [H * W + 1] (api.compact_offsets of the count image): pixel p
+        folds positions [offsets[p], offsets[p + 1]) in ascending order and keeps every bit where that run is empty
+        (statmc_compact_accumulate: the bits of statmc_accumulate_records on the same samples).  n_samples: the arenas' length in
+        samples, None = the shortest tensor's; split_above: None = api.RECORDS_SPLIT_DEFAULT."""
+        fuse = self.fused_prepass and "radiance" in samples
+        sts, fmts = [], []
+        for t in self.types:
+            if t not in samples:
+                continue
+            if samples[t].dtype not in (torch.float32, torch.float16):
+                raise TypeError("FilmStats.accumulate_compact: samples of %r are %s; torch.float32 or torch.float16" % (t, samples[t].dtype))
+            sts.append(api.make_stat_type_compact(samples[t], STAT_TYPES[t]["channels"], self.state[t], STAT_TYPES[t]["transform"],
+                                                  STAT_TYPES[t]["max_moment"], prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None))
+            fmts.append(api.SAMPLES_F16 if samples[t].dtype == torch.float16 else api.SAMPLES_F32)
+        api.compact_accumulate(self.width, self.height, sts, offsets, n_samples=n_samples,
+                               sample_formats=fmts if api.SAMPLES_F16 in fmts else None, split_above=split_above)
+        # pixels with an empty run keep their mean-corr / discriminator: current only if they were current before
+        key = self._prepass_key()
+        self._prepass_current = key if (fuse and self._prepass_current == key) else None
+
     def combine_(self, other):
         """Combines the statistics of `other` -- the same film, its own samples -- into self, so that self holds the
         statistics of the union of both sample sets (statmc_combine_statistics: one launch).  Every stat type is weighed

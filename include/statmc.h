@@ -911,6 +911,35 @@ int statmc_compact_offsets(uint16_t width, uint16_t height, const int32_t *sampl
 int statmc_compact_accumulate(uint16_t width, uint16_t height, const statmc_stat_type *types, const int32_t *sample_formats,
                               int n_types, const int64_t *offsets, int64_t n_samples, int32_t split_above, void *stream);
 
+/* statmc_compact_accumulate_interleaved: the fold of a compact arena of interleaved records -- ONE array, record i at
+ * (char *)records + i * layout->stride, holding every type's values: the struct a renderer with one thread per planned sample
+ * stores at slot offsets[p] + s.  layout->stride, sample_offset[t] and sample_format[t] mean what they mean for
+ * statmc_accumulate_records_interleaved and obey its rules: the stride a multiple of 4 and at least 4; an offset a multiple of the
+ * element size with the field inside the stride; fields in any order, padded or overlapping; records 4-byte aligned.
+ * layout->pixel_offset is neither read nor checked: a compact record needs no pixel field.  types[t].samples and
+ * types[t].n_samples are ignored.  Positions and byte offsets are 64-bit throughout: n_records has no 2^31 limit.
+ * DEFINITION, per pixel p:  start = clamp(offsets[p], 0, n_records),  end = clamp(offsets[p + 1], start, n_records), clamped before
+ * anything is derived from them.  The call leaves, bit for bit, what statmc_compact_accumulate leaves when it gets the same offsets
+ * and split_above, n_samples = n_records, and as type t's arena the [n_records][channels] array of every record's field t in that
+ * field's format.  Hence it equals statmc_accumulate_records on the same samples, statmc_accumulate_records_split above
+ * split_above, and statmc_accumulate_records_interleaved[_split] on the same records with the owners written into a pixel field;
+ * and everything statmc_compact_accumulate promises carries over: c == 0 keeps every bit, the stored state is continued, the
+ * pre-pass epilogue runs where a type has mean_corr / discriminator, the same inputs give the same bits on every run, the call is
+ * asynchronous on `stream`, reads nothing back and allocates nothing -- no workspace, no sort --, and no value of offsets[] becomes
+ * an address outside [records, records + n_records * stride).
+ * One lane per pixel folds every stat type from one read of each record where the type set is one of the fused records fold's
+ * (one RGB type with the transform and three moments, up to two mean-only RGB and up to two mean-only 1-channel types, every field
+ * fp32 or the feature fields half); every other valid call is served by one lane per pixel and type.  Runs above split_above are
+ * folded by the 64 lanes of a wave in a launch of their own behind the fused one.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument: n_types outside [0, 16]; NULL types, layout,
+ * records or offsets with work to do; n_records < 0; a stride, records address, sample format, channel count (1 or 3) or sample
+ * offset outside the rules; offsets not 8-byte aligned; split_above < 1.  STATMC_ERR_NO_DEVICE before statmc_setup, after those
+ * checks; then a zero width or height and the descriptors' own rules.  Zero types or zero records is a no-op.
+ * Measured at 1920 x 1080: DESIGN.md 4.1k, profiles/accumulate_compact_interleaved.jsonl. */
+int statmc_compact_accumulate_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                                          const void *records, const statmc_record_layout *layout,
+                                          const int64_t *offsets, int64_t n_records, int32_t split_above, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

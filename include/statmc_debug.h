@@ -94,6 +94,26 @@ int statmc_debug_compact_path(int path);
  * per-wave count. */
 int statmc_debug_last_compact_path(void);
 
+/* statmc_compact_accumulate_interleaved, the kernel of its fold: 0 = the default (DESIGN.md 4.1k says which and why); 1 = the
+ * fused kernel, staged: one lane per pixel holds every type's state, and a wave whose 64 clamped runs tile one span of records
+ * that fits the wave's LDS window (and holds no run above split_above) lands that span in LDS and folds out of it -- every other
+ * wave of the launch folds directly; 2 = the fused kernel, direct: every lane walks its run straight from global memory; 3 = the
+ * general kernel, one lane per pixel and stat type.  1 and 2 apply where the type set is one of the fused fold's; elsewhere the
+ * general kernel runs.  Same bits every way.  Any other value: STATMC_ERR_INVALID. */
+#define STATMC_COMPACT_ILV_PATH_FUSED_STAGED 1
+#define STATMC_COMPACT_ILV_PATH_FUSED_DIRECT 2
+#define STATMC_COMPACT_ILV_PATH_GENERAL 3
+#define STATMC_COMPACT_ILV_PATH_SPLIT 4
+int statmc_debug_compact_interleaved_path(int path);
+/* What the calling thread's last statmc_compact_accumulate_interleaved call launched: one of the three kernels above, plus
+ * STATMC_COMPACT_ILV_PATH_SPLIT when the call had a split_above below INT32_MAX (runs above it folded by the 64 lanes of a wave:
+ * behind a fused kernel in a second launch of the general one); 0 if it launched nothing (no call yet, a no-op, a refused call).
+ * As statmc_debug_last_compact_path, the report names the KERNEL, not what each wave did. */
+int statmc_debug_last_compact_interleaved_path(void);
+/* The staged kernel's LDS window per wave, bytes: a multiple of 1024 in [1024, 65536], or 0 for the default.  One wave per
+ * workgroup: the window decides how many waves share a CU (tools/time_accumulate_compact_interleaved.py times the choices). */
+int statmc_debug_compact_interleaved_window(int bytes);
+
 /* The placed allocator's probe (statmc_amd/csrc/statmc_placement.hip) on memory of the caller's: streams [stream_ptr, + stream_bytes)
  * while every fourth step read-modify-writes 16 bytes inside [rmw_ptr, + rmw_bytes) -- the words there change.  Best of five, ms.
  * Two buffers in the same interference class: ~ 9 % slower than two in different ones (1-GiB stream, 64-MiB window). */

@@ -1329,6 +1329,29 @@ class Estimator {
                                         stream.handle()));
     }
 
+    // ... the same arena as a renderer with one thread per planned sample holds it: ONE array of nRecords interleaved records
+    // (statmc_compact_accumulate_interleaved), the record of pixel p's sample s at slot d_offsets[p] + s, every listed (type,
+    // bounce) at its field's offset and in its format.  layout.pixelOffset is ignored: a compact record needs no pixel field.
+    // The bits of AccumulateCompact on the de-interleaved arenas; flushing, device, stream, splitAbove and withPrepass as there.
+    // At most 16 fields per call.
+    void AccumulateCompactInterleaved(int64_t nRecords, const void *d_records, const RecordLayout &layout, const std::vector<RecordField> &typeList,
+                                      const int64_t *d_offsets, int splitAbove = STATMC_RECORDS_SPLIT_DEFAULT) {
+        if (typeList.size() > 16) throw Error(STATMC_ERR_INVALID, "AccumulateCompactInterleaved: at most 16 fields per call");
+        std::vector<statmc_stat_type> types;
+        statmc_record_layout l{};
+        l.stride = layout.stride;
+        l.pixel_offset = layout.pixelOffset;
+        for (const RecordField &f : typeList) {
+            statmc_stat_type t = DeviceStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
+            l.sample_offset[types.size()] = f.offset;
+            l.sample_format[types.size()] = f.format;
+            types.push_back(t);
+        }
+        check(statmc_set_device(device));
+        check(statmc_compact_accumulate_interleaved((uint16_t)width, (uint16_t)height, types.data(), (int)types.size(), d_records, &l, d_offsets, nRecords,
+                                                    splitAbove, stream.handle()));
+    }
+
     // (tile, buffer) merges handed over by flushes so far, and the number of flushes
     size_t stagedMerges() const { std::lock_guard<std::mutex> lk(acc.mu); return acc.flushedMerges; }
     // bytes of samples the flushes have handed to the device (dryRun: would have) since EnableDeviceAccumulation(): per merged

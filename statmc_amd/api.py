@@ -123,7 +123,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -235,6 +235,11 @@ def load():
                                               C.c_int32, C.c_void_p]
     lib.statmc_debug_compact_path.argtypes = [C.c_int]
     lib.statmc_debug_last_compact_path.restype = C.c_int
+    lib.statmc_compact_accumulate_interleaved.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.POINTER(RecordLayout),
+                                                          C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.statmc_debug_compact_interleaved_path.argtypes = [C.c_int]
+    lib.statmc_debug_compact_interleaved_window.argtypes = [C.c_int]
+    lib.statmc_debug_last_compact_interleaved_path.restype = C.c_int
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -1070,6 +1075,48 @@ def last_compact_path():
     """What the calling thread's last compact_accumulate launched: COMPACT_PATH_STAGED or _DIRECT, plus COMPACT_PATH_SPLIT when the
     call's split_above was below INT32_MAX (0: nothing)."""
     return int(load().statmc_debug_last_compact_path())
+
+
+COMPACT_ILV_PATH_AUTO, COMPACT_ILV_PATH_FUSED_STAGED, COMPACT_ILV_PATH_FUSED_DIRECT, COMPACT_ILV_PATH_GENERAL, COMPACT_ILV_PATH_SPLIT = 0, 1, 2, 3, 4   # include/statmc_debug.h
+
+
+def compact_accumulate_interleaved(width, height, stat_types, records, layout, offsets, n_records=None, split_above=None, stream=None):
+    """statmc_compact_accumulate_interleaved (include/statmc.h): `records` is a contiguous uint8 or int32 device tensor of n_records
+    records of layout.stride bytes each (default: as many as the tensor holds), pixel p's at slots [offsets[p], offsets[p + 1]) --
+    clamped into [0, n_records) --; stat_types from make_stat_type_record_field, in the order of the layout's fields
+    (make_record_layout; its pixel_offset is ignored).  offsets: int64 CUDA tensor of width * height + 1 entries (compact_offsets).
+    The bits of compact_accumulate on the de-interleaved arenas.  split_above: None = RECORDS_SPLIT_DEFAULT."""
+    tc = _torch()
+    if records.dtype not in (tc.uint8, tc.int32) or not records.is_contiguous() or (records.numel() and not records.is_cuda):
+        raise ValueError("compact_accumulate_interleaved: records must be a contiguous uint8 or int32 CUDA tensor")
+    if offsets.dtype != tc.int64 or not offsets.is_cuda or not offsets.is_contiguous() or offsets.numel() != int(width) * int(height) + 1:
+        raise ValueError("compact_accumulate_interleaved: offsets must be a contiguous int64 CUDA tensor of width * height + 1 entries")
+    nbytes = records.numel() * records.element_size()
+    if n_records is None:
+        n_records = nbytes // layout.stride if layout.stride > 0 else 0
+    elif int(n_records) * layout.stride > nbytes:
+        raise ValueError("compact_accumulate_interleaved: %d records of %d bytes do not fit the tensor (%d bytes)" % (n_records, layout.stride, nbytes))
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    check(load().statmc_compact_accumulate_interleaved(int(width), int(height), arr, len(stat_types), records.data_ptr(), C.byref(layout),
+                                                       offsets.data_ptr(), int(n_records),
+                                                       RECORDS_SPLIT_DEFAULT if split_above is None else int(split_above),
+                                                       stream if stream is not None else current_stream_handle()))
+
+
+def compact_interleaved_path(path):
+    """statmc_debug_compact_interleaved_path: COMPACT_ILV_PATH_AUTO | _FUSED_STAGED | _FUSED_DIRECT | _GENERAL."""
+    check(load().statmc_debug_compact_interleaved_path(int(path)))
+
+
+def compact_interleaved_window(nbytes):
+    """statmc_debug_compact_interleaved_window: the staged kernel's LDS bytes per wave (a multiple of 1024 up to 65536; 0: the default)."""
+    check(load().statmc_debug_compact_interleaved_window(int(nbytes)))
+
+
+def last_compact_interleaved_path():
+    """What the calling thread's last compact_accumulate_interleaved launched: COMPACT_ILV_PATH_FUSED_STAGED, _FUSED_DIRECT or
+    _GENERAL, plus COMPACT_ILV_PATH_SPLIT when the call's split_above was below INT32_MAX (0: nothing)."""
+    return int(load().statmc_debug_last_compact_interleaved_path())
 
 
 def calculate_mean_vars(n, film_m2, film_var, row_n_quirk=True, stream=None):

@@ -10,7 +10,7 @@ SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
            "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_compact.hip"]
-HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_compact_args.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -106,6 +106,8 @@ POOL_BIN = os.path.join(ROOT, "tools", "bin", "test_pool_statistics")   # tests/
 PLAN_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_plan_args")   # tests/cpp/test_plan_args.cpp: statmc_plan_args.h, no device, no library
 PLAN_BIN = os.path.join(ROOT, "tools", "bin", "test_plan_samples")   # tests/cpp/test_plan_samples.cpp: Estimator::PlanSamples
 COMPACT_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_args")   # tests/cpp/test_compact_args.cpp: statmc_compact_args.h, no device, no library
+COMPACT_ILV_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_interleaved_args")   # tests/cpp/test_compact_interleaved_args.cpp: statmc_compact_interleaved_args.h, no device, no library
+COMPACT_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_accumulate_interleaved")   # tests/cpp/test_compact_accumulate_interleaved.cpp: Estimator::AccumulateCompactInterleaved
 COMPACT_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_accumulate")   # tests/cpp/test_compact_accumulate.cpp: Estimator::CompactOffsets / AccumulateCompact
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
@@ -124,6 +126,8 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          PLAN_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_plan_args.cpp"),
          PLAN_BIN: os.path.join("..", "tests", "cpp", "test_plan_samples.cpp"),
          COMPACT_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_args.cpp"),
+         COMPACT_ILV_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_interleaved_args.cpp"),
+         COMPACT_ILV_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate_interleaved.cpp"),
          COMPACT_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
@@ -147,7 +151,8 @@ def tools_hash():
     files.append(os.path.join(CSRC, "statmc_records_plan.h"))    # ... test_records_interleaved_plan.cpp the records entries' host decisions
     files.append(os.path.join(CSRC, "statmc_pool_args.h"))    # ... test_pool_args.cpp the pooling entry's checks
     files.append(os.path.join(CSRC, "statmc_plan_args.h"))    # ... test_plan_args.cpp the planning entries' checks
-    files.append(os.path.join(CSRC, "statmc_compact_args.h"))    # ... and test_compact_args.cpp the compact entries' checks
+    files.append(os.path.join(CSRC, "statmc_compact_args.h"))    # ... test_compact_args.cpp the compact entries' checks
+    files.append(os.path.join(CSRC, "statmc_compact_interleaved_args.h"))    # ... and test_compact_interleaved_args.cpp the interleaved compact entry's
     for path in files:
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
@@ -181,7 +186,7 @@ def build_tools(force=False):
     for binary, src in TOOLS.items():
         tmp = binary + ".tmp%d" % os.getpid()
         extra = ["-L", os.path.dirname(DEVICE_EXAMPLE_SO), "-lstatmc_device_example", "-Wl,-rpath,$ORIGIN"] if binary == DEVICE_ACC_BIN else []
-        if binary in (ACC_PLAN_BIN, ACC_ARGS_BIN, COMPACT_ARGS_BIN):      # statmc_device.h includes the HIP runtime's header
+        if binary in (ACC_PLAN_BIN, ACC_ARGS_BIN, COMPACT_ARGS_BIN, COMPACT_ILV_ARGS_BIN):      # statmc_device.h includes the HIP runtime's header
             extra = ["-D__HIP_PLATFORM_AMD__", "-I", rocm_inc]
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread",
                                "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", src), "-o", tmp,

@@ -18,6 +18,7 @@
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
 #include "statmc_compact_args.h"
+#include "statmc_compact_interleaved_args.h"
 
 #include <atomic>
 
@@ -33,6 +34,7 @@ thread_local const int *g_last_redo = nullptr;   // the item flags of the callin
 thread_local int g_last_redo_n = 0;
 thread_local int g_last_acc_counted = 0;    // the calling thread's last accumulate call: 0 no counted kernel, 1 counted, vector path, 2 counted, element by element
 thread_local int g_last_compact_path = 0;   // what the calling thread's last statmc_compact_accumulate call launched (0: nothing)
+thread_local int g_last_compact_ilv_path = 0;   // ... and its last statmc_compact_accumulate_interleaved call (0: nothing)
 thread_local int g_last_rec_ilv_path = 0;   // the fold the calling thread's last statmc_accumulate_records_interleaved call planned (0: none)
 std::mutex g_mu;
 
@@ -54,6 +56,8 @@ struct DeviceState {
     int rec_phases = 3;                                       // statmc_accumulate_records: 1 grouping, 2 fold, 3 both (statmc_debug_accumulate_records_phases; timing)
     int rec_ilv_path = 0;                                     // statmc_accumulate_records_interleaved's fold: 0 by the type set, 1 general, 2 fused where eligible (statmc_debug_accumulate_records_interleaved_path)
     int compact_path = 0;                                     // statmc_compact_accumulate's kernel: 0 the default, 1 staged, 2 direct (statmc_debug_compact_path)
+    int compact_ilv_path = 0;                                 // statmc_compact_accumulate_interleaved's kernel: 0 the default, 1 fused staged, 2 fused direct, 3 general
+    int compact_ilv_window = statmc::kCompactIlvWindowDefault;   // ... and the staged variant's LDS bytes per wave (statmc_debug_compact_interleaved_window)
     int tiles_umul = 2, tiles_order = 2, tiles_wg_per_cu = 0; // tile-fed accumulation (deeper prefetch of the mean-only types; a workgroup = four consecutive tiles of one type)
 };
 std::unordered_map<int, DeviceState> g_dev;  // guarded by g_mu
@@ -1618,6 +1622,27 @@ int statmc_compact_accumulate(uint16_t width, uint16_t height, const statmc_stat
     g_last_compact_path = path;
     return STATMC_OK;
 }
+// The compact arena as ONE array of interleaved records.  The entry's own order: every argument rule (the layout's among them),
+// the device, the film size, the descriptors.
+int statmc_compact_accumulate_interleaved(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
+                                          const statmc_record_layout *layout, const int64_t *offsets, int64_t n_records, int32_t split_above,
+                                          void *stream) {
+    g_last_compact_ilv_path = 0;
+    ARG_TRY(statmc::check_compact_interleaved_call(types, n_types, records, layout, offsets, n_records, split_above, why()));
+    NEED_READY();
+    if (width == 0 || height == 0) return fail(STATMC_ERR_INVALID, "empty image");
+    if (n_types == 0 || n_records == 0) return STATMC_OK;
+    statmc::CompactInterleavedArgs k;
+    memset(&k, 0, sizeof(k));
+    bool epilogue = false;
+    ARG_TRY(statmc::fill_compact_interleaved_args(k, width, height, types, n_types, records, *layout, offsets, n_records, split_above, epilogue, why()));
+    if (int rc = epilogue ? prepass_context(dstate, k.ctx) : STATMC_OK) return rc;
+    int kernel = 0, path = 0;
+    const statmc::RecordsInterleavedPlan plan = statmc::plan_compact_interleaved(k.t, n_types, *layout, dstate.compact_ilv_path, &kernel);
+    HIP_TRY(statmc::launch_compact_accumulate_interleaved(k, plan, kernel, dstate.compact_ilv_window, S(stream), &path));
+    g_last_compact_ilv_path = path;
+    return STATMC_OK;
+}
 
 int statmc_merge_tiles(uint16_t width, uint16_t height, int channels, int transform, const void *tile_pixels,
                        const int32_t *tile_bounds, const int64_t *tile_offsets, int n_tiles, int max_tile_pixels,
@@ -1744,6 +1769,16 @@ int statmc_debug_compact_path(int path) {   // statmc_compact_accumulate's kerne
     STATMC_DEBUG_SET(d.compact_path = path);
 }
 int statmc_debug_last_compact_path(void) { return g_last_compact_path; }
+int statmc_debug_compact_interleaved_path(int path) {   // statmc_compact_accumulate_interleaved's kernel: 0 the default, 1 fused staged, 2 fused direct, 3 general
+    if (path < 0 || path > 3) return fail(STATMC_ERR_INVALID, "statmc_debug_compact_interleaved_path(%d): 0, 1, 2 or 3", path);
+    STATMC_DEBUG_SET(d.compact_ilv_path = path);
+}
+int statmc_debug_compact_interleaved_window(int bytes) {   // the staged variant's LDS bytes per wave; 0: the default
+    if (bytes != 0 && !statmc::compact_interleaved_window_valid(bytes))
+        return fail(STATMC_ERR_INVALID, "statmc_debug_compact_interleaved_window(%d): 0 or a multiple of 1024 in [1024, 65536]", bytes);
+    STATMC_DEBUG_SET(d.compact_ilv_window = bytes ? bytes : statmc::kCompactIlvWindowDefault);
+}
+int statmc_debug_last_compact_interleaved_path(void) { return g_last_compact_ilv_path; }
 int statmc_debug_force_filter_parts(int k) { return statmc_set_filter_split(k < 0 ? 0 : k); }   // the older name of the pin
 int statmc_debug_last_filter_parts(void) { return g_last_parts; }
 // the tail split of the calling thread's last pair-symmetric launch: parts of the last `*tail_rows` tile rows (0: uniform)

@@ -13,11 +13,17 @@
 //             records_split_chunk's (statmc_records_plan.h), the merge is statmc::device::merge_lanes<64>.  Positions are 64-bit:
 //             the records fold's 32-bit run starts and its order[] array have no counterpart here, which is why this file has a
 //             walk of its own; nothing of the arithmetic is restated.
+//   records   statmc_compact_accumulate_interleaved: the same arena as ONE array of interleaved records (statmc_record_layout), folded
+//             in place by a general kernel (one lane per pixel and stat type) or a fused one (one lane per pixel holds every type and
+//             reads each record once; direct, or with a wave's span of records staged through LDS).  Its own section below; the host
+//             checks and the plan are statmc_compact_interleaved_args.h's.  DESIGN.md 4.1k.
 #include "statmc_device.h"
 #include "statmc_compact_args.h"
 #include "statmc_scan.h"
 #define STATMC_PLAN_HOST_DEVICE __host__ __device__      // records_split_chunk runs in the fold
 #include "statmc_records_plan.h"
+#include "statmc_compact_interleaved_args.h"
+#include "statmc_record_field.h"
 
 #include "../../include/statmc_device_api.hpp"
 
@@ -381,6 +387,314 @@ __global__ __launch_bounds__(kCompactBlock) void compact_staged_kernel(CompactAr
     compact_dispatch_type<StagedFold>(t, half, ctx, p, (long long)start, cnt, a.split_above, staged, first, static_cast<const unsigned *>(ring));
 }
 
+// ---------------------------------------------------------------- interleaved records: statmc_compact_accumulate_interleaved
+// The arena is ONE array of records, `stride` bytes each, record i holding every type's field (statmc_record_layout; a record's
+// field as it is requested and decoded: statmc_record_field.h).  Pixel p owns records [offsets[p], offsets[p + 1]), clamped by
+// compact_run before anything is derived from them.  DESIGN.md 4.1k.
+//
+// The walk over the cnt records that start at `run`, `stride` bytes apart, in ascending position: compact_walk's batches -- four
+// records in two register sets, past the last whole batch the requests repeat the run's last four records (inside the run, never
+// folded) -- with the request and the fold handed in: gather(record, s) loads only, fold(s) folds.
+template <class S, class G, class F>
+__device__ __forceinline__ void compact_walk_records(const char *__restrict__ run, long long stride, int cnt, G gather, F fold) {
+    int j = 0;
+    if (cnt >= kCompactBatch) {
+        const int last = cnt - kCompactBatch;
+        S A[kCompactBatch], B[kCompactBatch];
+#pragma unroll
+        for (int u = 0; u < kCompactBatch; u++) gather(run + u * stride, A[u]);
+        // batch 0 passes through an empty asm: loaded in front of the loop AND in it, it would become one load at the loop's head
+#pragma unroll
+        for (int u = 0; u < kCompactBatch; u++) A[u].pin();
+        // invariant: A = the records of batch j / 4 (requested)
+        for (; j + 2 * kCompactBatch <= cnt; j += 2 * kCompactBatch) {
+            const char *b = run + (long long)min(j + kCompactBatch, last) * stride;
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) gather(b + u * stride, B[u]);
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) fold(A[u]);
+            const char *a = run + (long long)min(j + 2 * kCompactBatch, last) * stride;
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) gather(a + u * stride, A[u]);
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) fold(B[u]);
+        }
+        if (j + kCompactBatch <= cnt) {   // an odd number of whole batches: the last one is in A
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) fold(A[u]);
+            j += kCompactBatch;
+        }
+    }
+    for (; j < cnt; j++) {   // the last cnt % 4 records, and runs shorter than a batch
+        S s;
+        gather(run + (long long)j * stride, s);
+        fold(s);
+    }
+}
+
+// The general fold: one lane per pixel and stat type, each reading its own field through the stride.  compact_fold's two phases
+// (field0 = records + the type's field offset); short_too == 0 skips phase 1: the fused kernel has served those runs.
+template <int C, int MAXM, bool TRANSFORM, bool HALF, bool SPLIT>
+__device__ __forceinline__ void compact_fold_records(const statmc_stat_type &t, const statmc_prepass_context &ctx, long long p, const char *field0,
+                                                     int stride_in, long long start, int cnt, int split_above, int short_too) {
+    using PS = device::PixelStats<C, MAXM, TRANSFORM>;
+    using Field = RecField<C, HALF ? kFieldHalfElems : kFieldF32>;
+    using S = RecRaw<Field::kRegs>;
+    const long long stride = stride_in;
+    auto gather = [](const char *at, S &s) __attribute__((always_inline)) { Field::load(at, s.r); };
+    if (short_too && cnt > 0 && (!SPLIT || cnt <= split_above)) {
+        PS ps;
+        ps.load(t, p);
+        compact_walk_records<S>(field0 + compact_record_byte(start, stride_in, 0), stride, cnt, gather, [&](const S &s) __attribute__((always_inline)) {
+            float v[C];
+            Field::decode(s.r, 0, v);
+            ps.add(v);
+        });
+        compact_store(ps, t, p, ctx);
+    }
+    if constexpr (SPLIT) {
+        static_assert(kRecSplitLanes == 64, "a split pixel's slots are the lanes of one wave");
+        const int lane = (int)(threadIdx.x & 63u);
+        const long long p0 = p - lane;   // the wave's first pixel
+        for (unsigned long long m = __ballot(cnt > split_above); m != 0; m &= m - 1) {
+            const int from = __ffsll((long long)m) - 1;
+            const long long s0 = __shfl(start, from, 64);
+            const int c0 = __shfl(cnt, from, 64);
+            int begin, len;
+            records_split_chunk(c0, lane, &begin, &len);
+            PS ps;
+            if (lane == 0) ps.load(t, p0 + from);
+            else ps.clear();
+            compact_walk_records<S>(field0 + compact_record_byte(s0 + begin, stride_in, 0), stride, len, gather, [&](const S &s) __attribute__((always_inline)) {
+                float v[C];
+                Field::decode(s.r, 0, v);
+                ps.add(v);
+            });
+            device::merge_lanes<kRecSplitLanes>(ps);
+            if (lane == 0) compact_store(ps, t, p0 + from, ctx);
+        }
+    }
+}
+
+template <bool SPLIT>
+struct RecordsFold {
+    template <int C, int MAXM, bool TRANSFORM, bool HALF>
+    static __device__ __forceinline__ void run(const statmc_stat_type &t, const statmc_prepass_context &ctx, long long p, const char *field0, int stride,
+                                               long long start, int cnt, int split_above, int short_too) {
+        compact_fold_records<C, MAXM, TRANSFORM, HALF, SPLIT>(t, ctx, p, field0, stride, start, cnt, split_above, short_too);
+    }
+};
+
+// Workgroups, types and early exits as compact_direct_kernel has them.
+template <bool SPLIT>
+__global__ __launch_bounds__(kCompactBlock) void compact_interleaved_general_kernel(CompactInterleavedArgs a, int short_too) {
+    const int ti = (int)(blockIdx.x % (unsigned)a.n_types);
+    const long long p = (long long)(blockIdx.x / (unsigned)a.n_types) * kCompactBlock + threadIdx.x;
+    if (!SPLIT && p >= a.n_px) return;
+    int64_t start = 0, end = 0;
+    if (!SPLIT || p < a.n_px) compact_run(a.offsets[p], a.offsets[p + 1], a.n_records, &start, &end);   // the clamp, first
+    const int cnt = compact_run_count(start, end);
+    if (!SPLIT && cnt <= 0) return;
+    // COPIED out of the by-value argument: a reference into it keeps the whole argument in scratch
+    const statmc_stat_type t = a.t[ti];
+    const statmc_prepass_context ctx = a.ctx;
+    const bool half = (a.half_mask >> ti) & 1u;
+    const char *field0 = a.records + a.off[ti];
+    compact_dispatch_type<RecordsFold<SPLIT>>(t, half, ctx, p, field0, a.stride, (long long)start, cnt, a.split_above, short_too);
+}
+
+// The fused fold: one lane per pixel holds the state of every type of the set (plan_records_interleaved's: the radiance type,
+// K <= 2 mean-only RGB types, M <= 2 mean-only 1-channel types) and reads every field of a record once, as dwords at 4-byte
+// alignment -- records_interleaved_fused_kernel's fold on a run that needs no order[].  offsets[] is read once per pixel, not once
+// per pixel and type.  A run above skip_above is left alone: the general split kernel follows and serves those runs alone
+// (short_too == 0), as the records entries have it -- the shipped five-type fp32 set already needs 188 VGPRs, two waves per SIMD
+// (features half 171, all half 164: DESIGN.md 4.1k lists the code objects), and 64 lanes' worth of merge state on top of
+// 16 + 4 K + 2 M state registers and two batches in flight would be paid by every short run.
+//   not STAGED   256 lanes per workgroup, no LDS; a lane walks its run straight from global memory (compact_walk_records).
+//   STAGED       one wave per workgroup with `window` bytes of LDS.  The clamped runs of the wave's 64 pixels tile ONE span of
+//                records that holds every type: where they do, the span plus its skew fits the window and no run is above
+//                skip_above, the wave lands the span by LDS-DMA in whole 16-byte pieces exactly as compact_staged_kernel does
+//                (pieces, clamp of the last piece and source-side swizzle are its), waits once, and every lane folds its records
+//                out of LDS: one staging area for all types.  Every other wave folds directly; the decision is wave-uniform.
+//                A record starts at any 4-byte boundary of the image (the stride is a multiple of 4, not of 16; the skew is one
+//                too), so a field is read dword by dword through the swizzle.
+struct CompactFusedArgs {
+    statmc_stat_type t[kRecFusedTypes];   // slot 0 the radiance type, then the K mean-only RGB types, then the M 1-channel types
+    statmc_prepass_context ctx;
+    const long long *offsets;
+    const char *records;
+    long long n_records, n_px;
+    int stride;
+    int off[kRecFusedTypes];
+    int skip_above;       // a run of more records is left alone; INT32_MAX: never
+    int window;           // STAGED: bytes of LDS, a multiple of 1024
+};
+
+template <int K, int M, int FMT, bool STAGED>
+__global__ __launch_bounds__(STAGED ? 64 : kCompactBlock) void compact_interleaved_fused_kernel(CompactFusedArgs a) {
+    using FRad = RecField<3, FMT == 2 ? kFieldHalfDwords : kFieldF32>;
+    using FRgb = RecField<3, FMT >= 1 ? kFieldHalfDwords : kFieldF32>;
+    using FOne = RecField<1, FMT >= 1 ? kFieldHalfDwords : kFieldF32>;
+    constexpr int kRgb0 = FRad::kRegs, kOne0 = kRgb0 + K * FRgb::kRegs;
+    using S = RecRaw<kOne0 + M * FOne::kRegs>;
+    constexpr int kAlign = FMT >= 1 ? ~3 : ~0;      // where a field's load starts: half fields at the dword that holds their first element
+    constexpr int kBlock = STAGED ? 64 : kCompactBlock;
+    extern __shared__ __attribute__((aligned(16))) unsigned ring[];   // STAGED: the wave's window
+
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    // a lane past the film carries the empty run at the film's end: it breaks no tiling
+    const long long pc = p < a.n_px ? p : a.n_px, pc1 = p + 1 < a.n_px ? p + 1 : a.n_px;
+    int64_t start, end;
+    compact_run(a.offsets[pc], a.offsets[pc1], a.n_records, &start, &end);   // the clamp, first
+    const int cnt = p < a.n_px ? compact_run_count(start, end) : 0;
+    const bool mine = cnt > 0 && cnt <= a.skip_above;
+    bool staged = false;
+    int first = 0;                                  // STAGED: the run's first dword in the wave's LDS image
+    if constexpr (STAGED) {
+        if (!__any(mine)) return;
+        const int lane = (int)(threadIdx.x & 63u);
+        const long long stride = a.stride;
+        const long long span0 = __shfl((long long)start, 0, 64), span1 = __shfl((long long)end, 63, 64);
+        const long long before = __shfl_up((long long)end, 1, 64);
+        const bool tiles = __all(lane == 0 || (long long)start == before);
+        const uintptr_t at = reinterpret_cast<uintptr_t>(a.records) + (uintptr_t)compact_record_byte(span0, a.stride, 0);
+        const long long skew = (long long)(at & 15);
+        // (span1 - span0 <= window / 4 is tested first: the product below then stays far inside 64 bits)
+        const bool fits = span1 >= span0 && span1 - span0 <= (long long)(a.window >> 2) && skew + (span1 - span0) * stride <= (long long)a.window;
+        staged = tiles && fits && !__any(cnt > a.skip_above);
+        if (staged) {
+            const long long bytes = skew + (span1 - span0) * stride;
+            const char *piece0 = reinterpret_cast<const char *>(at - (uintptr_t)skew);
+            const int n_pieces = (int)((bytes + 15) >> 4);      // >= 1: bytes > 0, some lane has records
+            const int n_dma = __builtin_amdgcn_readfirstlane((n_pieces + 63) >> 6);
+#pragma unroll 1
+            for (int k = 0; k < n_dma; k++) {
+                const int src = compact_swizzle_piece(64 * k + lane);   // LDS piece 64 k + lane holds span piece src
+                const char *from = piece0 + 16ll * (src < n_pieces ? src : n_pieces - 1);
+                __builtin_amdgcn_global_load_lds(reinterpret_cast<const float *>(from), (__attribute__((address_space(3))) void *)(ring + 256 * k), 16, 0, 2);
+            }
+            first = (int)((skew + ((long long)start - span0) * stride) >> 2);
+        }
+    }
+    if (!mine) return;
+    // COPIED out of the by-value argument; every index below is a constant after unrolling
+    const statmc_stat_type t_rad = a.t[0];
+    statmc_stat_type t_rgb[K > 0 ? K : 1], t_one[M > 0 ? M : 1];
+    int rgb_off[K > 0 ? K : 1], one_off[M > 0 ? M : 1];         // where the field's load starts in a record, bytes
+    int rgb_shift[K > 0 ? K : 1], one_shift[M > 0 ? M : 1];
+    const int rad_off = a.off[0] & (FMT == 2 ? ~3 : ~0);
+    const int rad_shift = (a.off[0] & 2) * 8;
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        t_rgb[i] = a.t[1 + i];
+        rgb_off[i] = a.off[1 + i] & kAlign;
+        rgb_shift[i] = (a.off[1 + i] & 2) * 8;
+    }
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        t_one[i] = a.t[1 + K + i];
+        one_off[i] = a.off[1 + K + i] & kAlign;
+        one_shift[i] = (a.off[1 + K + i] & 2) * 8;
+    }
+    const statmc_prepass_context ctx = a.ctx;
+
+    device::PixelStats<3, 3, true> rad;
+    device::PixelStats<3, 1, false> rgb[K > 0 ? K : 1];
+    device::PixelStats<1, 1, false> one[M > 0 ? M : 1];
+    rad.load(t_rad, p);
+#pragma unroll
+    for (int i = 0; i < K; i++) rgb[i].load(t_rgb[i], p);
+#pragma unroll
+    for (int i = 0; i < M; i++) one[i].load(t_one[i], p);
+
+    auto fold = [&](const S &s) __attribute__((always_inline)) {
+        float v[3];
+        FRad::decode(s.r, rad_shift, v);
+        rad.add(v);
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            FRgb::decode(s.r + kRgb0 + i * FRgb::kRegs, rgb_shift[i], v);
+            rgb[i].add(v);
+        }
+#pragma unroll
+        for (int i = 0; i < M; i++) {
+            FOne::decode(s.r + kOne0 + i * FOne::kRegs, one_shift[i], v);
+            one[i].add(v);
+        }
+    };
+
+    if (STAGED && staged) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's DMA pieces have landed (and the state)
+        const int stride_dw = a.stride >> 2;
+        auto lds = [&](int e) __attribute__((always_inline)) { return ring[(compact_swizzle_piece(e >> 2) << 2) | (e & 3)]; };
+        // batches of four records are read ahead of the four folds (LDS reads do not depend on the fold's chain); past the run's
+        // end the reads repeat its last record and nothing is folded
+        for (int j = 0; j < cnt; j += kCompactBatch) {
+            S s[kCompactBatch];
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++) {
+                const int e = first + min(j + u, cnt - 1) * stride_dw;
+#pragma unroll
+                for (int r = 0; r < FRad::kRegs; r++) s[u].r[r] = lds(e + (rad_off >> 2) + r);
+#pragma unroll
+                for (int i = 0; i < K; i++)
+#pragma unroll
+                    for (int r = 0; r < FRgb::kRegs; r++) s[u].r[kRgb0 + i * FRgb::kRegs + r] = lds(e + (rgb_off[i] >> 2) + r);
+#pragma unroll
+                for (int i = 0; i < M; i++) s[u].r[kOne0 + i] = lds(e + (one_off[i] >> 2));
+            }
+#pragma unroll
+            for (int u = 0; u < kCompactBatch; u++)
+                if (j + u < cnt) fold(s[u]);
+        }
+    } else {
+        compact_walk_records<S>(
+            a.records + compact_record_byte(start, a.stride, 0), (long long)a.stride, cnt,
+            [&](const char *at, S &s) __attribute__((always_inline)) {
+                FRad::load(at + rad_off, s.r);
+#pragma unroll
+                for (int i = 0; i < K; i++) FRgb::load(at + rgb_off[i], s.r + kRgb0 + i * FRgb::kRegs);
+#pragma unroll
+                for (int i = 0; i < M; i++) FOne::load(at + one_off[i], s.r + kOne0 + i * FOne::kRegs);
+            },
+            fold);
+    }
+
+    compact_store(rad, t_rad, p, ctx);
+#pragma unroll
+    for (int i = 0; i < K; i++) rgb[i].store(t_rgb[i], p);
+#pragma unroll
+    for (int i = 0; i < M; i++) one[i].store(t_one[i], p);
+}
+
+template <int FMT, bool STAGED>
+hipError_t launch_compact_fused(const CompactFusedArgs &f, int K, int M, hipStream_t s) {
+    constexpr int kBlock = STAGED ? 64 : kCompactBlock;
+    const dim3 grid((unsigned)((f.n_px + kBlock - 1) / kBlock)), block(kBlock);
+    const size_t lds = STAGED ? (size_t)f.window : 0;
+    switch (3 * K + M) {
+    case 1: hipLaunchKernelGGL((compact_interleaved_fused_kernel<0, 1, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 2: hipLaunchKernelGGL((compact_interleaved_fused_kernel<0, 2, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 3: hipLaunchKernelGGL((compact_interleaved_fused_kernel<1, 0, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 4: hipLaunchKernelGGL((compact_interleaved_fused_kernel<1, 1, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 5: hipLaunchKernelGGL((compact_interleaved_fused_kernel<1, 2, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 6: hipLaunchKernelGGL((compact_interleaved_fused_kernel<2, 0, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 7: hipLaunchKernelGGL((compact_interleaved_fused_kernel<2, 1, FMT, STAGED>), grid, block, lds, s, f); break;
+    case 8: hipLaunchKernelGGL((compact_interleaved_fused_kernel<2, 2, FMT, STAGED>), grid, block, lds, s, f); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template <bool STAGED>
+hipError_t launch_compact_fused(const CompactFusedArgs &f, const RecordsInterleavedPlan &plan, hipStream_t s) {
+    switch (plan.fmt) {
+    case 0: return launch_compact_fused<0, STAGED>(f, plan.K, plan.M, s);
+    case 1: return launch_compact_fused<1, STAGED>(f, plan.K, plan.M, s);
+    case 2: return launch_compact_fused<2, STAGED>(f, plan.K, plan.M, s);
+    }
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------- the host side
@@ -407,6 +721,39 @@ hipError_t launch_compact_accumulate(const CompactArgs &a, int force, hipStream_
     else if (split) hipLaunchKernelGGL(compact_direct_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(compact_direct_kernel<false>, grid, block, 0, s, a);
     *path = kernel | (split ? kCompactSplitBit : 0);
+    return hipGetLastError();
+}
+
+// kernel: plan_compact_interleaved's answer.  window: the staged variant's LDS bytes per wave.  path (out): the kernel that ran, with
+// kCompactIlvSplitBit where the call asked for runs above split_above to be split.
+hipError_t launch_compact_accumulate_interleaved(const CompactInterleavedArgs &a, const RecordsInterleavedPlan &plan, int kernel, int window,
+                                                 hipStream_t s, int *path) {
+    const bool split = a.split_above != INT32_MAX;
+    const dim3 grid((unsigned)((a.n_px + kCompactBlock - 1) / kCompactBlock * a.n_types)), block(kCompactBlock);
+    int short_too = 1;
+    if (kernel != kCompactIlvGeneral) {
+        CompactFusedArgs f{};
+        for (int j = 0; j < 1 + plan.K + plan.M; j++) {
+            f.t[j] = a.t[plan.order[j]];
+            f.off[j] = a.off[plan.order[j]];
+        }
+        f.ctx = a.ctx;
+        f.offsets = a.offsets;
+        f.records = a.records;
+        f.n_records = a.n_records;
+        f.n_px = a.n_px;
+        f.stride = a.stride;
+        f.skip_above = a.split_above;
+        f.window = window;
+        const hipError_t e = kernel == kCompactIlvFusedStaged ? launch_compact_fused<true>(f, plan, s) : launch_compact_fused<false>(f, plan, s);
+        *path = kernel | (split ? kCompactIlvSplitBit : 0);
+        // the fused fold has left the runs above split_above alone: the split kernel below serves them, and them alone
+        if (e != hipSuccess || !split) return e;
+        short_too = 0;
+    }
+    if (split) hipLaunchKernelGGL(compact_interleaved_general_kernel<true>, grid, block, 0, s, a, short_too);
+    else hipLaunchKernelGGL(compact_interleaved_general_kernel<false>, grid, block, 0, s, a, short_too);
+    *path = kernel | (split ? kCompactIlvSplitBit : 0);
     return hipGetLastError();
 }
 

@@ -222,6 +222,13 @@ struct CompactArgs;
 hipError_t launch_compact_offsets(const CompactOffsetsArgs &a, hipStream_t s);
 // force: statmc_debug_compact_path's value; path (out): what statmc_debug_last_compact_path reports
 hipError_t launch_compact_accumulate(const CompactArgs &a, int force, hipStream_t s, int *path);
+// statmc_compact_accumulate_interleaved (statmc_compact.hip): argument block, checks and the plan are statmc_compact_interleaved_args.h's
+struct CompactInterleavedArgs;
+struct RecordsInterleavedPlan;
+// kernel: plan_compact_interleaved's; window: the staged variant's LDS bytes per wave; path (out): what
+// statmc_debug_last_compact_interleaved_path reports
+hipError_t launch_compact_accumulate_interleaved(const CompactInterleavedArgs &a, const RecordsInterleavedPlan &plan, int kernel, int window,
+                                                 hipStream_t s, int *path);
 
 struct MergeTilesArgs {
     const void *tile_pixels;

@@ -94,12 +94,30 @@ class FilmStats:
         else:
             self._prepass_current = self._prepass_key() if fuse else None
 
-    def accumulate_compact(self, samples, offsets, n_samples=None, split_above=None):
+    def accumulate_compact(self, samples=None, offsets=None, n_samples=None, split_above=None, records=None, layout=None):
         """samples: {type: [n_samples, C]} compact arenas -- every pixel's samples back to back, pixels in raster order -- in
         torch.float32 or torch.float16; offsets: int64 CUDA tensor [H * W + 1] (api.compact_offsets of the count image): pixel p
         folds positions [offsets[p], offsets[p + 1]) in ascending order and keeps every bit where that run is empty
         (statmc_compact_accumulate: the bits of statmc_accumulate_records on the same samples).  n_samples: the arenas' length in
-        samples, None = the shortest tensor's; split_above: None = api.RECORDS_SPLIT_DEFAULT."""
+        samples, None = the shortest tensor's; split_above: None = api.RECORDS_SPLIT_DEFAULT.
+        records=, layout= instead of samples: the same arena as ONE array of interleaved records (uint8 or int32 CUDA tensor; the
+        record of pixel p's sample s at slot offsets[p] + s) -- layout = (stride, {type: byte offset | (byte offset, api.SAMPLES_F32 |
+        api.SAMPLES_F16)}); n_samples counts records then (statmc_compact_accumulate_interleaved: the bits of the call on the
+        de-interleaved arenas)."""
+        if offsets is None or (samples is None) == (records is None) or (records is None) != (layout is None):
+            raise ValueError("FilmStats.accumulate_compact: offsets with either samples, or records and layout")
+        if records is not None:
+            stride, fields = layout
+            fuse = self.fused_prepass and "radiance" in fields
+            names = [t for t in self.types if t in fields]
+            sts = [api.make_stat_type_record_field(STAT_TYPES[t]["channels"], self.state[t], STAT_TYPES[t]["transform"], STAT_TYPES[t]["max_moment"],
+                                                   prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None) for t in names]
+            at = [fields[t] if isinstance(fields[t], (tuple, list)) else (fields[t], api.SAMPLES_F32) for t in names]
+            lay = api.make_record_layout(stride, 0, [o for o, _ in at], [f for _, f in at])
+            api.compact_accumulate_interleaved(self.width, self.height, sts, records, lay, offsets, n_records=n_samples, split_above=split_above)
+            key = self._prepass_key()
+            self._prepass_current = key if (fuse and self._prepass_current == key) else None
+            return
         fuse = self.fused_prepass and "radiance" in samples
         sts, fmts = [], []
         for t in self.types:

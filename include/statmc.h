@@ -940,6 +940,56 @@ int statmc_compact_accumulate_interleaved(uint16_t width, uint16_t height, const
                                           const void *records, const statmc_record_layout *layout,
                                           const int64_t *offsets, int64_t n_records, int32_t split_above, void *stream);
 
+/* ---- the state of a pixel as a thing that travels: unordered (pixel, state) records.  The dense entries put whole films together
+ * (statmc_combine_statistics, statmc_combine_many, statmc_pool_statistics); these two move the states of LISTED pixels, any number in
+ * any order.  Who needs them: a wavefront renderer whose waves fold a pixel's samples in registers
+ * (statmc::device::PixelStats) without owning the pixel -- it writes one record per (wave, pixel) with PixelStats::write_record
+ * instead of one sample record per sample --, and a helper device that re-rendered a few per cent of a film and ships those
+ * pixels' states instead of whole images.
+ *
+ * THE STATE RECORD of a stat type with C channels, max_moment M and the transform flag is D = 1 + C * (M + (transform ? 2 : 0))
+ * dwords: dword 0 the int32 count n, then per channel mean, m2 (M >= 2), m3 (M = 3), film_mean, film_m2 (transform types only),
+ * every float as its bits -- the order of statmc::device::map_state (include/statmc_device_api.hpp), which PixelStats::write_record /
+ * read_record write and read.  D = 16 for the radiance type (3 channels, transform, M = 3), 4 for normal / albedo, 2 for a mean-only
+ * 1-channel type.  statmc_state_dwords returns D; it is pure, needs no device and returns 0 for values a stat type cannot have
+ * (channels other than 1 and 3, max_moment outside 1 .. 3).  It agrees with statmc::device::state_dwords<C, MAXM, TRANSFORM>().
+ * states is a HOST array of n_types DEVICE pointers; states[t] is record-major [n_records][D_t] dwords, 4-byte aligned.
+ *
+ * statmc_gather_states: record i of type t receives, bit for bit, the stored state of pixel pixels[i].  A pixel value outside
+ * [0, width * height) gets the state of no samples -- n = 0, every field +0 -- and never becomes an address.  Duplicates are fine;
+ * the images are only read.  types[t].samples, n_samples, mean_corr and discriminator are ignored.  No workspace.
+ *
+ * statmc_combine_records: DEFINITION, per pixel p and type t.  The run of p is the records of this call with pixels[i] == p, in
+ * ascending i; c is its length.  A record whose count for type t is <= 0 carries nothing for that type and is passed over: no field
+ * of it is read into any formula.
+ *   c <= split_above  start from the stored state S; for each record R_i of the run in order with n_i > 0, S.merge(R_i) with S as
+ *                     part A and the record as part B: bit for bit a chain of two-part statmc_combine_statistics calls in that
+ *                     order, and the left fold statmc_combine_many computes from the same parts.
+ *   c >  split_above  the run is cut into STATMC_RECORDS_SPLIT_LANES chunks of ceil(c / 64) records, a function of c alone (the
+ *                     chunk rule of statmc_accumulate_records_split); slot 0 starts from the stored state, every slot j > 0 from
+ *                     the state of no samples; each slot left-folds its chunk as above; the 64 states are merged in the tree of
+ *                     merge_lanes<64> (include/statmc_device_api.hpp): the relation statmc_accumulate_records_split has to
+ *                     statmc_accumulate_records.  split_above >= 1; INT32_MAX: never split.
+ * A pixel and type with at least one record of positive count is stored, its pre-pass to mean_corr / discriminator where the type
+ * has them (max_moment 3).  Every other pixel keeps every bit of every image, mean_corr / discriminator included.
+ * Hence, as for the records entries: a dead pixel value never becomes an address; the result does not depend on how records of
+ * different pixels interleave; without a split, a call over [0, n) equals calls over [0, m) and [m, n); the same inputs give the
+ * same bits on every run.  The grouping is the stable sort of statmc_accumulate_records, in the same per-(device, stream)
+ * workspace.  Every type carries its own n (no borrowed counts); the counts of a pixel sum below 2^24.  types[t].samples and
+ * n_samples are ignored.
+ *
+ * Both calls are asynchronous on `stream` and read nothing back.  STATMC_ERR_INVALID before any launch, statmc_last_error() naming
+ * the argument: n_types outside [0, 16]; n_records outside [0, 2^31); split_above < 1; then, with work to do, NULL types, pixels or
+ * states, pixels or a states[t] NULL or not 4-byte aligned, a zero width or height, and the descriptors' own rules
+ * (statmc_accumulate_records').  Zero types or zero records is a no-op.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080: DESIGN.md 4.2d, profiles/combine_records.jsonl. */
+size_t statmc_state_dwords(int channels, int max_moment, int transform); /* dwords; pure, no device needed */
+int statmc_gather_states(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                         const int32_t *pixels, int64_t n_records, void *const *states, void *stream);
+int statmc_combine_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types,
+                           const int32_t *pixels, int64_t n_records, const void *const *states,
+                           int32_t split_above, void *stream);
+
 /* Scatter of reference-layout AoS tiles (StatTilePixel<T>, estimator.h:104-124: 64 B for
  * T=float, 128 B for T=Vec3) that were accumulated on the host into the planar device images:
  * Estimator::MergeTile / MergeTransformTile.  tile_bounds = {x0,y0,x1,y1} per tile (device,

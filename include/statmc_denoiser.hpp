@@ -1182,6 +1182,44 @@ class Estimator {
         check(statmc_accumulate_records_split(width, height, types.data(), (int)types.size(), d_pixels, n_records, splitAbove, stream.handle()));
     }
 
+    // ---- states that travel: unordered (pixel, state) records (statmc_gather_states / statmc_combine_records, include/statmc.h)
+    // d_pixels[i] = y * width + x of record i (anything outside the film: the gather writes the state of no samples there, the
+    // combine skips the record), and per listed (type, bounce) one state record per entry at d_states + i * D dwords, D =
+    // statmc_state_dwords of the type's configuration (the count, then per channel mean, m2, m3, film-mean, film-m2 as far as the
+    // type has them), all on this Estimator's device.  GatherStates lifts the stored states of the listed pixels into the
+    // records (the images are only read; withPrepass is ignored).  CombineRecords merges the records into the images: per pixel
+    // in ascending i, the stored state as part A and every record with a positive count as part B -- the bits of CombineStatistics on the
+    // same parts in that order --, and a pixel without such a record keeps every bit; a pixel with more than splitAbove records
+    // is folded by the 64 lanes of a wave (INT32_MAX: never).  withPrepass: the epilogue also writes the "-mean-corr" /
+    // "-discriminator" images of the pixels it touched (max_moment 3).  Both need EnableDeviceAccumulation(); samples staged by
+    // Merge*Tile(s) so far are flushed first; the launches go to DeviceStream(), so the arrays must stay valid (and the combine's
+    // unchanged) until work enqueued there behind the call has run.  At most 16 buffers per call.
+    struct StateRecords {
+        unsigned char statTypeIndex, bounceIndex;
+        void *d_states;              // device, int32 dwords, [n_records][statmc_state_dwords of the type]
+        bool withPrepass = false;
+    };
+    void GatherStates(const int32_t *d_pixels, int64_t n_records, const std::vector<StateRecords> &buffers) {
+        std::vector<statmc_stat_type> types;
+        std::vector<void *> states;
+        for (const StateRecords &r : buffers) {
+            types.push_back(DeviceStatistics(r.statTypeIndex, r.bounceIndex, false));   // validates, flushes staged samples
+            states.push_back(r.d_states);
+        }
+        check(statmc_set_device(device));
+        check(statmc_gather_states(width, height, types.data(), (int)types.size(), d_pixels, n_records, states.data(), stream.handle()));
+    }
+    void CombineRecords(const int32_t *d_pixels, int64_t n_records, const std::vector<StateRecords> &buffers, int splitAbove = INT32_MAX) {
+        std::vector<statmc_stat_type> types;
+        std::vector<const void *> states;
+        for (const StateRecords &r : buffers) {
+            types.push_back(DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass));
+            states.push_back(r.d_states);
+        }
+        check(statmc_set_device(device));
+        check(statmc_combine_records(width, height, types.data(), (int)types.size(), d_pixels, n_records, states.data(), splitAbove, stream.handle()));
+    }
+
     // ---- the same queue as the renderer holds it: one interleaved record per finished sample (statmc_accumulate_records_interleaved)
     // d_records: n_records records of layout.stride bytes on this Estimator's device, 4-byte aligned; each holds its int32 pixel
     // index at layout.pixelOffset and, per listed (type, bounce), the type's channels at `offset` as fp32 (STATMC_SAMPLES_F32) or

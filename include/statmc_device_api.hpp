@@ -10,6 +10,9 @@
 //
 // and put the states of several slots of one pixel together before the store: ps.merge(other) where one thread holds both,
 // merge_lanes<G>(ps) across the lanes of a wave and merge_waves<NW>(ps, lds) across the waves of a workgroup (all below).
+// A thread that holds a partial state of a pixel it does NOT own -- another wave holds more samples of the same pixel -- must not
+// store(): it writes the state as a record, ps.write_record(rec), and the host hands the (pixel, record) pairs to
+// statmc_combine_records (include/statmc.h), which merges them into the film in record order.
 // The result is bit for bit what statmc_accumulate leaves after the same samples (one launch or several: the state is the
 // same), and store(t, pixel, ctx) writes what the accumulation's pre-pass epilogue writes.  This header is the one
 // definition of that arithmetic: libstatmc_hip.so's kernels include it too.
@@ -200,6 +203,11 @@ __device__ __forceinline__ void combine_elem(ElemState &a, const ElemState &b, c
 // bits of a reduction depend on the order of its merges (fp32 addition is not associative): a left fold in slot order,
 // s[0].merge(s[1]); s[0].merge(s[2]); ..., leaves what statmc_combine_many leaves from the same parts in that order.
 template <int C, int MAXM, bool TRANSFORM>
+struct PixelStats;
+template <int C, int MAXM, bool TRANSFORM, class F>
+__device__ __forceinline__ void map_state(PixelStats<C, MAXM, TRANSFORM> &ps, F f);   // (below: the reductions)
+
+template <int C, int MAXM, bool TRANSFORM>
 struct PixelStats {
     static_assert(C == 1 || C == 3, "a stat type has 1 or 3 channels");
     static_assert(MAXM >= 1 && MAXM <= 3, "max_moment is 1, 2 or 3");
@@ -274,6 +282,25 @@ struct PixelStats {
             t.mean_corr[e] = m;
             t.discriminator[e] = d;
         }
+    }
+    // The state as a record that travels (statmc_gather_states / statmc_combine_records, include/statmc.h): state_dwords<C, MAXM,
+    // TRANSFORM>() dwords at rec, 4-byte aligned -- n, then per channel the fields the instantiation has, map_state's list and
+    // order, every float as its bits.  A kernel whose thread holds a partial state of a pixel it does not own writes it with
+    // write_record next to the pixel's index and hands both to statmc_combine_records instead of store(); read_record is the
+    // inverse (fields the instantiation lacks become 0, as after load()).  Neither looks at the count: a record with n <= 0 is one
+    // the library passes over.
+    __device__ __forceinline__ void write_record(int32_t *rec) const {
+#pragma clang fp contract(off)
+        PixelStats copy = *this;
+        map_state(copy, [&rec](int v) {
+            *rec++ = v;
+            return v;
+        });
+    }
+    __device__ __forceinline__ void read_record(const int32_t *rec) {
+#pragma clang fp contract(off)
+        clear();
+        map_state(*this, [&rec](int) { return *rec++; });
     }
 };
 

@@ -123,7 +123,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -240,6 +240,11 @@ def load():
     lib.statmc_debug_compact_interleaved_path.argtypes = [C.c_int]
     lib.statmc_debug_compact_interleaved_window.argtypes = [C.c_int]
     lib.statmc_debug_last_compact_interleaved_path.restype = C.c_int
+    lib.statmc_state_dwords.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.statmc_state_dwords.restype = C.c_size_t
+    lib.statmc_gather_states.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_void_p]
+    lib.statmc_combine_records.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(StatType), C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int32,
+                                           C.c_void_p]
     lib.statmc_merge_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]
     lib.statmc_tile_moments.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_int,
@@ -1117,6 +1122,61 @@ def last_compact_interleaved_path():
     """What the calling thread's last compact_accumulate_interleaved launched: COMPACT_ILV_PATH_FUSED_STAGED, _FUSED_DIRECT or
     _GENERAL, plus COMPACT_ILV_PATH_SPLIT when the call's split_above was below INT32_MAX (0: nothing)."""
     return int(load().statmc_debug_last_compact_interleaved_path())
+
+
+def state_dwords(channels, max_moment, transform):
+    """statmc_state_dwords: the dwords of one state record of such a stat type -- the int32 count, then per channel mean, m2, m3,
+    film_mean, film_m2 as far as the type has them; 0 for values a stat type cannot have (no device needed)."""
+    return int(load().statmc_state_dwords(int(channels), int(max_moment), int(bool(transform))))
+
+
+def _state_arrays(stat_types, n, states, who, device=None):
+    """One contiguous int32 CUDA tensor [n, D_t] per stat type: the caller's, checked, or (states None) new ones on `device`."""
+    tc = _torch()
+    dw = [state_dwords(t.channels, t.max_moment, t.transform) for t in stat_types]
+    if states is None:
+        return [tc.empty((n, d), dtype=tc.int32, device=device) for d in dw]
+    if len(states) != len(stat_types):
+        raise ValueError("%s: one state array per stat type" % who)
+    for i, (s, d) in enumerate(zip(states, dw)):
+        if s.dtype != tc.int32 or not s.is_contiguous() or (s.numel() and not s.is_cuda) or s.numel() != n * d:
+            raise ValueError("%s: states[%d] must be a contiguous int32 CUDA tensor of %d x %d dwords" % (who, i, n, d))
+    return list(states)
+
+
+def gather_states(width, height, stat_types, pixels, out=None, stream=None):
+    """statmc_gather_states (include/statmc.h): `pixels` is an int32 device tensor, one entry per record; record i of every stat
+    type receives the stored state of pixel pixels[i] as state_dwords(...) dwords -- a value outside the film the state of no
+    samples.  stat_types: make_stat_type_record_field (the images only).  Returns one int32 tensor [n, D_t] per stat type (out:
+    the caller's, written in place).  Asynchronous; the images are only read."""
+    tc = _torch()
+    if pixels.dtype != tc.int32 or not pixels.is_contiguous():
+        raise ValueError("gather_states: pixels must be a contiguous int32 tensor")
+    n = pixels.numel()
+    states = _state_arrays(stat_types, n, out, "gather_states", device=pixels.device)
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    ptrs = (C.c_void_p * max(len(states), 1))(*[s.data_ptr() for s in states])
+    check(load().statmc_gather_states(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), n, ptrs,
+                                      stream if stream is not None else current_stream_handle()))
+    return states
+
+
+def combine_records(width, height, stat_types, pixels, states, split_above=None, stream=None):
+    """statmc_combine_records (include/statmc.h): merges the records (pixels[i], states[t][i]) into the images of stat_types
+    (make_stat_type_record_field) -- per pixel in ascending record index, the stored state as part A and every record with a
+    positive count as part B of a two-part combine: the bits of combine_statistics / combine_many on the same parts.  A pixel
+    without such a record keeps every bit.  split_above = k: a pixel with more than k records is folded by the 64 lanes of a wave
+    (64 chunks, merged in a fixed tree); None: INT32_MAX, never split.  Asynchronous; the tensors must stay alive until it ran."""
+    tc = _torch()
+    if pixels.dtype != tc.int32 or not pixels.is_contiguous():
+        raise ValueError("combine_records: pixels must be a contiguous int32 tensor")
+    n = pixels.numel()
+    states = _state_arrays(stat_types, n, states, "combine_records")
+    arr = (StatType * max(len(stat_types), 1))(*stat_types)
+    ptrs = (C.c_void_p * max(len(states), 1))(*[s.data_ptr() for s in states])
+    check(load().statmc_combine_records(int(width), int(height), arr, len(stat_types), pixels.data_ptr(), n, ptrs,
+                                        INT32_MAX if split_above is None else int(split_above),
+                                        stream if stream is not None else current_stream_handle()))
 
 
 def calculate_mean_vars(n, film_m2, film_var, row_n_quirk=True, stream=None):

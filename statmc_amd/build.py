@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
-           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_compact.hip"]
-HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_compact.hip", "statmc_state_records.hip"]
+HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_state_records_args.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -109,6 +109,8 @@ COMPACT_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_args")   # t
 COMPACT_ILV_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_interleaved_args")   # tests/cpp/test_compact_interleaved_args.cpp: statmc_compact_interleaved_args.h, no device, no library
 COMPACT_ILV_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_accumulate_interleaved")   # tests/cpp/test_compact_accumulate_interleaved.cpp: Estimator::AccumulateCompactInterleaved
 COMPACT_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_accumulate")   # tests/cpp/test_compact_accumulate.cpp: Estimator::CompactOffsets / AccumulateCompact
+STATE_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_state_records_args")   # tests/cpp/test_state_records_args.cpp: statmc_state_records_args.h, no device, no library
+STATE_BIN = os.path.join(ROOT, "tools", "bin", "test_state_records")   # tests/cpp/test_state_records.cpp: Estimator::GatherStates / CombineRecords
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
          DEVICE_ACC_BIN: os.path.join("..", "tests", "cpp", "test_device_accumulate.cpp"),
@@ -128,7 +130,9 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          COMPACT_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_args.cpp"),
          COMPACT_ILV_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_interleaved_args.cpp"),
          COMPACT_ILV_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate_interleaved.cpp"),
-         COMPACT_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate.cpp")}
+         COMPACT_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate.cpp"),
+         STATE_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_state_records_args.cpp"),
+         STATE_BIN: os.path.join("..", "tests", "cpp", "test_state_records.cpp")}
 # A renderer's own kernel accumulating through include/statmc_device_api.hpp (tools/device_accumulate_example.hip), built with
 # hipcc's DEFAULT floating-point flags -- not the library's -ffp-contract=off: the header's bits must not depend on them.
 DEVICE_EXAMPLE_SO = os.path.join(ROOT, "tools", "bin", "libstatmc_device_example.so")
@@ -153,6 +157,7 @@ def tools_hash():
     files.append(os.path.join(CSRC, "statmc_plan_args.h"))    # ... test_plan_args.cpp the planning entries' checks
     files.append(os.path.join(CSRC, "statmc_compact_args.h"))    # ... test_compact_args.cpp the compact entries' checks
     files.append(os.path.join(CSRC, "statmc_compact_interleaved_args.h"))    # ... and test_compact_interleaved_args.cpp the interleaved compact entry's
+    files.append(os.path.join(CSRC, "statmc_state_records_args.h"))    # ... and test_state_records_args.cpp the state-record entries'
     for path in files:
         with open(path, "rb") as f:
             h.update(os.path.basename(path).encode() + b"\0" + f.read())
@@ -186,7 +191,7 @@ def build_tools(force=False):
     for binary, src in TOOLS.items():
         tmp = binary + ".tmp%d" % os.getpid()
         extra = ["-L", os.path.dirname(DEVICE_EXAMPLE_SO), "-lstatmc_device_example", "-Wl,-rpath,$ORIGIN"] if binary == DEVICE_ACC_BIN else []
-        if binary in (ACC_PLAN_BIN, ACC_ARGS_BIN, COMPACT_ARGS_BIN, COMPACT_ILV_ARGS_BIN):      # statmc_device.h includes the HIP runtime's header
+        if binary in (ACC_PLAN_BIN, ACC_ARGS_BIN, COMPACT_ARGS_BIN, COMPACT_ILV_ARGS_BIN, STATE_ARGS_BIN):      # statmc_device.h includes the HIP runtime's header
             extra = ["-D__HIP_PLATFORM_AMD__", "-I", rocm_inc]
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-pthread",
                                "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", src), "-o", tmp,

@@ -19,6 +19,7 @@
 #include "statmc_plan_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
+#include "statmc_state_records_args.h"
 
 #include <atomic>
 
@@ -1592,6 +1593,39 @@ int statmc_accumulate_records_interleaved(uint16_t width, uint16_t height, const
 int statmc_accumulate_records_interleaved_split(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const void *records,
                                                 const statmc_record_layout *layout, int64_t n_records, int32_t split_above, void *stream) {
     return accumulate_records(statmc::RecordsCall{width, height, types, n_types, nullptr, records, layout, true, n_records, &split_above, stream});
+}
+
+// statmc_gather_states / statmc_combine_records: every rule of include/statmc.h ahead of the device (statmc_state_records_args.h), the
+// descriptors' own among them; zero types or zero records is a no-op wherever it is asked.  The combine groups its records in the
+// records entries' per-(device, stream) workspace; the gather has none.  Nothing is read back.
+int statmc_gather_states(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels, int64_t n_records,
+                         void *const *states, void *stream) {
+    ARG_TRY(statmc::check_gather_states_call(width, height, types, n_types, pixels, n_records, states, why()));
+    if (n_types == 0 || n_records == 0) return STATMC_OK;
+    statmc::StateRecordsArgs k;
+    memset(&k, 0, sizeof(k));
+    bool epilogue = false;
+    ARG_TRY(statmc::fill_state_records_args(k, width, height, types, n_types, pixels, n_records, states, INT32_MAX, true, epilogue, why()));
+    NEED_READY();
+    HIP_TRY(statmc::launch_gather_states(k, S(stream)));
+    return STATMC_OK;
+}
+int statmc_combine_records(uint16_t width, uint16_t height, const statmc_stat_type *types, int n_types, const int32_t *pixels, int64_t n_records,
+                           const void *const *states, int32_t split_above, void *stream) {
+    ARG_TRY(statmc::check_combine_records_call(width, height, types, n_types, pixels, n_records, states, split_above, why()));
+    if (n_types == 0 || n_records == 0) return STATMC_OK;
+    statmc::StateRecordsArgs k;
+    memset(&k, 0, sizeof(k));
+    bool epilogue = false;
+    ARG_TRY(statmc::fill_state_records_args(k, width, height, types, n_types, pixels, n_records, states, split_above, false, epilogue, why()));
+    NEED_READY();
+    if (int rc = epilogue ? prepass_context(dstate, k.ctx) : STATMC_OK) return rc;
+    statmc::RecordsWorkspace w;
+    char *ws = nullptr;
+    HIP_TRY(statmc::records_workspace_layout(k.n_records, k.n_px, w));
+    if (int rc = records_workspace(w.bytes, stream, &ws)) return rc;
+    HIP_TRY(statmc::launch_combine_records(k, w, ws, S(stream)));
+    return STATMC_OK;
 }
 
 // statmc_compact_offsets / statmc_compact_accumulate: every rule of include/statmc.h ahead of the device (statmc_compact_args.h),

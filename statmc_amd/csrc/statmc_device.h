@@ -206,6 +206,15 @@ hipError_t records_interleaved_workspace_layout(long long n_records, long long n
 hipError_t launch_accumulate_records_interleaved(const RecordsInterleavedArgs &a, const RecordsInterleavedPlan &plan, const RecordsWorkspace &w, char *ws,
                                                  int phases, int split_above, hipStream_t s);
 
+// statmc_gather_states / statmc_combine_records (statmc_state_records.hip): argument block and checks are statmc_state_records_args.h's.
+// The combine groups its records as statmc_accumulate_records does -- group_records_by_pixel is that entry's grouping step on its
+// own (statmc_records.hip): seg[] zeroed, the stable sort of the record indices by pixel into order[], seg[], in the workspace
+// block ws that records_workspace_layout laid out.
+struct StateRecordsArgs;
+hipError_t group_records_by_pixel(const int32_t *pixels, long long n_records, long long n_px, const RecordsWorkspace &w, char *ws, hipStream_t s);
+hipError_t launch_gather_states(const StateRecordsArgs &a, hipStream_t s);
+hipError_t launch_combine_records(const StateRecordsArgs &a, const RecordsWorkspace &w, char *ws, hipStream_t s);
+
 // statmc_pool_statistics (statmc_pool.hip): the argument block and its checks are statmc_pool_args.h's, a host-only header
 struct PoolArgs;
 hipError_t launch_pool(const PoolArgs &a, hipStream_t s);

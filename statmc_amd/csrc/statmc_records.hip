@@ -590,14 +590,17 @@ hipError_t records_interleaved_workspace_layout(long long n_records, long long n
     return hipSuccess;
 }
 
+// the grouping of the per-array source on its own: statmc_combine_records' records are grouped like samples (statmc_state_records.hip)
+hipError_t group_records_by_pixel(const int32_t *pixels, long long n_records, long long n_px, const RecordsWorkspace &w, char *ws, hipStream_t s) {
+    size_t temp_bytes = w.temp_bytes;
+    return group_records(KeyIterator(pixels, RecordKey{(unsigned)n_px}), n_records, (unsigned)n_px, w, ws, temp_bytes, s);
+}
+
 hipError_t launch_accumulate_records(const RecordsArgs &a_in, const int32_t *pixels, const RecordsWorkspace &w, char *ws, int phases,
                                      int split_above, hipStream_t s) {
     RecordsArgs a = a_in;
     if (phases & 1) {
-        size_t temp_bytes = w.temp_bytes;
-        if (hipError_t e = group_records(KeyIterator(pixels, RecordKey{(unsigned)a.n_px}), a.n_records, (unsigned)a.n_px, w, ws, temp_bytes, s);
-            e != hipSuccess)
-            return e;
+        if (hipError_t e = group_records_by_pixel(pixels, a.n_records, a.n_px, w, ws, s); e != hipSuccess) return e;
     }
     if (phases & 2) {
         a.order = reinterpret_cast<const int32_t *>(ws + w.order_off);

@@ -134,6 +134,33 @@ class FilmStats:
         key = self._prepass_key()
         self._prepass_current = key if (fuse and self._prepass_current == key) else None
 
+    def _state_types(self, prepass):
+        fuse = prepass and self.fused_prepass and "radiance" in self.types
+        return [api.make_stat_type_record_field(STAT_TYPES[t]["channels"], self.state[t], STAT_TYPES[t]["transform"], STAT_TYPES[t]["max_moment"],
+                                                prepass_into=(self.mean_corr, self.disc) if (fuse and t == "radiance") else None)
+                for t in self.types], fuse
+
+    def gather_states(self, pixels):
+        """The states of the listed pixels as records: pixels is an int32 CUDA tensor of y * width + x (a value outside the film:
+        the state of no samples).  Returns {type: int32 tensor [n, D]} (statmc_gather_states); the film is only read.  The list of
+        the pixels a plan touches is api.compact_offsets(counts, cap=1, owners_capacity=...)[1]."""
+        sts, _ = self._state_types(False)
+        return dict(zip(self.types, api.gather_states(self.width, self.height, sts, pixels)))
+
+    def combine_records(self, pixels, states, split_above=None):
+        """Merges (pixel, state) records -- gather_states of another film of the same types, or records a renderer's kernel wrote
+        with PixelStats::write_record -- into this film: per pixel in ascending record index, the bits of combine_ with the same
+        parts in that order; a pixel without a record of positive count keeps every bit (statmc_combine_records).  states: {type:
+        int32 tensor [n, D]} for every type of this film.  split_above: None = never split.  With fused_prepass the touched pixels'
+        mean-corr / discriminator are written by the launch's epilogue."""
+        if set(states) != set(self.types):
+            raise ValueError("combine_records: states must carry this film's stat types (%s / %s)" % (self.types, sorted(states)))
+        sts, fuse = self._state_types(True)
+        api.combine_records(self.width, self.height, sts, pixels, [states[t] for t in self.types], split_above=split_above)
+        # pixels without a record keep their mean-corr / discriminator: current only if they were current before
+        key = self._prepass_key()
+        self._prepass_current = key if (fuse and self._prepass_current == key) else None
+
     def combine_(self, other):
         """Combines the statistics of `other` -- the same film, its own samples -- into self, so that self holds the
         statistics of the union of both sample sets (statmc_combine_statistics: one launch).  Every stat type is weighed

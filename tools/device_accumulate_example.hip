@@ -16,6 +16,9 @@
 //               the slots' states combined by two-part statmc_combine_statistics calls in the header's tree order
 //               (tests/test_device_reduce_gpu.py)
 //   gen_fold_lanes  gen_fold with G lanes per pixel
+//   fold_arena_records  fold_arena for a kernel that does not own its pixels: one thread per pixel folds the arena's samples from
+//               clear() and writes the state as a record (PixelStats::write_record) instead of storing it -- what
+//               statmc_combine_records merges into a film (tests/test_state_records_gpu.py)
 //
 // Every launcher returns 0 or a negative STATMC_ERR_* (include/statmc.h), and only enqueues on `stream`.
 #include <hip/hip_runtime.h>
@@ -59,6 +62,40 @@ __global__ __launch_bounds__(kBlock) void fold_arena_kernel(statmc_stat_type t, 
         }
     }
     ps.store(t, p);
+}
+
+// ------------------------------------------------------------------ fold_arena_records
+// The partial state of a pixel this kernel does not own: folded from clear(), never stored; record p -- state_dwords<C, MAXM,
+// TRANSFORM>() dwords at records + p * D -- goes to statmc_combine_records with pixels[p] = p.
+template <int C, int MAXM, bool TRANSFORM>
+__global__ __launch_bounds__(kBlock) void fold_arena_records_kernel(long long n_px, const float *arena, int n_samples, int32_t *records) {
+    const long long p = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_px) return;
+    PixelStats<C, MAXM, TRANSFORM> ps;
+    ps.clear();
+    for (int s = 0; s < n_samples; s++) {
+        const float *q = arena + ((long long)s * n_px + p) * C;
+        float smp[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) smp[c] = q[c];
+        ps.add(smp);
+    }
+    ps.write_record(records + p * statmc::device::state_dwords<C, MAXM, TRANSFORM>());
+}
+template <int C>
+int records_dispatch(int transform, int max_moment, long long n_px, const float *arena, int n_samples, int32_t *records, hipStream_t s) {
+#define STATMC_RECORDS(m, t)                                                                                                        \
+    hipLaunchKernelGGL((fold_arena_records_kernel<C, m, t>), dim3(grid_for(n_px)), dim3(kBlock), 0, s, n_px, arena, n_samples, records); \
+    return launched();
+    if (transform) {
+        if (max_moment == 3) { STATMC_RECORDS(3, true) }
+        if (max_moment == 2) { STATMC_RECORDS(2, true) }
+        STATMC_RECORDS(1, true)
+    }
+    if (max_moment == 3) { STATMC_RECORDS(3, false) }
+    if (max_moment == 2) { STATMC_RECORDS(2, false) }
+    STATMC_RECORDS(1, false)
+#undef STATMC_RECORDS
 }
 
 // ------------------------------------------------------------------ fold_arena_slots
@@ -527,6 +564,18 @@ int gen_fold_lanes(uint32_t seed, int width, int height, int sample0, int n_samp
     const statmc_prepass_context c = ctx ? *ctx : statmc_prepass_context{nullptr, 0, 0};
     return launch_gen_fold_lanes(seed, (long long)width * height, sample0, n_samples, G, ft, c, ctx ? 1 : 0,
                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+// fold_arena without a film: every pixel's samples folded from the state of no samples and written as state record p of
+// `records` (device, [width * height][statmc_state_dwords(channels, max_moment, transform)] dwords, 4-byte aligned).
+int fold_arena_records(int channels, int transform, int max_moment, int width, int height, const float *arena, int n_samples, int32_t *records,
+                       void *stream) {
+    if (width <= 0 || height <= 0 || n_samples < 0 || (n_samples > 0 && !arena) || !records) return STATMC_ERR_INVALID;
+    if ((channels != 1 && channels != 3) || max_moment < 1 || max_moment > 3) return STATMC_ERR_INVALID;
+    const long long n_px = (long long)width * height;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return channels == 3 ? records_dispatch<3>(transform, max_moment, n_px, arena, n_samples, records, s)
+                         : records_dispatch<1>(transform, max_moment, n_px, arena, n_samples, records, s);
 }
 
 }  // extern "C"

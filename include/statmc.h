@@ -862,6 +862,62 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
                         int32_t *sample_counts, statmc_plan_result *result,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- order statistics and threshold counts of a score image (no counterpart in the reference): what a stopping rule asks of the
+ * error map -- "the 95th percentile of the relative score is under 2 %", "at most 1 % of the pixels are above tau" -- answered on
+ * the device, one small struct read back.  `score` is statmc_sample_scores' or the renderer's own metric, a packed width x height
+ * plane.
+ *
+ * DEFINITION.  The key of a score is integer arithmetic on its bit pattern b, so no denormal mode and no comparison instruction
+ * reaches a bit:
+ *     key(b) = 0   if (b & 0x7FFFFFFF) > 0x7F800000     (NaN, either sign)
+ *            = 0   if b has the sign bit                (-0, negatives, -inf)
+ *            = b   otherwise                            (+0, subnormals, normals, +inf: bit order is value order)
+ * A pixel statmc_plan_samples calls dead through NaN or a negative score sorts with +0.  The classes are statmc_plan_samples',
+ * stated on keys:  saturated  key > 0x5D800000 (2^60);  live  0x21800000 <= key <= 0x5D800000;  dead  the rest.
+ *
+ * statmc_score_select: `ranks` is a HOST array of n_ranks entries, 1 <= n_ranks <= STATMC_SELECT_MAX_RANKS, each in
+ * [0, width * height), in any order, repeats allowed.  With sorted_keys the film's keys in non-decreasing order:
+ *     value_bits[i] = sorted_keys[rank[i]]          (the rank[i]-th smallest key, 0-based; a float bit pattern, never NaN)
+ *     n_below[i]    = the number of pixels with key <  value_bits[i]
+ *     n_equal[i]    = the number of pixels with key == value_bits[i]
+ * Slots n_ranks .. 7 of the four arrays are written as 0.  Hence n_below[i] <= rank[i] < n_below[i] + n_equal[i], value_bits is
+ * non-decreasing in rank, and the same inputs give the same bits on every run: everything is an integer count, so no order
+ * reaches a bit.  n_live / n_saturated equal statmc_plan_result's for the same score image.
+ * Asynchronous on `stream`; nothing is read back and nothing allocated.  The caller owns `workspace`, at least
+ * statmc_score_select_workspace() bytes (a pure function, no device needed) and 8-byte aligned; the call zeroes it on `stream` -- a
+ * workspace full of garbage gives the same result -- and leaves nothing of use in it.  `result` is device memory, 8-byte aligned;
+ * besides the workspace only `result` is written.  A most-significant-digit radix select on the device: four passes of one 8-bit
+ * digit each, every workgroup deriving the prefixes that hold the ranks from the totals of the passes before, then one small
+ * launch that writes the result; no kernel waits for another workgroup.
+ *
+ * statmc_score_count_above: `thresholds` is a HOST array of n_thresholds entries, 1 to 8, none of them NaN;
+ *     counts[i] = the number of pixels with key(score_p) > key(thresholds[i])
+ * so a negative threshold counts the pixels above +0.  counts is device memory, n_thresholds entries, 8-byte aligned.  One pass over
+ * the score image behind the zeroing of counts on `stream`; asynchronous on `stream`.  For a threshold equal to a select's
+ * value_bits[i], counts = n_px - n_below[i] - n_equal[i].
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL score,
+ * result / counts, ranks / thresholds or workspace; score not 4-byte aligned; result, counts or workspace not 8-byte aligned;
+ * n_ranks / n_thresholds outside 1 to 8; a rank outside the film; a NaN threshold; workspace_bytes below the helper's answer; result
+ * or counts overlapping score, result overlapping the workspace, the workspace overlapping score.  STATMC_ERR_NO_DEVICE before
+ * statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2e, profiles/score_select.jsonl. */
+#define STATMC_SELECT_MAX_RANKS 8
+typedef struct statmc_select_result { /* device, written by the call */
+    int64_t n_px, n_live, n_saturated; /* n_live / n_saturated equal statmc_plan_result's for the same score image */
+    int32_t n_ranks, pad;
+    int64_t rank[STATMC_SELECT_MAX_RANKS];        /* as asked */
+    uint32_t value_bits[STATMC_SELECT_MAX_RANKS]; /* key of the rank[i]-th smallest pixel, 0-based: sorted_keys[rank[i]] */
+    int64_t n_below[STATMC_SELECT_MAX_RANKS];     /* pixels with key <  value_bits[i] */
+    int64_t n_equal[STATMC_SELECT_MAX_RANKS];     /* pixels with key == value_bits[i] */
+} statmc_select_result;
+
+size_t statmc_score_select_workspace(void); /* bytes; pure, no device needed */
+int statmc_score_select(uint16_t width, uint16_t height, const float *score, const int64_t *ranks, int n_ranks,
+                        statmc_select_result *result, void *workspace, size_t workspace_bytes, void *stream);
+int statmc_score_count_above(uint16_t width, uint16_t height, const float *score, const float *thresholds, int n_thresholds,
+                             int64_t *counts, void *stream);
+
 /* ---- the compact arena of a planned iteration: every pixel's samples back to back, pixels in raster order (CSR).  Pixel p owns
  * positions [offsets[p], offsets[p + 1]) of a sample-major [total][channels] array per stat type: no pixel index per sample, no
  * sort, no dead slots, `total` samples of memory.  The loop: statmc_plan_samples -> statmc_compact_offsets -> the renderer writes

@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <condition_variable>
 #include <cmath>
 #include <cstdint>
@@ -38,6 +39,7 @@
 #include <memory>
 #include <mutex>
 #include <regex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <unordered_set>
@@ -1028,6 +1030,7 @@ class Estimator {
     void EnableDeviceAccumulation(size_t maxHostBytes = (size_t)2 << 30, bool dryRun = false) {
         if (!allocateDevice && !dryRun) throw Error(STATMC_ERR_INVALID, "device accumulation needs device images");
         std::lock_guard<std::mutex> lk(acc.mu);
+        plan.touched++;   // (the statistics are zeroed below)
         acc.enabled = true;
         acc.dry = dryRun;
         acc.arenas.clear();
@@ -1069,6 +1072,7 @@ class Estimator {
     // Statistics of one stat type back to zero (the reference re-creates the it-radiance tiles
     // every iteration, statpath.cpp:194-207).
     void ResetStatistics(const unsigned char statTypeIndex) {
+        plan.touched++;
         for (auto *bufs : {&nBuffers, &meanBuffers, &m2Buffers, &m3Buffers, &filmBuffers, &filmM2Buffers})
             for (Buffer &b : (*bufs)[statTypeIndex])
                 check(statmc_memset(b.gpuMat.data(), 0, b.gpuMat.bytes(), stream.handle()));
@@ -1121,22 +1125,14 @@ class Estimator {
     // (max_moment 3; its statmc_prepass_context comes from statmc_get_prepass_context).  Needs EnableDeviceAccumulation(); samples
     // staged by Merge*Tile(s) so far are flushed first, so that a kernel enqueued on DeviceStream() afterwards folds its samples
     // behind them.  After such a kernel Upload / Denoise / Download and DownloadStatistics behave as after a flush.
+    // The descriptor may be kept: the images never move, and whoever holds it -- a kernel of the renderer's, a C-ABI
+    // statmc_accumulate* call -- may write the statistics at any later time without this Estimator seeing it.  So once the
+    // descriptor of a (type, bounce) has been handed out here, PlanSamples / ScoreSelect / ScoreCountAbove score that (type, bounce)
+    // afresh on every call, for good (the Estimator's own Accumulate* entries do not count: the Estimator sees those).
     statmc_stat_type DeviceStatistics(unsigned char statTypeIndex, unsigned char bounceIndex, bool withPrepass = false) {
-        {
-            std::lock_guard<std::mutex> lk(acc.mu);
-            if (!acc.enabled || acc.dry)
-                throw Error(STATMC_ERR_INVALID, "DeviceStatistics: call EnableDeviceAccumulation() first (the statistics must live on the device)");
-        }
-        if (statTypeIndex >= statTypeConfigs.nEnabled || bounceIndex >= statTypeConfigs.configs[statTypeIndex].nBounces)
-            throw Error(STATMC_ERR_INVALID, "DeviceStatistics: no such buffer");
-        const StatTypeConfig &cfg = statTypeConfigs.configs[statTypeIndex];
-        if (withPrepass && cfg.maxMoment < 3) throw Error(STATMC_ERR_INVALID, "DeviceStatistics: the pre-pass needs max_moment 3");
-        FlushSamples();
-        statmc_stat_type t = statTypeFor(statTypeIndex, bounceIndex, nullptr);   // (film_mean / film_m2: transform types only)
-        if (withPrepass) {
-            t.mean_corr = static_cast<float *>(meanCorrBuffers[statTypeIndex][bounceIndex].gpuMat.data());
-            t.discriminator = static_cast<float *>(discriminatorBuffers[statTypeIndex][bounceIndex].gpuMat.data());
-        }
+        const statmc_stat_type t = writableStatistics(statTypeIndex, bounceIndex, withPrepass);
+        std::lock_guard<std::mutex> lk(acc.mu);
+        plan.handedOut.insert({statTypeIndex, bounceIndex});
         return t;
     }
     // The stream (hipStream_t) this Estimator enqueues on: a renderer launches its accumulating kernel there, between
@@ -1160,7 +1156,7 @@ class Estimator {
     void AccumulateRecords(const int32_t *d_pixels, int64_t n_records, const std::vector<RecordSamples> &buffers) {
         std::vector<statmc_stat_type> types;
         for (const RecordSamples &r : buffers) {
-            statmc_stat_type t = DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);   // validates, flushes staged samples
+            statmc_stat_type t = writableStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);   // validates, flushes staged samples
             t.samples = r.d_samples;
             types.push_back(t);
         }
@@ -1174,7 +1170,7 @@ class Estimator {
     void AccumulateRecords(const int32_t *d_pixels, int64_t n_records, const std::vector<RecordSamples> &buffers, int splitAbove) {
         std::vector<statmc_stat_type> types;
         for (const RecordSamples &r : buffers) {
-            statmc_stat_type t = DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);
+            statmc_stat_type t = writableStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass);
             t.samples = r.d_samples;
             types.push_back(t);
         }
@@ -1203,7 +1199,7 @@ class Estimator {
         std::vector<statmc_stat_type> types;
         std::vector<void *> states;
         for (const StateRecords &r : buffers) {
-            types.push_back(DeviceStatistics(r.statTypeIndex, r.bounceIndex, false));   // validates, flushes staged samples
+            types.push_back(deviceImages(r.statTypeIndex, r.bounceIndex, false));   // validates, flushes staged samples; only read
             states.push_back(r.d_states);
         }
         check(statmc_set_device(device));
@@ -1213,7 +1209,7 @@ class Estimator {
         std::vector<statmc_stat_type> types;
         std::vector<const void *> states;
         for (const StateRecords &r : buffers) {
-            types.push_back(DeviceStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass));
+            types.push_back(writableStatistics(r.statTypeIndex, r.bounceIndex, r.withPrepass));
             states.push_back(r.d_states);
         }
         check(statmc_set_device(device));
@@ -1253,7 +1249,7 @@ class Estimator {
         l.stride = layout.stride;
         l.pixel_offset = layout.pixelOffset;
         for (const RecordField &f : fields) {
-            statmc_stat_type t = DeviceStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
+            statmc_stat_type t = writableStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
             l.sample_offset[types.size()] = f.offset;
             l.sample_format[types.size()] = f.format;
             types.push_back(t);
@@ -1288,7 +1284,7 @@ class Estimator {
         std::vector<statmc_stat_type> types;
         std::vector<int32_t> formats;
         for (const FilmSamples &b : buffers) {
-            statmc_stat_type t = DeviceStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
+            statmc_stat_type t = writableStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
             t.samples = static_cast<const float *>(b.d_samples);
             t.n_samples = nSamples;
             types.push_back(t);
@@ -1311,19 +1307,14 @@ class Estimator {
     };
     SamplePlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, int64_t budget, int32_t cMin, int32_t cMax,
                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
-        const statmc_stat_type t = DeviceStatistics(statTypeIndex, bounceIndex);   // validates, flushes staged samples
-        joinUploads();
-        check(statmc_set_device(device));
+        statmc_stat_type t;
+        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true);   // validates, flushes staged samples
         const size_t px = (size_t)width * height, wsBytes = statmc_plan_samples_workspace((uint16_t)width, (uint16_t)height);
-        plan.scores.reserve(px * sizeof(float));
         plan.counts.reserve(px * sizeof(int32_t));
         plan.workspace.reserve(wsBytes);
         plan.result.reserve(sizeof(statmc_plan_result));
-        float *scores = static_cast<float *>(plan.scores.ptr);
         int32_t *counts = static_cast<int32_t *>(plan.counts.ptr);
         statmc_plan_result *d_result = static_cast<statmc_plan_result *>(plan.result.ptr);
-        check(statmc_sample_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, t.n, t.film_mean ? t.film_mean : t.mean,
-                                   t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
         check(statmc_plan_samples((uint16_t)width, (uint16_t)height, scores, t.n, budget, cMin, cMax, counts, d_result, plan.workspace.ptr, wsBytes,
                                   stream.handle()));
         SamplePlan out{counts, statmc_plan_result{}};
@@ -1331,6 +1322,49 @@ class Estimator {
         Synchronize();
         return out;
     }
+
+    // ---- order statistics of the noise score, for a stopping rule (statmc_score_select / statmc_score_count_above;
+    // include/statmc.h has the definitions).  The score of (type, bounce) as PlanSamples computes it.  PlanSamples scores on every
+    // call; these two read the score image a PlanSamples, ScoreSelect or ScoreCountAbove of the same type, bounce, metric and eps
+    // left, instead of computing it twice, only where this Estimator knows the statistics unchanged since: no flush of staged
+    // samples, no Accumulate* / CombineRecords / ResetStatistics / CombineStatistics / EnableDeviceAccumulation, no PoolStatistics
+    // into this Estimator -- and the (type, bounce)'s descriptor never handed out through DeviceStatistics (see there).  Both enqueue on DeviceStream() and return without
+    // waiting; the device pointers they return stay valid until the next call of the same method.  `ranks`: 1 to 8 ranks in
+    // [0, width * height); `thresholds`: 1 to 8, none NaN.  Needs EnableDeviceAccumulation(); staged samples are flushed first.
+    const statmc_select_result *ScoreSelect(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<int64_t> &ranks,
+                                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+        statmc_stat_type t;
+        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t);
+        const size_t wsBytes = statmc_score_select_workspace();
+        plan.selectWorkspace.reserve(wsBytes);
+        plan.selectResult.reserve(sizeof(statmc_select_result));
+        statmc_select_result *d_result = static_cast<statmc_select_result *>(plan.selectResult.ptr);
+        check(statmc_score_select((uint16_t)width, (uint16_t)height, scores, ranks.data(), (int)ranks.size(), d_result, plan.selectWorkspace.ptr,
+                                  wsBytes, stream.handle()));
+        return d_result;
+    }
+    const int64_t *ScoreCountAbove(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<float> &thresholds,
+                                   int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+        statmc_stat_type t;
+        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t);
+        plan.aboveCounts.reserve(STATMC_SELECT_MAX_RANKS * sizeof(int64_t));
+        int64_t *d_counts = static_cast<int64_t *>(plan.aboveCounts.ptr);
+        check(statmc_score_count_above((uint16_t)width, (uint16_t)height, scores, thresholds.data(), (int)thresholds.size(), d_counts, stream.handle()));
+        return d_counts;
+    }
+    // The rank of the q-quantile among nPixels keys by the nearest-rank rule, max(0, ceil(q * nPixels) - 1), in integer arithmetic
+    // on q as the double it is: what ScoreSelect takes for "the 95th percentile".  q in [0, 1].
+    static int64_t NearestRank(double q, int64_t nPixels) {
+        if (!(q > 0.0) || nPixels <= 0) return 0;
+        int e;
+        const double m = std::frexp(std::min(q, 1.0), &e);                                  // q = m 2^e, 0.5 <= m < 1, e <= 1
+        const unsigned __int128 num = (unsigned __int128)(uint64_t)std::ldexp(m, 53) * (uint64_t)nPixels;   // q nPixels = num 2^(e - 53)
+        const int sh = 53 - e;
+        const unsigned __int128 up = sh >= 128 ? (unsigned __int128)1 : (num >> sh) + ((num & (((unsigned __int128)1 << sh) - 1)) != 0);
+        return (int64_t)up - 1;   // (num > 0: up >= 1)
+    }
+    // how many times a score image was computed (tests: the reuse above)
+    size_t ScoreImagesComputed() const { return nScoreImages; }
 
     // ---- the compact arena of a planned iteration (statmc_compact_offsets + statmc_compact_accumulate; include/statmc.h).  The
     // loop: PlanSamples -> CompactOffsets(plan.d_counts, cap, d_offsets) -> the renderer writes pixel p's sample s at position
@@ -1357,7 +1391,7 @@ class Estimator {
         std::vector<statmc_stat_type> types;
         std::vector<int32_t> formats;
         for (const FilmSamples &b : buffers) {
-            statmc_stat_type t = DeviceStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
+            statmc_stat_type t = writableStatistics(b.statTypeIndex, b.bounceIndex, b.withPrepass);   // validates, flushes staged samples
             t.samples = static_cast<const float *>(b.d_samples);
             types.push_back(t);
             formats.push_back(b.format);
@@ -1380,7 +1414,7 @@ class Estimator {
         l.stride = layout.stride;
         l.pixel_offset = layout.pixelOffset;
         for (const RecordField &f : typeList) {
-            statmc_stat_type t = DeviceStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
+            statmc_stat_type t = writableStatistics(f.statTypeIndex, f.bounceIndex, f.withPrepass);   // validates, flushes staged samples
             l.sample_offset[types.size()] = f.offset;
             l.sample_format[types.size()] = f.format;
             types.push_back(t);
@@ -1499,6 +1533,7 @@ class Estimator {
             first.push_back(rest.back());
             rest.pop_back();
         }
+        coarse.plan.touched++;
         check(statmc_pool_statistics(width, height, k, first.data(), (int)first.size(), coarse.stream.handle()));
         for (size_t q = 0; q < rest.size(); q += cap)
             check(statmc_pool_statistics(width, height, k, rest.data() + q, (int)std::min(cap, rest.size() - q), coarse.stream.handle()));
@@ -1512,6 +1547,59 @@ class Estimator {
             same = a[i].type == b[i].type && a[i].nChannels == b[i].nChannels && a[i].transform == b[i].transform &&
                    a[i].maxMoment == b[i].maxMoment && a[i].bounceStart == b[i].bounceStart && a[i].nBounces == b[i].nBounces;
         return same;
+    }
+    // DeviceStatistics' checks, flush and descriptor, for a call of this Estimator's that only reads the statistics ...
+    statmc_stat_type deviceImages(unsigned char statTypeIndex, unsigned char bounceIndex, bool withPrepass = false) {
+        {
+            std::lock_guard<std::mutex> lk(acc.mu);
+            if (!acc.enabled || acc.dry)
+                throw Error(STATMC_ERR_INVALID, "DeviceStatistics: call EnableDeviceAccumulation() first (the statistics must live on the device)");
+        }
+        if (statTypeIndex >= statTypeConfigs.nEnabled || bounceIndex >= statTypeConfigs.configs[statTypeIndex].nBounces)
+            throw Error(STATMC_ERR_INVALID, "DeviceStatistics: no such buffer");
+        const StatTypeConfig &cfg = statTypeConfigs.configs[statTypeIndex];
+        if (withPrepass && cfg.maxMoment < 3) throw Error(STATMC_ERR_INVALID, "DeviceStatistics: the pre-pass needs max_moment 3");
+        FlushSamples();
+        statmc_stat_type t = statTypeFor(statTypeIndex, bounceIndex, nullptr);   // (film_mean / film_m2: transform types only)
+        if (withPrepass) {
+            t.mean_corr = static_cast<float *>(meanCorrBuffers[statTypeIndex][bounceIndex].gpuMat.data());
+            t.discriminator = static_cast<float *>(discriminatorBuffers[statTypeIndex][bounceIndex].gpuMat.data());
+        }
+        return t;
+    }
+    // ... and for one that writes them: a score image computed before is stale
+    statmc_stat_type writableStatistics(unsigned char statTypeIndex, unsigned char bounceIndex, bool withPrepass = false) {
+        const statmc_stat_type t = deviceImages(statTypeIndex, bounceIndex, withPrepass);
+        plan.touched++;
+        return t;
+    }
+    size_t nScoreImages = 0;
+    // plan.scores holding the score image of (type, bounce, metric, eps) for the statistics as they stand; t: the statistics'
+    // device images.  Computed unless `always` is false, the key of the image held says it is this one (Planning::ScoreKey) and
+    // the descriptor of (type, bounce) was never handed out.
+    const float *scoreImage(unsigned char statTypeIndex, unsigned char bounceIndex, int metric, float eps, statmc_stat_type &t, bool always = false) {
+        t = deviceImages(statTypeIndex, bounceIndex);   // validates, flushes staged samples
+        joinUploads();
+        check(statmc_set_device(device));
+        Planning::ScoreKey now;
+        now.valid = true, now.type = statTypeIndex, now.bounce = bounceIndex, now.metric = metric;
+        std::memcpy(&now.epsBits, &eps, sizeof(eps));
+        {
+            std::lock_guard<std::mutex> lk(acc.mu);
+            now.flushes = acc.nFlushes;
+            always = always || plan.handedOut.count({statTypeIndex, bounceIndex}) != 0;
+        }
+        now.touched = plan.touched.load();
+        plan.scores.reserve((size_t)width * height * sizeof(float));
+        float *scores = static_cast<float *>(plan.scores.ptr);
+        if (always || !(plan.scoresOf == now)) {
+            plan.scoresOf.valid = false;
+            check(statmc_sample_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, t.n, t.film_mean ? t.film_mean : t.mean,
+                                       t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
+            plan.scoresOf = now;
+            nScoreImages++;
+        }
+        return scores;
     }
     // one side of a combine or pool entry: the device images of (type i, bounce j) of Estimator e
     static statmc_stat_type statSide(Estimator &e, unsigned char i, unsigned char j, bool own) {
@@ -1634,6 +1722,7 @@ class Estimator {
                 check(statmc_combine_statistics(width, height, v.data(), (int)n, stream.handle()));
             }
         };
+        plan.touched++;
         call(first.data(), first.size());
         for (size_t k = 0; k < rest.size(); k += cap) call(rest.data() + k, std::min(cap, rest.size() - k));
     }
@@ -1785,8 +1874,26 @@ class Estimator {
         std::unordered_set<const Buffer *> deviceProduced;
     };
     mutable Accumulation acc;
-    struct Planning {                    // PlanSamples: allocated by the first call, kept
+    struct Planning {                    // PlanSamples / ScoreSelect / ScoreCountAbove: allocated by the first call, kept
         DeviceBytes scores, counts, workspace, result;
+        DeviceBytes selectWorkspace, selectResult, aboveCounts;
+        // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
+        // flushes of staged samples so far and `touched`, which every call that may write the statistics otherwise bumps
+        // (every Accumulate* entry and CombineRecords, ResetStatistics, CombineStatistics, PoolStatistics, EnableDeviceAccumulation)
+        struct ScoreKey {
+            bool valid = false;
+            unsigned char type = 0, bounce = 0;
+            int metric = 0;
+            uint32_t epsBits = 0;
+            size_t flushes = 0;
+            uint64_t touched = 0;
+            bool operator==(const ScoreKey &o) const {
+                return valid == o.valid && type == o.type && bounce == o.bounce && metric == o.metric && epsBits == o.epsBits &&
+                       flushes == o.flushes && touched == o.touched;
+            }
+        } scoresOf;
+        std::atomic<uint64_t> touched{0};
+        std::set<std::pair<unsigned char, unsigned char>> handedOut;   // (type, bounce) whose descriptor DeviceStatistics gave away; under acc.mu
     };
     Planning plan;
     DeviceBytes compactWorkspace;        // CompactOffsets: allocated by the first call, kept

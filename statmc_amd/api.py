@@ -110,6 +110,16 @@ class PlanResult(C.Structure):
                 ("n_live", C.c_int32), ("n_saturated", C.c_int32)]
 
 
+SELECT_MAX_RANKS = 8
+
+
+class SelectResult(C.Structure):
+    """statmc_select_result: what statmc_score_select writes to device memory."""
+    _fields_ = [("n_px", C.c_int64), ("n_live", C.c_int64), ("n_saturated", C.c_int64), ("n_ranks", C.c_int32), ("pad", C.c_int32),
+                ("rank", C.c_int64 * SELECT_MAX_RANKS), ("value_bits", C.c_uint32 * SELECT_MAX_RANKS),
+                ("n_below", C.c_int64 * SELECT_MAX_RANKS), ("n_equal", C.c_int64 * SELECT_MAX_RANKS)]
+
+
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
 PLAN_LEVEL_LO, PLAN_LEVEL_HI = 0x20000000, 0x5F000000   # statmc_plan_samples' level range [U_LO, U_HI]: 2^-63 .. 2^63
 PLAN_MAX_COUNT = 1 << 20
@@ -123,7 +133,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -227,6 +237,11 @@ def load():
     lib.statmc_plan_samples_workspace.restype = C.c_size_t
     lib.statmc_plan_samples.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                         C.POINTER(PlanResult), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.statmc_score_select_workspace.argtypes = []
+    lib.statmc_score_select_workspace.restype = C.c_size_t
+    lib.statmc_score_select.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(SelectResult), C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
+    lib.statmc_score_count_above.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_compact_offsets_workspace.restype = C.c_size_t
     lib.statmc_compact_offsets.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
@@ -768,6 +783,80 @@ def plan_samples(score, budget, c_min, c_max, n=None, out=None, workspace=None, 
         return out
     check(load().statmc_synchronize(st))
     return out, plan_result_dict(result)
+
+
+def score_select_workspace():
+    """statmc_score_select_workspace: the bytes of workspace statmc_score_select wants, for every film size (no device needed)."""
+    return int(load().statmc_score_select_workspace())
+
+
+_SELECT_WORDS = C.sizeof(SelectResult) // 8
+_select_scratch = {}    # (device index, stream handle) -> (workspace, result), as _plan_scratch
+
+
+def _score_image(score, what):
+    tc = _torch()
+    if score.dtype != tc.float32 or not score.is_cuda or not score.is_contiguous() or score.dim() != 2:
+        raise ValueError("%s: score must be a contiguous float32 CUDA tensor [H, W]" % what)
+    return int(score.shape[0]), int(score.shape[1])
+
+
+def read_select_result(t):
+    """The statmc_select_result a score_select call wrote into the int64 [32] device tensor `t`, as a dict whose per-rank fields are
+    lists of n_ranks entries; "values" are value_bits as numpy float32.  One small device-to-host copy: it synchronises with the work
+    that wrote `t` on the current stream; after a call on another stream synchronise that one first."""
+    import numpy as np
+    r = SelectResult.from_buffer_copy(t.cpu().numpy().tobytes())
+    k = int(r.n_ranks)
+    out = {f: int(getattr(r, f)) for f in ("n_px", "n_live", "n_saturated", "n_ranks")}
+    for f in ("rank", "value_bits", "n_below", "n_equal"):
+        out[f] = [int(v) for v in getattr(r, f)[:k]]
+    out["values"] = np.array(out["value_bits"], np.uint32).view(np.float32)
+    return out
+
+
+def score_select(score, ranks, workspace=None, result=None, stream=None):
+    """statmc_score_select: the ranks[i]-th smallest keys (0-based; 1 to 8 ranks, any order) of the float32 score image [H, W], with
+    the number of pixels below and equal to each, and the class counts (include/statmc.h).  Returns the device result, an int64 [32]
+    tensor holding the statmc_select_result's 256 bytes: read_select_result(t) downloads it.  Asynchronous; workspace (uint8, at
+    least score_select_workspace() bytes) and result are the caller's or, if None, tensors kept per (device, stream) until the next
+    call on that stream."""
+    tc = _torch()
+    h, w = _score_image(score, "score_select")
+    ranks = [int(r) for r in ranks]
+    st = stream if stream is not None else current_stream_handle()
+    if workspace is None or result is None:
+        key = (score.device.index, st.value if hasattr(st, "value") else int(st or 0))
+        held = _select_scratch.get(key)
+        if held is None:
+            held = (tc.empty(score_select_workspace(), dtype=tc.uint8, device=score.device),
+                    tc.empty(_SELECT_WORDS, dtype=tc.int64, device=score.device))
+            _select_scratch[key] = held
+        workspace = workspace if workspace is not None else held[0]
+        result = result if result is not None else held[1]
+    if result.dtype != tc.int64 or not result.is_cuda or not result.is_contiguous() or result.numel() < _SELECT_WORDS:
+        raise ValueError("score_select: result must be a contiguous int64 CUDA tensor of %d words" % _SELECT_WORDS)
+    arr = (C.c_int64 * max(len(ranks), 1))(*ranks)
+    check(load().statmc_score_select(w, h, score.data_ptr(), arr, len(ranks), C.cast(result.data_ptr(), C.POINTER(SelectResult)),
+                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), st))
+    return result
+
+
+def score_count_above(score, thresholds, out=None, stream=None):
+    """statmc_score_count_above: per threshold (1 to 8, none NaN) the number of pixels of the float32 score image [H, W] whose key is
+    above the threshold's (include/statmc.h).  Returns the int64 device tensor [len(thresholds)] (`out`, or a new one).
+    Asynchronous."""
+    tc = _torch()
+    h, w = _score_image(score, "score_count_above")
+    thresholds = [float(t) for t in thresholds]
+    if out is None:
+        out = tc.empty(max(len(thresholds), 1), dtype=tc.int64, device=score.device)[:len(thresholds)]
+    elif out.dtype != tc.int64 or not out.is_cuda or not out.is_contiguous() or out.numel() != len(thresholds):
+        raise ValueError("score_count_above: out must be a contiguous int64 CUDA tensor of one count per threshold")
+    arr = (C.c_float * max(len(thresholds), 1))(*thresholds)
+    check(load().statmc_score_count_above(w, h, score.data_ptr(), arr, len(thresholds), out.data_ptr() if out.numel() else None,
+                                          stream if stream is not None else current_stream_handle()))
+    return out
 
 
 def make_stat_type_arena(arena, channels, state, transform, max_moment, prepass_into=None):

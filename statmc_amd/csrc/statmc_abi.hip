@@ -17,6 +17,7 @@
 #include "statmc_records_plan.h"
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
+#include "statmc_select_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
 #include "statmc_state_records_args.h"
@@ -1470,6 +1471,29 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
     statmc::PlanArgs a;
     statmc::fill_plan_args(a, width, height, score, n, budget, c_min, c_max, sample_counts, result, workspace);
     HIP_TRY(statmc::launch_plan_samples(a, statmc::plan_workspace_bytes(width, height), S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_score_select / statmc_score_count_above: every rule of include/statmc.h ahead of the device (statmc_select_args.h), then the
+// launches of statmc_select.hip on `stream`; nothing is allocated and nothing read back.
+int statmc_score_select(uint16_t width, uint16_t height, const float *score, const int64_t *ranks, int n_ranks, statmc_select_result *result,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+    ARG_TRY(statmc::check_select_call(width, height, score, ranks, n_ranks, result, workspace, workspace_bytes,
+                                      statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::SelectArgs a;
+    statmc::fill_select_args(a, width, height, score, ranks, n_ranks, result, workspace);
+    HIP_TRY(statmc::launch_score_select(a, S(stream)));
+    return STATMC_OK;
+}
+
+int statmc_score_count_above(uint16_t width, uint16_t height, const float *score, const float *thresholds, int n_thresholds, int64_t *counts,
+                             void *stream) {
+    ARG_TRY(statmc::check_count_above_call(width, height, score, thresholds, n_thresholds, counts, statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::CountAboveArgs a;
+    statmc::fill_count_above_args(a, width, height, score, thresholds, n_thresholds, counts);
+    HIP_TRY(statmc::launch_score_count_above(a, S(stream)));
     return STATMC_OK;
 }
 

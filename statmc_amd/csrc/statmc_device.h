@@ -225,6 +225,12 @@ struct PlanArgs;
 hipError_t launch_sample_scores(const ScoreArgs &a, hipStream_t s);
 hipError_t launch_plan_samples(const PlanArgs &a, size_t workspace_bytes, hipStream_t s);
 
+// statmc_score_select / statmc_score_count_above (statmc_select.hip): argument blocks and checks are statmc_select_args.h's, host-only
+struct SelectArgs;
+struct CountAboveArgs;
+hipError_t launch_score_select(const SelectArgs &a, hipStream_t s);
+hipError_t launch_score_count_above(const CountAboveArgs &a, hipStream_t s);
+
 // statmc_compact_offsets / statmc_compact_accumulate (statmc_compact.hip): argument blocks and checks are statmc_compact_args.h's
 struct CompactOffsetsArgs;
 struct CompactArgs;

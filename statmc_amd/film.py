@@ -222,11 +222,35 @@ class FilmStats:
         (statmc_sample_scores over its n and raw-sample Welford planes, then statmc_plan_samples with its n as the counts so far).
         Returns an int32 tensor [H, W] that accumulate(samples, counts=) takes as it is; with return_result=True, (counts, the
         statmc_plan_result as a dict) after a synchronisation.  The film is only read."""
+        return api.plan_samples(self._scores(metric, eps, type), budget, c_min, c_max, n=self.state[type]["n"], return_result=return_result)
+
+    def _scores(self, metric, eps, type):
+        """the noise score image of stat type `type` as it stands (statmc_sample_scores over its n and raw-sample Welford planes)"""
         st = self.state[type]
         film_mean = st["film_mean"] if st["film_mean"] is not None else st["mean"]
         film_m2 = st["film_m2"] if st["film_m2"] is not None else st["m2"]
-        score = api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
-        return api.plan_samples(score, budget, c_min, c_max, n=st["n"], return_result=return_result)
+        return api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+
+    def score_quantiles(self, qs, metric="relative", eps=1e-3, type="radiance"):
+        """The q-quantiles (1 to 8 values of q in [0, 1]) of the noise score of stat type `type` as plan_samples computes it, by the
+        nearest-rank rule: rank(q) = max(0, ceil(q P) - 1) of the P pixels' keys in ascending order (statmc_score_select).  A
+        renderer's stopping rule: "the 95th percentile of the relative score is under 2 %".  Returns the values as numpy float32, one
+        per q, after one synchronisation and the download of one 256-byte struct; the film is only read."""
+        import math
+        from fractions import Fraction
+        px = self.width * self.height
+        ranks = []
+        for q in qs:
+            if not 0 <= q <= 1:
+                raise ValueError("score_quantiles: q = %r is outside [0, 1]" % (q,))
+            ranks.append(max(0, math.ceil(Fraction(float(q)) * px) - 1))     # Python integers: exact in q as the double it is (numpy scalars too)
+        return api.read_select_result(api.score_select(self._scores(metric, eps, type), ranks))["values"]
+
+    def score_count_above(self, thresholds, metric="relative", eps=1e-3, type="radiance"):
+        """Per threshold (1 to 8) the number of pixels whose noise score, as plan_samples computes it, is above it
+        (statmc_score_count_above: NaN and negative scores count as 0).  "At most 1 % of the pixels are above tau."  Returns a list of
+        Python integers after one synchronisation and one small download; the film is only read."""
+        return [int(c) for c in api.score_count_above(self._scores(metric, eps, type), thresholds).cpu().numpy()]
 
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())

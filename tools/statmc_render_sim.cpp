@@ -20,9 +20,11 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels] [--placed] [--half-features]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T]] [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
 // --adaptive-pixels: per-pixel sample budgets planned on the device (Estimator::PlanSamples); see RenderLoop.
+// --stop-at Q:T: with --adaptive-pixels, the stopping rule: after every iteration the Q-quantile (nearest rank) of the relative radiance
+//                   score is selected on the device (Estimator::ScoreSelect); once it is <= T the remaining iterations are skipped.
 // --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
 //                   half (Estimator::SetSampleFormat); radiance stays fp32.  "Staged bytes:" at the end counts what went up.
 // --config denoise: Render<Vec3>, RGB radiance + normal + albedo, filter<float3> (scenes/render-denoise.pbrt).
@@ -36,6 +38,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <string>
 #include <thread>
@@ -110,6 +113,9 @@ struct Options {
     float filterSD = 10.f;
     int filterRadius = 20;
     bool denoise = true, acrr = false, smis = false, warmUp = false, tileStats = false, adaptive = false, adaptivePixels = false, halfFeatures = false;
+    bool stopAt = false;       // --stop-at Q:T
+    double stopQuantile = 0.0;
+    float stopThreshold = 0.f;
     std::string stem, outputRegex = ".*";
 };
 
@@ -285,7 +291,24 @@ static void Render(const Options &o) {
             std::cout << "Adaptive: samples per pixel so far " << lo << " .. " << hi << " over " << nTilesTotal << " tiles" << std::endl;
         }
 
-        if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations) {
+        // --stop-at: the Q-quantile of the relative score, one 256-byte struct back
+        bool converged = false;
+        if (o.stopAt && sCfgs[Radiance].enable) {
+            const int64_t rank = Estimator::NearestRank(o.stopQuantile, (int64_t)width * height);
+            statmc_select_result sel;
+            check(statmc_download(&sel, estimator.ScoreSelect(sCfgs[Radiance].index, 0, {rank}), sizeof(sel), estimator.DeviceStream()));
+            estimator.Synchronize();
+            float v;
+            std::memcpy(&v, &sel.value_bits[0], sizeof(v));
+            if (v <= o.stopThreshold) {
+                converged = true;
+                char value[32];
+                std::snprintf(value, sizeof(value), "%.9g", (double)v);
+                std::cout << "Converged: iteration " << i << ", quantile " << o.stopQuantile << " of the relative score = " << value << std::endl;
+            }
+        }
+
+        if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations && !converged) {
             const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
             const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next));
             pixelTarget.resize((size_t)width * height);
@@ -338,6 +361,7 @@ static void Render(const Options &o) {
         }
         end = std::chrono::steady_clock::now();
         std::cout << "Output time [ns]: " << std::chrono::duration_cast<std::chrono::nanoseconds>(end - begin).count() << std::endl;
+        if (converged) break;
     }
     };
 
@@ -385,7 +409,21 @@ int main(int argc, char **argv) {
         else if (a == "--tilestats") o.tileStats = true;
         else if (a == "--adaptive") o.adaptive = true;
         else if (a == "--adaptive-pixels") o.adaptivePixels = true;
-        else if (a == "--half-features") o.halfFeatures = true;
+        else if (a == "--stop-at") {
+            const std::string v = next();
+            const size_t colon = v.find(':');
+            char *end = nullptr;
+            if (colon != std::string::npos) {
+                o.stopQuantile = std::strtod(v.c_str(), &end);
+                o.stopAt = end == v.c_str() + colon && colon > 0;
+                o.stopThreshold = std::strtof(v.c_str() + colon + 1, &end);
+                o.stopAt = o.stopAt && *end == 0 && end != v.c_str() + colon + 1;
+            }
+            if (!o.stopAt || !(o.stopQuantile >= 0.0 && o.stopQuantile <= 1.0) || o.stopThreshold != o.stopThreshold) {
+                std::fprintf(stderr, "--stop-at takes Q:T, a quantile in [0, 1] and a threshold\n");
+                return 2;
+            }
+        } else if (a == "--half-features") o.halfFeatures = true;
         else if (a == "--placed") statmc::usePlacedMemory() = true;   // device images and sample arenas from statmc_malloc_placed
         else if (a == "--config") {
             const std::string c = next();
@@ -410,6 +448,10 @@ int main(int argc, char **argv) {
     if (o.width <= 0 || o.height <= 0 || o.width > 65535 || o.height > 65535 || o.spp <= 0 || o.iterations <= 0 ||
         o.threads <= 0 || o.trackedBounces < 1 || o.trackedBounces > 16) {
         std::fprintf(stderr, "bad size / spp / iterations / threads / trackedbounces\n");
+        return 2;
+    }
+    if (o.stopAt && !o.adaptivePixels) {
+        std::fprintf(stderr, "--stop-at needs --adaptive-pixels\n");
         return 2;
     }
     try {

@@ -918,6 +918,35 @@ int statmc_score_select(uint16_t width, uint16_t height, const float *score, con
 int statmc_score_count_above(uint16_t width, uint16_t height, const float *score, const float *thresholds, int n_thresholds,
                              int64_t *counts, void *stream);
 
+/* ---- window maximum / minimum of a score image (no counterpart in the reference): the error map regularised over a neighbourhood
+ * before a plan spends by it.  A pixel's sample standard deviation after a handful of samples is itself noisy: a pixel beside a
+ * caustic that has not yet drawn a bright sample reports a small score and the plan starves it.  MAX gives every pixel the worst
+ * score within `radius` pixels (a dilation); MIN then MAX with the same radius (an opening) removes isolated spikes first.
+ *
+ * DEFINITION.  key(b) is statmc_score_select's above: NaN of either sign and everything with the sign bit are 0, the rest their own
+ * bit pattern.  The window of pixel (x, y) is the pixels (x', y') of the film with |x' - x| <= radius and |y' - y| <= radius: taps
+ * outside the film are skipped (the border is clipped), the centre is always a member.
+ *     out[y][x] = the float whose bit pattern is the maximum (op STATMC_SCORE_WINDOW_MAX) or the minimum (STATMC_SCORE_WINDOW_MIN),
+ *                 as unsigned integers, of key(score[y'][x']) over the window.
+ * Hence the output is never NaN and never has the sign bit; radius 0 canonicalises an image (the identity on non-negative, non-NaN
+ * scores); the same inputs give the same bits on every run (integer maxima: no order reaches a bit); window(op, r2) of
+ * window(op, r1) equals window(op, r1 + r2) bit for bit, clipped borders included; on a non-negative, non-NaN image MAX is a
+ * (2 radius + 1)^2 max-pooling with stride 1 and implicit -inf padding, bit for bit.  The classes statmc_plan_samples and
+ * statmc_score_select assign are those of the output's keys: `out` is what both take as `score`.
+ * Asynchronous on `stream`: one launch, no workspace, nothing allocated, nothing read back; only `out` is written, exactly its
+ * width * height floats.  A workgroup stages a tile and its halo as keys in LDS, reduces along rows, then along columns, each by
+ * doubling -- log2(2 radius + 1) steps, not 2 radius + 1 taps.
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL score
+ * or out; score or out not 4-byte aligned; op not one of the two; radius outside [0, STATMC_SCORE_WINDOW_MAX_RADIUS]; out
+ * overlapping score (there is no in-place mode).  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2f, profiles/score_window.jsonl. */
+#define STATMC_SCORE_WINDOW_MAX 0
+#define STATMC_SCORE_WINDOW_MIN 1
+#define STATMC_SCORE_WINDOW_MAX_RADIUS 32
+int statmc_score_window(uint16_t width, uint16_t height, const float *score, int op, int radius,
+                        float *out, void *stream);
+
 /* ---- the compact arena of a planned iteration: every pixel's samples back to back, pixels in raster order (CSR).  Pixel p owns
  * positions [offsets[p], offsets[p + 1]) of a sample-major [total][channels] array per stat type: no pixel index per sample, no
  * sort, no dead slots, `total` samples of memory.  The loop: statmc_plan_samples -> statmc_compact_offsets -> the renderer writes

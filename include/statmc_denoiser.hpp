@@ -1301,14 +1301,15 @@ class Estimator {
     // what AccumulateFilm(nSamples, buffers, d_counts) takes; it, the score image and the workspace are members allocated by the first
     // call, and d_counts stays valid and unchanged until the next PlanSamples.  Needs EnableDeviceAccumulation(); staged samples are
     // flushed first; the launches go to DeviceStream() and the call blocks until the 32 bytes of the result are back.
+    // scoreDilate = r > 0: the plan spends by the worst score within r pixels (statmc_score_window, MAX: see windowedScores below).
     struct SamplePlan {
         const int32_t *d_counts;      // device, int32 [height][width]
         statmc_plan_result result;
     };
     SamplePlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, int64_t budget, int32_t cMin, int32_t cMax,
-                           int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+                           int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
         statmc_stat_type t;
-        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true);   // validates, flushes staged samples
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true), scoreDilate);   // validates, flushes staged samples
         const size_t px = (size_t)width * height, wsBytes = statmc_plan_samples_workspace((uint16_t)width, (uint16_t)height);
         plan.counts.reserve(px * sizeof(int32_t));
         plan.workspace.reserve(wsBytes);
@@ -1331,10 +1332,12 @@ class Estimator {
     // into this Estimator -- and the (type, bounce)'s descriptor never handed out through DeviceStatistics (see there).  Both enqueue on DeviceStream() and return without
     // waiting; the device pointers they return stay valid until the next call of the same method.  `ranks`: 1 to 8 ranks in
     // [0, width * height); `thresholds`: 1 to 8, none NaN.  Needs EnableDeviceAccumulation(); staged samples are flushed first.
+    // scoreDilate = r > 0: the statistics of the MAX window of radius r of that score image, as PlanSamples spends by it; the reuse
+    // rule above is the raw image's, the windowed one is made anew by every call.
     const statmc_select_result *ScoreSelect(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<int64_t> &ranks,
-                                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+                                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
         statmc_stat_type t;
-        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t);
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t), scoreDilate);
         const size_t wsBytes = statmc_score_select_workspace();
         plan.selectWorkspace.reserve(wsBytes);
         plan.selectResult.reserve(sizeof(statmc_select_result));
@@ -1344,9 +1347,9 @@ class Estimator {
         return d_result;
     }
     const int64_t *ScoreCountAbove(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<float> &thresholds,
-                                   int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+                                   int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
         statmc_stat_type t;
-        const float *scores = scoreImage(statTypeIndex, bounceIndex, metric, eps, t);
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t), scoreDilate);
         plan.aboveCounts.reserve(STATMC_SELECT_MAX_RANKS * sizeof(int64_t));
         int64_t *d_counts = static_cast<int64_t *>(plan.aboveCounts.ptr);
         check(statmc_score_count_above((uint16_t)width, (uint16_t)height, scores, thresholds.data(), (int)thresholds.size(), d_counts, stream.handle()));
@@ -1365,6 +1368,14 @@ class Estimator {
     }
     // how many times a score image was computed (tests: the reuse above)
     size_t ScoreImagesComputed() const { return nScoreImages; }
+    // ---- statmc_score_window on DeviceStream(), for a host with its own metric: d_out[y][x] = the maximum (op
+    // STATMC_SCORE_WINDOW_MAX) or minimum (STATMC_SCORE_WINDOW_MIN) of the keys of d_in within `radius` pixels of (x, y), the border
+    // clipped.  d_in and d_out are the caller's packed width x height float images on this Estimator's device and may not overlap.
+    // MIN then MAX with one radius is the opening: isolated spikes go, what is left is dilated.  Returns without waiting.
+    void ScoreWindow(const float *d_in, int op, int radius, float *d_out) {
+        check(statmc_set_device(device));
+        check(statmc_score_window((uint16_t)width, (uint16_t)height, d_in, op, radius, d_out, stream.handle()));
+    }
 
     // ---- the compact arena of a planned iteration (statmc_compact_offsets + statmc_compact_accumulate; include/statmc.h).  The
     // loop: PlanSamples -> CompactOffsets(plan.d_counts, cap, d_offsets) -> the renderer writes pixel p's sample s at position
@@ -1600,6 +1611,15 @@ class Estimator {
             nScoreImages++;
         }
         return scores;
+    }
+    // `scores` (plan.scores) as it is for radius 0 -- no launch, nothing canonicalised -- else its MAX window of that radius in
+    // plan.windowed, made anew by every call: the raw image and its reuse rule know nothing of it.
+    const float *windowedScores(const float *scores, int radius) {
+        if (radius == 0) return scores;
+        plan.windowed.reserve((size_t)width * height * sizeof(float));
+        float *out = static_cast<float *>(plan.windowed.ptr);
+        check(statmc_score_window((uint16_t)width, (uint16_t)height, scores, STATMC_SCORE_WINDOW_MAX, radius, out, stream.handle()));
+        return out;
     }
     // one side of a combine or pool entry: the device images of (type i, bounce j) of Estimator e
     static statmc_stat_type statSide(Estimator &e, unsigned char i, unsigned char j, bool own) {
@@ -1876,6 +1896,7 @@ class Estimator {
     mutable Accumulation acc;
     struct Planning {                    // PlanSamples / ScoreSelect / ScoreCountAbove: allocated by the first call, kept
         DeviceBytes scores, counts, workspace, result;
+        DeviceBytes windowed;            // the MAX window of `scores` a call with scoreDilate > 0 reads (made anew by each)
         DeviceBytes selectWorkspace, selectResult, aboveCounts;
         // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
         // flushes of staged samples so far and `touched`, which every call that may write the statistics otherwise bumps

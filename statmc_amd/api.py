@@ -121,6 +121,8 @@ class SelectResult(C.Structure):
 
 
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
+SCORE_WINDOW_MAX, SCORE_WINDOW_MIN = 0, 1  # statmc_score_window's op
+SCORE_WINDOW_MAX_RADIUS = 32
 PLAN_LEVEL_LO, PLAN_LEVEL_HI = 0x20000000, 0x5F000000   # statmc_plan_samples' level range [U_LO, U_HI]: 2^-63 .. 2^63
 PLAN_MAX_COUNT = 1 << 20
 MAX_COMBINE_SOURCES = 15
@@ -133,7 +135,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -242,6 +244,7 @@ def load():
     lib.statmc_score_select.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(SelectResult), C.c_void_p,
                                         C.c_size_t, C.c_void_p]
     lib.statmc_score_count_above.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
+    lib.statmc_score_window.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_compact_offsets_workspace.restype = C.c_size_t
     lib.statmc_compact_offsets.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
@@ -856,6 +859,27 @@ def score_count_above(score, thresholds, out=None, stream=None):
     arr = (C.c_float * max(len(thresholds), 1))(*thresholds)
     check(load().statmc_score_count_above(w, h, score.data_ptr(), arr, len(thresholds), out.data_ptr() if out.numel() else None,
                                           stream if stream is not None else current_stream_handle()))
+    return out
+
+
+_WINDOW_OPS = {"max": SCORE_WINDOW_MAX, "min": SCORE_WINDOW_MIN}
+
+
+def score_window(score, radius, op="max", out=None, stream=None):
+    """statmc_score_window: per pixel the maximum ("max": a dilation) or minimum ("min": an erosion) of the keys of the float32 score
+    image [H, W] over the pixels within `radius` (0 to SCORE_WINDOW_MAX_RADIUS) to every side, the border clipped (include/statmc.h).
+    Returns the float32 image [H, W] (`out`, or a new tensor; never `score` itself): what plan_samples, score_select and
+    score_count_above take as score.  score_window(score_window(s, r, "min"), r) is the opening, which drops isolated spikes first.
+    Asynchronous."""
+    tc = _torch()
+    h, w = _score_image(score, "score_window")
+    if out is None:
+        out = tc.empty(h, w, dtype=tc.float32, device=score.device)
+    elif out.dtype != tc.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() != h * w:
+        raise ValueError("score_window: out must be a contiguous float32 CUDA tensor of H * W values")
+    o = _WINDOW_OPS[op] if isinstance(op, str) else int(op)
+    check(load().statmc_score_window(w, h, score.data_ptr(), o, int(radius), out.data_ptr(),
+                                     stream if stream is not None else current_stream_handle()))
     return out
 
 

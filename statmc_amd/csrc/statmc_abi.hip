@@ -18,6 +18,7 @@
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
 #include "statmc_select_args.h"
+#include "statmc_score_window_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
 #include "statmc_state_records_args.h"
@@ -1494,6 +1495,17 @@ int statmc_score_count_above(uint16_t width, uint16_t height, const float *score
     statmc::CountAboveArgs a;
     statmc::fill_count_above_args(a, width, height, score, thresholds, n_thresholds, counts);
     HIP_TRY(statmc::launch_score_count_above(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_score_window: every rule of include/statmc.h ahead of the device (statmc_score_window_args.h), then the one launch of
+// statmc_score_window.hip on `stream`; nothing is allocated and nothing read back.
+int statmc_score_window(uint16_t width, uint16_t height, const float *score, int op, int radius, float *out, void *stream) {
+    ARG_TRY(statmc::check_score_window_call(width, height, score, op, radius, out, statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::ScoreWindowArgs a;
+    statmc::fill_score_window_args(a, width, height, score, op, radius, out);
+    HIP_TRY(statmc::launch_score_window(a, S(stream)));
     return STATMC_OK;
 }
 

@@ -231,6 +231,10 @@ struct CountAboveArgs;
 hipError_t launch_score_select(const SelectArgs &a, hipStream_t s);
 hipError_t launch_score_count_above(const CountAboveArgs &a, hipStream_t s);
 
+// statmc_score_window (statmc_score_window.hip): argument block and checks are statmc_score_window_args.h's, host-only
+struct ScoreWindowArgs;
+hipError_t launch_score_window(const ScoreWindowArgs &a, hipStream_t s);
+
 // statmc_compact_offsets / statmc_compact_accumulate (statmc_compact.hip): argument blocks and checks are statmc_compact_args.h's
 struct CompactOffsetsArgs;
 struct CompactArgs;

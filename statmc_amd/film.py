@@ -217,25 +217,29 @@ class FilmStats:
         coarse._prepass_current = coarse._prepass_key() if fuse else None
         return coarse
 
-    def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False):
+    def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False, dilate=0):
         """The per-pixel sample counts of the next accumulation: `budget` samples spent by the noise of stat type `type` as it stands
         (statmc_sample_scores over its n and raw-sample Welford planes, then statmc_plan_samples with its n as the counts so far).
         Returns an int32 tensor [H, W] that accumulate(samples, counts=) takes as it is; with return_result=True, (counts, the
-        statmc_plan_result as a dict) after a synchronisation.  The film is only read."""
-        return api.plan_samples(self._scores(metric, eps, type), budget, c_min, c_max, n=self.state[type]["n"], return_result=return_result)
+        statmc_plan_result as a dict) after a synchronisation.  dilate = r > 0: the plan spends by the worst score within r pixels
+        (statmc_score_window, MAX), so a pixel beside a noisy one is not starved; 0: the pointwise score as it is, no extra launch.  The
+        film is only read."""
+        return api.plan_samples(self._scores(metric, eps, type, dilate), budget, c_min, c_max, n=self.state[type]["n"], return_result=return_result)
 
-    def _scores(self, metric, eps, type):
-        """the noise score image of stat type `type` as it stands (statmc_sample_scores over its n and raw-sample Welford planes)"""
+    def _scores(self, metric, eps, type, dilate=0):
+        """the noise score image of stat type `type` as it stands (statmc_sample_scores over its n and raw-sample Welford planes);
+        dilate > 0: its MAX window of that radius (statmc_score_window)"""
         st = self.state[type]
         film_mean = st["film_mean"] if st["film_mean"] is not None else st["mean"]
         film_m2 = st["film_m2"] if st["film_m2"] is not None else st["m2"]
-        return api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+        scores = api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+        return api.score_window(scores, dilate, "max") if dilate else scores
 
-    def score_quantiles(self, qs, metric="relative", eps=1e-3, type="radiance"):
+    def score_quantiles(self, qs, metric="relative", eps=1e-3, type="radiance", dilate=0):
         """The q-quantiles (1 to 8 values of q in [0, 1]) of the noise score of stat type `type` as plan_samples computes it, by the
         nearest-rank rule: rank(q) = max(0, ceil(q P) - 1) of the P pixels' keys in ascending order (statmc_score_select).  A
         renderer's stopping rule: "the 95th percentile of the relative score is under 2 %".  Returns the values as numpy float32, one
-        per q, after one synchronisation and the download of one 256-byte struct; the film is only read."""
+        per q, after one synchronisation and the download of one 256-byte struct; the film is only read.  dilate: as plan_samples'."""
         import math
         from fractions import Fraction
         px = self.width * self.height
@@ -244,13 +248,13 @@ class FilmStats:
             if not 0 <= q <= 1:
                 raise ValueError("score_quantiles: q = %r is outside [0, 1]" % (q,))
             ranks.append(max(0, math.ceil(Fraction(float(q)) * px) - 1))     # Python integers: exact in q as the double it is (numpy scalars too)
-        return api.read_select_result(api.score_select(self._scores(metric, eps, type), ranks))["values"]
+        return api.read_select_result(api.score_select(self._scores(metric, eps, type, dilate), ranks))["values"]
 
-    def score_count_above(self, thresholds, metric="relative", eps=1e-3, type="radiance"):
+    def score_count_above(self, thresholds, metric="relative", eps=1e-3, type="radiance", dilate=0):
         """Per threshold (1 to 8) the number of pixels whose noise score, as plan_samples computes it, is above it
         (statmc_score_count_above: NaN and negative scores count as 0).  "At most 1 % of the pixels are above tau."  Returns a list of
-        Python integers after one synchronisation and one small download; the film is only read."""
-        return [int(c) for c in api.score_count_above(self._scores(metric, eps, type), thresholds).cpu().numpy()]
+        Python integers after one synchronisation and one small download; the film is only read.  dilate: as plan_samples'."""
+        return [int(c) for c in api.score_count_above(self._scores(metric, eps, type, dilate), thresholds).cpu().numpy()]
 
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())

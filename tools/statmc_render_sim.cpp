@@ -20,11 +20,13 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T]] [--placed] [--half-features]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--score-dilate R]] [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
 // --adaptive-pixels: per-pixel sample budgets planned on the device (Estimator::PlanSamples); see RenderLoop.
 // --stop-at Q:T: with --adaptive-pixels, the stopping rule: after every iteration the Q-quantile (nearest rank) of the relative radiance
 //                   score is selected on the device (Estimator::ScoreSelect); once it is <= T the remaining iterations are skipped.
+// --score-dilate R: with --adaptive-pixels, the plan and --stop-at's quantile read the worst score within R pixels (0 to 32) of every
+//                   pixel instead of the pixel's own (statmc_score_window, MAX: Estimator::PlanSamples' / ScoreSelect's scoreDilate).
 // --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
 //                   half (Estimator::SetSampleFormat); radiance stays fp32.  "Staged bytes:" at the end counts what went up.
 // --config denoise: Render<Vec3>, RGB radiance + normal + albedo, filter<float3> (scenes/render-denoise.pbrt).
@@ -116,6 +118,8 @@ struct Options {
     bool stopAt = false;       // --stop-at Q:T
     double stopQuantile = 0.0;
     float stopThreshold = 0.f;
+    bool scoreDilateGiven = false;   // --score-dilate R
+    int scoreDilate = 0;
     std::string stem, outputRegex = ".*";
 };
 
@@ -296,7 +300,7 @@ static void Render(const Options &o) {
         if (o.stopAt && sCfgs[Radiance].enable) {
             const int64_t rank = Estimator::NearestRank(o.stopQuantile, (int64_t)width * height);
             statmc_select_result sel;
-            check(statmc_download(&sel, estimator.ScoreSelect(sCfgs[Radiance].index, 0, {rank}), sizeof(sel), estimator.DeviceStream()));
+            check(statmc_download(&sel, estimator.ScoreSelect(sCfgs[Radiance].index, 0, {rank}, STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate), sizeof(sel), estimator.DeviceStream()));
             estimator.Synchronize();
             float v;
             std::memcpy(&v, &sel.value_bits[0], sizeof(v));
@@ -310,7 +314,8 @@ static void Render(const Options &o) {
 
         if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations && !converged) {
             const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
-            const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next));
+            const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next),
+                                                                     STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate);
             pixelTarget.resize((size_t)width * height);
             check(statmc_download(pixelTarget.data(), plan.d_counts, pixelTarget.size() * sizeof(int32_t), estimator.DeviceStream()));
             estimator.Synchronize();
@@ -423,6 +428,16 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--stop-at takes Q:T, a quantile in [0, 1] and a threshold\n");
                 return 2;
             }
+        } else if (a == "--score-dilate") {
+            const std::string v = next();
+            char *end = nullptr;
+            const long r = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != 0 || r < 0 || r > STATMC_SCORE_WINDOW_MAX_RADIUS) {
+                std::fprintf(stderr, "--score-dilate takes a radius, 0 to %d\n", STATMC_SCORE_WINDOW_MAX_RADIUS);
+                return 2;
+            }
+            o.scoreDilateGiven = true;
+            o.scoreDilate = (int)r;
         } else if (a == "--half-features") o.halfFeatures = true;
         else if (a == "--placed") statmc::usePlacedMemory() = true;   // device images and sample arenas from statmc_malloc_placed
         else if (a == "--config") {
@@ -452,6 +467,10 @@ int main(int argc, char **argv) {
     }
     if (o.stopAt && !o.adaptivePixels) {
         std::fprintf(stderr, "--stop-at needs --adaptive-pixels\n");
+        return 2;
+    }
+    if (o.scoreDilateGiven && !o.adaptivePixels) {
+        std::fprintf(stderr, "--score-dilate needs --adaptive-pixels\n");
         return 2;
     }
     try {

@@ -862,10 +862,76 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
                         int32_t *sample_counts, statmc_plan_result *result,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the error of the mean as a score image, and the counts that bring it to a tolerance (no counterpart in the reference).
+ * statmc_sample_scores' sample standard deviation converges to the pixel's true sigma: it is what the budget plan spends by, and it
+ * does not fall as samples arrive.  A stopping rule needs a quantity that does: the standard error of the mean, sqrt(v / n), or the
+ * half-width of the mean's confidence interval, that times the Student-t quantile at n - 1 degrees of freedom.
+ *
+ * statmc_error_scores: channels, metric, eps and the images are statmc_sample_scores'.  `table` is STATMC_ERROR_NO_TABLE (the standard
+ * error) or 0..5, numbered as in statmc_set_t_quantiles, alpha_index + 3 * sides: the score is the half-width of that confidence
+ * interval.  T[table] is the CURRENT DEVICE's table as it stands when the call is made, quantiles loaded by the caller included.
+ * DEFINITION, per pixel; every operation is one fp32 rounding in this order, nothing is contracted, `/` and sqrt are the correctly
+ * rounded IEEE quotient and root:
+ *     n < 2:      score = +inf
+ *     otherwise   fn1 = (float)(n - 1);  v = film_m2[0] / fn1  (+ film_m2[1] / fn1) (+ film_m2[2] / fn1)    (statmc_sample_scores' v)
+ *                 vm = v / (float)n;  e = sqrt(vm)
+ *       table >= 0:               q = T[table][min(n - 1, 4096) - 1];  e = q * e
+ *       STATMC_SCORE_RELATIVE:    e = e / (eps + a),  a as in statmc_sample_scores
+ *                 score = e
+ * Non-finite or negative statistics pass through as the arithmetic has it.  The library is built without a denormal flush:
+ * subnormal m2, quotients and products are part of the definition, and a numpy float32 restatement gives the same bits.  For
+ * n = 4^k and a normal v, vm = v / 4^k is exact, so the absolute standard error is 2^-k times statmc_sample_scores' absolute score
+ * bit for bit.  Planes that are all 16-byte aligned move four pixels per lane; any other alignment, and the film's last partial
+ * group of four, go pixel by pixel to the same bits.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; channels not
+ * 1 or 3; a metric other than the two; table outside -1..5; with STATMC_SCORE_RELATIVE an eps that is not positive and finite; a NULL
+ * or not 4-byte aligned image; score overlapping n, film_mean or film_m2.  STATMC_ERR_NO_DEVICE before statmc_setup, after those
+ * checks.  Asynchronous on `stream`: one launch.
+ *
+ * statmc_plan_to_target: error image + counts so far + tolerance -> count image.  `error` is statmc_error_scores' image, a window of
+ * it (statmc_score_window), or the renderer's own metric that falls like 1 / sqrt(n).  n is required.  target is finite and in
+ * [2^-60, 2^60]; 0 <= c_min <= c_max <= 2^20.
+ * DEFINITION.  The classes of `error` are statmc_plan_samples': saturated e > 2^60, live 2^-60 <= e <= 2^60, dead the rest; n_live
+ * and n_saturated count those classes and nothing else.  nn = clamp(n, 0, 2^30).  Per pixel:
+ *     saturated, or live with nn < 2 (nobody can judge it):   c = c_max
+ *     dead:                                                   c = c_min
+ *     live, nn >= 2, e <= target (at the target):             c = c_min
+ *     live, nn >= 2, e >  target (open):
+ *         r = e / target;  r2 = r * r;  t = r2 * (float)nn;  N = (t >= 2^30) ? 2^30 : (int)ceil(t)
+ *         d = max(N - nn, 0);  c = clamp(d, c_min, c_max)
+ * At a fixed deviation and quantile the error falls like 1 / sqrt(n): n (e / target)^2 samples in all bring it to the target.  On an
+ * open pixel r >= 1, so every intermediate is a normal number or +inf: denormal modes reach no bit, and inf * nn with nn >= 2 is
+ * +inf, never NaN.  Hence counts are non-increasing in target; every count lies in [c_min, c_max]; the sums are integer sums, so
+ * the same inputs give the same bits on every run; sample_counts is what the counted and compact entries take.
+ * One launch behind the zeroing of `result` on `stream` -- a result full of garbage gives the same bits; no workspace, nothing
+ * allocated, nothing read back.  `result` is device memory, 8-byte aligned.
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL error, n,
+ * sample_counts or result; error, n or sample_counts not 4-byte aligned, result not 8-byte aligned; a target outside [2^-60, 2^60]
+ * (NaN included); c_min / c_max outside 0 <= c_min <= c_max <= 2^20; sample_counts overlapping error, n or result.
+ * STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2g, profiles/error_scores.jsonl. */
+#define STATMC_ERROR_NO_TABLE (-1)
+int statmc_error_scores(uint16_t width, uint16_t height, int channels, int metric, float eps, int table,
+                        const int32_t *n, const float *film_mean, const float *film_m2,
+                        float *score, void *stream);
+
+typedef struct statmc_target_result { /* device, written by the call; 48 bytes */
+    int64_t total;      /* sum of sample_counts */
+    int64_t need;       /* sum over open pixels of max(N - nn, 0), before the clamp: samples still missing, at the present estimates */
+    int64_t n_open;     /* judged pixels above the target */
+    int64_t n_capped;   /* open pixels whose need exceeds c_max: not reachable in this iteration */
+    int64_t n_unjudged; /* saturated pixels, and live ones with fewer than 2 samples */
+    int32_t n_live, n_saturated; /* statmc_plan_result's, for the same image */
+} statmc_target_result;
+int statmc_plan_to_target(uint16_t width, uint16_t height, const float *error, const int32_t *n, float target,
+                          int32_t c_min, int32_t c_max, int32_t *sample_counts, statmc_target_result *result,
+                          void *stream);
+
 /* ---- order statistics and threshold counts of a score image (no counterpart in the reference): what a stopping rule asks of the
- * error map -- "the 95th percentile of the relative score is under 2 %", "at most 1 % of the pixels are above tau" -- answered on
- * the device, one small struct read back.  `score` is statmc_sample_scores' or the renderer's own metric, a packed width x height
- * plane.
+ * error map -- "the 95th percentile of the relative error of the mean is under 2 %", "at most 1 % of the pixels are above tau" --
+ * answered on the device, one small struct read back.  `score` is statmc_error_scores' for such a rule (statmc_sample_scores' sample
+ * deviation does not fall with the sample count: a threshold on it is never met by rendering more), or the renderer's own metric; a
+ * packed width x height plane.
  *
  * DEFINITION.  The key of a score is integer arithmetic on its bit pattern b, so no denormal mode and no comparison instruction
  * reaches a bit:

@@ -1308,8 +1308,13 @@ class Estimator {
     };
     SamplePlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, int64_t budget, int32_t cMin, int32_t cMax,
                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
+        return PlanSamples(statTypeIndex, bounceIndex, budget, cMin, cMax, metric, eps, scoreDilate, ScoreOfDeviation);
+    }
+    // ... with the trailing scoreOf (see below): which quantity the plan spends by
+    SamplePlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, int64_t budget, int32_t cMin, int32_t cMax, int metric, float eps,
+                           int scoreDilate, int scoreOf) {
         statmc_stat_type t;
-        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true), scoreDilate);   // validates, flushes staged samples
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true, scoreOf), scoreDilate);   // validates, flushes staged samples
         const size_t px = (size_t)width * height, wsBytes = statmc_plan_samples_workspace((uint16_t)width, (uint16_t)height);
         plan.counts.reserve(px * sizeof(int32_t));
         plan.workspace.reserve(wsBytes);
@@ -1321,6 +1326,51 @@ class Estimator {
         SamplePlan out{counts, statmc_plan_result{}};
         check(statmc_download(&out.result, d_result, sizeof(out.result), stream.handle()));
         Synchronize();
+        return out;
+    }
+
+    // ---- which quantity PlanSamples / ScoreSelect / ScoreCountAbove / PlanToTarget score, their trailing scoreOf (the three take it
+    // behind scoreDilate; without it they are the calls they were before it existed):
+    //   ScoreOfDeviation  the sample standard deviation (statmc_sample_scores): what a budget is spent by.  It converges to
+    //                              the pixel's true sigma and does NOT fall as samples arrive: no stopping rule can be met on it.
+    //   ScoreOfStdErr     the standard error of the mean (statmc_error_scores without a table): falls like 1 / sqrt(n).
+    //   ScoreOfCI         the two-sided confidence half-width of the mean at statmc_get_significance() of this Estimator's
+    //                              device (statmc_error_scores, table alpha_index + 3 * STATMC_SIDES_TWO), read at the time of the call.
+    // The score image's reuse rule (below) also compares scoreOf and the table index, so a changed significance level never returns a
+    // stale image.  (Quantiles reloaded through statmc_set_t_quantiles are not seen: call PlanSamples, which always scores, or change
+    // any other part of the key.)
+    enum { ScoreOfDeviation = 0, ScoreOfStdErr = 1, ScoreOfCI = 2 };
+
+    // ---- the per-pixel counts that bring the error of the mean to `target` (statmc_error_scores + statmc_plan_to_target;
+    // include/statmc.h has both definitions): error scores of (type, bounce) by scoreOf (ScoreOfStdErr or ScoreOfCI; ScoreOfDeviation is
+    // refused, it does not fall with n), their MAX window for scoreDilate > 0, then the plan into the member count image PlanSamples
+    // also writes; the call blocks until the 48 bytes of the result are back.  budget >= 0 and target.total > budget: the iteration
+    // cannot afford the plan, so the budget is spent as PlanSamples spends it -- by the sample-deviation score of the same metric, eps
+    // and dilation -- and byBudget is true; `target` still says how far the film is from done.  budget < 0: no budget.
+    struct TargetPlan {
+        const int32_t *d_counts;      // device, int32 [height][width]: the plan that ran
+        statmc_target_result target;  // of the plan to the target, whether or not it ran
+        bool byBudget;                // the fallback ran: d_counts and `budgeted` are PlanSamples'
+        statmc_plan_result budgeted;  // zero unless byBudget
+    };
+    TargetPlan PlanToTarget(unsigned char statTypeIndex, unsigned char bounceIndex, float target, int64_t budget, int32_t cMin, int32_t cMax,
+                            int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreOf = ScoreOfCI, int scoreDilate = 0 /* the pointwise error */) {
+        if (scoreOf != ScoreOfStdErr && scoreOf != ScoreOfCI)
+            throw Error(STATMC_ERR_INVALID, "PlanToTarget: scoreOf must be ScoreOfStdErr or ScoreOfCI");
+        statmc_stat_type t;
+        const float *errors = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true, scoreOf), scoreDilate);
+        plan.counts.reserve((size_t)width * height * sizeof(int32_t));
+        plan.targetResult.reserve(sizeof(statmc_target_result));
+        int32_t *counts = static_cast<int32_t *>(plan.counts.ptr);
+        statmc_target_result *d_result = static_cast<statmc_target_result *>(plan.targetResult.ptr);
+        check(statmc_plan_to_target((uint16_t)width, (uint16_t)height, errors, t.n, target, cMin, cMax, counts, d_result, stream.handle()));
+        TargetPlan out{counts, statmc_target_result{}, false, statmc_plan_result{}};
+        check(statmc_download(&out.target, d_result, sizeof(out.target), stream.handle()));
+        Synchronize();
+        if (budget >= 0 && out.target.total > budget) {
+            const SamplePlan p = PlanSamples(statTypeIndex, bounceIndex, budget, cMin, cMax, metric, eps, scoreDilate);
+            out.d_counts = p.d_counts, out.byBudget = true, out.budgeted = p.result;
+        }
         return out;
     }
 
@@ -1336,8 +1386,12 @@ class Estimator {
     // rule above is the raw image's, the windowed one is made anew by every call.
     const statmc_select_result *ScoreSelect(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<int64_t> &ranks,
                                             int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
+        return ScoreSelect(statTypeIndex, bounceIndex, ranks, metric, eps, scoreDilate, ScoreOfDeviation);
+    }
+    const statmc_select_result *ScoreSelect(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<int64_t> &ranks, int metric,
+                                            float eps, int scoreDilate, int scoreOf) {
         statmc_stat_type t;
-        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t), scoreDilate);
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, false, scoreOf), scoreDilate);
         const size_t wsBytes = statmc_score_select_workspace();
         plan.selectWorkspace.reserve(wsBytes);
         plan.selectResult.reserve(sizeof(statmc_select_result));
@@ -1348,8 +1402,12 @@ class Estimator {
     }
     const int64_t *ScoreCountAbove(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<float> &thresholds,
                                    int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0) {
+        return ScoreCountAbove(statTypeIndex, bounceIndex, thresholds, metric, eps, scoreDilate, ScoreOfDeviation);
+    }
+    const int64_t *ScoreCountAbove(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<float> &thresholds, int metric, float eps,
+                                   int scoreDilate, int scoreOf) {
         statmc_stat_type t;
-        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t), scoreDilate);
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, false, scoreOf), scoreDilate);
         plan.aboveCounts.reserve(STATMC_SELECT_MAX_RANKS * sizeof(int64_t));
         int64_t *d_counts = static_cast<int64_t *>(plan.aboveCounts.ptr);
         check(statmc_score_count_above((uint16_t)width, (uint16_t)height, scores, thresholds.data(), (int)thresholds.size(), d_counts, stream.handle()));
@@ -1588,12 +1646,19 @@ class Estimator {
     // plan.scores holding the score image of (type, bounce, metric, eps) for the statistics as they stand; t: the statistics'
     // device images.  Computed unless `always` is false, the key of the image held says it is this one (Planning::ScoreKey) and
     // the descriptor of (type, bounce) was never handed out.
-    const float *scoreImage(unsigned char statTypeIndex, unsigned char bounceIndex, int metric, float eps, statmc_stat_type &t, bool always = false) {
+    // scoreOf: ScoreOfDeviation statmc_sample_scores; ScoreOfStdErr / ScoreOfCI statmc_error_scores without a table / with the
+    // two-sided table at the device's significance level, which is read here and is part of the key.
+    const float *scoreImage(unsigned char statTypeIndex, unsigned char bounceIndex, int metric, float eps, statmc_stat_type &t, bool always = false,
+                            int scoreOf = 0) {
+        if (scoreOf < ScoreOfDeviation || scoreOf > ScoreOfCI)
+            throw Error(STATMC_ERR_INVALID, "scoreOf must be ScoreOfDeviation, ScoreOfStdErr or ScoreOfCI");
         t = deviceImages(statTypeIndex, bounceIndex);   // validates, flushes staged samples
         joinUploads();
         check(statmc_set_device(device));
         Planning::ScoreKey now;
         now.valid = true, now.type = statTypeIndex, now.bounce = bounceIndex, now.metric = metric;
+        now.scoreOf = scoreOf;
+        now.table = scoreOf == ScoreOfCI ? statmc_get_significance() + 3 * STATMC_SIDES_TWO : STATMC_ERROR_NO_TABLE;
         std::memcpy(&now.epsBits, &eps, sizeof(eps));
         {
             std::lock_guard<std::mutex> lk(acc.mu);
@@ -1605,8 +1670,12 @@ class Estimator {
         float *scores = static_cast<float *>(plan.scores.ptr);
         if (always || !(plan.scoresOf == now)) {
             plan.scoresOf.valid = false;
-            check(statmc_sample_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, t.n, t.film_mean ? t.film_mean : t.mean,
-                                       t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
+            if (scoreOf == ScoreOfDeviation)
+                check(statmc_sample_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, t.n, t.film_mean ? t.film_mean : t.mean,
+                                           t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
+            else
+                check(statmc_error_scores((uint16_t)width, (uint16_t)height, t.channels, metric, eps, now.table, t.n,
+                                          t.film_mean ? t.film_mean : t.mean, t.film_m2 ? t.film_m2 : t.m2, scores, stream.handle()));
             plan.scoresOf = now;
             nScoreImages++;
         }
@@ -1896,6 +1965,7 @@ class Estimator {
     mutable Accumulation acc;
     struct Planning {                    // PlanSamples / ScoreSelect / ScoreCountAbove: allocated by the first call, kept
         DeviceBytes scores, counts, workspace, result;
+        DeviceBytes targetResult;        // PlanToTarget's statmc_target_result
         DeviceBytes windowed;            // the MAX window of `scores` a call with scoreDilate > 0 reads (made anew by each)
         DeviceBytes selectWorkspace, selectResult, aboveCounts;
         // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
@@ -1905,11 +1975,13 @@ class Estimator {
             bool valid = false;
             unsigned char type = 0, bounce = 0;
             int metric = 0;
+            int scoreOf = 0, table = STATMC_ERROR_NO_TABLE;   // which quantity, and for the confidence half-width which quantile table
             uint32_t epsBits = 0;
             size_t flushes = 0;
             uint64_t touched = 0;
             bool operator==(const ScoreKey &o) const {
-                return valid == o.valid && type == o.type && bounce == o.bounce && metric == o.metric && epsBits == o.epsBits &&
+                return valid == o.valid && type == o.type && bounce == o.bounce && metric == o.metric && scoreOf == o.scoreOf && table == o.table &&
+                       epsBits == o.epsBits &&
                        flushes == o.flushes && touched == o.touched;
             }
         } scoresOf;

@@ -110,6 +110,12 @@ class PlanResult(C.Structure):
                 ("n_live", C.c_int32), ("n_saturated", C.c_int32)]
 
 
+class TargetResult(C.Structure):
+    """statmc_target_result: what statmc_plan_to_target writes to device memory next to the count image (48 bytes)."""
+    _fields_ = [("total", C.c_int64), ("need", C.c_int64), ("n_open", C.c_int64), ("n_capped", C.c_int64), ("n_unjudged", C.c_int64),
+                ("n_live", C.c_int32), ("n_saturated", C.c_int32)]
+
+
 SELECT_MAX_RANKS = 8
 
 
@@ -121,6 +127,7 @@ class SelectResult(C.Structure):
 
 
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
+ERROR_NO_TABLE = -1                       # statmc_error_scores' table: the standard error, no quantile
 SCORE_WINDOW_MAX, SCORE_WINDOW_MIN = 0, 1  # statmc_score_window's op
 SCORE_WINDOW_MAX_RADIUS = 32
 PLAN_LEVEL_LO, PLAN_LEVEL_HI = 0x20000000, 0x5F000000   # statmc_plan_samples' level range [U_LO, U_HI]: 2^-63 .. 2^63
@@ -135,7 +142,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -243,6 +250,10 @@ def load():
     lib.statmc_score_select_workspace.restype = C.c_size_t
     lib.statmc_score_select.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(SelectResult), C.c_void_p,
                                         C.c_size_t, C.c_void_p]
+    lib.statmc_error_scores.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+    lib.statmc_plan_to_target.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.POINTER(TargetResult), C.c_void_p]
     lib.statmc_score_count_above.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_score_window.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
@@ -786,6 +797,87 @@ def plan_samples(score, budget, c_min, c_max, n=None, out=None, workspace=None, 
         return out
     check(load().statmc_synchronize(st))
     return out, plan_result_dict(result)
+
+
+_ERRORS = {"stderr": ERROR_NO_TABLE}    # "ci": the two-sided table at the device's significance level (error_table)
+
+
+def error_table(error):
+    """statmc_error_scores' `table` of an error kind: "stderr" -> ERROR_NO_TABLE; "ci" -> the two-sided table at the current device's
+    significance level (get_significance(): the two-sided tables are 0..2); an int -1..5 is taken as it is."""
+    if error == "ci":
+        return get_significance()
+    if isinstance(error, str):
+        if error not in _ERRORS:
+            raise ValueError("error must be None, \"stderr\", \"ci\" or a table index, not %r" % (error,))
+        return _ERRORS[error]
+    return int(error)
+
+
+def error_scores(n, film_mean, film_m2, metric="relative", eps=1e-3, table=ERROR_NO_TABLE, out=None, stream=None):
+    """statmc_error_scores: the per-pixel error of the mean of the running statistics n [H, W] int32 and film_mean / film_m2 [H, W, C]
+    float32 (C = 1 or 3) -- table ERROR_NO_TABLE (or "stderr"): the standard error sqrt(v / n); table 0..5 (alpha_index + 3 * sides; or
+    "ci": two-sided at the device's significance level): that times the device's Student-t quantile at n - 1 degrees of freedom, the
+    half-width of the confidence interval; "relative": over eps + sum |film_mean|; +inf where n < 2.  Returns the float32 image [H, W]
+    (`out`, or a new tensor): what plan_to_target, score_window, score_select and score_count_above take."""
+    tc = _torch()
+    h, w = int(n.shape[0]), int(n.shape[1])
+    ch = int(film_mean.shape[2]) if film_mean.dim() == 3 else 1
+    for name, t, dt in (("n", n, tc.int32), ("film_mean", film_mean, tc.float32), ("film_m2", film_m2, tc.float32)):
+        if t.dtype != dt or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("error_scores: %s must be a contiguous %s CUDA tensor" % (name, dt))
+    if film_mean.numel() != h * w * ch or film_m2.numel() != h * w * ch:
+        raise ValueError("error_scores: film_mean and film_m2 must hold [H, W, C] = [%d, %d, %d] values" % (h, w, ch))
+    if out is None:
+        out = tc.empty(h, w, dtype=tc.float32, device=n.device)
+    elif out.dtype != tc.float32 or not out.is_cuda or not out.is_contiguous() or out.numel() != h * w:
+        raise ValueError("error_scores: out must be a contiguous float32 CUDA tensor of H * W values")
+    m = _METRICS[metric] if isinstance(metric, str) else int(metric)
+    check(load().statmc_error_scores(w, h, ch, m, float(eps), error_table(table), n.data_ptr(), film_mean.data_ptr(), film_m2.data_ptr(),
+                                     out.data_ptr(), stream if stream is not None else current_stream_handle()))
+    return out
+
+
+_TARGET_WORDS = C.sizeof(TargetResult) // 8
+_target_scratch = {}    # (device index, stream handle) -> result, as _plan_scratch
+
+
+def target_result_dict(result):
+    """The statmc_target_result a plan_to_target call wrote into the int64 [6] device tensor `result`, as a dict (a device-to-host
+    copy: synchronises with the work that wrote it on the current stream; after a call on another stream synchronise that one first)."""
+    r = TargetResult.from_buffer_copy(result.cpu().numpy().tobytes())
+    return {k: int(getattr(r, k)) for k, _ in TargetResult._fields_}
+
+
+def plan_to_target(error, n, target, c_min, c_max, out=None, result=None, stream=None, return_result=False):
+    """statmc_plan_to_target: per pixel the samples that bring the float32 error image [H, W] (error_scores', a window of it, or a
+    metric of the renderer's that falls like 1 / sqrt(n)) to `target`, n (error / target)^2 - n clamped to [c_min, c_max]; c_min where
+    the error is at the target already, c_max where nobody can judge the pixel yet (include/statmc.h).  n: int32 [H, W] counts so far.
+    Returns the int32 count image [H, W] (`out`, or a new tensor): what accumulate(..., sample_counts=) takes as it is.  Asynchronous;
+    result (int64 [6], the statmc_target_result's 48 bytes) is the caller's or, if None, a tensor kept per (device, stream) until the
+    next call on that stream.  return_result=True: waits for the call and returns (counts, result as a dict)."""
+    tc = _torch()
+    h, w = _score_image(error, "plan_to_target")
+    if n is None or n.dtype != tc.int32 or not n.is_cuda or not n.is_contiguous() or n.numel() != h * w:
+        raise ValueError("plan_to_target: n must be a contiguous int32 CUDA tensor of H * W counts")
+    if out is None:
+        out = tc.empty(h, w, dtype=tc.int32, device=error.device)
+    else:
+        _counts_pointer(out, w, h, "plan_to_target")
+    st = stream if stream is not None else current_stream_handle()
+    if result is None:
+        key = (error.device.index, st.value if hasattr(st, "value") else int(st or 0))
+        result = _target_scratch.get(key)
+        if result is None:
+            result = _target_scratch[key] = tc.empty(_TARGET_WORDS, dtype=tc.int64, device=error.device)
+    if result.dtype != tc.int64 or not result.is_cuda or not result.is_contiguous() or result.numel() < _TARGET_WORDS:
+        raise ValueError("plan_to_target: result must be a contiguous int64 CUDA tensor of %d words" % _TARGET_WORDS)
+    check(load().statmc_plan_to_target(w, h, error.data_ptr(), n.data_ptr(), float(target), int(c_min), int(c_max), out.data_ptr(),
+                                       C.cast(result.data_ptr(), C.POINTER(TargetResult)), st))
+    if not return_result:
+        return out
+    check(load().statmc_synchronize(st))
+    return out, target_result_dict(result)
 
 
 def score_select_workspace():

@@ -17,6 +17,7 @@
 #include "statmc_records_plan.h"
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
+#include "statmc_error_args.h"
 #include "statmc_select_args.h"
 #include "statmc_score_window_args.h"
 #include "statmc_compact_args.h"
@@ -1472,6 +1473,36 @@ int statmc_plan_samples(uint16_t width, uint16_t height, const float *score, con
     statmc::PlanArgs a;
     statmc::fill_plan_args(a, width, height, score, n, budget, c_min, c_max, sample_counts, result, workspace);
     HIP_TRY(statmc::launch_plan_samples(a, statmc::plan_workspace_bytes(width, height), S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_error_scores / statmc_plan_to_target: every rule of include/statmc.h ahead of the device (statmc_error_args.h), then the one
+// launch of statmc_error.hip on `stream`; nothing is allocated and nothing read back.  The table is the current device's, as it
+// stands when the call is made.
+int statmc_error_scores(uint16_t width, uint16_t height, int channels, int metric, float eps, int table, const int32_t *n,
+                        const float *film_mean, const float *film_m2, float *score, void *stream) {
+    ARG_TRY(statmc::check_error_scores_call(width, height, channels, metric, eps, table, n, film_mean, film_m2, score,
+                                            statmc::PlanMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    const float *tq = nullptr;
+    if (table != STATMC_ERROR_NO_TABLE) {
+        tq = statmc::t_table_device_ptr(table);
+        if (!tq) return fail(STATMC_ERR_HIP, "the device's quantile tables cannot be addressed");
+    }
+    statmc::ErrorArgs a;
+    statmc::fill_error_args(a, width, height, channels, metric, eps, tq, n, film_mean, film_m2, score);
+    HIP_TRY(statmc::launch_error_scores(a, S(stream)));
+    return STATMC_OK;
+}
+
+int statmc_plan_to_target(uint16_t width, uint16_t height, const float *error, const int32_t *n, float target, int32_t c_min, int32_t c_max,
+                          int32_t *sample_counts, statmc_target_result *result, void *stream) {
+    ARG_TRY(statmc::check_target_call(width, height, error, n, target, c_min, c_max, sample_counts, result,
+                                      statmc::PlanMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::TargetArgs a;
+    statmc::fill_target_args(a, width, height, error, n, target, c_min, c_max, sample_counts, result);
+    HIP_TRY(statmc::launch_plan_to_target(a, S(stream)));
     return STATMC_OK;
 }
 

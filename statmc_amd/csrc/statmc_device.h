@@ -225,6 +225,12 @@ struct PlanArgs;
 hipError_t launch_sample_scores(const ScoreArgs &a, hipStream_t s);
 hipError_t launch_plan_samples(const PlanArgs &a, size_t workspace_bytes, hipStream_t s);
 
+// statmc_error_scores / statmc_plan_to_target (statmc_error.hip): argument blocks and checks are statmc_error_args.h's, host-only
+struct ErrorArgs;
+struct TargetArgs;
+hipError_t launch_error_scores(const ErrorArgs &a, hipStream_t s);
+hipError_t launch_plan_to_target(const TargetArgs &a, hipStream_t s);
+
 // statmc_score_select / statmc_score_count_above (statmc_select.hip): argument blocks and checks are statmc_select_args.h's, host-only
 struct SelectArgs;
 struct CountAboveArgs;

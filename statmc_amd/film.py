@@ -217,29 +217,61 @@ class FilmStats:
         coarse._prepass_current = coarse._prepass_key() if fuse else None
         return coarse
 
-    def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False, dilate=0):
+    def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False, dilate=0, error=None):
         """The per-pixel sample counts of the next accumulation: `budget` samples spent by the noise of stat type `type` as it stands
         (statmc_sample_scores over its n and raw-sample Welford planes, then statmc_plan_samples with its n as the counts so far).
         Returns an int32 tensor [H, W] that accumulate(samples, counts=) takes as it is; with return_result=True, (counts, the
         statmc_plan_result as a dict) after a synchronisation.  dilate = r > 0: the plan spends by the worst score within r pixels
         (statmc_score_window, MAX), so a pixel beside a noisy one is not starved; 0: the pointwise score as it is, no extra launch.  The
-        film is only read."""
-        return api.plan_samples(self._scores(metric, eps, type, dilate), budget, c_min, c_max, n=self.state[type]["n"], return_result=return_result)
+        film is only read.  error: which quantity is scored -- None: the sample standard deviation, what a budget is best spent by;
+        "stderr" / "ci": the error of the mean (see score_quantiles)."""
+        return api.plan_samples(self._scores(metric, eps, type, dilate, error), budget, c_min, c_max, n=self.state[type]["n"], return_result=return_result)
 
-    def _scores(self, metric, eps, type, dilate=0):
-        """the noise score image of stat type `type` as it stands (statmc_sample_scores over its n and raw-sample Welford planes);
-        dilate > 0: its MAX window of that radius (statmc_score_window)"""
+    def _scores(self, metric, eps, type, dilate=0, error=None):
+        """the score image of stat type `type` as it stands over its n and raw-sample Welford planes -- error None: the sample standard
+        deviation (statmc_sample_scores); "stderr" / "ci": the standard error of the mean / the two-sided confidence half-width at the
+        device's significance level (statmc_error_scores); dilate > 0: its MAX window of that radius (statmc_score_window)"""
         st = self.state[type]
         film_mean = st["film_mean"] if st["film_mean"] is not None else st["mean"]
         film_m2 = st["film_m2"] if st["film_m2"] is not None else st["m2"]
-        scores = api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+        if error is None:
+            scores = api.sample_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps)
+        elif error in ("stderr", "ci"):
+            scores = api.error_scores(st["n"], film_mean, film_m2, metric=metric, eps=eps, table=error)
+        else:
+            raise ValueError("error must be None, \"stderr\" or \"ci\", not %r" % (error,))
         return api.score_window(scores, dilate, "max") if dilate else scores
 
-    def score_quantiles(self, qs, metric="relative", eps=1e-3, type="radiance", dilate=0):
-        """The q-quantiles (1 to 8 values of q in [0, 1]) of the noise score of stat type `type` as plan_samples computes it, by the
+    def plan_to_target(self, target, c_min, c_max, budget=None, metric="relative", eps=1e-3, type="radiance", error="ci", dilate=0,
+                       return_result=False):
+        """The per-pixel sample counts that bring the error of the mean of stat type `type` to `target`: statmc_error_scores ("ci": the
+        two-sided confidence half-width at the device's significance level; "stderr": the standard error), its MAX window for dilate > 0,
+        then statmc_plan_to_target with the type's n -- n (error / target)^2 - n per open pixel, clamped to [c_min, c_max]; c_min where
+        the pixel is at the target, c_max where it cannot be judged yet.  budget: if not None and the plan's total exceeds it, the budget
+        is spent instead as plan_samples spends it (the sample-deviation score of the same metric, eps and dilation).  Returns an int32
+        tensor [H, W] that accumulate(samples, counts=) takes as it is; with return_result=True, (counts, the statmc_target_result as a
+        dict with "by_budget" and, where the fallback ran, "budgeted": the statmc_plan_result).  One synchronisation and one 48-byte
+        download when budget or return_result asks for the result, none otherwise; the film is only read."""
+        if error not in ("stderr", "ci"):
+            raise ValueError("plan_to_target: error must be \"stderr\" or \"ci\", not %r" % (error,))
+        n = self.state[type]["n"]
+        errors = self._scores(metric, eps, type, dilate, error)
+        if budget is None and not return_result:
+            return api.plan_to_target(errors, n, target, c_min, c_max)
+        counts, res = api.plan_to_target(errors, n, target, c_min, c_max, return_result=True)
+        res["by_budget"] = budget is not None and res["total"] > budget
+        if res["by_budget"]:
+            counts, res["budgeted"] = api.plan_samples(self._scores(metric, eps, type, dilate), budget, c_min, c_max, n=n, out=counts,
+                                                       return_result=True)
+        return (counts, res) if return_result else counts
+
+    def score_quantiles(self, qs, metric="relative", eps=1e-3, type="radiance", dilate=0, error=None):
+        """The q-quantiles (1 to 8 values of q in [0, 1]) of the score of stat type `type` as plan_samples computes it, by the
         nearest-rank rule: rank(q) = max(0, ceil(q P) - 1) of the P pixels' keys in ascending order (statmc_score_select).  A
-        renderer's stopping rule: "the 95th percentile of the relative score is under 2 %".  Returns the values as numpy float32, one
-        per q, after one synchronisation and the download of one 256-byte struct; the film is only read.  dilate: as plan_samples'."""
+        renderer's stopping rule reads the error of the mean, error="stderr" or "ci": "the 95th percentile of the relative confidence
+        half-width is under 2 %".  error=None is the sample standard deviation, which converges to the pixel's sigma and does not fall
+        as samples arrive: no such rule can be met on it.  Returns the values as numpy float32, one per q, after one synchronisation
+        and the download of one 256-byte struct; the film is only read.  dilate: as plan_samples'."""
         import math
         from fractions import Fraction
         px = self.width * self.height
@@ -248,13 +280,13 @@ class FilmStats:
             if not 0 <= q <= 1:
                 raise ValueError("score_quantiles: q = %r is outside [0, 1]" % (q,))
             ranks.append(max(0, math.ceil(Fraction(float(q)) * px) - 1))     # Python integers: exact in q as the double it is (numpy scalars too)
-        return api.read_select_result(api.score_select(self._scores(metric, eps, type, dilate), ranks))["values"]
+        return api.read_select_result(api.score_select(self._scores(metric, eps, type, dilate, error), ranks))["values"]
 
-    def score_count_above(self, thresholds, metric="relative", eps=1e-3, type="radiance", dilate=0):
-        """Per threshold (1 to 8) the number of pixels whose noise score, as plan_samples computes it, is above it
+    def score_count_above(self, thresholds, metric="relative", eps=1e-3, type="radiance", dilate=0, error=None):
+        """Per threshold (1 to 8) the number of pixels whose score, as plan_samples computes it, is above it
         (statmc_score_count_above: NaN and negative scores count as 0).  "At most 1 % of the pixels are above tau."  Returns a list of
-        Python integers after one synchronisation and one small download; the film is only read.  dilate: as plan_samples'."""
-        return [int(c) for c in api.score_count_above(self._scores(metric, eps, type, dilate), thresholds).cpu().numpy()]
+        Python integers after one synchronisation and one small download; the film is only read.  dilate, error: as score_quantiles'."""
+        return [int(c) for c in api.score_count_above(self._scores(metric, eps, type, dilate, error), thresholds).cpu().numpy()]
 
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())

@@ -20,11 +20,19 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--score-dilate R]] [--placed] [--half-features]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-metric sd|stderr|ci] [--target-error T] [--score-dilate R]]
+//                     [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
 // --adaptive-pixels: per-pixel sample budgets planned on the device (Estimator::PlanSamples); see RenderLoop.
 // --stop-at Q:T: with --adaptive-pixels, the stopping rule: after every iteration the Q-quantile (nearest rank) of the relative radiance
 //                   score is selected on the device (Estimator::ScoreSelect); once it is <= T the remaining iterations are skipped.
+// --stop-metric M: which quantity --stop-at's quantile (and --target-error's plan) reads.  sd, the default: the sample standard
+//                   deviation, which does not fall as samples arrive -- only T = 0 or a T above the film's noise make sense with it;
+//                   stderr: the standard error of the mean; ci: the two-sided confidence half-width at the device's significance
+//                   level (Estimator's scoreOf).  With stderr or ci every iteration prints a "Stop metric:" line with the quantile.
+// --target-error T: with --adaptive-pixels, the next iteration's counts are the samples that bring every pixel's relative error
+//                   (--stop-metric's; ci if that is sd) to T, 1 .. 4 * target per pixel (Estimator::PlanToTarget), under the schedule's
+//                   budget: a plan that asks for more falls back to the budget plan.  Prints "Planned to target:".
 // --score-dilate R: with --adaptive-pixels, the plan and --stop-at's quantile read the worst score within R pixels (0 to 32) of every
 //                   pixel instead of the pixel's own (statmc_score_window, MAX: Estimator::PlanSamples' / ScoreSelect's scoreDilate).
 // --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
@@ -118,6 +126,10 @@ struct Options {
     bool stopAt = false;       // --stop-at Q:T
     double stopQuantile = 0.0;
     float stopThreshold = 0.f;
+    int stopMetric = Estimator::ScoreOfDeviation;   // --stop-metric sd|stderr|ci
+    bool stopMetricGiven = false;
+    bool targetErrorGiven = false;   // --target-error T
+    float targetError = 0.f;
     bool scoreDilateGiven = false;   // --score-dilate R
     int scoreDilate = 0;
     std::string stem, outputRegex = ".*";
@@ -300,19 +312,39 @@ static void Render(const Options &o) {
         if (o.stopAt && sCfgs[Radiance].enable) {
             const int64_t rank = Estimator::NearestRank(o.stopQuantile, (int64_t)width * height);
             statmc_select_result sel;
-            check(statmc_download(&sel, estimator.ScoreSelect(sCfgs[Radiance].index, 0, {rank}, STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate), sizeof(sel), estimator.DeviceStream()));
+            check(statmc_download(&sel, estimator.ScoreSelect(sCfgs[Radiance].index, 0, {rank}, STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate, o.stopMetric), sizeof(sel), estimator.DeviceStream()));
             estimator.Synchronize();
             float v;
             std::memcpy(&v, &sel.value_bits[0], sizeof(v));
+            const char *what = o.stopMetric == Estimator::ScoreOfStdErr ? "standard error" : o.stopMetric == Estimator::ScoreOfCI ? "confidence half-width" : "score";
+            char value[32];
+            std::snprintf(value, sizeof(value), "%.9g", (double)v);
+            if (o.stopMetric != Estimator::ScoreOfDeviation)
+                std::cout << "Stop metric: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
             if (v <= o.stopThreshold) {
                 converged = true;
-                char value[32];
-                std::snprintf(value, sizeof(value), "%.9g", (double)v);
-                std::cout << "Converged: iteration " << i << ", quantile " << o.stopQuantile << " of the relative score = " << value << std::endl;
+                std::cout << "Converged: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
             }
         }
 
-        if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations && !converged) {
+        if (o.adaptivePixels && o.targetErrorGiven && sCfgs[Radiance].enable && i < nIterations && !converged) {
+            const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
+            const int scoreOf = o.stopMetric == Estimator::ScoreOfDeviation ? (int)Estimator::ScoreOfCI : o.stopMetric;
+            const Estimator::TargetPlan plan = estimator.PlanToTarget(sCfgs[Radiance].index, 0, o.targetError, (int64_t)width * height * next, 1,
+                                                                      (int32_t)(4 * next), STATMC_SCORE_RELATIVE, 1e-3f, scoreOf, o.scoreDilate);
+            pixelTarget.resize((size_t)width * height);
+            check(statmc_download(pixelTarget.data(), plan.d_counts, pixelTarget.size() * sizeof(int32_t), estimator.DeviceStream()));
+            estimator.Synchronize();
+            std::cout << "Planned to target: total " << plan.target.total << ", need " << plan.target.need << ", n_open " << plan.target.n_open
+                      << ", n_capped " << plan.target.n_capped << ", by " << (plan.byBudget ? "budget" : "target") << std::endl;
+            if (plan.byBudget) {
+                int32_t lo = pixelTarget[0], hi = pixelTarget[0];
+                for (int32_t v : pixelTarget) { lo = std::min(lo, v); hi = std::max(hi, v); }
+                char level[16];
+                std::snprintf(level, sizeof(level), "%08x", (unsigned)plan.budgeted.level_bits);
+                std::cout << "Planned: " << plan.budgeted.total << " samples, " << lo << " .. " << hi << " per pixel, level 0x" << level << std::endl;
+            }
+        } else if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations && !converged) {
             const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
             const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next),
                                                                      STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate);
@@ -428,6 +460,23 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--stop-at takes Q:T, a quantile in [0, 1] and a threshold\n");
                 return 2;
             }
+        } else if (a == "--stop-metric") {
+            const std::string v = next();
+            if (v != "sd" && v != "stderr" && v != "ci") {
+                std::fprintf(stderr, "--stop-metric takes sd, stderr or ci\n");
+                return 2;
+            }
+            o.stopMetricGiven = true;
+            o.stopMetric = v == "sd" ? Estimator::ScoreOfDeviation : v == "stderr" ? Estimator::ScoreOfStdErr : Estimator::ScoreOfCI;
+        } else if (a == "--target-error") {
+            const std::string v = next();
+            char *end = nullptr;
+            o.targetError = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end != 0 || !(o.targetError >= 0x1p-60f && o.targetError <= 0x1p60f)) {
+                std::fprintf(stderr, "--target-error takes a tolerance in [2^-60, 2^60]\n");
+                return 2;
+            }
+            o.targetErrorGiven = true;
         } else if (a == "--score-dilate") {
             const std::string v = next();
             char *end = nullptr;
@@ -467,6 +516,10 @@ int main(int argc, char **argv) {
     }
     if (o.stopAt && !o.adaptivePixels) {
         std::fprintf(stderr, "--stop-at needs --adaptive-pixels\n");
+        return 2;
+    }
+    if ((o.stopMetricGiven || o.targetErrorGiven) && !o.adaptivePixels) {
+        std::fprintf(stderr, "--stop-metric and --target-error need --adaptive-pixels\n");
         return 2;
     }
     if (o.scoreDilateGiven && !o.adaptivePixels) {

@@ -787,6 +787,40 @@ typedef struct statmc_pool_entry {
 
 int statmc_pool_statistics(uint16_t width, uint16_t height, int k, const statmc_pool_entry *entries, int n_entries, void *stream);
 
+/* ---- the way back up (no counterpart in the reference): the FILTERED image of a film pooled k x k, brought onto the fine film by a
+ * statistics-gated joint upsampling.  `fine` and `coarse` are the argument blocks the filter entries take for the two films; the
+ * coarse one has been through statmc_prepass and statmc_window_filter, the fine one through statmc_prepass (or a fused epilogue).
+ * One HBM-bound launch per buffer on fine->stream; the fine film is only read, nothing is allocated or read back.
+ *   read from `fine`, per buffer b < n_buffers: mean_corr[b], discriminator[b], the colour image (film_buffer if denoise_film and
+ *     b == 0 and channels == 3, else film[b]), g_buffers / g_channel_counts / g_dr_factors / n_g_buffers, the ROI (all-zero: the
+ *     whole film), stream;
+ *   read from `coarse`: mean_corr[b], discriminator[b], g_buffers, and its filtered image (film_filtered_buffer if denoise_film and
+ *     b == 0 and channels == 3, else film_filtered[b]);
+ *   written: the fine filtered image of every buffer, for the pixels of the ROI.  Nothing else.
+ * The filter spec is the current device's (gate, channel_rule, border; sides and small_n are already inside the images).
+ * DEFINITION, per fine pixel p = (x, y) and buffer; every float operation rounds once, in this order, no contraction:
+ *   t = 2 x + 1 - k;  X0 = floor(t / 2k) (-1 in the left half-block);  a = t - 2k X0, odd, in [1, 2k - 1];
+ *   wx[0] = (2k - a) / 2k, wx[1] = a / 2k (dyadic: exact);  the same in y.  The tents sit on the regular grid of block centres; a
+ *   partial edge block does not move its centre.
+ *   Candidates Q = (X0 + i, Y0 + j) in the order (j, i) = (0,0) (0,1) (1,0) (1,1).  Outside the coarse image: skipped under
+ *   STATMC_BORDER_CLIP, coordinates clamped under STATMC_BORDER_CLAMP.  A candidate that is not a valid pixel -- corrected mean and
+ *   FILTERED colour finite, discriminator not NaN, every G-buffer value finite -- is skipped.
+ *   (p, Q) is a member by the window filter's pair test under STATMC_DOF_PIXEL: p supplies D_p, Q supplies D_q, with the fma where
+ *   the gates above have it, all three gates and both channel rules.
+ *   e = 0;  per G-buffer: dist2 = d0 d0, then fma(dc, dc, dist2) per further channel;  e = fma(dr_g, dist2, e), G(p) fine, G(Q) coarse;
+ *   w = (wx[i] wy[j]) exp(e);   sum_w += w;   acc[c] += w * filtered(Q)[c]   (multiply and add rounded separately).
+ *   out[c] = acc[c] / sum_w if sum_w > 0, else the bits of p's own colour; a p that is not a valid pixel (its own colour in the
+ *   colour's place) passes its colour through bit for bit, NaN included.
+ * exp may be the hardware exponential (<= 1e-5 relative L2 against a double evaluation, as every filter kernel here); it is exactly 1
+ * where e == 0 -- no G-buffers, all factors 0, equal features --, and there the whole result is this definition bit for bit.
+ * STATMC_ERR_INVALID, statmc_last_error() naming the argument: a NULL block; k not 2, 4 or 8; channels not 1 or 3; a coarse size
+ * other than ceil(width / k) x ceil(height / k); n_buffers, n_g_buffers or a channel count differing between the blocks; a NULL table
+ * or image; a bad ROI; an output overlapping any image the call reads.  STATMC_ERR_UNSUPPORTED, nothing written: STATMC_DOF_WELCH
+ * (its discriminator image is not a discriminator); packed_inputs on either side; pitched images; more than two RGB or two
+ * one-channel G-buffers.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.  One level per call: a host may chain
+ * 8 -> 4 -> 2 -> 1, each call defined on its own.  Measured: DESIGN.md 4.2h, profiles/upsample.jsonl. */
+int statmc_upsample_filtered(const statmc_filter_args *fine, const statmc_filter_args *coarse, int k, int channels);
+
 /* ---- planning per-pixel sample counts from the statistics (no counterpart in the reference): what feeds the sample_counts of
  * statmc_accumulate_counted / statmc_accumulate_tiles_counted.  Two entries: a pointwise noise score, and the allocation of a
  * budget by a score image.  Minimising the summed variance of the mean, sum_p s_p^2 / (n_p + c_p), under a fixed sum of c_p gives

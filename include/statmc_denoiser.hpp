@@ -870,21 +870,7 @@ class Estimator {
     void Denoise() {  // estimator.cpp:427-489
         if (usePlacedMemory() && !placementTrimmed) TrimPlacedMemory();   // (the trim synchronises the device itself)
         stat_denoiser::FilterCall calls[2];
-        int nCalls = 0;
-        if (floatBufferCounts[DenoiseGroup] > 0) {
-            const Tables &t = floatTables[DenoiseGroup];
-            stat_denoiser::fillFilterCall<float>(calls[nCalls++], floatBufferCounts[DenoiseGroup], width, height, filterDSFactor,
-                                                 filterRadius, denoiseFilm, t.n, t.mean, t.m2, t.m3, t.film, filmBuffer.gpuMat,
-                                                 gBufferImages, gBufferChannelCounts, gBufferDRFactors, gBuffers.size(),
-                                                 t.meanCorr, t.discriminator, t.filmFiltered, filmFilteredBuffer.gpuMat, stream);
-        }
-        if (rgbBufferCounts[DenoiseGroup] > 0) {
-            const Tables &t = rgbTables[DenoiseGroup];
-            stat_denoiser::fillFilterCall<float3>(calls[nCalls++], rgbBufferCounts[DenoiseGroup], width, height, filterDSFactor,
-                                                  filterRadius, denoiseFilm, t.n, t.mean, t.m2, t.m3, t.film, filmBuffer.gpuMat,
-                                                  gBufferImages, gBufferChannelCounts, gBufferDRFactors, gBuffers.size(),
-                                                  t.meanCorr, t.discriminator, t.filmFiltered, filmFilteredBuffer.gpuMat, stream);
-        }
+        const int nCalls = denoiseCalls(calls);
         if (pipe.downloading) {   // copies out of an earlier Download() still read the images this call rewrites
             check(statmc_event_record(pipe.join, pipe.down));
             check(statmc_stream_wait_event(stream.handle(), pipe.join));
@@ -1608,7 +1594,90 @@ class Estimator {
             check(statmc_pool_statistics(width, height, k, rest.data() + q, (int)std::min(cap, rest.size() - q), coarse.stream.handle()));
     }
 
+    // The way back up: brings `coarse`'s filtered images -- this Estimator pooled k x k (PoolStatistics) and denoised -- onto this
+    // Estimator's filtered images, "film-f" among them, by statmc_upsample_filtered (include/statmc.h has the definition): per fine
+    // pixel the four coarse pixels around it, weighed by a bilinear tent and the G-buffer range term, where they pass the filter's
+    // membership test against the fine pixel, and the pixel's own colour where none does.  Needs this Estimator's mean-corr /
+    // discriminator images (the pre-pass; DenoisePreview runs it) and coarse.Denoise().  The same checks as PoolStatistics.  Pending
+    // device-accumulation samples are flushed first; the launch is enqueued on this Estimator's stream, behind everything on
+    // `coarse`'s.  Statistics are only read; Download() afterwards fetches the film-sized "film-f".
+    void UpsampleFiltered(Estimator &coarse, int k) {
+        upsampleChecks(coarse, k, "UpsampleFiltered");
+        upsampleJoin(coarse);
+        stat_denoiser::FilterCall fine[2], low[2];
+        const int nCalls = denoiseCalls(fine);
+        if (coarse.denoiseCalls(low) != nCalls) throw Error(STATMC_ERR_INVALID, "UpsampleFiltered: the Estimators denoise different buffer groups");
+        for (int c = 0; c < nCalls; c++) check(statmc_upsample_filtered(&fine[c].a, &low[c].a, k, fine[c].channels));
+        pipe.denoised = 0;   // Download() fetches whole images behind `stream`
+    }
+    // A film-sized denoised image at the price of a filter pass over ceil(width / k) x ceil(height / k) pixels: PoolStatistics(coarse,
+    // k), coarse.Denoise(), this Estimator's pre-pass, UpsampleFiltered(coarse, k).  Call it where Denoise() would be called, after
+    // Upload(); the last iteration of a progressive render still calls Denoise().  borrowCounts: as for PoolStatistics.
+    void DenoisePreview(Estimator &coarse, int k, const std::vector<unsigned char> &borrowCounts = {}) {
+        upsampleChecks(coarse, k, "DenoisePreview");
+        PoolStatistics(coarse, k, borrowCounts);
+        coarse.Denoise();
+        if (pipe.downloading) {   // copies out of an earlier Download() still read the images this call rewrites
+            check(statmc_event_record(pipe.join, pipe.down));
+            check(statmc_stream_wait_event(stream.handle(), pipe.join));
+        }
+        joinUploads();
+        pipe.uploaded = 0;
+        stat_denoiser::FilterCall fine[2];
+        const int nCalls = denoiseCalls(fine);
+        for (int c = 0; c < nCalls; c++) check(statmc_prepass(&fine[c].a, fine[c].channels));
+        UpsampleFiltered(coarse, k);
+    }
+
   private:
+    void upsampleChecks(const Estimator &coarse, int k, const char *who) const {
+        const std::string w(who);
+        if (k != 2 && k != 4 && k != 8) throw Error(STATMC_ERR_INVALID, w + ": k must be 2, 4 or 8");
+        if (&coarse == this) throw Error(STATMC_ERR_INVALID, w + ": an Estimator cannot be its own coarse film");
+        if (!allocateDevice || !coarse.allocateDevice) throw Error(STATMC_ERR_INVALID, w + " needs device images");
+        if (coarse.device != device) throw Error(STATMC_ERR_INVALID, w + ": both Estimators must be on one device");
+        if (coarse.width != (width + k - 1) / k || coarse.height != (height + k - 1) / k)
+            throw Error(STATMC_ERR_INVALID, w + ": the coarse film must have ceil(width / k) x ceil(height / k) pixels");
+        if (!sameConfiguration(coarse)) throw Error(STATMC_ERR_INVALID, w + ": the Estimators have different stat type configurations");
+    }
+    // flushes and uploads of both sides done, this stream behind the coarse one's
+    void upsampleJoin(Estimator &coarse) {
+        check(statmc_set_device(device));
+        if (acc.enabled) FlushSamples();
+        if (coarse.acc.enabled) coarse.FlushSamples();
+        joinUploads();
+        coarse.joinUploads();
+        if (!coarse.combineEvent) {
+            void *ev = nullptr;
+            check(statmc_event_create(&ev));
+            coarse.combineEvent.reset(ev, [](void *e) { statmc_event_destroy(e); });
+        }
+        check(statmc_event_record(coarse.combineEvent.get(), coarse.stream.handle()));
+        check(statmc_stream_wait_event(stream.handle(), coarse.combineEvent.get()));
+        if (pipe.downloading) {   // copies out of an earlier Download() still read the images the launch rewrites
+            check(statmc_event_record(pipe.join, pipe.down));
+            check(statmc_stream_wait_event(stream.handle(), pipe.join));
+        }
+    }
+    // the filter<float> and filter<float3> argument blocks of the denoise group, as Denoise() passes them
+    int denoiseCalls(stat_denoiser::FilterCall (&calls)[2]) {
+        int nCalls = 0;
+        if (floatBufferCounts[DenoiseGroup] > 0) {
+            const Tables &t = floatTables[DenoiseGroup];
+            stat_denoiser::fillFilterCall<float>(calls[nCalls++], floatBufferCounts[DenoiseGroup], width, height, filterDSFactor,
+                                                 filterRadius, denoiseFilm, t.n, t.mean, t.m2, t.m3, t.film, filmBuffer.gpuMat,
+                                                 gBufferImages, gBufferChannelCounts, gBufferDRFactors, gBuffers.size(),
+                                                 t.meanCorr, t.discriminator, t.filmFiltered, filmFilteredBuffer.gpuMat, stream);
+        }
+        if (rgbBufferCounts[DenoiseGroup] > 0) {
+            const Tables &t = rgbTables[DenoiseGroup];
+            stat_denoiser::fillFilterCall<float3>(calls[nCalls++], rgbBufferCounts[DenoiseGroup], width, height, filterDSFactor,
+                                                  filterRadius, denoiseFilm, t.n, t.mean, t.m2, t.m3, t.film, filmBuffer.gpuMat,
+                                                  gBufferImages, gBufferChannelCounts, gBufferDRFactors, gBuffers.size(),
+                                                  t.meanCorr, t.discriminator, t.filmFiltered, filmFilteredBuffer.gpuMat, stream);
+        }
+        return nCalls;
+    }
     bool sameConfiguration(const Estimator &other) const {
         const auto &a = statTypeConfigs, &b = other.statTypeConfigs;
         bool same = a.nEnabled == b.nEnabled;

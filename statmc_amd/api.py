@@ -142,7 +142,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -241,6 +241,7 @@ def load():
     lib.statmc_combine_statistics.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineEntry), C.c_int, C.c_void_p]
     lib.statmc_combine_many.argtypes = [C.c_uint16, C.c_uint16, C.POINTER(CombineManyEntry), C.c_int, C.c_int, C.c_void_p]
     lib.statmc_pool_statistics.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.POINTER(PoolEntry), C.c_int, C.c_void_p]
+    lib.statmc_upsample_filtered.argtypes = [C.POINTER(FilterArgs), C.POINTER(FilterArgs), C.c_int, C.c_int]
     lib.statmc_sample_scores.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.statmc_plan_samples_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_plan_samples_workspace.restype = C.c_size_t
@@ -720,6 +721,13 @@ def pool_statistics(width, height, k, entries, stream=None):
     arr = (PoolEntry * max(len(entries), 1))(*entries)
     check(load().statmc_pool_statistics(int(width), int(height), int(k), arr, len(entries),
                                         stream if stream is not None else current_stream_handle()))
+
+
+def upsample_filtered(fine_args, coarse_args, k, channels):
+    """The filtered image of the film pooled k x k (coarse_args: after its pre-pass and window filter) onto the fine film's filtered
+    image (fine_args: after its pre-pass), by statmc_upsample_filtered: one launch per buffer on fine_args.stream, the fine film is
+    only read.  Both blocks are make_filter_args'."""
+    check(load().statmc_upsample_filtered(C.byref(fine_args), C.byref(coarse_args), int(k), int(channels)))
 
 
 _METRICS = {"absolute": SCORE_ABSOLUTE, "relative": SCORE_RELATIVE}

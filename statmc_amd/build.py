@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
-           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_error.hip", "statmc_select.hip", "statmc_score_window.hip", "statmc_compact.hip", "statmc_state_records.hip"]
-HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_state_records_args.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_error_args.h", "statmc_select_args.h", "statmc_score_window_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_error.hip", "statmc_upsample.hip", "statmc_select.hip", "statmc_score_window.hip", "statmc_compact.hip", "statmc_state_records.hip"]
+HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_state_records_args.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_error_args.h", "statmc_upsample_args.h", "statmc_select_args.h", "statmc_score_window_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -117,7 +117,9 @@ STATE_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_state_records_args")  
 STATE_BIN = os.path.join(ROOT, "tools", "bin", "test_state_records")   # tests/cpp/test_state_records.cpp: Estimator::GatherStates / CombineRecords
 ERROR_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_error_args")   # tests/cpp/test_error_args.cpp: statmc_error_args.h, no device, no library
 TARGET_BIN = os.path.join(ROOT, "tools", "bin", "test_plan_to_target")   # tests/cpp/test_plan_to_target.cpp: Estimator::PlanToTarget / scoreOf
+UPSAMPLE_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_upsample_args")   # tests/cpp/test_upsample_args.cpp: statmc_upsample_args.h, no device, no library
 TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.cpp",
+         UPSAMPLE_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_upsample_args.cpp"),
          ERROR_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_error_args.cpp"),
          TARGET_BIN: os.path.join("..", "tests", "cpp", "test_plan_to_target.cpp"),
          CV_ADAPTOR_BIN: os.path.join("..", "tests", "cpp", "test_cv_adaptor.cpp"),
@@ -168,6 +170,7 @@ def tools_hash():
     files.append(os.path.join(CSRC, "statmc_pool_args.h"))    # ... test_pool_args.cpp the pooling entry's checks
     files.append(os.path.join(CSRC, "statmc_plan_args.h"))    # ... test_plan_args.cpp the planning entries' checks
     files.append(os.path.join(CSRC, "statmc_error_args.h"))    # ... test_error_args.cpp the error entries' checks
+    files.append(os.path.join(CSRC, "statmc_upsample_args.h"))    # ... test_upsample_args.cpp the upsampling entry's checks
     files.append(os.path.join(CSRC, "statmc_select_args.h"))  # ... test_select_args.cpp the order-statistics entries' checks
     files.append(os.path.join(CSRC, "statmc_score_window_args.h"))    # ... test_score_window_args.cpp the window entry's checks
     files.append(os.path.join(CSRC, "statmc_compact_args.h"))    # ... test_compact_args.cpp the compact entries' checks

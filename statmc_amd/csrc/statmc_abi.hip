@@ -18,6 +18,7 @@
 #include "statmc_pool_args.h"
 #include "statmc_plan_args.h"
 #include "statmc_error_args.h"
+#include "statmc_upsample_args.h"
 #include "statmc_select_args.h"
 #include "statmc_score_window_args.h"
 #include "statmc_compact_args.h"
@@ -1503,6 +1504,21 @@ int statmc_plan_to_target(uint16_t width, uint16_t height, const float *error, c
     statmc::TargetArgs a;
     statmc::fill_target_args(a, width, height, error, n, target, c_min, c_max, sample_counts, result);
     HIP_TRY(statmc::launch_plan_to_target(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_upsample_filtered: every rule of include/statmc.h ahead of the device (statmc_upsample_args.h) -- the spec is the current
+// device's, as it stands when the call is made --, then one launch of statmc_upsample.hip per buffer on the fine block's stream;
+// nothing is allocated and nothing read back.
+int statmc_upsample_filtered(const statmc_filter_args *fine, const statmc_filter_args *coarse, int k, int channels) {
+    const DeviceState dstate = current_state();
+    if (int rc = statmc::check_upsample_call(fine, coarse, k, channels, dstate.spec.dof, statmc::UpsampleMsg{g_err, sizeof(g_err)})) return rc;
+    if (!dstate.ready) return fail(STATMC_ERR_NO_DEVICE, "statmc_setup() has not been called for the current device");
+    for (int b = 0; b < fine->n_buffers; b++) {
+        statmc::UpsampleArgs a;
+        statmc::fill_upsample_args(a, fine, coarse, k, channels, b, dstate.spec);
+        HIP_TRY(statmc::launch_upsample(a, S(fine->stream)));
+    }
     return STATMC_OK;
 }
 

@@ -231,6 +231,10 @@ struct TargetArgs;
 hipError_t launch_error_scores(const ErrorArgs &a, hipStream_t s);
 hipError_t launch_plan_to_target(const TargetArgs &a, hipStream_t s);
 
+// statmc_upsample_filtered (statmc_upsample.hip): the argument block and its checks are statmc_upsample_args.h's, a host-only header
+struct UpsampleArgs;
+hipError_t launch_upsample(const UpsampleArgs &a, hipStream_t s);
+
 // statmc_score_select / statmc_score_count_above (statmc_select.hip): argument blocks and checks are statmc_select_args.h's, host-only
 struct SelectArgs;
 struct CountAboveArgs;

@@ -59,6 +59,7 @@ class FilmStats:
         self.mean_corr, self.disc, self.film, self.film_f = z3(), z3(), z3(), z3()
         self.fused_prepass = bool(fused_prepass)
         self._prepass_current = None      # (filter spec, significance) under which the epilogue's result was written
+        self._previews = {}               # k -> the coarse film of preview(k), kept for the next call at that k
 
     def reset(self):
         self._prepass_current = None
@@ -205,6 +206,11 @@ class FilmStats:
         wc, hc = api.pooled_size(self.width, self.height, k)
         coarse = FilmStats(wc, hc, self.device, types=self.types, filter_sd=self.filter_sd, radius=self.radius,
                            g_buffers=self.g_names, g_sds=self.g_sds, placed=self.placed, fused_prepass=self.fused_prepass)
+        self._pool_into(coarse, k)
+        return coarse
+
+    def _pool_entries(self, coarse):
+        """the entries of pooled(k)'s launch into `coarse`: every stat type with its own counts, "film" with the radiance counts"""
         fuse = self.fused_prepass and "radiance" in self.types
         entries = []
         for t in self.types:
@@ -213,9 +219,44 @@ class FilmStats:
                                                prepass_into=(coarse.mean_corr, coarse.disc) if (fuse and t == "radiance") else None))
         if "radiance" in self.types and self.film is not None:
             entries.append(api.make_pool_entry({"mean": coarse.film}, {"mean": self.film}, 3, 1, count_of=self.types.index("radiance")))
+        return entries, fuse
+
+    def _pool_into(self, coarse, k):
+        """pooled(k)'s launch into an existing coarse film of the right size and types: every plane of it is written"""
+        entries, fuse = self._pool_entries(coarse)
         api.pool_statistics(self.width, self.height, k, entries)
         coarse._prepass_current = coarse._prepass_key() if fuse else None
-        return coarse
+
+    def upsample_from(self, coarse, k, roi=None):
+        """The filtered image of `coarse` -- this film pooled k x k, denoised -- brought onto this film's filtered image by
+        statmc_upsample_filtered: per fine pixel the four coarse pixels around it, weighed by a bilinear tent and the G-buffer range
+        term, where they pass the filter's membership test against the fine pixel; the pixel's own colour where none does.  Needs this
+        film's mean-corr / discriminator (prepass()) and the coarse film's pre-pass and window filter.  One launch; the statistics of
+        both films are only read.  For a host that holds its own pyramid; preview(k) runs the whole path.  Returns film_f."""
+        if (coarse.width, coarse.height) != api.pooled_size(self.width, self.height, k) or coarse.device != self.device:
+            raise ValueError("upsample_from: coarse must be this film pooled by k = %d, %dx%d on %s" %
+                             ((k,) + api.pooled_size(self.width, self.height, k) + (self.device,)))
+        if coarse.g_names != self.g_names:
+            raise ValueError("upsample_from: both films must carry the same G-buffers (%s / %s)" % (self.g_names, coarse.g_names))
+        fine_args, keep_f = self.filter_args(roi=roi)
+        coarse_args, keep_c = coarse.filter_args()
+        api.upsample_filtered(fine_args, coarse_args, k, 3)
+        return self.film_f
+
+    def preview(self, k):
+        """A film-sized denoised image at the price of a filter pass over ceil(W / k) x ceil(H / k) pixels: pooled(k), the coarse
+        film's pre-pass and window filter, this film's pre-pass (nothing to do after a fused epilogue), upsample_from.  k = 2, 4 or 8.
+        The coarse FilmStats stays on self and is pooled into again by the next preview at the same k; this film's statistics are only
+        read.  Returns film_f -- the image denoise() writes; the last iteration of a progressive render still calls denoise()."""
+        coarse = self._previews.get(k)
+        if coarse is None:
+            coarse = self._previews[k] = self.pooled(k)
+        else:
+            self._pool_into(coarse, k)
+        coarse.prepass()
+        coarse.window_filter()
+        self.prepass()
+        return self.upsample_from(coarse, k)
 
     def plan_samples(self, budget, c_min, c_max, metric="relative", eps=1e-3, type="radiance", return_result=False, dilate=0, error=None):
         """The per-pixel sample counts of the next accumulation: `budget` samples spent by the noise of stat type `type` as it stands

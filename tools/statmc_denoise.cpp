@@ -11,6 +11,7 @@
 //                  [--placed]                          device images from statmc_malloc_placed (statmc::usePlacedMemory())
 //                  [--combine S1[,S2,..] --output-stem O [--write-combined] [--combine-mem GiB]]   dumps of independent renders, combined
 //                  [--pool 2|4|8 [--output-stem O]]    k x k pixel blocks pooled into a coarser film, which is denoised and written
+//                  [--pool 2|4|8 --upsample]           ... and its film-f brought back onto the fine film: outputs at the fine size
 //   statmc_denoise --catalogue [--config denoise|acrr|smis|proden|ours] [--width W --height H]
 //
 // Per iteration it reads "<stem>-<spp>-film.pfm" and every "<stem>-<spp>-t<i>-b<j>-<suffix>.pfm"
@@ -36,6 +37,9 @@
 // film of ceil(width / k) x ceil(height / k) pixels (Estimator::PoolStatistics, statmc_pool_statistics: k^2 times the samples per
 // pixel, 1 / k^2 of the pixels); that film is denoised and the selected buffers are written at its size, under the input's names
 // or under "<O>-<spp>-<buffer>.pfm" with --output-stem.  Types without an n file are pooled with t0-b0-n, as under --combine.
+// --pool k --upsample: the coarse film's filtered images are upsampled onto the fine film (Estimator::DenoisePreview,
+// statmc_upsample_filtered: a preview of the denoise pass at a fraction of its cost); the selected buffers are the FINE film's and are
+// written at its size, film-f among them.  Without --upsample the output of --pool is what it was.
 #include <chrono>
 #include <memory>
 #include <cmath>
@@ -130,7 +134,7 @@ static StatPathParams shippedConfig(const std::string &name) {
 int main(int argc, char **argv) {
     try {
         std::string stem, sppList, output = "film-f", config = "denoise", compareStem, tqFile, specText, gridText, devicesText;
-        bool noWrite = false, writeCombined = false;
+        bool noWrite = false, writeCombined = false, upsample = false;
         std::string combineText, outputStem;
         size_t combineMemBytes = 8ull << 30;   // --combine-mem GiB: the images of the other stems held at once
         int forceParts = 0, bands = 0, pool = 0;
@@ -175,6 +179,7 @@ int main(int argc, char **argv) {
             else if (a == "--combine-mem") combineMemBytes = (size_t)(std::stod(next()) * (double)(1ull << 30));
             else if (a == "--write-combined") writeCombined = true;
             else if (a == "--pool") pool = std::stoi(next());
+            else if (a == "--upsample") upsample = true;
             else if (a == "--width") width = std::stoi(next());
             else if (a == "--height") height = std::stoi(next());
             else throw std::runtime_error("unknown option " + a);
@@ -188,6 +193,7 @@ int main(int argc, char **argv) {
         } else if ((!outputStem.empty() && !pool) || writeCombined) {
             throw std::runtime_error("--output-stem goes with --combine or --pool, --write-combined with --combine");
         }
+        if (upsample && !pool) throw std::runtime_error("--upsample goes with --pool (the coarse film it brings back up)");
         if (pool) {
             if (pool != 2 && pool != 4 && pool != 8) throw std::runtime_error("--pool 2 | 4 | 8");
             if (!gridText.empty()) throw std::runtime_error("--pool cannot be used with --grid (the coarse film is denoised on one device)");
@@ -259,8 +265,9 @@ int main(int argc, char **argv) {
             coarseEst->SetPipelineBands(1);
             std::cout << "pool: " << width << " x " << height << " pooled " << pool << " x " << pool << " into " << wc << " x " << hc << std::endl;
         }
-        Estimator &work = pool ? *coarseEst : est;                 // what is denoised and written
-        const BufferRegistry &workReg = pool ? *coarseReg : reg;
+        const bool coarseOut = pool && !upsample;                  // --upsample: the fine film is written again
+        Estimator &work = coarseOut ? *coarseEst : est;            // what is written
+        const BufferRegistry &workReg = coarseOut ? *coarseReg : reg;
         const int outWidth = work.width, outHeight = work.height;
         // --combine: the dumps of up to STATMC_MAX_COMBINE_SOURCES other stems at a time, as many as fit the memory bound
         struct Part {
@@ -417,13 +424,14 @@ int main(int argc, char **argv) {
             } else if (!outputStem.empty()) {
                 outPrefix = outputStem + "-" + spp + "-";
             }
-            if (pool) est.PoolStatistics(*coarseEst, pool, borrow);   // (enqueued on the coarse Estimator's stream, behind est's)
+            if (coarseOut) est.PoolStatistics(*coarseEst, pool, borrow);   // (enqueued on the coarse Estimator's stream, behind est's)
             auto t1 = clk::now();
             std::cout << "I/O time [ns]: " << std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count() << std::endl;
             t0 = clk::now();
             if (combineStems.empty() && !pool) est.Upload();   // (--combine, --pool: uploaded above)
             const auto tu = clk::now();
             if (shards) shards->Denoise();   // film blocks + halo exchange (statmc_halo_exchange), same result bit for bit
+            else if (upsample) est.DenoisePreview(*coarseEst, pool, borrow);   // pool, coarse denoise, fine pre-pass, upsample
             else work.Denoise();
             const auto td = clk::now();
             work.Download();

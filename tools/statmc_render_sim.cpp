@@ -37,6 +37,10 @@
 //                   pixel instead of the pixel's own (statmc_score_window, MAX: Estimator::PlanSamples' / ScoreSelect's scoreDilate).
 // --half-features: every stat type without the radiance transform (normal, albedo, the MIS tallies) is staged and uploaded in IEEE
 //                   half (Estimator::SetSampleFormat); radiance stays fp32.  "Staged bytes:" at the end counts what went up.
+// --preview K: every iteration but the last denoises through the preview path -- the film pooled K x K (2, 4 or 8), that coarse film
+//                   denoised, its result brought back onto the fine film (Estimator::DenoisePreview, statmc_upsample_filtered) --, the last
+//                   through the full filter.  The dumps and the timing lines keep their form.  Not with --stop-at: which iteration is the
+//                   last is then not known before its denoise pass.
 // --config denoise: Render<Vec3>, RGB radiance + normal + albedo, filter<float3> (scenes/render-denoise.pbrt).
 // --config acrr:    Render<Float>, "multichannelstats" false: the luminance of the path prefix up to each
 //                   of the tracked bounces is one float stat buffer, filtered together by filter<float>
@@ -50,6 +54,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <thread>
 
@@ -132,6 +137,7 @@ struct Options {
     float targetError = 0.f;
     bool scoreDilateGiven = false;   // --score-dilate R
     int scoreDilate = 0;
+    int preview = 0;           // --preview K
     std::string stem, outputRegex = ".*";
 };
 
@@ -158,6 +164,18 @@ static void Render(const Options &o) {
         for (unsigned char t = 0; t < estimator.statTypeConfigs.nEnabled; t++)
             if (!estimator.statTypeConfigs.configs[t].transform) estimator.SetSampleFormat(t, STATMC_SAMPLES_F16);
     estimator.EnableDeviceAccumulation((size_t)o.stageMb << 20);
+    // --preview: the coarse film, an Estimator of the same configuration that nothing accumulates into
+    std::unique_ptr<Buffer> coarseFilm;
+    std::unique_ptr<BufferRegistry> coarseReg;
+    std::unique_ptr<Estimator> coarseEst;
+    if (o.preview) {
+        const int wc = (width + o.preview - 1) / o.preview, hc = (height + o.preview - 1) / o.preview;
+        coarseFilm.reset(new Buffer("film", HostImage(hc, wc, F32C3)));
+        coarseReg.reset(new BufferRegistry(*coarseFilm));
+        coarseEst.reset(new Estimator(*coarseFilm, sCfgs, o.filterSD, (unsigned char)o.filterRadius, /*denoiseFilm=*/false, o.acrr, o.smis, *coarseReg));
+        coarseEst->AllocateBuffers(*coarseReg);
+        coarseEst->SetPipelineBands(1);
+    }
 
     std::vector<StatTypeConfig> enabledRGBFeatureCfgs;  // statpath.cpp:160-163
     for (unsigned char t : {(unsigned char)StatMaterialID, (unsigned char)StatDepth, (unsigned char)StatNormal,
@@ -294,7 +312,8 @@ static void Render(const Options &o) {
         begin = std::chrono::steady_clock::now();
         estimator.Upload();  // stages + accumulates the iteration's samples on the device
         if (estimator.runCUDA) {
-            estimator.Denoise();
+            if (o.preview && i < nIterations) estimator.DenoisePreview(*coarseEst, o.preview);
+            else estimator.Denoise();
             estimator.Download();
         }
         estimator.Synchronize();
@@ -468,6 +487,12 @@ int main(int argc, char **argv) {
             }
             o.stopMetricGiven = true;
             o.stopMetric = v == "sd" ? Estimator::ScoreOfDeviation : v == "stderr" ? Estimator::ScoreOfStdErr : Estimator::ScoreOfCI;
+        } else if (a == "--preview") {
+            o.preview = std::atoi(next());
+            if (o.preview != 2 && o.preview != 4 && o.preview != 8) {
+                std::fprintf(stderr, "--preview 2 | 4 | 8\n");
+                return 2;
+            }
         } else if (a == "--target-error") {
             const std::string v = next();
             char *end = nullptr;
@@ -512,6 +537,10 @@ int main(int argc, char **argv) {
     if (o.width <= 0 || o.height <= 0 || o.width > 65535 || o.height > 65535 || o.spp <= 0 || o.iterations <= 0 ||
         o.threads <= 0 || o.trackedBounces < 1 || o.trackedBounces > 16) {
         std::fprintf(stderr, "bad size / spp / iterations / threads / trackedbounces\n");
+        return 2;
+    }
+    if (o.preview && o.stopAt) {
+        std::fprintf(stderr, "--preview cannot be used with --stop-at (the last iteration is denoised in full, and --stop-at decides it late)\n");
         return 2;
     }
     if (o.stopAt && !o.adaptivePixels) {

@@ -1018,6 +1018,53 @@ int statmc_score_select(uint16_t width, uint16_t height, const float *score, con
 int statmc_score_count_above(uint16_t width, uint16_t height, const float *score, const float *thresholds, int n_thresholds,
                              int64_t *counts, void *stream);
 
+/* ---- exact sums of a score image (no counterpart in the reference): what a mean or RMS stopping rule asks of the error map --
+ * "the mean relative half-width is under 1 %", "the RMS relative error is under T" -- answered on the device with the same bits on
+ * every run, one small struct read back.  `score` is what statmc_score_select takes: a packed width x height plane.
+ *
+ * DEFINITION.  key(b) is statmc_score_select's above: NaN of either sign and everything with the sign bit are 0, the rest their own
+ * bit pattern.  For a key k with 0 < k < 0x7F800000:
+ *     e = k >> 23,  m = k & 0x7FFFFF,  M = e ? (m | 0x800000) : m,  s = e ? e - 1 : 0
+ *     val(k) = M * 2^(s - 149)                          (the float's value, an exact rational);  val(0) = 0
+ * `caps` is a HOST array of n_caps entries, 1 <= n_caps <= STATMC_SUM_MAX_CAPS, none of them NaN, in any order, repeats allowed.
+ * For cap j, pixel p contributes c = min(key_p, key(caps[j])), taken as unsigned integers (bit order is value order); a pixel whose
+ * c is 0x7F800000 is left out of slot j, which is only possible when the cap is +inf: how a caller asks for "no cap".
+ *     cap_bits[j]  = key(caps[j])
+ *     n_clipped[j] = the number of pixels with key > cap_bits[j]          (statmc_score_count_above's at caps[j])
+ *     sum[j]       = the double nearest, ties to even, to the exact sum of val(c) over the pixels
+ *     sum_sq[j]    = the double nearest, ties to even, to the exact sum of val(c)^2 over the pixels
+ * Neither can overflow or leave a double's normal range: a non-zero one lies in [2^-298, 2^288).  n_zero / n_finite / n_infinite
+ * count the pixels by key: == 0; 0 < key < 0x7F800000; == 0x7F800000; they add up to n_px.  Slots n_caps .. 3 of the four arrays
+ * are written as 0.  Every quantity is an integer count or the rounding of an integer (a multiple of 2^-149, of 2^-298 for the
+ * squares), so the same inputs give the same bits on every run, any permutation of the image gives the same bits, and a
+ * restatement in integers of any width is equal bit for bit (tests/score_sum_reference.py).  A mean over the judged pixels is
+ * sum / n_px for a finite cap and sum / (n_px - n_infinite) for a cap of +inf; the division is the caller's.
+ * Asynchronous on `stream`; nothing is read back and nothing allocated.  The caller owns `workspace`, at least
+ * statmc_score_sum_workspace() bytes (a pure function, no device needed) and 8-byte aligned; the call zeroes it on `stream` -- a
+ * workspace full of garbage gives the same result -- and leaves nothing of use in it.  `result` is device memory, 8-byte aligned;
+ * besides the workspace only `result` is written.  One pass over the image adds every pixel into fixed-point integers of 32-bit
+ * limbs held in 64-bit words, one set per interval between the sorted caps; one small launch propagates the carries, forms the
+ * capped totals and rounds; no kernel waits for another workgroup.
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL score,
+ * result, caps or workspace; score not 4-byte aligned; result or workspace not 8-byte aligned; n_caps outside 1 to 4; a NaN cap;
+ * workspace_bytes below the helper's answer; result overlapping score, result overlapping the workspace, the workspace overlapping
+ * score.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2i, profiles/score_sum.jsonl. */
+#define STATMC_SUM_MAX_CAPS 4
+typedef struct statmc_sum_result { /* device, written by the call */
+    int64_t n_px, n_zero, n_finite, n_infinite; /* by key: == 0; 0 < key < 0x7F800000; == 0x7F800000 */
+    int32_t n_caps, pad;
+    uint32_t cap_bits[STATMC_SUM_MAX_CAPS]; /* key(caps[j]) */
+    int64_t n_clipped[STATMC_SUM_MAX_CAPS]; /* pixels with key > cap_bits[j] */
+    double sum[STATMC_SUM_MAX_CAPS];
+    double sum_sq[STATMC_SUM_MAX_CAPS];
+} statmc_sum_result;
+
+size_t statmc_score_sum_workspace(void); /* bytes; pure, no device needed */
+int statmc_score_sum(uint16_t width, uint16_t height, const float *score, const float *caps, int n_caps,
+                     statmc_sum_result *result, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- window maximum / minimum of a score image (no counterpart in the reference): the error map regularised over a neighbourhood
  * before a plan spends by it.  A pixel's sample standard deviation after a handful of samples is itself noisy: a pixel beside a
  * caustic that has not yet drawn a bright sample reports a small score and the plan starves it.  MAX gives every pixel the worst

@@ -1399,6 +1399,24 @@ class Estimator {
         check(statmc_score_count_above((uint16_t)width, (uint16_t)height, scores, thresholds.data(), (int)thresholds.size(), d_counts, stream.handle()));
         return d_counts;
     }
+    // ---- exact sums of the same score image, for a mean or RMS stopping rule (statmc_score_sum; include/statmc.h has the
+    // definition): per cap (1 to 4, none NaN; +inf: no cap, the pixels nobody can judge yet are left out) the sum and the sum of
+    // squares of min(score, cap), each rounded once to a double, the same bits on every run.  The checks, the flush of staged
+    // samples, the reuse of the score image and scoreDilate are ScoreSelect's; scoreOf defaults to the standard error, the quantity
+    // such a rule is met on.  Enqueues on DeviceStream() and returns without waiting; the device pointer stays valid until the
+    // next ScoreSum.  mean = sum / n_px, or sum / (n_px - n_infinite) for a cap of +inf: the division is the caller's.
+    const statmc_sum_result *ScoreSum(unsigned char statTypeIndex, unsigned char bounceIndex, const std::vector<float> &caps,
+                                      int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0, int scoreOf = ScoreOfStdErr) {
+        statmc_stat_type t;
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, false, scoreOf), scoreDilate);
+        const size_t wsBytes = statmc_score_sum_workspace();
+        plan.sumWorkspace.reserve(wsBytes);
+        plan.sumResult.reserve(sizeof(statmc_sum_result));
+        statmc_sum_result *d_result = static_cast<statmc_sum_result *>(plan.sumResult.ptr);
+        check(statmc_score_sum((uint16_t)width, (uint16_t)height, scores, caps.data(), (int)caps.size(), d_result, plan.sumWorkspace.ptr, wsBytes,
+                               stream.handle()));
+        return d_result;
+    }
     // The rank of the q-quantile among nPixels keys by the nearest-rank rule, max(0, ceil(q * nPixels) - 1), in integer arithmetic
     // on q as the double it is: what ScoreSelect takes for "the 95th percentile".  q in [0, 1].
     static int64_t NearestRank(double q, int64_t nPixels) {
@@ -2037,6 +2055,7 @@ class Estimator {
         DeviceBytes targetResult;        // PlanToTarget's statmc_target_result
         DeviceBytes windowed;            // the MAX window of `scores` a call with scoreDilate > 0 reads (made anew by each)
         DeviceBytes selectWorkspace, selectResult, aboveCounts;
+        DeviceBytes sumWorkspace, sumResult;   // ScoreSum's
         // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
         // flushes of staged samples so far and `touched`, which every call that may write the statistics otherwise bumps
         // (every Accumulate* entry and CombineRecords, ResetStatistics, CombineStatistics, PoolStatistics, EnableDeviceAccumulation)

@@ -126,6 +126,16 @@ class SelectResult(C.Structure):
                 ("n_below", C.c_int64 * SELECT_MAX_RANKS), ("n_equal", C.c_int64 * SELECT_MAX_RANKS)]
 
 
+SUM_MAX_CAPS = 4
+
+
+class SumResult(C.Structure):
+    """statmc_sum_result: what statmc_score_sum writes to device memory (152 bytes)."""
+    _fields_ = [("n_px", C.c_int64), ("n_zero", C.c_int64), ("n_finite", C.c_int64), ("n_infinite", C.c_int64), ("n_caps", C.c_int32), ("pad", C.c_int32),
+                ("cap_bits", C.c_uint32 * SUM_MAX_CAPS), ("n_clipped", C.c_int64 * SUM_MAX_CAPS),
+                ("sum", C.c_double * SUM_MAX_CAPS), ("sum_sq", C.c_double * SUM_MAX_CAPS)]
+
+
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
 ERROR_NO_TABLE = -1                       # statmc_error_scores' table: the standard error, no quantile
 SCORE_WINDOW_MAX, SCORE_WINDOW_MIN = 0, 1  # statmc_score_window's op
@@ -142,7 +152,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_sum_workspace", "statmc_score_sum", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -256,6 +266,10 @@ def load():
     lib.statmc_plan_to_target.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
                                           C.POINTER(TargetResult), C.c_void_p]
     lib.statmc_score_count_above.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]
+    lib.statmc_score_sum_workspace.argtypes = []
+    lib.statmc_score_sum_workspace.restype = C.c_size_t
+    lib.statmc_score_sum.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(SumResult), C.c_void_p,
+                                     C.c_size_t, C.c_void_p]
     lib.statmc_score_window.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_compact_offsets_workspace.restype = C.c_size_t
@@ -960,6 +974,59 @@ def score_count_above(score, thresholds, out=None, stream=None):
     check(load().statmc_score_count_above(w, h, score.data_ptr(), arr, len(thresholds), out.data_ptr() if out.numel() else None,
                                           stream if stream is not None else current_stream_handle()))
     return out
+
+
+def score_sum_workspace():
+    """statmc_score_sum_workspace: the bytes of workspace statmc_score_sum wants, for every film size (no device needed)."""
+    return int(load().statmc_score_sum_workspace())
+
+
+_SUM_WORDS = C.sizeof(SumResult) // 8
+_sum_scratch = {}    # (device index, stream handle) -> (workspace, result), as _plan_scratch
+
+
+def read_sum_result(t):
+    """The statmc_sum_result a score_sum call wrote into the int64 [19] device tensor `t`, as a dict whose per-cap fields are lists
+    of n_caps entries: "sum" and "sum_sq" as Python floats (the doubles, bit for bit), "caps" the caps' keys as numpy float32.  One
+    small device-to-host copy: it synchronises with the work that wrote `t` on the current stream; after a call on another stream
+    synchronise that one first."""
+    import numpy as np
+    r = SumResult.from_buffer_copy(t.cpu().numpy().tobytes())
+    k = int(r.n_caps)
+    out = {f: int(getattr(r, f)) for f in ("n_px", "n_zero", "n_finite", "n_infinite", "n_caps")}
+    for f in ("cap_bits", "n_clipped"):
+        out[f] = [int(v) for v in getattr(r, f)[:k]]
+    for f in ("sum", "sum_sq"):
+        out[f] = [float(v) for v in getattr(r, f)[:k]]
+    out["caps"] = np.array(out["cap_bits"], np.uint32).view(np.float32)
+    return out
+
+
+def score_sum(score, caps, workspace=None, result=None, stream=None):
+    """statmc_score_sum: per cap (1 to 4, none NaN, any order; +inf: no cap, the +inf pixels are left out) the exact sum and sum of
+    squares of min(score, cap) over the float32 score image [H, W], each rounded once to a double, with the number of pixels above
+    the cap and the class counts (include/statmc.h).  Returns the device result, an int64 [19] tensor holding the statmc_sum_result's
+    152 bytes: read_sum_result(t) downloads it.  Asynchronous; workspace (uint8, at least score_sum_workspace() bytes) and result are
+    the caller's or, if None, tensors kept per (device, stream) until the next call on that stream."""
+    tc = _torch()
+    h, w = _score_image(score, "score_sum")
+    caps = [float(c) for c in caps]
+    st = stream if stream is not None else current_stream_handle()
+    if workspace is None or result is None:
+        key = (score.device.index, st.value if hasattr(st, "value") else int(st or 0))
+        held = _sum_scratch.get(key)
+        if held is None:
+            held = (tc.empty(score_sum_workspace(), dtype=tc.uint8, device=score.device),
+                    tc.empty(_SUM_WORDS, dtype=tc.int64, device=score.device))
+            _sum_scratch[key] = held
+        workspace = workspace if workspace is not None else held[0]
+        result = result if result is not None else held[1]
+    if result.dtype != tc.int64 or not result.is_cuda or not result.is_contiguous() or result.numel() < _SUM_WORDS:
+        raise ValueError("score_sum: result must be a contiguous int64 CUDA tensor of %d words" % _SUM_WORDS)
+    arr = (C.c_float * max(len(caps), 1))(*caps)
+    check(load().statmc_score_sum(w, h, score.data_ptr(), arr, len(caps), C.cast(result.data_ptr(), C.POINTER(SumResult)),
+                                  workspace.data_ptr(), workspace.numel() * workspace.element_size(), st))
+    return result
 
 
 _WINDOW_OPS = {"max": SCORE_WINDOW_MAX, "min": SCORE_WINDOW_MIN}

@@ -21,6 +21,7 @@
 #include "statmc_upsample_args.h"
 #include "statmc_select_args.h"
 #include "statmc_score_window_args.h"
+#include "statmc_score_sum_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
 #include "statmc_state_records_args.h"
@@ -1542,6 +1543,18 @@ int statmc_score_count_above(uint16_t width, uint16_t height, const float *score
     statmc::CountAboveArgs a;
     statmc::fill_count_above_args(a, width, height, score, thresholds, n_thresholds, counts);
     HIP_TRY(statmc::launch_score_count_above(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_score_sum: every rule of include/statmc.h ahead of the device (statmc_score_sum_args.h), then the launches of
+// statmc_score_sum.hip on `stream`; nothing is allocated and nothing read back.
+int statmc_score_sum(uint16_t width, uint16_t height, const float *score, const float *caps, int n_caps, statmc_sum_result *result,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    ARG_TRY(statmc::check_sum_call(width, height, score, caps, n_caps, result, workspace, workspace_bytes, statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::SumArgs a;
+    statmc::fill_sum_args(a, width, height, score, caps, n_caps, result, workspace);
+    HIP_TRY(statmc::launch_score_sum(a, S(stream)));
     return STATMC_OK;
 }
 

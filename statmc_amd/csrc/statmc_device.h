@@ -241,6 +241,10 @@ struct CountAboveArgs;
 hipError_t launch_score_select(const SelectArgs &a, hipStream_t s);
 hipError_t launch_score_count_above(const CountAboveArgs &a, hipStream_t s);
 
+// statmc_score_sum (statmc_score_sum.hip): argument block, checks and finalisation are statmc_score_sum_args.h's, host-only
+struct SumArgs;
+hipError_t launch_score_sum(const SumArgs &a, hipStream_t s);
+
 // statmc_score_window (statmc_score_window.hip): argument block and checks are statmc_score_window_args.h's, host-only
 struct ScoreWindowArgs;
 hipError_t launch_score_window(const ScoreWindowArgs &a, hipStream_t s);

@@ -329,6 +329,24 @@ class FilmStats:
         Python integers after one synchronisation and one small download; the film is only read.  dilate, error: as score_quantiles'."""
         return [int(c) for c in api.score_count_above(self._scores(metric, eps, type, dilate, error), thresholds).cpu().numpy()]
 
+    def score_mean(self, caps=(float("inf"),), metric="relative", eps=1e-3, type="radiance", dilate=0, error="stderr"):
+        """The mean and the RMS of the score of stat type `type`, per cap (1 to 4): every pixel counts as min(score, cap), NaN and
+        negative scores as 0 (statmc_score_sum: exact sums, the same bits on every run).  "The mean relative half-width is under
+        1 %", "the RMS relative error is under T".  A cap of +inf is no cap: the pixels nobody can judge yet (+inf, fewer than 2
+        samples) are left out of the sums and of the divisor.  The score pipeline is score_quantiles': the error of the mean
+        (error="stderr" or "ci"; None: the sample standard deviation, on which no such rule can be met), then the optional window.
+        Returns a dict after one synchronisation and the download of one 152-byte struct; the film is only read:
+        "mean" = sum / n and "rms" = sqrt(sum_sq / n) per cap, in float64 on the host, n = n_px, or n_px - n_infinite for a cap of
+        +inf (NaN where n is 0); "caps", "sum", "sum_sq", "n_clipped" per cap; "n_px", "n_zero", "n_finite", "n_infinite"."""
+        import math
+        r = api.read_sum_result(api.score_sum(self._scores(metric, eps, type, dilate, error), caps))
+        r["mean"], r["rms"] = [], []
+        for j in range(r["n_caps"]):
+            n = r["n_px"] - (r["n_infinite"] if r["cap_bits"][j] == 0x7F800000 else 0)
+            r["mean"].append(r["sum"][j] / n if n else float("nan"))
+            r["rms"].append(math.sqrt(r["sum_sq"][j] / n) if n else float("nan"))
+        return r
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

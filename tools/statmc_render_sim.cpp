@@ -20,12 +20,19 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-metric sd|stderr|ci] [--target-error T] [--score-dilate R]]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-mean mean|rms:T[:CAP]] [--stop-metric sd|stderr|ci] [--target-error T]
+//                     [--score-dilate R]]
 //                     [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
 // --adaptive-pixels: per-pixel sample budgets planned on the device (Estimator::PlanSamples); see RenderLoop.
 // --stop-at Q:T: with --adaptive-pixels, the stopping rule: after every iteration the Q-quantile (nearest rank) of the relative radiance
 //                   score is selected on the device (Estimator::ScoreSelect); once it is <= T the remaining iterations are skipped.
+// --stop-mean mean|rms:T[:CAP]: with --adaptive-pixels, a mean rule: after every iteration the exact sums of the relative radiance
+//                   score are formed on the device (Estimator::ScoreSum), every pixel counting as min(score, CAP); once their mean
+//                   (sum / n) or RMS (sqrt(sum of squares / n)) is <= T the remaining iterations are skipped.  CAP defaults to +inf:
+//                   no cap, and the pixels nobody can judge yet (+inf) are left out of the sums and of n.  Reads --stop-metric's
+//                   quantity and --score-dilate's window as --stop-at does; with --stop-at as well, both rules must hold.  Every
+//                   iteration prints a "Mean rule:" line.  Not with --preview, for --stop-at's reason.
 // --stop-metric M: which quantity --stop-at's quantile (and --target-error's plan) reads.  sd, the default: the sample standard
 //                   deviation, which does not fall as samples arrive -- only T = 0 or a T above the film's noise make sense with it;
 //                   stderr: the standard error of the mean; ci: the two-sided confidence half-width at the device's significance
@@ -131,6 +138,9 @@ struct Options {
     bool stopAt = false;       // --stop-at Q:T
     double stopQuantile = 0.0;
     float stopThreshold = 0.f;
+    bool stopMean = false;     // --stop-mean mean|rms:T[:CAP]
+    bool stopMeanRms = false;
+    float stopMeanTarget = 0.f, stopMeanCap = INFINITY;
     int stopMetric = Estimator::ScoreOfDeviation;   // --stop-metric sd|stderr|ci
     bool stopMetricGiven = false;
     bool targetErrorGiven = false;   // --target-error T
@@ -326,8 +336,26 @@ static void Render(const Options &o) {
             std::cout << "Adaptive: samples per pixel so far " << lo << " .. " << hi << " over " << nTilesTotal << " tiles" << std::endl;
         }
 
+        const char *what = o.stopMetric == Estimator::ScoreOfStdErr ? "standard error" : o.stopMetric == Estimator::ScoreOfCI ? "confidence half-width" : "score";
+        // --stop-mean: the mean or RMS of the relative score under the cap, one 152-byte struct back; the divisions are done here
+        bool meanMet = true;
+        if (o.stopMean && sCfgs[Radiance].enable) {
+            statmc_sum_result sum;
+            check(statmc_download(&sum, estimator.ScoreSum(sCfgs[Radiance].index, 0, {o.stopMeanCap}, STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate, o.stopMetric), sizeof(sum), estimator.DeviceStream()));
+            estimator.Synchronize();
+            const int64_t judged = sum.n_px - (sum.cap_bits[0] == 0x7F800000u ? sum.n_infinite : 0);
+            const double v = judged ? (o.stopMeanRms ? std::sqrt(sum.sum_sq[0] / (double)judged) : sum.sum[0] / (double)judged) : (double)NAN;
+            meanMet = v <= (double)o.stopMeanTarget;   // (no judged pixel: not met)
+            char value[32], cap[32], target[32];
+            std::snprintf(value, sizeof(value), "%.9g", v);
+            std::snprintf(cap, sizeof(cap), "%.9g", (double)o.stopMeanCap);
+            std::snprintf(target, sizeof(target), "%.9g", (double)o.stopMeanTarget);
+            std::cout << "Mean rule: iteration " << i << ", " << (o.stopMeanRms ? "rms" : "mean") << " of the relative " << what << " under " << cap << " = "
+                      << value << " over " << judged << " pixels, target " << target << ": " << (meanMet ? "met" : "open") << std::endl;
+        }
+
         // --stop-at: the Q-quantile of the relative score, one 256-byte struct back
-        bool converged = false;
+        bool converged = o.stopMean && !o.stopAt && meanMet && sCfgs[Radiance].enable;
         if (o.stopAt && sCfgs[Radiance].enable) {
             const int64_t rank = Estimator::NearestRank(o.stopQuantile, (int64_t)width * height);
             statmc_select_result sel;
@@ -335,12 +363,11 @@ static void Render(const Options &o) {
             estimator.Synchronize();
             float v;
             std::memcpy(&v, &sel.value_bits[0], sizeof(v));
-            const char *what = o.stopMetric == Estimator::ScoreOfStdErr ? "standard error" : o.stopMetric == Estimator::ScoreOfCI ? "confidence half-width" : "score";
             char value[32];
             std::snprintf(value, sizeof(value), "%.9g", (double)v);
             if (o.stopMetric != Estimator::ScoreOfDeviation)
                 std::cout << "Stop metric: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
-            if (v <= o.stopThreshold) {
+            if (v <= o.stopThreshold && meanMet) {
                 converged = true;
                 std::cout << "Converged: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
             }
@@ -479,6 +506,28 @@ int main(int argc, char **argv) {
                 std::fprintf(stderr, "--stop-at takes Q:T, a quantile in [0, 1] and a threshold\n");
                 return 2;
             }
+        } else if (a == "--stop-mean") {
+            const std::string v = next();
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            const std::string rule = v.substr(0, c1);
+            char *end = nullptr;
+            bool ok = c1 != std::string::npos && (rule == "mean" || rule == "rms");
+            if (ok) {
+                const std::string t = v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+                o.stopMeanTarget = std::strtof(t.c_str(), &end);
+                ok = !t.empty() && *end == 0 && o.stopMeanTarget >= 0.f;   // (a NaN fails the comparison)
+            }
+            if (ok && c2 != std::string::npos) {
+                const std::string c = v.substr(c2 + 1);
+                o.stopMeanCap = std::strtof(c.c_str(), &end);
+                ok = !c.empty() && *end == 0 && o.stopMeanCap == o.stopMeanCap;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "--stop-mean takes mean:T, rms:T or either with :CAP, a target >= 0 and a cap that is not NaN\n");
+                return 2;
+            }
+            o.stopMean = true;
+            o.stopMeanRms = rule == "rms";
         } else if (a == "--stop-metric") {
             const std::string v = next();
             if (v != "sd" && v != "stderr" && v != "ci") {
@@ -541,6 +590,14 @@ int main(int argc, char **argv) {
     }
     if (o.preview && o.stopAt) {
         std::fprintf(stderr, "--preview cannot be used with --stop-at (the last iteration is denoised in full, and --stop-at decides it late)\n");
+        return 2;
+    }
+    if (o.preview && o.stopMean) {
+        std::fprintf(stderr, "--preview cannot be used with --stop-mean (the last iteration is denoised in full, and --stop-mean decides it late)\n");
+        return 2;
+    }
+    if (o.stopMean && !o.adaptivePixels) {
+        std::fprintf(stderr, "--stop-mean needs --adaptive-pixels\n");
         return 2;
     }
     if (o.stopAt && !o.adaptivePixels) {

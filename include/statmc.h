@@ -1065,6 +1065,50 @@ size_t statmc_score_sum_workspace(void); /* bytes; pure, no device needed */
 int statmc_score_sum(uint16_t width, uint16_t height, const float *score, const float *caps, int n_caps,
                      statmc_sum_result *result, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- exact per-tile statistics of a score image (no counterpart in the reference): what a renderer that works tile by tile asks of
+ * the error map -- which tiles are still open, how bad the worst tile is, which tiles go on the next iteration's work list -- in one
+ * launch.  `score` is what statmc_score_sum takes: a packed width x height plane.
+ *
+ * DEFINITION.  key(b), val(k), M and s are statmc_score_sum's above.  With T = tile, tiles_x = ceil(width / T) and
+ * tiles_y = ceil(height / T), tile (tx, ty) holds the pixels with tx T <= x < min((tx + 1) T, width) and
+ * ty T <= y < min((ty + 1) T, height): a partial tile at the right or bottom edge is a tile like any other.  Let ck = key(cap);
+ * a cap of +inf means "no cap", as in statmc_score_sum.  Per tile, at entry ty * tiles_x + tx of each plane:
+ *     n_px       = the number of pixels of the tile
+ *     n_zero     = the number with key == 0;   n_infinite = the number with key == 0x7F800000
+ *     n_clipped  = the number with key > ck                                  (statmc_score_count_above's rule at `cap`)
+ *     c_p        = min(key_p, ck) as unsigned integers; a pixel whose c_p is 0x7F800000 is left out of the sums, which is only
+ *                  possible when ck is: n_counted = n_px - (ck == 0x7F800000 ? n_infinite : 0)
+ *     sum        = the double nearest, ties to even, to the exact sum of val(c_p) over the counted pixels; a sum of 0 is +0
+ *     sum_sq     = the same of val(c_p)^2
+ *     mean       = the float nearest, ties to even, to the exact rational (sum of val(c_p)) / n_counted -- a subnormal result is
+ *                  exact in the same way, float's unit 2^-149 being the sums' own --; +0 where n_counted == 0.  It cannot
+ *                  overflow: a mean is at most the largest counted value, a finite float
+ *     max        = the float whose bit pattern is the maximum of key_p over the tile: not capped, never NaN, never signed
+ * Every quantity is an integer count or one rounding of an exact integer or rational: the same inputs give the same bits on every
+ * run, any permutation of a tile's pixels gives the same bits, and a restatement in integers of any width is equal bit for bit
+ * (tests/score_tiles_reference.py).  `mean` and `max` are tiles_y x tiles_x score images: statmc_score_select,
+ * statmc_score_count_above, statmc_score_window and statmc_plan_samples take them as they are; `n_clipped` is a count image that
+ * statmc_compact_offsets(..., cap = 1, owners) turns into the list of open tiles.
+ * `out` is a HOST struct of DEVICE pointers to packed row-major planes of tiles_y * tiles_x entries; a NULL plane is not formed, at
+ * least one is not NULL.  Asynchronous on `stream`: one launch, no workspace, nothing zeroed, nothing allocated, nothing read back,
+ * no global atomic; exactly the tiles_x * tiles_y entries of every non-NULL plane are written and nothing else.  A tile belongs to
+ * one workgroup (for tile 8 and 16 to part of one wave, to one wave): its pixels are added into fixed-point integers of 32-bit
+ * limbs in LDS and the carries, the capped totals, the division and the roundings follow in the same kernel.
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL score
+ * or out; every plane NULL; score not 4-byte aligned; a float or int32_t plane not 4-byte aligned, a double plane not 8-byte
+ * aligned; tile not one of 8, 16, 32, 64; a NaN cap; a plane overlapping score or another plane.  STATMC_ERR_NO_DEVICE before
+ * statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2j, profiles/score_tiles.jsonl. */
+#define STATMC_SCORE_TILES_MAX_TILE 64
+typedef struct statmc_tile_scores { /* HOST struct of DEVICE pointers: packed planes of tiles_y * tiles_x entries, row-major; any may be NULL, not all */
+    double *sum, *sum_sq;
+    float *mean, *max;
+    int32_t *n_px, *n_zero, *n_infinite, *n_clipped;
+} statmc_tile_scores;
+int statmc_score_tiles(uint16_t width, uint16_t height, const float *score, int tile, float cap,
+                       const statmc_tile_scores *out, void *stream);
+
 /* ---- window maximum / minimum of a score image (no counterpart in the reference): the error map regularised over a neighbourhood
  * before a plan spends by it.  A pixel's sample standard deviation after a handful of samples is itself noisy: a pixel beside a
  * caustic that has not yet drawn a bright sample reports a small score and the plan starves it.  MAX gives every pixel the worst

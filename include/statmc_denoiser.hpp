@@ -1417,6 +1417,42 @@ class Estimator {
                                stream.handle()));
         return d_result;
     }
+    // ---- the same statistics per tile x tile block of the film (8, 16, 32 or 64; partial blocks at the right and bottom edges are
+    // blocks like any other), for a renderer that decides region by region (statmc_score_tiles; include/statmc.h has the
+    // definition): exact sum and sum of squares of min(score, cap), their mean as a correctly rounded float, the block's maximum,
+    // and the counts of pixels, of score 0, of +inf and above the cap, as packed planes of TilesAcross(height, tile) x
+    // TilesAcross(width, tile) entries.  `out` names the caller's device planes on this Estimator's device; a NULL plane is not
+    // formed.  The mean and max planes are score images of the tile grid (statmc_score_count_above: "no tile's mean is above T"),
+    // the n_clipped plane a count image for statmc_compact_offsets with cap 1: the list of open tiles.  The checks, the flush of
+    // staged samples, the reuse of the score image, scoreDilate and scoreOf are ScoreSum's.  One launch on DeviceStream(); returns
+    // without waiting.
+    void ScoreTiles(unsigned char statTypeIndex, unsigned char bounceIndex, int tile, float cap, const statmc_tile_scores &out,
+                    int scoreDilate = 0, int scoreOf = ScoreOfStdErr, int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+        statmc_stat_type t;
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, false, scoreOf), scoreDilate);
+        check(statmc_score_tiles((uint16_t)width, (uint16_t)height, scores, tile, cap, &out, stream.handle()));
+    }
+    // ... into planes this Estimator keeps (allocated by the first call, valid until the next ScoreTiles of this form): all eight.
+    statmc_tile_scores ScoreTiles(unsigned char statTypeIndex, unsigned char bounceIndex, int tile, float cap, int scoreDilate = 0,
+                                  int scoreOf = ScoreOfStdErr, int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f) {
+        if (tile != 8 && tile != 16 && tile != 32 && tile != 64) throw Error(STATMC_ERR_INVALID, "ScoreTiles: tile must be 8, 16, 32 or 64");
+        const size_t n = (size_t)TilesAcross(width, tile) * TilesAcross(height, tile);
+        plan.tilePlanes.reserve(n * (2 * sizeof(double) + 2 * sizeof(float) + 4 * sizeof(int32_t)));
+        char *p = static_cast<char *>(plan.tilePlanes.ptr);   // the doubles first: every plane keeps its alignment
+        statmc_tile_scores out;
+        out.sum = reinterpret_cast<double *>(p), out.sum_sq = out.sum + n;
+        out.mean = reinterpret_cast<float *>(out.sum_sq + n), out.max = out.mean + n;
+        out.n_px = reinterpret_cast<int32_t *>(out.max + n), out.n_zero = out.n_px + n, out.n_infinite = out.n_zero + n, out.n_clipped = out.n_infinite + n;
+        ScoreTiles(statTypeIndex, bounceIndex, tile, cap, out, scoreDilate, scoreOf, metric, eps);
+        return out;
+    }
+    static int TilesAcross(int extent, int tile) { return (extent + tile - 1) / tile; }
+    // one int64 of device memory on this Estimator's device for a count over those planes (statmc_score_count_above's `counts` with
+    // one threshold: the open tiles of a tile rule); valid for the Estimator's lifetime
+    int64_t *TileRuleCount() {
+        plan.tileCount.reserve(sizeof(int64_t));
+        return static_cast<int64_t *>(plan.tileCount.ptr);
+    }
     // The rank of the q-quantile among nPixels keys by the nearest-rank rule, max(0, ceil(q * nPixels) - 1), in integer arithmetic
     // on q as the double it is: what ScoreSelect takes for "the 95th percentile".  q in [0, 1].
     static int64_t NearestRank(double q, int64_t nPixels) {
@@ -2056,6 +2092,7 @@ class Estimator {
         DeviceBytes windowed;            // the MAX window of `scores` a call with scoreDilate > 0 reads (made anew by each)
         DeviceBytes selectWorkspace, selectResult, aboveCounts;
         DeviceBytes sumWorkspace, sumResult;   // ScoreSum's
+        DeviceBytes tilePlanes, tileCount;     // ScoreTiles' own planes, TileRuleCount's word
         // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
         // flushes of staged samples so far and `touched`, which every call that may write the statistics otherwise bumps
         // (every Accumulate* entry and CombineRecords, ResetStatistics, CombineStatistics, PoolStatistics, EnableDeviceAccumulation)

@@ -136,6 +136,16 @@ class SumResult(C.Structure):
                 ("sum", C.c_double * SUM_MAX_CAPS), ("sum_sq", C.c_double * SUM_MAX_CAPS)]
 
 
+SCORE_TILES_MAX_TILE = 64
+TILE_PLANES = ("sum", "sum_sq", "mean", "max", "n_px", "n_zero", "n_infinite", "n_clipped")      # statmc_tile_scores' fields, in its order
+
+
+class TileScores(C.Structure):
+    """statmc_tile_scores: a HOST struct of DEVICE pointers to the planes statmc_score_tiles writes; NULL: not formed."""
+    _fields_ = [("sum", C.c_void_p), ("sum_sq", C.c_void_p), ("mean", C.c_void_p), ("max", C.c_void_p),
+                ("n_px", C.c_void_p), ("n_zero", C.c_void_p), ("n_infinite", C.c_void_p), ("n_clipped", C.c_void_p)]
+
+
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
 ERROR_NO_TABLE = -1                       # statmc_error_scores' table: the standard error, no quantile
 SCORE_WINDOW_MAX, SCORE_WINDOW_MIN = 0, 1  # statmc_score_window's op
@@ -152,7 +162,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_sum_workspace", "statmc_score_sum", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_sum_workspace", "statmc_score_sum", "statmc_score_tiles", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -270,6 +280,7 @@ def load():
     lib.statmc_score_sum_workspace.restype = C.c_size_t
     lib.statmc_score_sum.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(SumResult), C.c_void_p,
                                      C.c_size_t, C.c_void_p]
+    lib.statmc_score_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_float, C.POINTER(TileScores), C.c_void_p]
     lib.statmc_score_window.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_compact_offsets_workspace.restype = C.c_size_t
@@ -1027,6 +1038,55 @@ def score_sum(score, caps, workspace=None, result=None, stream=None):
     check(load().statmc_score_sum(w, h, score.data_ptr(), arr, len(caps), C.cast(result.data_ptr(), C.POINTER(SumResult)),
                                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), st))
     return result
+
+
+def tile_grid(height, width, tile):
+    """(tiles_y, tiles_x) of statmc_score_tiles' planes for a film of height x width pixels"""
+    tile = int(tile)
+    return -(-int(height) // tile), -(-int(width) // tile)
+
+
+def _tile_plane_dtypes():
+    tc = _torch()
+    return {"sum": tc.float64, "sum_sq": tc.float64, "mean": tc.float32, "max": tc.float32,
+            "n_px": tc.int32, "n_zero": tc.int32, "n_infinite": tc.int32, "n_clipped": tc.int32}
+
+
+def score_tiles(score, tile, cap=float("inf"), planes=TILE_PLANES, out=None, stream=None):
+    """statmc_score_tiles: per tile x tile block (8, 16, 32 or 64; partial blocks at the right and bottom edges included) of the
+    float32 score image [H, W] the exact sum and sum of squares of min(score, cap) as doubles, their mean as a correctly rounded
+    float32, the maximum key, and the counts of pixels, of key 0, of +inf and above the cap (include/statmc.h).  cap = +inf: no cap,
+    the +inf pixels are left out of sum, sum_sq and mean.  Returns {name: device tensor [tiles_y, tiles_x]} for the names in
+    `planes` (TILE_PLANES' names; a plane not named is not formed); `out` may hand in the tensors to write, contiguous and of
+    tile_grid's shape.  "mean" and "max" are score images that score_select, score_count_above, score_window and plan_samples take;
+    "n_clipped" is a count image that compact_offsets(..., cap=1) turns into the list of open tiles.  Asynchronous: one launch,
+    no workspace."""
+    tc = _torch()
+    h, w = _score_image(score, "score_tiles")
+    planes = tuple(planes)
+    dtypes = _tile_plane_dtypes()
+    for p in planes:
+        if p not in dtypes:
+            raise ValueError("score_tiles: no plane %r: one of %s" % (p, ", ".join(TILE_PLANES)))
+    shape = tile_grid(h, w, tile) if int(tile) > 0 else (0, 0)
+    res, ptrs = {}, TileScores()
+    for p in planes:
+        t = None if out is None else out.get(p)
+        if t is None:
+            t = tc.empty(shape, dtype=dtypes[p], device=score.device)
+        elif t.dtype != dtypes[p] or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError("score_tiles: out[%r] must be a contiguous %s CUDA tensor of shape %s" % (p, dtypes[p], shape))
+        res[p] = t
+        setattr(ptrs, p, t.data_ptr() if t.numel() else None)
+    check(load().statmc_score_tiles(w, h, score.data_ptr(), int(tile), float(cap), C.byref(ptrs),
+                                    stream if stream is not None else current_stream_handle()))
+    return res
+
+
+def read_tile_scores(res):
+    """The planes a score_tiles call returned, as numpy arrays of the same shapes and types.  Small device-to-host copies: they
+    synchronise with the work that wrote them on the current stream; after a call on another stream synchronise that one first."""
+    return {p: t.cpu().numpy() for p, t in res.items()}
 
 
 _WINDOW_OPS = {"max": SCORE_WINDOW_MAX, "min": SCORE_WINDOW_MIN}

@@ -22,6 +22,7 @@
 #include "statmc_select_args.h"
 #include "statmc_score_window_args.h"
 #include "statmc_score_sum_args.h"
+#include "statmc_score_tiles_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
 #include "statmc_state_records_args.h"
@@ -1555,6 +1556,17 @@ int statmc_score_sum(uint16_t width, uint16_t height, const float *score, const 
     statmc::SumArgs a;
     statmc::fill_sum_args(a, width, height, score, caps, n_caps, result, workspace);
     HIP_TRY(statmc::launch_score_sum(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_score_tiles: every rule of include/statmc.h ahead of the device (statmc_score_tiles_args.h), then the one launch of
+// statmc_score_tiles.hip on `stream`; nothing is allocated, zeroed or read back.
+int statmc_score_tiles(uint16_t width, uint16_t height, const float *score, int tile, float cap, const statmc_tile_scores *out, void *stream) {
+    ARG_TRY(statmc::check_score_tiles_call(width, height, score, tile, cap, out, statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::TilesArgs a;
+    statmc::fill_score_tiles_args(a, width, height, score, tile, cap, out);
+    HIP_TRY(statmc::launch_score_tiles(a, S(stream)));
     return STATMC_OK;
 }
 

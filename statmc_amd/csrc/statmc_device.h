@@ -245,6 +245,10 @@ hipError_t launch_score_count_above(const CountAboveArgs &a, hipStream_t s);
 struct SumArgs;
 hipError_t launch_score_sum(const SumArgs &a, hipStream_t s);
 
+// statmc_score_tiles (statmc_score_tiles.hip): argument block, checks and finalisation are statmc_score_tiles_args.h's, host-only
+struct TilesArgs;
+hipError_t launch_score_tiles(const TilesArgs &a, hipStream_t s);
+
 // statmc_score_window (statmc_score_window.hip): argument block and checks are statmc_score_window_args.h's, host-only
 struct ScoreWindowArgs;
 hipError_t launch_score_window(const ScoreWindowArgs &a, hipStream_t s);

@@ -347,6 +347,18 @@ class FilmStats:
             r["rms"].append(math.sqrt(r["sum_sq"][j] / n) if n else float("nan"))
         return r
 
+    def score_tiles(self, tile, cap=float("inf"), metric="relative", eps=1e-3, type="radiance", dilate=0, error="stderr",
+                    planes=api.TILE_PLANES):
+        """Per tile x tile block (8, 16, 32 or 64) of the film the statistics of the score of stat type `type`
+        (statmc_score_tiles: exact, the same bits on every run): "sum", "sum_sq" of min(score, cap) as doubles, "mean" as a
+        correctly rounded float32, "max" the block's largest score, "n_px", "n_zero", "n_infinite", "n_clipped" (above the cap).  A
+        renderer that works tile by tile reads its rule per region from them: the "mean" and "max" planes are score images for
+        api.score_count_above / score_select / plan_samples on the tile grid, "n_clipped" a count image for api.compact_offsets
+        (cap=1: the open tiles).  cap = +inf is no cap: the pixels nobody can judge yet are left out.  The score pipeline is
+        score_mean's.  Returns {name: device tensor [tiles_y, tiles_x]}; no synchronisation, nothing downloaded; the film is only
+        read."""
+        return api.score_tiles(self._scores(metric, eps, type, dilate, error), tile, cap, planes=planes)
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

@@ -20,7 +20,7 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-mean mean|rms:T[:CAP]] [--stop-metric sd|stderr|ci] [--target-error T]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-mean mean|rms:T[:CAP]] [--stop-tiles T:TOL[:CAP]] [--stop-metric sd|stderr|ci] [--target-error T]
 //                     [--score-dilate R]]
 //                     [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
@@ -33,6 +33,12 @@
 //                   no cap, and the pixels nobody can judge yet (+inf) are left out of the sums and of n.  Reads --stop-metric's
 //                   quantity and --score-dilate's window as --stop-at does; with --stop-at as well, both rules must hold.  Every
 //                   iteration prints a "Mean rule:" line.  Not with --preview, for --stop-at's reason.
+// --stop-tiles T:TOL[:CAP]: with --adaptive-pixels, a rule per region: after every iteration the relative radiance score's exact mean
+//                   under CAP is formed per T x T tile on the device (T = 8, 16, 32 or 64; Estimator::ScoreTiles), and the tiles whose
+//                   mean is above TOL -- the open tiles -- are counted on the tile grid (statmc_score_count_above on the mean plane):
+//                   one int64 comes back.  Once no tile is open the remaining iterations are skipped.  CAP defaults to +inf.  Reads
+//                   --stop-metric's quantity and --score-dilate's window; with --stop-at or --stop-mean as well, every rule must
+//                   hold.  Every iteration prints a "Tile rule:" line with "open tiles k / N".  Not with --preview.
 // --stop-metric M: which quantity --stop-at's quantile (and --target-error's plan) reads.  sd, the default: the sample standard
 //                   deviation, which does not fall as samples arrive -- only T = 0 or a T above the film's noise make sense with it;
 //                   stderr: the standard error of the mean; ci: the two-sided confidence half-width at the device's significance
@@ -141,6 +147,9 @@ struct Options {
     bool stopMean = false;     // --stop-mean mean|rms:T[:CAP]
     bool stopMeanRms = false;
     float stopMeanTarget = 0.f, stopMeanCap = INFINITY;
+    bool stopTiles = false;    // --stop-tiles T:TOL[:CAP]
+    int stopTilesTile = 0;
+    float stopTilesTol = 0.f, stopTilesCap = INFINITY;
     int stopMetric = Estimator::ScoreOfDeviation;   // --stop-metric sd|stderr|ci
     bool stopMetricGiven = false;
     bool targetErrorGiven = false;   // --target-error T
@@ -354,8 +363,28 @@ static void Render(const Options &o) {
                       << value << " over " << judged << " pixels, target " << target << ": " << (meanMet ? "met" : "open") << std::endl;
         }
 
+        // --stop-tiles: the tiles whose mean relative score under the cap is above the tolerance, one int64 back
+        bool tilesMet = true;
+        if (o.stopTiles && sCfgs[Radiance].enable) {
+            const statmc_tile_scores planes = estimator.ScoreTiles(sCfgs[Radiance].index, 0, o.stopTilesTile, o.stopTilesCap, o.scoreDilate, o.stopMetric);
+            const int tilesX = Estimator::TilesAcross(width, o.stopTilesTile), tilesY = Estimator::TilesAcross(height, o.stopTilesTile);
+            const float tol = o.stopTilesTol;
+            int64_t *d_open = estimator.TileRuleCount();
+            check(statmc_score_count_above((uint16_t)tilesX, (uint16_t)tilesY, planes.mean, &tol, 1, d_open, estimator.DeviceStream()));
+            int64_t open = 0;
+            check(statmc_download(&open, d_open, sizeof(open), estimator.DeviceStream()));
+            estimator.Synchronize();
+            tilesMet = open == 0;
+            char cap[32], tolerance[32];
+            std::snprintf(cap, sizeof(cap), "%.9g", (double)o.stopTilesCap);
+            std::snprintf(tolerance, sizeof(tolerance), "%.9g", (double)o.stopTilesTol);
+            std::cout << "Tile rule: iteration " << i << ", open tiles " << open << " / " << (int64_t)tilesX * tilesY << " of " << o.stopTilesTile << " x "
+                      << o.stopTilesTile << " pixels, mean of the relative " << what << " under " << cap << " above " << tolerance << ": "
+                      << (tilesMet ? "met" : "open") << std::endl;
+        }
+
         // --stop-at: the Q-quantile of the relative score, one 256-byte struct back
-        bool converged = o.stopMean && !o.stopAt && meanMet && sCfgs[Radiance].enable;
+        bool converged = (o.stopMean || o.stopTiles) && !o.stopAt && meanMet && tilesMet && sCfgs[Radiance].enable;
         if (o.stopAt && sCfgs[Radiance].enable) {
             const int64_t rank = Estimator::NearestRank(o.stopQuantile, (int64_t)width * height);
             statmc_select_result sel;
@@ -367,7 +396,7 @@ static void Render(const Options &o) {
             std::snprintf(value, sizeof(value), "%.9g", (double)v);
             if (o.stopMetric != Estimator::ScoreOfDeviation)
                 std::cout << "Stop metric: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
-            if (v <= o.stopThreshold && meanMet) {
+            if (v <= o.stopThreshold && meanMet && tilesMet) {
                 converged = true;
                 std::cout << "Converged: iteration " << i << ", quantile " << o.stopQuantile << " of the relative " << what << " = " << value << std::endl;
             }
@@ -528,6 +557,32 @@ int main(int argc, char **argv) {
             }
             o.stopMean = true;
             o.stopMeanRms = rule == "rms";
+        } else if (a == "--stop-tiles") {
+            const std::string v = next();
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            char *end = nullptr;
+            bool ok = c1 != std::string::npos;
+            if (ok) {
+                const std::string t = v.substr(0, c1);
+                const long tile = std::strtol(t.c_str(), &end, 10);
+                ok = !t.empty() && *end == 0 && (tile == 8 || tile == 16 || tile == 32 || tile == 64);
+                o.stopTilesTile = (int)tile;
+            }
+            if (ok) {
+                const std::string t = v.substr(c1 + 1, c2 == std::string::npos ? c2 : c2 - c1 - 1);
+                o.stopTilesTol = std::strtof(t.c_str(), &end);
+                ok = !t.empty() && *end == 0 && o.stopTilesTol >= 0.f;   // (a NaN fails the comparison)
+            }
+            if (ok && c2 != std::string::npos) {
+                const std::string c = v.substr(c2 + 1);
+                o.stopTilesCap = std::strtof(c.c_str(), &end);
+                ok = !c.empty() && *end == 0 && o.stopTilesCap == o.stopTilesCap;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "--stop-tiles takes T:TOL or T:TOL:CAP, a tile of 8, 16, 32 or 64, a tolerance >= 0 and a cap that is not NaN\n");
+                return 2;
+            }
+            o.stopTiles = true;
         } else if (a == "--stop-metric") {
             const std::string v = next();
             if (v != "sd" && v != "stderr" && v != "ci") {
@@ -594,6 +649,14 @@ int main(int argc, char **argv) {
     }
     if (o.preview && o.stopMean) {
         std::fprintf(stderr, "--preview cannot be used with --stop-mean (the last iteration is denoised in full, and --stop-mean decides it late)\n");
+        return 2;
+    }
+    if (o.preview && o.stopTiles) {
+        std::fprintf(stderr, "--preview cannot be used with --stop-tiles (the last iteration is denoised in full, and --stop-tiles decides it late)\n");
+        return 2;
+    }
+    if (o.stopTiles && !o.adaptivePixels) {
+        std::fprintf(stderr, "--stop-tiles needs --adaptive-pixels\n");
         return 2;
     }
     if (o.stopMean && !o.adaptivePixels) {

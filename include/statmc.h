@@ -1109,6 +1109,80 @@ typedef struct statmc_tile_scores { /* HOST struct of DEVICE pointers: packed pl
 int statmc_score_tiles(uint16_t width, uint16_t height, const float *score, int tile, float cap,
                        const statmc_tile_scores *out, void *stream);
 
+/* ---- exact per-tile order statistics of a score image, and a per-tile decision brought back to the pixels (no counterpart in the
+ * reference): the rule statmc_score_select answers for the film -- "the 95th percentile of the relative half-width is under 2 %" --
+ * answered per region in one launch, and the regions that met it closed for good.
+ *
+ * statmc_score_tile_select.  DEFINITION.  key(b) is statmc_score_select's above; the tile grid is statmc_score_tiles': tile is 8,
+ * 16, 32 or 64, tiles_x = ceil(width / tile), tiles_y = ceil(height / tile), a partial tile at the right or bottom edge is a tile like
+ * any other.  `q_num` is a HOST array of n_ranks entries, 1 <= n_ranks <= STATMC_TILE_SELECT_MAX_RANKS; 1 <= q_den <= 65536 and
+ * 0 <= q_num[i] <= q_den.  For a tile of n pixels (n <= 4096, so n * q_num[i] <= 2^28: integers throughout)
+ *     rank_i = max(0, ceil(n * q_num[i] / q_den) - 1)
+ * the nearest-rank rule (Estimator::NearestRank) for q = q_num[i] / q_den: q = 1 is the tile's maximum, q = 0 its minimum, 1/2 the
+ * lower median.  With sorted the tile's keys in non-decreasing order, at entry ty * tiles_x + tx of the planes of slot i:
+ *     value[i]   = the float whose bit pattern is sorted[rank_i]: never NaN, never signed
+ *     n_below[i] = the number of the tile's pixels with key <  that value
+ *     n_equal[i] = the number of the tile's pixels with key == that value
+ * so n_below[i] <= rank_i < n_below[i] + n_equal[i].  +inf pixels are counted like any other and sort on top: a tile of pixels nobody
+ * can judge yet stays open under every finite threshold.  Everything is an integer count or a bit pattern found by counting: the same
+ * inputs give the same bits on every run, any permutation of a tile's pixels gives the same bits, and np.sort of the keys per tile
+ * is equal bit for bit (tests/tile_select_reference.py).  The `value` planes are tiles_y x tiles_x score images:
+ * statmc_score_count_above, statmc_score_select, statmc_score_window, statmc_plan_samples and statmc_gate_tiles take them as they
+ * are; value at q = 1 is statmc_score_tiles' max.
+ * `out` is a HOST struct of DEVICE pointers to packed row-major planes of tiles_y * tiles_x entries.  Any plane may be NULL and is
+ * then not formed; at least one plane is not NULL, and every plane of the slots n_ranks .. 3 is NULL.  Asynchronous on `stream`: one
+ * launch, no workspace, nothing zeroed, nothing allocated, nothing read back, no global atomic; exactly the tiles_x * tiles_y entries
+ * of every non-NULL plane are written and nothing else.  A tile belongs to 16 lanes (tile 8), a wave (16) or a workgroup (32, 64);
+ * its keys stay in registers and all ranks descend together over the 31 key bits, one count per bit.
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL score,
+ * q_num or out; every plane NULL, or -- for n_ranks in 1 .. 4 -- a plane in a slot >= n_ranks; score not 4-byte aligned; a plane not
+ * 4-byte aligned; tile not one of 8, 16, 32, 64; n_ranks outside 1 .. 4; q_den outside 1 .. 65536; a q_num[i] outside 0 .. q_den; a
+ * plane overlapping score or another plane.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ *
+ * statmc_gate_tiles.  DEFINITION.  `tile_value`, `closed` and `open` are planes of the same tile grid.  Per tile t:
+ *     was_closed = closed != NULL && closed[t] != 0
+ *     above      = key(tile_value[t]) > key(threshold)        (statmc_score_count_above's rule; a NaN threshold is refused)
+ *     open[t]    = !was_closed && above ? 1 : 0
+ *     closed[t]  = was_closed ? as it was : (above ? 0 : 1)    (only if closed is given)
+ * A closed tile never reopens; a caller starts from a plane zeroed with statmc_memset.  `result`, if given, is device memory, 8-byte
+ * aligned: n_tiles; n_open = the number of tiles with open[t] == 1; n_closed_now = the number with !was_closed && !above;
+ * n_px_open = the number of pixels of the open tiles, from the grid's geometry.  `src` and `dst` are HOST arrays of n_images,
+ * 0 <= n_images <= STATMC_GATE_MAX_IMAGES, device images of width x height 32-bit words; per image i and pixel p, as words,
+ *     dst_i[p] = open[tile of p] ? src_i[p] : 0
+ * The all-zero word is +0 of a score image and 0 of a count image: one entry gates both.  A score image gated before
+ * statmc_plan_samples sends the budget to the open tiles (with c_min = 0 a closed pixel gets nothing); a count image gated after
+ * the plan is exactly 0 in closed tiles whatever c_min was, and statmc_compact_offsets gives the new total.  dst_i may be exactly
+ * src_i (in place).  `open` is the count image that statmc_compact_offsets(tiles_x, tiles_y, ..., cap = 1, owners) turns into the
+ * list of open tiles.  Asynchronous on `stream`, nothing read back, nothing allocated: `result` is zeroed on the stream; a tile pass
+ * decides, updates closed -- each word read and written by one lane only -- and writes open and, one 64-bit atomic per workgroup and
+ * count, the result; a pixel pass (not launched for n_images == 0) moves aligned quads of all images at once.
+ *
+ * STATMC_ERR_INVALID before any launch, statmc_last_error() naming the argument, in this order: a zero width or height; NULL
+ * tile_value or open; n_images outside 0 .. 4; with n_images > 0, NULL src or dst, then a NULL src[i] or dst[i]; tile_value, closed,
+ * open, a src[i] or a dst[i] not 4-byte aligned; result not 8-byte aligned; tile not one of 8, 16, 32, 64; a NaN threshold; overlaps:
+ * of two of tile_value, closed, open and result; of src[i] and dst[i] unless they are equal; of an image with tile_value, closed,
+ * open or result; of dst[i] with src[j] or dst[j], j != i.  STATMC_ERR_NO_DEVICE before statmc_setup, after those checks.
+ * Measured at 1920 x 1080 and 3840 x 2160: DESIGN.md 4.2k, profiles/score_tile_select.jsonl. */
+#define STATMC_TILE_SELECT_MAX_RANKS 4
+#define STATMC_GATE_MAX_IMAGES 4
+typedef struct statmc_tile_quantiles { /* HOST struct of DEVICE pointers: packed tiles_y x tiles_x planes, row-major */
+    float *value[STATMC_TILE_SELECT_MAX_RANKS];
+    int32_t *n_below[STATMC_TILE_SELECT_MAX_RANKS];
+    int32_t *n_equal[STATMC_TILE_SELECT_MAX_RANKS];
+} statmc_tile_quantiles;
+int statmc_score_tile_select(uint16_t width, uint16_t height, const float *score, int tile,
+                             const int32_t *q_num, int32_t q_den, int n_ranks,
+                             const statmc_tile_quantiles *out, void *stream);
+typedef struct statmc_gate_result { int64_t n_tiles, n_open, n_closed_now, n_px_open; } statmc_gate_result; /* device, 8-byte aligned */
+int statmc_gate_tiles(uint16_t width, uint16_t height, int tile,
+                      const float *tile_value, float threshold,
+                      int32_t *closed,              /* in/out tiles plane, may be NULL */
+                      int32_t *open,                /* out tiles plane, required */
+                      const void *const *src, void *const *dst, int n_images,   /* HOST arrays, 0..4 device images of width x height 32-bit words */
+                      statmc_gate_result *result,   /* may be NULL */
+                      void *stream);
+
 /* ---- window maximum / minimum of a score image (no counterpart in the reference): the error map regularised over a neighbourhood
  * before a plan spends by it.  A pixel's sample standard deviation after a handful of samples is itself noisy: a pixel beside a
  * caustic that has not yet drawn a bright sample reports a small score and the plan starves it.  MAX gives every pixel the worst

@@ -1446,6 +1446,111 @@ class Estimator {
         ScoreTiles(statTypeIndex, bounceIndex, tile, cap, out, scoreDilate, scoreOf, metric, eps);
         return out;
     }
+    // ---- order statistics of the same score image per tile x tile block (statmc_score_tile_select; include/statmc.h has the
+    // definition): per quantile nums[i] / den (1 to 4; 1 <= den <= 65536, 0 <= nums[i] <= den) the block's key at the nearest rank
+    // max(0, ceil(n nums[i] / den) - 1) of its n pixels -- NearestRank's rule per block --, with the number of the block's pixels
+    // below and equal to it: "the 95th percentile of the relative half-width in this tile is under 2 %".  `out` names the caller's
+    // device planes on this Estimator's device; a NULL plane is not formed.  The value planes are score images of the tile grid for
+    // statmc_score_count_above and GateTiles.  The checks, the flush of staged samples, the reuse of the score image, scoreDilate and
+    // scoreOf are ScoreTiles'.  One launch on DeviceStream(); returns without waiting.
+    void ScoreTileQuantiles(unsigned char statTypeIndex, unsigned char bounceIndex, int tile, const std::vector<int32_t> &nums, int32_t den,
+                            const statmc_tile_quantiles &out, int scoreDilate = 0, int scoreOf = ScoreOfStdErr, int metric = STATMC_SCORE_RELATIVE,
+                            float eps = 1e-3f) {
+        statmc_stat_type t;
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, false, scoreOf), scoreDilate);
+        check(statmc_score_tile_select((uint16_t)width, (uint16_t)height, scores, tile, nums.data(), den, (int)nums.size(), &out, stream.handle()));
+    }
+    // ... into planes this Estimator keeps (allocated by the first call, valid until the next ScoreTileQuantiles of this form): the
+    // three planes of every quantile asked for.
+    statmc_tile_quantiles ScoreTileQuantiles(unsigned char statTypeIndex, unsigned char bounceIndex, int tile, const std::vector<int32_t> &nums,
+                                             int32_t den, int scoreDilate = 0, int scoreOf = ScoreOfStdErr, int metric = STATMC_SCORE_RELATIVE,
+                                             float eps = 1e-3f) {
+        if (tile != 8 && tile != 16 && tile != 32 && tile != 64) throw Error(STATMC_ERR_INVALID, "ScoreTileQuantiles: tile must be 8, 16, 32 or 64");
+        if (nums.empty() || nums.size() > STATMC_TILE_SELECT_MAX_RANKS) throw Error(STATMC_ERR_INVALID, "ScoreTileQuantiles: 1 to 4 quantiles");
+        const size_t n = (size_t)TilesAcross(width, tile) * TilesAcross(height, tile);
+        plan.quantilePlanes.reserve(3 * nums.size() * n * sizeof(int32_t));
+        int32_t *p = static_cast<int32_t *>(plan.quantilePlanes.ptr);
+        statmc_tile_quantiles out{};
+        for (size_t i = 0; i < nums.size(); i++) {
+            out.value[i] = reinterpret_cast<float *>(p + 3 * i * n);
+            out.n_below[i] = p + (3 * i + 1) * n, out.n_equal[i] = p + (3 * i + 2) * n;
+        }
+        ScoreTileQuantiles(statTypeIndex, bounceIndex, tile, nums, den, out, scoreDilate, scoreOf, metric, eps);
+        return out;
+    }
+    // ---- a per-tile decision brought back to the pixels (statmc_gate_tiles; include/statmc.h has the definition): the tiles whose
+    // d_tileValue -- a value plane of ScoreTileQuantiles, a mean or max plane of ScoreTiles -- is above `threshold`, and that
+    // d_closed (may be NULL: no memory) has not closed before, are open; d_closed is updated, d_open written, and every image of
+    // `src` is copied to `dst` (the same pointer: in place) with the pixels of the other tiles set to the all-zero word.  All device
+    // memory of this Estimator's device.  Two launches on DeviceStream(); the call blocks until the 32 bytes of the result are back.
+    statmc_gate_result GateTiles(int tile, const float *d_tileValue, float threshold, int32_t *d_closed, int32_t *d_open,
+                                 const std::vector<const void *> &src = {}, const std::vector<void *> &dst = {}) {
+        if (src.size() != dst.size()) throw Error(STATMC_ERR_INVALID, "GateTiles: one destination per source image");
+        check(statmc_set_device(device));
+        plan.gateResult.reserve(sizeof(statmc_gate_result));
+        statmc_gate_result *d_result = static_cast<statmc_gate_result *>(plan.gateResult.ptr);
+        check(statmc_gate_tiles((uint16_t)width, (uint16_t)height, tile, d_tileValue, threshold, d_closed, d_open, src.data(), dst.data(),
+                                (int)src.size(), d_result, stream.handle()));
+        statmc_gate_result out{};
+        check(statmc_download(&out, d_result, sizeof(out), stream.handle()));
+        Synchronize();
+        return out;
+    }
+    // the planes of a gate this Estimator keeps per tile size: `closed` zeroed when first asked for (and when the tile size changes),
+    // `open` as the last GateTiles left it; valid for the Estimator's lifetime or until another tile size is asked for
+    struct TileGatePlanes { int32_t *d_closed, *d_open; };
+    TileGatePlanes GatePlanes(int tile) {
+        if (tile != 8 && tile != 16 && tile != 32 && tile != 64) throw Error(STATMC_ERR_INVALID, "GatePlanes: tile must be 8, 16, 32 or 64");
+        const size_t n = (size_t)TilesAcross(width, tile) * TilesAcross(height, tile);
+        if (plan.gateTile != tile) {
+            check(statmc_set_device(device));
+            plan.gatePlanes.reserve(2 * n * sizeof(int32_t));
+            check(statmc_memset(plan.gatePlanes.ptr, 0, 2 * n * sizeof(int32_t), stream.handle()));
+            plan.gateTile = tile;
+        }
+        int32_t *p = static_cast<int32_t *>(plan.gatePlanes.ptr);
+        return TileGatePlanes{p, p + n};
+    }
+    // ---- PlanSamples restricted to the open tiles of a gate: the score image is gated (closed pixels score +0), the budget is
+    // samplesPerOpenPixel times the gate's n_px_open, the plan runs with the given bounds and the planned counts are gated again, so a
+    // closed pixel gets exactly 0 whatever cMin is.  gate.d_closed is updated as GateTiles updates it; the gate's decision is
+    // idempotent under an unchanged d_tileValue and threshold, so a GateTiles before this call and the two gates inside it agree.  With
+    // no open pixel the counts are all 0 and result is zero.  Blocks as PlanSamples does.
+    struct TileGate {
+        int tile;
+        const float *d_tileValue;
+        float threshold;
+        int32_t *d_closed, *d_open;
+    };
+    struct GatedPlan {
+        const int32_t *d_counts;
+        statmc_plan_result result;
+        statmc_gate_result gate;
+    };
+    GatedPlan PlanSamples(unsigned char statTypeIndex, unsigned char bounceIndex, const TileGate &gate, int64_t samplesPerOpenPixel, int32_t cMin,
+                          int32_t cMax, int metric = STATMC_SCORE_RELATIVE, float eps = 1e-3f, int scoreDilate = 0, int scoreOf = ScoreOfDeviation) {
+        statmc_stat_type t;
+        const float *scores = windowedScores(scoreImage(statTypeIndex, bounceIndex, metric, eps, t, /*always=*/true, scoreOf), scoreDilate);
+        const size_t px = (size_t)width * height, wsBytes = statmc_plan_samples_workspace((uint16_t)width, (uint16_t)height);
+        plan.gatedScores.reserve(px * sizeof(float));
+        plan.counts.reserve(px * sizeof(int32_t));
+        plan.workspace.reserve(wsBytes);
+        plan.result.reserve(sizeof(statmc_plan_result));
+        int32_t *counts = static_cast<int32_t *>(plan.counts.ptr);
+        GatedPlan out{counts, statmc_plan_result{}, statmc_gate_result{}};
+        out.gate = GateTiles(gate.tile, gate.d_tileValue, gate.threshold, gate.d_closed, gate.d_open, {scores}, {plan.gatedScores.ptr});
+        if (out.gate.n_px_open == 0) {
+            check(statmc_memset(counts, 0, px * sizeof(int32_t), stream.handle()));
+            Synchronize();
+            return out;
+        }
+        statmc_plan_result *d_result = static_cast<statmc_plan_result *>(plan.result.ptr);
+        check(statmc_plan_samples((uint16_t)width, (uint16_t)height, static_cast<const float *>(plan.gatedScores.ptr), t.n,
+                                  samplesPerOpenPixel * out.gate.n_px_open, cMin, cMax, counts, d_result, plan.workspace.ptr, wsBytes, stream.handle()));
+        check(statmc_download(&out.result, d_result, sizeof(out.result), stream.handle()));
+        GateTiles(gate.tile, gate.d_tileValue, gate.threshold, gate.d_closed, gate.d_open, {counts}, {counts});
+        return out;
+    }
     static int TilesAcross(int extent, int tile) { return (extent + tile - 1) / tile; }
     // one int64 of device memory on this Estimator's device for a count over those planes (statmc_score_count_above's `counts` with
     // one threshold: the open tiles of a tile rule); valid for the Estimator's lifetime
@@ -2093,6 +2198,8 @@ class Estimator {
         DeviceBytes selectWorkspace, selectResult, aboveCounts;
         DeviceBytes sumWorkspace, sumResult;   // ScoreSum's
         DeviceBytes tilePlanes, tileCount;     // ScoreTiles' own planes, TileRuleCount's word
+        DeviceBytes quantilePlanes, gateResult, gatePlanes, gatedScores;   // ScoreTileQuantiles' own planes; GateTiles' result; GatePlanes'; the gated PlanSamples' score
+        int gateTile = 0;                      // the tile size gatePlanes is laid out for
         // what `scores` holds: the (type, bounce, metric, eps) it was computed for and the state of the statistics then -- the
         // flushes of staged samples so far and `touched`, which every call that may write the statistics otherwise bumps
         // (every Accumulate* entry and CombineRecords, ResetStatistics, CombineStatistics, PoolStatistics, EnableDeviceAccumulation)

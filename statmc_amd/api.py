@@ -146,6 +146,24 @@ class TileScores(C.Structure):
                 ("n_px", C.c_void_p), ("n_zero", C.c_void_p), ("n_infinite", C.c_void_p), ("n_clipped", C.c_void_p)]
 
 
+TILE_SELECT_MAX_RANKS = 4
+TILE_SELECT_MAX_DEN = 65536
+TILE_QUANTILE_FIELDS = ("value", "n_below", "n_equal")      # statmc_tile_quantiles' fields, in its order
+GATE_MAX_IMAGES = 4
+
+
+class TileQuantiles(C.Structure):
+    """statmc_tile_quantiles: a HOST struct of DEVICE pointers to the planes statmc_score_tile_select writes, one per field and rank
+    slot; NULL: not formed."""
+    _fields_ = [("value", C.c_void_p * TILE_SELECT_MAX_RANKS), ("n_below", C.c_void_p * TILE_SELECT_MAX_RANKS),
+                ("n_equal", C.c_void_p * TILE_SELECT_MAX_RANKS)]
+
+
+class GateResult(C.Structure):
+    """statmc_gate_result: what statmc_gate_tiles writes to device memory (32 bytes)."""
+    _fields_ = [("n_tiles", C.c_int64), ("n_open", C.c_int64), ("n_closed_now", C.c_int64), ("n_px_open", C.c_int64)]
+
+
 SCORE_ABSOLUTE, SCORE_RELATIVE = 0, 1     # statmc_sample_scores' metric
 ERROR_NO_TABLE = -1                       # statmc_error_scores' table: the standard error, no quantile
 SCORE_WINDOW_MAX, SCORE_WINDOW_MIN = 0, 1  # statmc_score_window's op
@@ -162,7 +180,7 @@ EXPORTS = [
     "statmc_stream_create", "statmc_stream_create_with_priority", "statmc_stream_destroy", "statmc_synchronize",
     "statmc_event_create", "statmc_event_destroy", "statmc_event_record", "statmc_stream_wait_event",
     "statmc_filter_f32", "statmc_filter_f32x3", "statmc_prepass", "statmc_window_filter", "statmc_pack_filter_inputs", "statmc_prepass_pack", "statmc_prepass_pack_rows",
-    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_sum_workspace", "statmc_score_sum", "statmc_score_tiles", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
+    "statmc_halo_exchange", "statmc_halo_exchange_rccl", "statmc_rccl_available", "statmc_rccl_unique_id", "statmc_rccl_comm_create", "statmc_rccl_comm_destroy", "statmc_copy_rect", "statmc_calculate_mean_vars", "statmc_accumulate", "statmc_accumulate_rows", "statmc_accumulate_row_ranges", "statmc_accumulate_formats", "statmc_accumulate_tiles", "statmc_accumulate_tiles_formats", "statmc_accumulate_counted", "statmc_accumulate_tiles_counted", "statmc_accumulate_records", "statmc_accumulate_records_interleaved", "statmc_accumulate_records_split", "statmc_accumulate_records_interleaved_split", "statmc_combine_statistics", "statmc_combine_many", "statmc_pool_statistics", "statmc_upsample_filtered", "statmc_sample_scores", "statmc_plan_samples_workspace", "statmc_plan_samples", "statmc_error_scores", "statmc_plan_to_target", "statmc_score_select_workspace", "statmc_score_select", "statmc_score_count_above", "statmc_score_sum_workspace", "statmc_score_sum", "statmc_score_tiles", "statmc_score_tile_select", "statmc_gate_tiles", "statmc_score_window", "statmc_compact_offsets_workspace", "statmc_compact_offsets", "statmc_compact_accumulate", "statmc_compact_accumulate_interleaved", "statmc_state_dwords", "statmc_gather_states", "statmc_combine_records", "statmc_get_prepass_context", "statmc_merge_tiles", "statmc_tile_moments", "statmc_film_update",
     "statmc_last_filter_variant", "statmc_version", "statmc_clock_probe",
 ]
 
@@ -281,6 +299,10 @@ def load():
     lib.statmc_score_sum.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(SumResult), C.c_void_p,
                                      C.c_size_t, C.c_void_p]
     lib.statmc_score_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_float, C.POINTER(TileScores), C.c_void_p]
+    lib.statmc_score_tile_select.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int32, C.c_int,
+                                             C.POINTER(TileQuantiles), C.c_void_p]
+    lib.statmc_gate_tiles.argtypes = [C.c_uint16, C.c_uint16, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_score_window.argtypes = [C.c_uint16, C.c_uint16, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.statmc_compact_offsets_workspace.argtypes = [C.c_uint16, C.c_uint16]
     lib.statmc_compact_offsets_workspace.restype = C.c_size_t
@@ -1087,6 +1109,115 @@ def read_tile_scores(res):
     """The planes a score_tiles call returned, as numpy arrays of the same shapes and types.  Small device-to-host copies: they
     synchronise with the work that wrote them on the current stream; after a call on another stream synchronise that one first."""
     return {p: t.cpu().numpy() for p, t in res.items()}
+
+
+def tile_quantile_fraction(q):
+    """(num, den) of a quantile given as a (num, den) pair or as a float in [0, 1]: a float goes through
+    Fraction(q).limit_denominator(65536), so 0.95 is 19/20 and 0.5 is 1/2."""
+    from fractions import Fraction
+    if isinstance(q, (tuple, list)):
+        num, den = int(q[0]), int(q[1])
+    else:
+        f = Fraction(float(q)).limit_denominator(TILE_SELECT_MAX_DEN)
+        num, den = f.numerator, f.denominator
+    return num, den
+
+
+def score_tile_select(score, tile, nums, den, fields=TILE_QUANTILE_FIELDS, out=None, stream=None):
+    """statmc_score_tile_select: per tile x tile block (8, 16, 32 or 64; partial blocks at the edges included) of the float32 score
+    image [H, W] and per quantile nums[i] / den (1 to 4 of them; 1 <= den <= 65536, 0 <= nums[i] <= den) the key at the nearest rank
+    max(0, ceil(n nums[i] / den) - 1) of the block's n pixels, with the number of the block's pixels below and equal to it
+    (include/statmc.h).  Returns {field: [device tensor [tiles_y, tiles_x] per quantile]} for the fields named ("value" float32,
+    "n_below" and "n_equal" int32; a field not named is not formed); `out` may hand in the tensors to write in the same shape of
+    dict, a None entry being left out.  The "value" planes are score images that score_count_above, score_select, score_window,
+    plan_samples and gate_tiles take.  Asynchronous: one launch, no workspace."""
+    tc = _torch()
+    h, w = _score_image(score, "score_tile_select")
+    nums = [int(v) for v in nums]
+    fields = tuple(fields)
+    for f in fields:
+        if f not in TILE_QUANTILE_FIELDS:
+            raise ValueError("score_tile_select: no field %r: one of %s" % (f, ", ".join(TILE_QUANTILE_FIELDS)))
+    if len(nums) > TILE_SELECT_MAX_RANKS:
+        raise ValueError("score_tile_select: %d quantiles: 1 to %d" % (len(nums), TILE_SELECT_MAX_RANKS))
+    shape = tile_grid(h, w, tile) if int(tile) > 0 else (0, 0)
+    res, ptrs = {}, TileQuantiles()
+    for f in fields:
+        res[f] = []
+        for i in range(len(nums)):
+            t = None if out is None or f not in out else out[f][i]
+            if t is None and out is not None and f in out:
+                res[f].append(None)
+                continue
+            dtype = tc.float32 if f == "value" else tc.int32
+            if t is None:
+                t = tc.empty(shape, dtype=dtype, device=score.device)
+            elif t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError("score_tile_select: out[%r][%d] must be a contiguous %s CUDA tensor of shape %s" % (f, i, dtype, shape))
+            res[f].append(t)
+            getattr(ptrs, f)[i] = t.data_ptr() if t.numel() else None
+    arr = (C.c_int32 * max(len(nums), 1))(*nums)
+    check(load().statmc_score_tile_select(w, h, score.data_ptr(), int(tile), arr, int(den), len(nums), C.byref(ptrs),
+                                          stream if stream is not None else current_stream_handle()))
+    return res
+
+
+def read_tile_quantiles(res):
+    """The planes a score_tile_select call returned, as numpy arrays in the same dict of lists (None stays None).  Small device-to-host
+    copies: they synchronise with the work that wrote them on the current stream; after a call on another stream synchronise that one
+    first."""
+    return {f: [None if t is None else t.cpu().numpy() for t in ts] for f, ts in res.items()}
+
+
+_GATE_WORDS = C.sizeof(GateResult) // 8
+
+
+def gate_tiles(height, width, tile, tile_value, threshold, closed=None, open=None, images=(), out=None, result=None, stream=None):
+    """statmc_gate_tiles: the tiles of the height x width film whose tile_value (a float32 plane of tile_grid's shape, e.g. a
+    score_tile_select "value" plane) is above `threshold` by score_count_above's rule, and that `closed` (an int32 plane, updated in
+    place; None: no memory) has not closed before, are open; `images` (0 to 4 contiguous [H, W] tensors of 4-byte elements, float32
+    scores and int32 counts alike) are copied with the pixels of every other tile set to the all-zero word (include/statmc.h).  `out`:
+    the tensors to write, one per image, the image itself for in place; None: new tensors.  Returns (open int32 [tiles_y, tiles_x],
+    the gated images as a list, the device result: an int64 [4] tensor read by read_gate_result).  A closed tile never reopens: start
+    `closed` from zeros.  Asynchronous: two launches."""
+    tc = _torch()
+    shape = tile_grid(height, width, tile) if int(tile) > 0 else (0, 0)
+    dev = tile_value.device
+    if tile_value.dtype != tc.float32 or not tile_value.is_cuda or not tile_value.is_contiguous() or tuple(tile_value.shape) != shape:
+        raise ValueError("gate_tiles: tile_value must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+    if open is None:
+        open = tc.empty(shape, dtype=tc.int32, device=dev)
+    for name, t in (("closed", closed), ("open", open)):
+        if t is not None and (t.dtype != tc.int32 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise ValueError("gate_tiles: %s must be a contiguous int32 CUDA tensor of shape %s" % (name, shape))
+    images = list(images)
+    outs = list(out) if out is not None else [tc.empty_like(im) for im in images]
+    if len(outs) != len(images):
+        raise ValueError("gate_tiles: out must hold one tensor per image")
+    for name, ts in (("images", images), ("out", outs)):
+        for i, t in enumerate(ts):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != 4 or t.numel() != int(height) * int(width):
+                raise ValueError("gate_tiles: %s[%d] must be a contiguous CUDA tensor of H * W 4-byte elements" % (name, i))
+    if result is None:
+        result = tc.empty(_GATE_WORDS, dtype=tc.int64, device=dev)
+    elif result.dtype != tc.int64 or not result.is_cuda or not result.is_contiguous() or result.numel() < _GATE_WORDS:
+        raise ValueError("gate_tiles: result must be a contiguous int64 CUDA tensor of %d words" % _GATE_WORDS)
+    k = len(images)
+    src = (C.c_void_p * max(k, 1))(*[t.data_ptr() for t in images])
+    dst = (C.c_void_p * max(k, 1))(*[t.data_ptr() for t in outs])
+    check(load().statmc_gate_tiles(int(width), int(height), int(tile), tile_value.data_ptr(), float(threshold),
+                                   closed.data_ptr() if closed is not None else None, open.data_ptr() if open.numel() else None,
+                                   src if k else None, dst if k else None, k, result.data_ptr(),
+                                   stream if stream is not None else current_stream_handle()))
+    return open, outs, result
+
+
+def read_gate_result(t):
+    """The statmc_gate_result a gate_tiles call wrote into the int64 [4] device tensor `t`, as a dict of Python integers.  One small
+    device-to-host copy: it synchronises with the work that wrote `t` on the current stream; after a call on another stream
+    synchronise that one first."""
+    r = GateResult.from_buffer_copy(t.cpu().numpy().tobytes())
+    return {f: int(getattr(r, f)) for f, _ in GateResult._fields_}
 
 
 _WINDOW_OPS = {"max": SCORE_WINDOW_MAX, "min": SCORE_WINDOW_MIN}

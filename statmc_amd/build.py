@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libstatmc_hip.so")
 DEFAULT_SO = SO
 SOURCES = ["statmc_pointwise.hip", "statmc_filter.hip", "statmc_filter_sym.hip", "statmc_placement.hip", "statmc_abi.hip", "statmc_rccl.hip",
-           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_error.hip", "statmc_upsample.hip", "statmc_select.hip", "statmc_score_window.hip", "statmc_score_sum.hip", "statmc_score_tiles.hip", "statmc_compact.hip", "statmc_state_records.hip"]
-HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_state_records_args.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_error_args.h", "statmc_upsample_args.h", "statmc_select_args.h", "statmc_score_window_args.h", "statmc_score_sum_args.h", "statmc_score_tiles_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
+           "statmc_records.hip", "statmc_counted.hip", "statmc_pool.hip", "statmc_plan.hip", "statmc_error.hip", "statmc_upsample.hip", "statmc_select.hip", "statmc_score_window.hip", "statmc_score_sum.hip", "statmc_score_tiles.hip", "statmc_tile_select.hip", "statmc_compact.hip", "statmc_state_records.hip"]
+HEADERS = ["statmc_device.h", "statmc_scan.h", "statmc_state_records_args.h", "statmc_compact_args.h", "statmc_compact_interleaved_args.h", "statmc_record_field.h", "statmc_accumulate_fold.h", "statmc_accumulate_args.h", "statmc_records_plan.h", "statmc_pool_args.h", "statmc_plan_args.h", "statmc_error_args.h", "statmc_upsample_args.h", "statmc_select_args.h", "statmc_score_window_args.h", "statmc_score_sum_args.h", "statmc_score_tiles_args.h", "statmc_tile_select_args.h", "statmc_filter_common.h", "t_quantiles.h", os.path.join("..", "..", "include", "statmc.h"),
            os.path.join("..", "..", "include", "statmc_pinned_spec.h"), os.path.join("..", "..", "include", "statmc_device_api.hpp")]
 # -ffp-contract=off: every fp32 op rounds once, in source order, like the CPU oracle build.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -110,6 +110,7 @@ SELECT_BIN = os.path.join(ROOT, "tools", "bin", "test_score_select")   # tests/c
 WINDOW_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_score_window_args")   # tests/cpp/test_score_window_args.cpp: statmc_score_window_args.h, no device, no library
 SUM_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_score_sum_args")   # tests/cpp/test_score_sum_args.cpp: statmc_score_sum_args.h, no device, no library
 TILES_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_score_tiles_args")   # tests/cpp/test_score_tiles_args.cpp: statmc_score_tiles_args.h, no device, no library
+TILE_SELECT_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_tile_select_args")   # tests/cpp/test_tile_select_args.cpp: statmc_tile_select_args.h, no device, no library
 WINDOW_BIN = os.path.join(ROOT, "tools", "bin", "test_score_window")   # tests/cpp/test_score_window.cpp: Estimator::PlanSamples(..., scoreDilate) / ScoreWindow
 COMPACT_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_args")   # tests/cpp/test_compact_args.cpp: statmc_compact_args.h, no device, no library
 COMPACT_ILV_ARGS_BIN = os.path.join(ROOT, "tools", "bin", "test_compact_interleaved_args")   # tests/cpp/test_compact_interleaved_args.cpp: statmc_compact_interleaved_args.h, no device, no library
@@ -145,6 +146,7 @@ TOOLS = {DENOISE_BIN: "statmc_denoise.cpp", RENDER_SIM_BIN: "statmc_render_sim.c
          WINDOW_BIN: os.path.join("..", "tests", "cpp", "test_score_window.cpp"),
          SUM_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_score_sum_args.cpp"),
          TILES_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_score_tiles_args.cpp"),
+         TILE_SELECT_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_tile_select_args.cpp"),
          COMPACT_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_args.cpp"),
          COMPACT_ILV_ARGS_BIN: os.path.join("..", "tests", "cpp", "test_compact_interleaved_args.cpp"),
          COMPACT_ILV_BIN: os.path.join("..", "tests", "cpp", "test_compact_accumulate_interleaved.cpp"),
@@ -179,6 +181,7 @@ def tools_hash():
     files.append(os.path.join(CSRC, "statmc_score_window_args.h"))    # ... test_score_window_args.cpp the window entry's checks
     files.append(os.path.join(CSRC, "statmc_score_sum_args.h"))    # ... test_score_sum_args.cpp the sum entry's checks and finalisation
     files.append(os.path.join(CSRC, "statmc_score_tiles_args.h"))    # ... test_score_tiles_args.cpp the tile entry's checks and finalisation
+    files.append(os.path.join(CSRC, "statmc_tile_select_args.h"))    # ... test_tile_select_args.cpp the tile select's and the gate's checks and host evaluation
     files.append(os.path.join(CSRC, "statmc_compact_args.h"))    # ... test_compact_args.cpp the compact entries' checks
     files.append(os.path.join(CSRC, "statmc_compact_interleaved_args.h"))    # ... and test_compact_interleaved_args.cpp the interleaved compact entry's
     files.append(os.path.join(CSRC, "statmc_state_records_args.h"))    # ... and test_state_records_args.cpp the state-record entries'

@@ -23,6 +23,7 @@
 #include "statmc_score_window_args.h"
 #include "statmc_score_sum_args.h"
 #include "statmc_score_tiles_args.h"
+#include "statmc_tile_select_args.h"
 #include "statmc_compact_args.h"
 #include "statmc_compact_interleaved_args.h"
 #include "statmc_state_records_args.h"
@@ -1567,6 +1568,29 @@ int statmc_score_tiles(uint16_t width, uint16_t height, const float *score, int 
     statmc::TilesArgs a;
     statmc::fill_score_tiles_args(a, width, height, score, tile, cap, out);
     HIP_TRY(statmc::launch_score_tiles(a, S(stream)));
+    return STATMC_OK;
+}
+
+// statmc_score_tile_select / statmc_gate_tiles: every rule of include/statmc.h ahead of the device (statmc_tile_select_args.h), then
+// the launches of statmc_tile_select.hip on `stream`; nothing is allocated or read back.
+int statmc_score_tile_select(uint16_t width, uint16_t height, const float *score, int tile, const int32_t *q_num, int32_t q_den, int n_ranks,
+                             const statmc_tile_quantiles *out, void *stream) {
+    ARG_TRY(statmc::check_tile_select_call(width, height, score, tile, q_num, q_den, n_ranks, out, statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::TileSelectArgs a;
+    statmc::fill_tile_select_args(a, width, height, score, tile, q_num, q_den, n_ranks, out);
+    HIP_TRY(statmc::launch_tile_select(a, S(stream)));
+    return STATMC_OK;
+}
+
+int statmc_gate_tiles(uint16_t width, uint16_t height, int tile, const float *tile_value, float threshold, int32_t *closed, int32_t *open,
+                      const void *const *src, void *const *dst, int n_images, statmc_gate_result *result, void *stream) {
+    ARG_TRY(statmc::check_gate_call(width, height, tile, tile_value, threshold, closed, open, src, dst, n_images, result,
+                                    statmc::SelectMsg{g_err, sizeof(g_err)}));
+    NEED_READY();
+    statmc::GateArgs a;
+    statmc::fill_gate_args(a, width, height, tile, tile_value, threshold, closed, open, src, dst, n_images, result);
+    HIP_TRY(statmc::launch_gate_tiles(a, S(stream)));
     return STATMC_OK;
 }
 

@@ -249,6 +249,12 @@ hipError_t launch_score_sum(const SumArgs &a, hipStream_t s);
 struct TilesArgs;
 hipError_t launch_score_tiles(const TilesArgs &a, hipStream_t s);
 
+// statmc_score_tile_select / statmc_gate_tiles (statmc_tile_select.hip): argument blocks and checks are statmc_tile_select_args.h's, host-only
+struct TileSelectArgs;
+struct GateArgs;
+hipError_t launch_tile_select(const TileSelectArgs &a, hipStream_t s);
+hipError_t launch_gate_tiles(const GateArgs &a, hipStream_t s);
+
 // statmc_score_window (statmc_score_window.hip): argument block and checks are statmc_score_window_args.h's, host-only
 struct ScoreWindowArgs;
 hipError_t launch_score_window(const ScoreWindowArgs &a, hipStream_t s);

@@ -359,6 +359,38 @@ class FilmStats:
         read."""
         return api.score_tiles(self._scores(metric, eps, type, dilate, error), tile, cap, planes=planes)
 
+    def score_tile_quantiles(self, tile, qs, metric="relative", eps=1e-3, type="radiance", dilate=0, error="stderr",
+                             fields=api.TILE_QUANTILE_FIELDS):
+        """Per tile x tile block (8, 16, 32 or 64) of the film the q-quantiles (1 to 4) of the score of stat type `type`, by the
+        nearest-rank rule within the block (statmc_score_tile_select: exact, the same bits on every run): "the 95th percentile of
+        the relative half-width in this tile is under 2 %".  `qs` are (num, den) pairs or floats in [0, 1]; all share one
+        denominator on the device, so pairs are brought to their least common multiple, which must not exceed 65536.  A float goes
+        through Fraction(q).limit_denominator(65536): 0.95 is 19/20, and a q that is no such fraction is replaced by the nearest
+        one.  The score pipeline is score_mean's.  Returns {"value": [float32 [tiles_y, tiles_x] per q], "n_below": [int32 ...],
+        "n_equal": [...]} for the fields named, device tensors; no synchronisation, nothing downloaded; the film is only read.  A
+        "value" plane goes to gate_tiles as it is."""
+        import math
+        pairs = [api.tile_quantile_fraction(q) for q in qs]
+        for num, den in pairs:
+            if den < 1 or not 0 <= num <= den:
+                raise ValueError("score_tile_quantiles: %d/%d is outside [0, 1]" % (num, den))
+        den = 1
+        for _, d in pairs:
+            den = den * d // math.gcd(den, d)
+        if den > api.TILE_SELECT_MAX_DEN:
+            raise ValueError("score_tile_quantiles: the quantiles' common denominator %d exceeds %d" % (den, api.TILE_SELECT_MAX_DEN))
+        nums = [num * (den // d) for num, d in pairs]
+        return api.score_tile_select(self._scores(metric, eps, type, dilate, error), tile, nums, den, fields=fields)
+
+    def gate_tiles(self, tile, tile_value, threshold, closed=None, images=(), out=None):
+        """Close the tiles of this film whose `tile_value` (a plane of score_tile_quantiles or score_tiles) is at or under
+        `threshold`, for good where `closed` (an int32 plane of the tile grid, zeros before the first call) is given, and zero the
+        pixels of every tile that is not open in `images` -- a score image before plan_samples, a count image after it
+        (statmc_gate_tiles).  Returns (open int32 [tiles_y, tiles_x], gated images, the statmc_gate_result as a dict) after one
+        synchronisation and one 32-byte download."""
+        is_open, gated, res = api.gate_tiles(self.height, self.width, tile, tile_value, threshold, closed=closed, images=images, out=out)
+        return is_open, gated, api.read_gate_result(res)
+
     def _prepass_key(self):
         return (api.get_filter_spec().as_tuple(), api.get_significance())
 

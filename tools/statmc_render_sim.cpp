@@ -20,7 +20,7 @@
 //   statmc_render_sim --width 96 --height 56 --spp 4 --iterations 3 --stem out/sim [--threads 4]
 //                     [--seed 1] [--filtersd 10] [--filterradius 20] [--stage-mb 2048] [--no-denoise]
 //                     [--config denoise|acrr|smis] [--trackedbounces 5] [--outputregex '.*'] [--warmup] [--tilestats]
-//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-mean mean|rms:T[:CAP]] [--stop-tiles T:TOL[:CAP]] [--stop-metric sd|stderr|ci] [--target-error T]
+//                     [--adaptive] [--adaptive-pixels [--stop-at Q:T] [--stop-mean mean|rms:T[:CAP]] [--stop-tiles T:TOL[:CAP] [--tile-quantile NUM/DEN] [--close-tiles]] [--stop-metric sd|stderr|ci] [--target-error T]
 //                     [--score-dilate R]]
 //                     [--placed] [--half-features]
 // --adaptive: per-tile sample budgets from the tile-local noise level (Estimator::TileNoise); see RenderLoop.
@@ -39,6 +39,15 @@
 //                   one int64 comes back.  Once no tile is open the remaining iterations are skipped.  CAP defaults to +inf.  Reads
 //                   --stop-metric's quantity and --score-dilate's window; with --stop-at or --stop-mean as well, every rule must
 //                   hold.  Every iteration prints a "Tile rule:" line with "open tiles k / N".  Not with --preview.
+// --tile-quantile NUM/DEN: with --stop-tiles, the tile's statistic is the NUM/DEN-quantile of its pixels' scores by the nearest-rank rule
+//                   (Estimator::ScoreTileQuantiles, 0 <= NUM <= DEN <= 65536) instead of their mean; CAP is not used.  The "Tile rule:" line
+//                   says "quantile NUM/DEN of the relative ..." then.
+// --close-tiles:    with --stop-tiles, a tile that has met the rule is closed for good: after every iteration the rule's plane goes through
+//                   Estimator::GateTiles with a closed plane kept over the run; the next plan's score is gated, its budget is the schedule's
+//                   samples per pixel times the open pixels, its lower bound 0, and the planned counts are gated again (Estimator::PlanSamples
+//                   with a TileGate).  The run ends when no tile is open.  Every iteration prints "Closed tiles: iteration i, closed now A,
+//                   open B / N, open pixels P".  A render tile whose pixels all have a count of 0 is skipped: no sample is added and its
+//                   Merge*Tile(s) calls are not made.  Not with --target-error.
 // --stop-metric M: which quantity --stop-at's quantile (and --target-error's plan) reads.  sd, the default: the sample standard
 //                   deviation, which does not fall as samples arrive -- only T = 0 or a T above the film's noise make sense with it;
 //                   stderr: the standard error of the mean; ci: the two-sided confidence half-width at the device's significance
@@ -150,6 +159,8 @@ struct Options {
     bool stopTiles = false;    // --stop-tiles T:TOL[:CAP]
     int stopTilesTile = 0;
     float stopTilesTol = 0.f, stopTilesCap = INFINITY;
+    bool tileQuantile = false, closeTiles = false;   // --tile-quantile NUM/DEN, --close-tiles
+    int tileQuantileNum = 0, tileQuantileDen = 1;
     int stopMetric = Estimator::ScoreOfDeviation;   // --stop-metric sd|stderr|ci
     bool stopMetricGiven = false;
     bool targetErrorGiven = false;   // --target-error T
@@ -270,6 +281,12 @@ static void Render(const Options &o) {
                     std::vector<StatTile<T>> &tileLs = lTiles[t];
                     std::vector<std::vector<StatTile<Vec3>>> &tileRGBFeatures = rgbFeatureTiles[t];
                     std::vector<std::vector<StatTile<float>>> &tileMISTallies = misTallyTiles[t];
+                    if (o.closeTiles && !pixelTarget.empty()) {   // a render tile inside closed tiles: nothing to add, nothing to merge
+                        bool any = false;
+                        for (int y = tb.pMin.y; y < tb.pMax.y && !any; y++)
+                            for (int x = tb.pMin.x; x < tb.pMax.x && !any; x++) any = pixelTarget[(size_t)y * width + x] > 0;
+                        if (!any) continue;
+                    }
                     for (int y = tb.pMin.y; y < tb.pMax.y; y++)
                         for (int x = tb.pMin.x; x < tb.pMax.x; x++) {
                             const Point2i actualPixel(x, y);
@@ -365,8 +382,27 @@ static void Render(const Options &o) {
 
         // --stop-tiles: the tiles whose mean relative score under the cap is above the tolerance, one int64 back
         bool tilesMet = true;
-        if (o.stopTiles && sCfgs[Radiance].enable) {
+        const float *tileRulePlane = nullptr;   // --close-tiles: what the gate of this iteration and of the next plan reads
+        if (o.stopTiles && o.tileQuantile && sCfgs[Radiance].enable) {
+            const statmc_tile_quantiles planes = estimator.ScoreTileQuantiles(sCfgs[Radiance].index, 0, o.stopTilesTile, {o.tileQuantileNum}, o.tileQuantileDen,
+                                                                             o.scoreDilate, o.stopMetric);
+            tileRulePlane = planes.value[0];
+            const int tilesX = Estimator::TilesAcross(width, o.stopTilesTile), tilesY = Estimator::TilesAcross(height, o.stopTilesTile);
+            const float tol = o.stopTilesTol;
+            int64_t *d_open = estimator.TileRuleCount();
+            check(statmc_score_count_above((uint16_t)tilesX, (uint16_t)tilesY, planes.value[0], &tol, 1, d_open, estimator.DeviceStream()));
+            int64_t open = 0;
+            check(statmc_download(&open, d_open, sizeof(open), estimator.DeviceStream()));
+            estimator.Synchronize();
+            tilesMet = open == 0;
+            char tolerance[32];
+            std::snprintf(tolerance, sizeof(tolerance), "%.9g", (double)o.stopTilesTol);
+            std::cout << "Tile rule: iteration " << i << ", open tiles " << open << " / " << (int64_t)tilesX * tilesY << " of " << o.stopTilesTile << " x "
+                      << o.stopTilesTile << " pixels, quantile " << o.tileQuantileNum << "/" << o.tileQuantileDen << " of the relative " << what << " above "
+                      << tolerance << ": " << (tilesMet ? "met" : "open") << std::endl;
+        } else if (o.stopTiles && sCfgs[Radiance].enable) {
             const statmc_tile_scores planes = estimator.ScoreTiles(sCfgs[Radiance].index, 0, o.stopTilesTile, o.stopTilesCap, o.scoreDilate, o.stopMetric);
+            tileRulePlane = planes.mean;
             const int tilesX = Estimator::TilesAcross(width, o.stopTilesTile), tilesY = Estimator::TilesAcross(height, o.stopTilesTile);
             const float tol = o.stopTilesTol;
             int64_t *d_open = estimator.TileRuleCount();
@@ -381,6 +417,16 @@ static void Render(const Options &o) {
             std::cout << "Tile rule: iteration " << i << ", open tiles " << open << " / " << (int64_t)tilesX * tilesY << " of " << o.stopTilesTile << " x "
                       << o.stopTilesTile << " pixels, mean of the relative " << what << " under " << cap << " above " << tolerance << ": "
                       << (tilesMet ? "met" : "open") << std::endl;
+        }
+        // --close-tiles: the rule's plane through the gate, with the closed plane of the run; a tile closed earlier stays closed
+        Estimator::TileGate tileGate{o.stopTilesTile, tileRulePlane, o.stopTilesTol, nullptr, nullptr};
+        if (o.closeTiles && tileRulePlane) {
+            const Estimator::TileGatePlanes gp = estimator.GatePlanes(o.stopTilesTile);
+            tileGate.d_closed = gp.d_closed, tileGate.d_open = gp.d_open;
+            const statmc_gate_result g = estimator.GateTiles(o.stopTilesTile, tileRulePlane, o.stopTilesTol, gp.d_closed, gp.d_open);
+            tilesMet = g.n_open == 0;
+            std::cout << "Closed tiles: iteration " << i << ", closed now " << g.n_closed_now << ", open " << g.n_open << " / " << g.n_tiles
+                      << ", open pixels " << g.n_px_open << std::endl;
         }
 
         // --stop-at: the Q-quantile of the relative score, one 256-byte struct back
@@ -419,6 +465,18 @@ static void Render(const Options &o) {
                 std::snprintf(level, sizeof(level), "%08x", (unsigned)plan.budgeted.level_bits);
                 std::cout << "Planned: " << plan.budgeted.total << " samples, " << lo << " .. " << hi << " per pixel, level 0x" << level << std::endl;
             }
+        } else if (o.adaptivePixels && o.closeTiles && tileRulePlane && i < nIterations && !converged) {
+            const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
+            const Estimator::GatedPlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, tileGate, (int64_t)next, 0, (int32_t)(4 * next),
+                                                                    STATMC_SCORE_RELATIVE, 1e-3f, o.scoreDilate);
+            pixelTarget.resize((size_t)width * height);
+            check(statmc_download(pixelTarget.data(), plan.d_counts, pixelTarget.size() * sizeof(int32_t), estimator.DeviceStream()));
+            estimator.Synchronize();
+            int32_t lo = pixelTarget[0], hi = pixelTarget[0];
+            for (int32_t v : pixelTarget) { lo = std::min(lo, v); hi = std::max(hi, v); }
+            char level[16];
+            std::snprintf(level, sizeof(level), "%08x", (unsigned)plan.result.level_bits);
+            std::cout << "Planned: " << plan.result.total << " samples, " << lo << " .. " << hi << " per pixel, level 0x" << level << std::endl;
         } else if (o.adaptivePixels && sCfgs[Radiance].enable && i < nIterations && !converged) {
             const unsigned next = (unsigned)o.spp << std::max(i - 1, 0);   // the schedule's target of iteration i + 1
             const Estimator::SamplePlan plan = estimator.PlanSamples(sCfgs[Radiance].index, 0, (int64_t)width * height * next, 1, (int32_t)(4 * next),
@@ -583,6 +641,26 @@ int main(int argc, char **argv) {
                 return 2;
             }
             o.stopTiles = true;
+        } else if (a == "--tile-quantile") {
+            const std::string v = next();
+            const size_t slash = v.find('/');
+            char *end = nullptr;
+            bool ok = slash != std::string::npos && slash > 0 && slash + 1 < v.size();
+            if (ok) {
+                const std::string n = v.substr(0, slash), d = v.substr(slash + 1);
+                const long num = std::strtol(n.c_str(), &end, 10);
+                ok = *end == 0;
+                const long den = std::strtol(d.c_str(), &end, 10);
+                ok = ok && *end == 0 && den >= 1 && den <= 65536 && num >= 0 && num <= den;
+                o.tileQuantileNum = (int)num, o.tileQuantileDen = (int)den;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "--tile-quantile takes NUM/DEN with 0 <= NUM <= DEN and 1 <= DEN <= 65536\n");
+                return 2;
+            }
+            o.tileQuantile = true;
+        } else if (a == "--close-tiles") {
+            o.closeTiles = true;
         } else if (a == "--stop-metric") {
             const std::string v = next();
             if (v != "sd" && v != "stderr" && v != "ci") {
@@ -653,6 +731,14 @@ int main(int argc, char **argv) {
     }
     if (o.preview && o.stopTiles) {
         std::fprintf(stderr, "--preview cannot be used with --stop-tiles (the last iteration is denoised in full, and --stop-tiles decides it late)\n");
+        return 2;
+    }
+    if ((o.tileQuantile || o.closeTiles) && !o.stopTiles) {
+        std::fprintf(stderr, "--tile-quantile and --close-tiles need --stop-tiles\n");
+        return 2;
+    }
+    if (o.closeTiles && o.targetErrorGiven) {
+        std::fprintf(stderr, "--close-tiles cannot be used with --target-error (the gated plan spends a budget)\n");
         return 2;
     }
     if (o.stopTiles && !o.adaptivePixels) {
